@@ -12,10 +12,15 @@ torch.distributed (through marl_llm_amd.dist_util) only provides the barrier and
 Prints ONE JSON line on rank 0 with the contract's keys plus
   "roofline":      HBM roofline of the step kernel: SURVEY section 8(d) algorithmic bytes / HIP-event-timed launch
                    duration / 8 TB/s
+and, with --full only (N = 1 only; they take runs of their own and are not part of the headline figure):
   "cpu_baseline":  the reference's CPU path (oracle/_ref: its own C++ compiled unmodified + a restatement of its numpy
                    glue) timed on this box's host cores on a bounded sample: all cores (independent worker processes
                    over envs, which is how the reference would use a host) and one core
-  "other_configs": kernel time + roofline fraction of the other shapes BASELINE.json names (N = 1 only)
+  "other_configs": kernel time + roofline fraction of the other shapes BASELINE.json names, the numpy API, the legacy
+                   symbols and the device rollout
+
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs) as DIR/<name>.npy.  The inputs of the
+warmup and timed steps depend on the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -67,8 +72,12 @@ def parse():
     ap.add_argument("--state", choices=["assembled", "scatter"], default="assembled")
     ap.add_argument("--assemble-steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=226)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline and the other configurations (cpu_baseline, other_configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip other_configs")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall budget of each CPU baseline leg")
     ap.add_argument("--cpu-workers", type=int, default=0, help="worker processes of the all-cores leg (0 = host cores)")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
@@ -250,6 +259,33 @@ def survey_bytes(n_agents, n_g):
     return float(len(n_g)) * n_agents * 821.0 + 8.0 * float(np.sum(n_g))
 
 
+DUMP_BYTES = 48 * 2 ** 20        # --dump-outputs stays well under 64 MB in all
+
+
+def dump_outputs(torch, dirname, sb, last):
+    """Write what the last timed step handed its caller -- obs, reward, done, a_prior -- and the state it left (p, dp)
+    as DIR/<name>.npy, one row per agent in env-major order: obs [rows, D], reward / done [rows], a_prior / p / dp
+    [rows, 2]; p and dp float64, the rest float32.  When every row would not fit in DUMP_BYTES, every array keeps the
+    same fixed, seeded sample of rows.  rows.npy holds the row indices (env * n_agents + agent) either way."""
+    obs, rew, done, pri = last
+    E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
+    p, dp = sb.get_state()                                             # [E, 2, N] float64
+    row_bytes = D * 4 + 4 + 4 + 2 * 4 + 2 * 2 * 8 + 8                 # obs, reward, done, a_prior, p + dp, rows
+    rows = np.arange(E * N)
+    if E * N * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(E * N, DUMP_BYTES // row_bytes, replace=False))
+    idx = torch.from_numpy(rows).to(sb.device)
+    take = lambda t, dt: t.reshape(E * N, -1).index_select(0, idx).to(dt).squeeze(1).cpu().numpy()
+    arrays = {"obs": take(obs, torch.float32), "reward": take(rew, torch.float32), "done": take(done, torch.float32),
+              "p": take(p.transpose(1, 2), torch.float64), "dp": take(dp.transpose(1, 2), torch.float64),
+              "rows": rows.astype(np.float64)}
+    if pri is not None:
+        arrays["a_prior"] = take(pri, torch.float32)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def measure(torch, n_a, E, state, steps, warmup, assemble_steps, seed, env_offset, device, barrier=None, shapes=None):
     """Set up E envs of n_a agents on `device`, bring them to `state`, return a closure that times `steps` steps (and the
     SwarmBatch + inputs for the CPU baseline).  shapes: a results.pkl-layout dict (default: the synthetic shape set)."""
@@ -278,15 +314,14 @@ def measure(torch, n_a, E, state, steps, warmup, assemble_steps, seed, env_offse
         act = pool[0]
 
     def one_step(k, act):
-        if state == "assembled":
-            return sb.step(act)[3]                    # next action := this step's prior (device tensor, no copy)
-        sb.step(pool[k % 8])
-        return None
+        """One step; returns its (obs, reward, done, a_prior).  assembled: next action := a_prior (device tensor, no copy)."""
+        return sb.step(act if state == "assembled" else pool[k % 8])
 
     def timed():
+        """Returns (wall s, kernel ms, outputs of the last timed step)."""
         nonlocal act
         for k in range(warmup):
-            act = one_step(k, act)
+            act = one_step(k, act)[3]
         torch.cuda.synchronize(dev)
         if barrier is not None:
             barrier()
@@ -294,25 +329,34 @@ def measure(torch, n_a, E, state, steps, warmup, assemble_steps, seed, env_offse
         sb.timer_start()                               # HIP events on the stream the kernel is launched on
         t0 = time.perf_counter()
         for k in range(steps):
-            act = one_step(k, act)
+            last = one_step(k, act)
+            act = last[3]
         kernel_ms = sb.timer_stop()                    # synchronizes on the stop event
         torch.cuda.synchronize(dev)
         if barrier is not None:
             barrier()
-        return time.perf_counter() - t0, kernel_ms
+        return time.perf_counter() - t0, kernel_ms, last
 
     def prewarm(ms):
         """Untimed steps of the same loop until `ms` of GPU time have passed (at least 20): the timed region then starts
-        at the clocks the chip holds under this load, whatever the host did before."""
+        at the clocks the chip holds under this load, whatever the host did before.  How many steps that takes varies
+        from run to run, so the state and action from before the prewarm are put back afterwards: the warmup and timed
+        steps then start from the same inputs in every run with the same arguments."""
         nonlocal act
+        p0, dp0 = sb.get_state()
+        act0 = act.clone()                             # act is a step output buffer that the prewarm steps overwrite
         n, k = 0, 0
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         while n < 20 or (time.perf_counter() - t0) * 1e3 < ms:
             for _ in range(20):
-                act = one_step(k, act); k += 1
+                act = one_step(k, act)[3]; k += 1
             n += 20
             torch.cuda.synchronize(dev)
+        sb.set_state(p0, dp0)
+        sb.observe()
+        act = act0
+        torch.cuda.synchronize(dev)
         return n
 
     return sb, sy, r_avoid, timed, prewarm
@@ -521,6 +565,8 @@ def main():
         sys.exit(latency_worker_main())
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr); sys.exit(2)
+    if args.steps < 1:
+        print("bench.py: --steps must be >= 1", file=sys.stderr); sys.exit(2)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))               # this process stays GPU-free; the children are the ranks
 
@@ -552,7 +598,7 @@ def main():
 
     # CPU-baseline workers start now, before this process initialises the GPU (they idle on stdin until the state exists)
     pool_all = pool_one = None
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     if want_cpu:
         pool_one = start_cpu_workers(1)
         pool_all = start_cpu_workers(args.cpu_workers or host_cores())
@@ -579,7 +625,9 @@ def main():
     # The timed region runs FIRST, straight after >= 50 ms of untimed steps of the same loop (steady-state clocks): the
     # CPU baseline keeps the host busy for ~16 s, after which a 3 ms timed region would start from idle GPU clocks.
     n_prewarm = prewarm(args.prewarm_ms)
-    dt, kernel_ms = timed()
+    dt, kernel_ms, last = timed()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, sb, last)
     dt = du.max_over_ranks(dt, device="cpu" if (args.rehearse_one_gpu or world == 1) else sb.device)
     # (RCCL gathers device tensors, gloo host tensors)
     coll_dev = "cpu" if (args.rehearse_one_gpu or world == 1) else sb.device
@@ -597,7 +645,7 @@ def main():
         cpu = cpu_baseline(cpu_state, r_avoid, n_a, pool_all, pool_one, args.cpu_seconds)
 
     others = []
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         from marl_llm_amd.shape_images import unpack_cells_npz
         fig = unpack_cells_npz(os.path.join(ROOT, "tests", "golden", "fig_cells.npz"))
         for (oa, oe, ost, osh, label) in (
@@ -609,7 +657,7 @@ def main():
                 (64, 32768, "assembled", None, "BASELINE config 3's 8-GPU total on ONE GPU")):
             osb, osy, _, otimed, oprewarm = measure(torch, oa, oe, ost, 50, 10, 100, args.seed, 0, f"cuda:{local_rank}", shapes=osh)
             oprewarm(args.prewarm_ms)
-            odt, okms = otimed()
+            odt, okms, _ = otimed()
             us = okms * 1e3 / 50
             b = survey_bytes(oa, osy["n_g"])
             others.append({"workload": f"assembly env, {oa} agents x {oe} envs, {ost} state"

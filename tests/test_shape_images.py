@@ -3,7 +3,7 @@
 
 Pins: (1) tiling / centring / scaling against a plain-loop restatement of assembly_cfg.py:56-134 written here the way the
 reference iterates (tile by tile); (2) the committed cell fixture tests/golden/fig_cells.npz against a fresh conversion of
-the reference's own fig/*.png when /root/reference is present (build container only); (3) the results.pkl layout round
+the reference's own fig/*.png, stored as tests/golden/fig/*.png; (3) the results.pkl layout round
 trip through the env's loader.  The cv2 grayscale + Otsu steps cannot be compared (cv2 is not installed): parity of
 those two calls is unpinned, see the module docstring."""
 import os
@@ -71,11 +71,9 @@ def test_otsu_separates_two_modes():
 
 
 def test_fig_fixture_matches_a_fresh_conversion():
-    """tests/golden/fig_cells.npz == shape_images.process_folder(/root/reference/fig) (build container only)."""
-    if not os.path.isdir("/root/reference/fig"):
-        pytest.skip("reference figures not present (GPU box)")
+    """tests/golden/fig_cells.npz == shape_images.process_folder(tests/golden/fig): the reference's fig/*.png."""
     from marl_llm_amd.shape_images import process_folder
-    fresh, fix = process_folder("/root/reference/fig"), fig_shapes()
+    fresh, fix = process_folder(os.path.join(GOLDEN_DIR, "fig")), fig_shapes()
     assert len(fresh["l_cell"]) == len(fix["l_cell"]) == 7
     for k in range(7):
         assert fresh["l_cell"][k] == fix["l_cell"][k] and np.array_equal(fresh["grid_coords"][k], fix["grid_coords"][k])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU call that regenerates the judged artefacts under gpurun_out/final/ (copy them into profiles/<round>/):
-#   bench_n1.json                 the default `python3 bench.py` line (cpu_baseline on all host cores, other_configs)
+#   bench_n1.json                 the `python3 bench.py --full` line (cpu_baseline on all host cores, other_configs)
 #   kernel_stats.csv              rocprofv3 --kernel-trace --stats of the same command (per-kernel average duration)
 #   kernel_stats_<shape>.csv      the same for every other shape BASELINE.json names (32x1024, 256x4096, 64x32768,
 #                                 scatter state, reference fig shapes through other_configs is covered by bench_n1.json)
@@ -14,7 +14,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/final
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python3 $R/bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -c 600 $OUT/bench_n1.json; echo
 kt() {   # name, bench args...
   local name=$1; shift
