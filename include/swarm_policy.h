@@ -38,9 +38,14 @@ int  swarm_policy_forward(swarm_policy_t *p, const float *obs, int64_t rows, flo
 int  swarm_policy_forward_bf16(swarm_policy_t *p, const void *obs_bf16, int64_t rows, float *act, void *stream);
 
 /* The rollout's exploring actor in one launch (agents.py:82-96, continuous branch): act = clamp(actor(obs) + noise_scale *
- * N(0, 1), -1, 1).  The normals come from a counter-based generator keyed by (seed, step, row, component) -- any row range
- * reproducible on any rank, nothing to store -- evaluated in the kernel's epilogue; noise_scale <= 0: plain forward.
- * `act` may point anywhere on the device (e.g. straight into a replay-buffer slot).  obs_is_bf16 as the two calls above. */
+ * N(0, 1), -1, 1).  The normals come from a counter-based generator keyed by (seed, step, row_offset + row, component),
+ * evaluated in the kernel's epilogue, nothing to store; noise_scale <= 0: plain forward.  row_offset is the global index of
+ * the call's first row: a rank that passes the start of its shard draws exactly the noise the same rows get in one call over
+ * the whole batch, and ranks that share (seed, step) draw different noise.  `act` may point anywhere on the device (e.g.
+ * straight into a replay-buffer slot).  obs_is_bf16 as the two calls above. */
+int  swarm_policy_forward_explore_at(swarm_policy_t *p, const void *obs, int obs_is_bf16, int64_t rows, float *act,
+                                     float noise_scale, uint64_t seed, uint64_t step, uint64_t row_offset, void *stream);
+/* The same with row_offset = 0: the noise is keyed by the call-local row index. */
 int  swarm_policy_forward_explore(swarm_policy_t *p, const void *obs, int obs_is_bf16, int64_t rows, float *act,
                                   float noise_scale, uint64_t seed, uint64_t step, void *stream);
 

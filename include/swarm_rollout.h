@@ -1,0 +1,72 @@
+/* swarm_rollout.h -- C ABI of the device rollout loop: K policy + env steps in one library call.
+ *
+ * The reference's unit of work is the episode (train_assembly.py:81-111): reset, then per step the exploring actor
+ * (agents.py:82-96: an epsilon coin picks a uniform action, otherwise actor(obs) + Gaussian noise), env.step, a buffer push
+ * and the step's reward mean / std.  swarm_rollout enqueues `steps` such steps on one stream and returns: no host
+ * synchronisation, no allocation, no graph capture.  The transitions land in a chained replay ring (the storage of the
+ * Python ChainedReplay): consecutive steps share their observation slot.
+ *
+ * Per step t, with c = (cur + t) % n_slots and n = (c + 1) % n_slots:
+ *   - uniform_steps[t] != 0: act[c] = the uniform actions below; otherwise act[c] = the policy of swarm_policy.h on obs[c]
+ *     (swarm_policy_forward_explore_at with (seed, step0 + t, row_offset));
+ *   - swarm_step(env, act[c]) writes obs[n], rew[c], done[c] and prior[c];
+ *   - reward_stats != NULL: reward_stats[t] = (mean, population std) of rew[c].
+ * The caller advances its own `cur` by `steps` after the call.
+ *
+ * Uniform actions (the epsilon branch, agents.py:89-91), counter-based, for global row g = row_offset + row:
+ *   key  = pmix64(pmix64(seed + 0x9E3779B97F4A7C15) ^ (0xD1B54A32D192ED03 * (step + 1)))   (the policy's noise key)
+ *   ukey = pmix64(key ^ 0x5851F42D4C957F2D)
+ *   h    = pmix64(ukey ^ g)
+ *   act[g][k] = (float)((h >> (40 - 24 k)) & 0xFFFFFF) * 2^-23 - 1,   k = 0, 1    (uniform on [-1, 1), exact in fp32)
+ * with pmix64(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ * (all arithmetic mod 2^64).
+ *
+ * Reward statistics: the env's rewards are in {0, 1} (swarm_env.h), so the kernel counts the ones as an integer c over the
+ * step's R = E * N rows and writes, in fp64, mean m = c / R and std = sqrt((c (1 - m)^2 + (R - c) m^2) / R) -- the two
+ * numbers train_assembly.py:109-110 accumulates; deterministic, the mean exact.  A reward outside {0, 1} is counted as 1 if
+ * nonzero, i.e. the statistics are only meaningful for this env.
+ *
+ * Validation comes first: a call that is rejected (bad handle, ring or shape; see swarm_rollout) enqueues nothing.
+ * Every pointer in the ring and reward_stats is a DEVICE pointer on the handles' device.
+ */
+#ifndef SWARM_ROLLOUT_H
+#define SWARM_ROLLOUT_H
+
+#include <stdint.h>
+
+#include "swarm_env.h"
+#include "swarm_policy.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct swarm_ring {
+    void    *obs;        /* [n_slots][rows][obs_dim] in obs_dtype (SWARM_F32 or SWARM_BF16) */
+    float   *act;        /* [n_slots][rows][2] */
+    float   *rew;        /* [n_slots][rows] */
+    uint8_t *done;       /* [n_slots][rows] */
+    void    *prior;      /* [n_slots][rows][2] in obs_dtype; NULL exactly when the env handle has no prior */
+    int64_t  rows;       /* = E * N of the env handle */
+    int32_t  obs_dim;    /* = swarm_obs_dim(env) = the policy's in_dim */
+    int32_t  obs_dtype;  /* = the env handle's obs dtype; SWARM_F64 handles are rejected */
+    int32_t  n_slots;    /* >= 2 */
+    int32_t  cur;        /* slot that holds the current observation, in [0, n_slots) */
+} swarm_ring_t;
+
+/* Enqueue `steps` steps on `stream` (a hipStream_t; NULL = the default stream; the env handle is pointed at it through
+ * swarm_set_stream).  uniform_steps: HOST [steps], 1 = the uniform (epsilon) branch for that step; NULL = none.
+ * reward_stats: DEVICE [steps][2] doubles, NULL = off.  The env handle must be observed (swarm_observe / swarm_reset) and
+ * the policy's act_dim must be 2.  Returns SWARM_OK, SWARM_ERR_INVALID / SWARM_ERR_STATE (nothing enqueued) or
+ * SWARM_ERR_HIP; the message is in swarm_rollout_last_error. */
+int swarm_rollout(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps,
+                  const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset,
+                  double *reward_stats, void *stream);
+
+/* Message of the last failing swarm_rollout on the calling thread. */
+const char *swarm_rollout_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SWARM_ROLLOUT_H */

@@ -26,6 +26,12 @@ class HostOut(ctypes.Structure):                # include/swarm_env.h swarm_host
                 ("reward", ctypes.POINTER(ctypes.c_double)), ("done", ctypes.POINTER(ctypes.c_uint8))]
 
 
+class SwarmRing(ctypes.Structure):               # include/swarm_rollout.h swarm_ring_t
+    _fields_ = [("obs", ctypes.c_void_p), ("act", ctypes.c_void_p), ("rew", ctypes.c_void_p), ("done", ctypes.c_void_p),
+                ("prior", ctypes.c_void_p), ("rows", ctypes.c_int64), ("obs_dim", ctypes.c_int32), ("obs_dtype", ctypes.c_int32),
+                ("n_slots", ctypes.c_int32), ("cur", ctypes.c_int32)]
+
+
 class SwarmError(RuntimeError):
     pass
 
@@ -39,7 +45,9 @@ BATCHED_SYMBOLS = ("swarm_abi_version", "swarm_default_config", "swarm_create", 
                    "swarm_step_algorithmic_bytes", "swarm_timer_start", "swarm_timer_stop", "swarm_lattice_envs", "swarm_set_shapes", "swarm_reset", "swarm_get_cells", "swarm_get_shape_index", "swarm_metrics", "swarm_rule_action",
                    "swarm_host_outputs", "swarm_observe_host", "swarm_step_host", "swarm_get_llm_action")
 POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_destroy", "swarm_policy_forward", "swarm_policy_forward_bf16",
-                  "swarm_policy_forward_explore", "swarm_policy_set_precision", "swarm_policy_last_error")   # include/swarm_policy.h
+                  "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_set_precision",
+                  "swarm_policy_last_error")   # include/swarm_policy.h
+ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_last_error")   # include/swarm_rollout.h
 LEGACY_SYMBOLS = ("_get_observation", "_get_reward", "_sf_b2b_all", "_get_dist_b2w", "calculateActionPrior",
                   "swarm_legacy_status", "swarm_legacy_last_error")
 
@@ -78,6 +86,13 @@ def load():
     lib.swarm_policy_forward_bf16.argtypes = [vp, vp, ctypes.c_int64, vp, vp]; lib.swarm_policy_forward_bf16.restype = i32
     lib.swarm_policy_forward_explore.argtypes = [vp, vp, i32, ctypes.c_int64, vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp]
     lib.swarm_policy_forward_explore.restype = i32
+    lib.swarm_policy_forward_explore_at.argtypes = [vp, vp, i32, ctypes.c_int64, vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
+                                                    ctypes.c_uint64, vp]
+    lib.swarm_policy_forward_explore_at.restype = i32
+    lib.swarm_rollout.argtypes = [vp, vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, vp, ctypes.c_float, ctypes.c_uint64,
+                                  ctypes.c_uint64, ctypes.c_uint64, vp, vp]
+    lib.swarm_rollout.restype = i32
+    lib.swarm_rollout_last_error.argtypes = []; lib.swarm_rollout_last_error.restype = ctypes.c_char_p
     lib.swarm_policy_set_precision.argtypes = [vp, i32]; lib.swarm_policy_set_precision.restype = i32
     lib.swarm_policy_last_error.argtypes = []; lib.swarm_policy_last_error.restype = ctypes.c_char_p
     lib.swarm_observe.argtypes = [vp, vp]; lib.swarm_observe.restype = i32

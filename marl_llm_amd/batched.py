@@ -119,10 +119,14 @@ class SwarmBatch:
                                                                n_g.ctypes.data_as(ctypes.c_void_p),
                                                                l_cell.ctypes.data_as(ctypes.c_void_p)))
 
-    def reset(self, seed, episode=0, env_offset=0):
-        """Batched device-side reset (swarm_reset): returns the first observation tensor."""
-        self._flip ^= 1
-        obs = self._obs[self._flip]
+    def reset(self, seed, episode=0, env_offset=0, out=None):
+        """Batched device-side reset (swarm_reset): returns the first observation tensor.  out: a caller-owned obs tensor
+        (see _out_ptrs, e.g. a replay-ring slot) written instead of the batch's own buffer."""
+        if out is not None:
+            obs = self._out_ptrs(dict(obs=out))["obs"].view(self.n_env, self.n_agents, self.obs_dim)
+        else:
+            self._flip ^= 1
+            obs = self._obs[self._flip]
         self._sync_stream()
         check(self.lib, self.handle, self.lib.swarm_reset(self.handle, int(seed), int(episode), int(env_offset), _ptr(obs)))
         return obs

@@ -10,7 +10,7 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SRCS = [os.path.join(PKG, "csrc", "swarm_env.hip"), os.path.join(PKG, "csrc", "legacy_shim.hip"),
-        os.path.join(PKG, "csrc", "policy_mlp.hip")]
+        os.path.join(PKG, "csrc", "policy_mlp.hip"), os.path.join(PKG, "csrc", "rollout.hip")]
 INC = os.path.join(ROOT, "include")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libswarmenv.so")
@@ -26,7 +26,8 @@ def hipcc_path():
 def needs_build():
     if not os.path.exists(LIB):
         return True
-    newest = max([os.path.getmtime(s) for s in SRCS] + [os.path.getmtime(os.path.join(INC, h)) for h in ("swarm_env.h", "swarm_policy.h")])
+    headers = [os.path.join(INC, h) for h in ("swarm_env.h", "swarm_policy.h", "swarm_rollout.h")] + [os.path.join(PKG, "csrc", "swarm_internal.h")]
+    newest = max([os.path.getmtime(s) for s in SRCS + headers])
     return os.path.getmtime(LIB) < newest
 
 

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "swarm_policy.h"
+#include "swarm_internal.h"
 
 namespace {
 
@@ -46,17 +47,14 @@ struct MlpParams {
     int in_dim, act_dim;
     long long rows;
     // exploration noise of the rollout (agents.py:93-96: action += scale * N(0, 1); clamp to [-1, 1]), fused into the epilogue:
-    // counter-based generator keyed by (seed, step, row), two normals per hash (Box-Muller)
+    // counter-based generator keyed by (seed, step, row_offset + row), two normals per hash (Box-Muller)
     float noise_scale;
     unsigned long long noise_key;      // mix64(seed, step), host-side
+    unsigned long long row_offset;     // global index of row 0 of this call (a rank's shard of the batch)
 };
 
-__host__ __device__ inline unsigned long long pmix64(unsigned long long z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+using swarm_internal::pmix64;
+using swarm_internal::swarm_noise_key;
 
 __device__ __forceinline__ int feat_of(int mt, int reg, int h) { return 32 * mt + (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
@@ -223,7 +221,7 @@ k_policy_mlp(const MlpParams P, const void *__restrict__ obs_, float *__restrict
                         float *y = act + (size_t)row * P.act_dim;
                         float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                         if (P.noise_scale > 0.0f) {
-                            unsigned long long hk = pmix64(P.noise_key ^ (unsigned long long)row);
+                            unsigned long long hk = pmix64(P.noise_key ^ (P.row_offset + (unsigned long long)row));
 #pragma unroll
                             for (int k = 0; k < 4; k += 2) {
                                 if (k < P.act_dim) {
@@ -275,6 +273,13 @@ struct swarm_policy {
     MlpParams p;
     bool smem_set;
 };
+
+int swarm_internal_policy_info(const swarm_policy_t *p, swarm_policy_info *out)
+{
+    if (!p || !out) return SWARM_POLICY_ERR_INVALID;
+    out->device = p->device; out->in_dim = p->in_dim; out->act_dim = p->act_dim;
+    return SWARM_POLICY_OK;
+}
 
 extern "C" {
 
@@ -358,7 +363,7 @@ int swarm_policy_create(const float *w1, const float *b1, const float *w2, const
     const bf8 *ld = wd + w_elems / 8;
     p->p.l1 = ld; p->p.l2 = ld + n_hid / 8; p->p.l3 = ld + 2 * n_hid / 8; p->p.l4 = ld + 3 * n_hid / 8;
     p->p.b1 = bd; p->p.b2 = bd + kKP; p->p.b3 = bd + 2 * kKP; p->p.b4 = bd + 3 * kKP;
-    p->p.in_dim = in_dim; p->p.act_dim = act_dim; p->p.rows = 0; p->p.noise_scale = 0.0f; p->p.noise_key = 0;
+    p->p.in_dim = in_dim; p->p.act_dim = act_dim; p->p.rows = 0; p->p.noise_scale = 0.0f; p->p.noise_key = 0; p->p.row_offset = 0;
     *out = p;
     return SWARM_POLICY_OK;
 }
@@ -375,7 +380,7 @@ void swarm_policy_destroy(swarm_policy_t *p)
 }
 
 static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int64_t rows, float *act, void *stream,
-                          float noise_scale = 0.0f, uint64_t seed = 0, uint64_t step = 0)
+                          float noise_scale = 0.0f, uint64_t seed = 0, uint64_t step = 0, uint64_t row_offset = 0)
 {
     if (!p || !obs || !act || rows < 0) { g_policy_error = "swarm_policy_forward: bad argument"; return SWARM_POLICY_ERR_INVALID; }
     if (in_bf16 && (p->in_dim & 7)) { g_policy_error = "swarm_policy_forward_bf16: in_dim must be a multiple of 8"; return SWARM_POLICY_ERR_INVALID; }
@@ -386,7 +391,8 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
     MlpParams q = p->p;
     q.rows = rows;
     q.noise_scale = noise_scale > 0.0f ? noise_scale : 0.0f;
-    q.noise_key = pmix64(pmix64(seed + 0x9E3779B97F4A7C15ull) ^ (0xD1B54A32D192ED03ull * (step + 1)));
+    q.noise_key = swarm_noise_key(seed, step);
+    q.row_offset = row_offset;
     // one row tile per wave; the two-tile instantiation (SWARM_POLICY_TPW=2, measurement knob) is slower: 98 vs 87 us on
     // 262144 bf16 rows, 118 vs 106 us on fp32 rows -- one wave per SIMD costs more than the halved LDS reads give back
     int tpw = 1;
@@ -443,6 +449,12 @@ int swarm_policy_forward_explore(swarm_policy_t *p, const void *obs, int obs_is_
                                  float noise_scale, uint64_t seed, uint64_t step, void *stream)
 {
     return policy_forward(p, obs, obs_is_bf16 != 0, rows, act, stream, noise_scale, seed, step);
+}
+
+int swarm_policy_forward_explore_at(swarm_policy_t *p, const void *obs, int obs_is_bf16, int64_t rows, float *act,
+                                    float noise_scale, uint64_t seed, uint64_t step, uint64_t row_offset, void *stream)
+{
+    return policy_forward(p, obs, obs_is_bf16 != 0, rows, act, stream, noise_scale, seed, step, row_offset);
 }
 
 }  // extern "C"

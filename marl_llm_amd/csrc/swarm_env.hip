@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "swarm_env.h"
+#include "swarm_internal.h"
 
 namespace {
 
@@ -2643,6 +2644,14 @@ int launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *ob
 }
 
 }  // namespace
+
+int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out)
+{
+    if (!h || !out) return SWARM_ERR_INVALID;
+    out->device = h->device; out->n_env = h->cfg.n_env; out->n_agents = h->cfg.n_agents; out->obs_dim = h->kp.obs_dim;
+    out->obs_dtype = h->cfg.obs_dtype; out->with_prior = h->cfg.with_prior != 0; out->observed = h->observed;
+    return SWARM_OK;
+}
 
 extern "C" {
 

@@ -10,6 +10,7 @@ ring buffer (train_assembly.py:91-111, maddpg.py:72-87, agents.py:69-96, buffer_
 * `DeviceReplay`  -- the ring buffer of buffer_agent.py:13-128 with one row per (env, agent) transition, as device tensors.
 * `ChainedReplay` -- the same transitions stored as a ring of env steps that share observation rows (half the copy per push).
 * `rollout`       -- obs -> policy -> exploration noise (agents.py:82-96 continuous branch) -> env.step_tensor -> push.
+* `rollout_device`-- the same loop (fused policy, chained ring) as ONE library call per episode: swarm_rollout.
 
 PyTorch is plumbing here (device memory, GEMMs); the environment step is the HIP library.
 """
@@ -168,7 +169,11 @@ class ChainedReplay:
     one observation block instead of two (the observations are ~97 % of a transition's bytes).  The K most recent steps
     are valid; the slot after the newest holds that step's next_obs and is excluded from sampling.  Same transitions as
     DeviceReplay / the reference's buffer (buffer_agent.py:67-128), different storage.  Call `break_chain()` when the
-    next pushed obs is NOT the previous next_obs (after an env reset)."""
+    next pushed obs is NOT the previous next_obs (after an env reset).
+
+    Episode boundaries without loss: `new_chain()` SEALS the ring instead -- the slot that holds the last next_obs of the
+    previous chain is kept, marked as no transition start (sample() and len() skip it), and the new chain starts in the
+    slot after it (rollout_device does this on every reset).  A ring that was never sealed samples exactly as before."""
 
     def __init__(self, n_steps, rows_per_step, obs_dim, act_dim, device, obs_dtype=torch.float32):
         self.K, self.S, self.n = int(n_steps), int(n_steps) + 1, int(rows_per_step)
@@ -178,6 +183,7 @@ class ChainedReplay:
         self.act, self.act_prior = z(act_dim), z(act_dim, obs_dtype)
         self.rew, self.done = z(1), z(1, torch.uint8)
         self.cur, self.count, self._chained = 0, 0, False
+        self._sealed = set()        # slots that hold a chain's last next_obs but start no transition (new_chain)
 
     # zero-copy use (rollout's fused path): the policy writes its action and the env step its outputs straight into the slots
     def begin_step(self, obs):
@@ -190,19 +196,49 @@ class ChainedReplay:
                     next_obs=self.obs[nx])
 
     def end_step(self):
+        self._sealed.discard(self.cur)
         self.cur, self.count, self._chained = (self.cur + 1) % self.S, min(self.count + 1, self.K), True
 
     def __len__(self):
-        return self.count * self.n
+        return (len(self._valid_starts()) if self._sealed else self.count) * self.n
 
     def break_chain(self):
+        """The next begin_step / push copies its obs into slot `cur` instead of assuming the chain holds it.  Hazard: slot
+        `cur` is also the next_obs of the newest stored transition, and that transition stays sampleable -- after an env
+        reset it is paired with the new episode's first observation.  new_chain() keeps it intact."""
         self._chained = False
+
+    def new_chain(self, obs=None):
+        """Start a new chain (an episode boundary) without corrupting the stored ones.  If slot `cur` holds the next_obs of
+        the newest stored transition, that slot is sealed -- kept, marked as no transition start -- and `cur` advances by
+        one (the ring's oldest step is dropped when it is full).  The new chain's first observation goes into the slot
+        `cur` then points at: copied from `obs` [E,N,D] if given, else left to the caller (e.g. an env reset writing into
+        self.obs[self.cur]).  Returns that slot index."""
+        if self.count > 0 and (self.cur - 1) % self.S not in self._sealed:
+            self._sealed.add(self.cur)
+            self.cur, self.count = (self.cur + 1) % self.S, min(self.count + 1, self.K)
+        if obs is not None:
+            self.obs[self.cur].copy_(obs.reshape(self.n, -1))
+        self._chained = True
+        return self.cur
+
+    def _advance(self, steps):
+        """Bookkeeping of `steps` transitions written from slot `cur` on (rollout_device)."""
+        for t in range(min(steps, self.S)):
+            self._sealed.discard((self.cur + t) % self.S)
+        self.cur, self.count, self._chained = (self.cur + steps) % self.S, min(self.count + steps, self.K), True
+
+    def _valid_starts(self):
+        """Slots of the stored transitions, newest first."""
+        w = [(self.cur - 1 - b) % self.S for b in range(self.count)]
+        return [j for j in w if j not in self._sealed]
 
     def push(self, obs, act, rew, next_obs, done, act_prior=None):
         n = self.n
         if obs.shape[0] * obs.shape[1] != n:
             raise ValueError("ChainedReplay takes whole env steps of %d rows" % n)
         c, nx = self.cur, (self.cur + 1) % self.S
+        self._sealed.discard(c)
         if not self._chained:
             self.obs[c] = obs.reshape(n, -1)
         self.obs[nx] = next_obs.reshape(n, -1)
@@ -214,8 +250,15 @@ class ChainedReplay:
 
     def sample(self, batch, generator=None):
         dev = self.obs.device
-        back = torch.randint(0, self.count, (batch,), device=dev, generator=generator)
-        j = (self.cur - 1 - back) % self.S
+        valid = self._valid_starts() if self._sealed else None
+        if valid is None or len(valid) == self.count:
+            back = torch.randint(0, self.count, (batch,), device=dev, generator=generator)
+            j = (self.cur - 1 - back) % self.S
+        else:                                   # sealed slots in the window: uniform over the transition starts only
+            if not valid:
+                raise ValueError("ChainedReplay.sample: no stored transition")
+            pick = torch.randint(0, len(valid), (batch,), device=dev, generator=generator)
+            j = torch.tensor(valid, device=dev)[pick]
         r = torch.randint(0, self.n, (batch,), device=dev, generator=generator)
         jn = (j + 1) % self.S
         return (self.obs[j, r], self.act[j, r], self.rew[j, r], self.obs[jn, r], self.done[j, r].to(torch.float32),
@@ -278,3 +321,101 @@ def rollout(env, policy, steps, obs, replay=None, noise_scale=0.0, epsilon=0.0, 
             rews[t] = rew.mean()
         obs = next_obs
     return obs, rews
+
+
+def _is_view_of(t, slot):
+    return (isinstance(t, torch.Tensor) and t.device == slot.device and t.dtype == slot.dtype and t.data_ptr() == slot.data_ptr()
+            and t.numel() == slot.numel() and t.is_contiguous())
+
+
+@torch.no_grad()
+def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, epsilon=0.0, host_rng=None, seed=0, step0=0,
+                   row_offset=0, reset=None, track_reward=True):
+    """`steps` exploring-actor + env steps in ONE library call (swarm_rollout, include/swarm_rollout.h): the launches are
+    enqueued on torch's current stream and the call returns without a host synchronisation.
+
+    env      : a SwarmBatch, or an AssemblySwarmEnv (agent_strategy 'input', not is_collected) through its backend.
+    policy   : a FusedPolicy (noise keyed by (seed, step0 + t, row_offset + row), swarm_policy.h).
+    replay   : a ChainedReplay (f32 or bf16 obs, the env's dtype), or None: a private two-slot ring kept on the env, whose
+               slots the next rollout_device call on that env reuses (the returned obs then stays valid for one more call).
+    obs / reset: the chain.  `obs` equal to the ring slot replay.obs[replay.cur] (what the previous call returned), or None
+               with a chained ring, continues it.  Any other `obs` [E,N,D], or reset=(seed, episode[, env_offset]) -- the
+               device reset swarm_reset writing straight into the ring (SwarmBatch only; the shape set must be uploaded) --
+               starts a new chain through replay.new_chain(): the stored transitions keep their true next_obs.
+    epsilon  : the coin of agents.py:89-91, drawn on the host before the call, one host_rng.random() per step (the order and
+               count rollout() uses); a coin step takes counter-based uniform actions instead of the policy.
+    Returns (obs [E,N,D] -- the ring slot of the last next_obs --, reward_stats [steps, 2] float64 (mean, population std
+    per step; train_assembly.py:109-110) or None).  On error nothing is enqueued, the ring is unchanged, SwarmError raises."""
+    import ctypes
+    import numpy as np
+    from . import _lib
+    from .batched import SwarmBatch
+    aenv = None
+    if isinstance(env, SwarmBatch):
+        sb = env
+    elif hasattr(env, "_flush_cells") and hasattr(env, "agent_strategy"):
+        if env.agent_strategy != "input" or env.is_collected:
+            raise ValueError("rollout_device drives the env with the policy's actions: needs agent_strategy 'input' and not is_collected")
+        if reset is not None:
+            raise ValueError("reset= needs a SwarmBatch; with an AssemblySwarmEnv call reset_tensor() and pass its obs")
+        aenv, sb = env, env._flush_cells()
+    else:
+        raise TypeError("env must be a SwarmBatch or an AssemblySwarmEnv")
+    if not isinstance(policy, FusedPolicy):
+        raise TypeError("rollout_device needs a FusedPolicy (the device loop runs the fused policy kernel)")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("steps must be >= 0")
+    E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
+    n = E * N
+    if replay is None:
+        replay = getattr(sb, "_rollout_ring", None)
+        if replay is None:
+            replay = sb._rollout_ring = ChainedReplay(1, n, D, 2, sb.device, obs_dtype=sb.obs_dtype)
+    elif not isinstance(replay, ChainedReplay):
+        raise TypeError("replay must be a ChainedReplay (or None)")
+    lib = _lib.load()
+    dt_code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float64: _lib.F64}[replay.obs.dtype]
+    stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
+
+    def call(k, coins, stats):
+        ring = _lib.SwarmRing(replay.obs.data_ptr(), replay.act.data_ptr(), replay.rew.data_ptr(), replay.done.data_ptr(),
+                              replay.act_prior.data_ptr() if sb.with_prior else None, replay.n, replay.obs.shape[-1], dt_code,
+                              replay.S, replay.cur)
+        rc = lib.swarm_rollout(sb.handle, policy.handle, ctypes.byref(ring), k,
+                               coins.ctypes.data_as(ctypes.c_void_p) if coins is not None else None, float(noise_scale),
+                               int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1),
+                               ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, stream)
+        if rc != 0 and not (k == 0 and rc == 3 and reset is not None):    # SWARM_ERR_STATE (not observed): the reset observes
+            raise _lib.SwarmError(f"libswarmenv error {rc}: {lib.swarm_rollout_last_error().decode()}")
+
+    cont = reset is None and (obs is None or _is_view_of(obs, replay.obs[replay.cur]))
+    if cont and obs is None and not replay._chained:
+        raise ValueError("rollout_device: the ring holds no current observation; pass obs or reset=")
+    if not cont and obs is not None and (not isinstance(obs, torch.Tensor) or obs.device != sb.device or obs.dtype != sb.obs_dtype
+                                         or obs.numel() != n * D):
+        raise ValueError(f"obs must be a {sb.obs_dtype} tensor [{E}, {N}, {D}] on {sb.device}")
+    call(0, None, None)                     # validation only: a rejected call raises before the ring is touched
+    if not cont:
+        kept = (replay.cur, replay.count, replay._chained, set(replay._sealed))
+        try:
+            if reset is not None:
+                r = tuple(reset)
+                slot = replay.new_chain()
+                sb.reset(r[0], r[1], r[2] if len(r) > 2 else 0, out=replay.obs[slot])
+            else:
+                replay.new_chain(obs)
+        except Exception:
+            replay.cur, replay.count, replay._chained, replay._sealed = kept
+            raise
+    coins = None
+    if epsilon > 0:
+        coin = host_rng if host_rng is not None else np.random
+        coins = np.array([coin.random() < epsilon for _ in range(steps)], dtype=np.uint8)          # agents.py:89
+    stats = torch.empty((steps, 2), dtype=torch.float64, device=sb.device) if track_reward else None
+    call(steps, coins, stats)
+    replay._advance(steps)
+    if aenv is not None:
+        aenv.simulation_time += aenv.dt * steps
+        aenv._state_version += 1
+    return replay.obs[replay.cur].view(E, N, D), stats
