@@ -170,9 +170,10 @@ class Oracle:
                     done=np.zeros((1, n_a), bool))
 
     def step_batch(self, p, dp, a, grid, n_g, l_cell, neighbor_index, r_avoid, d_sen=D_SEN, boundary=BOUNDARY,
-                   is_boundary=True, with_self=True):
+                   is_boundary=True, with_self=True, indices=False):
         """E envs: p, dp, a [E,2,N]; grid [E,2,NG_MAX]; n_g, l_cell [E]; neighbor_index [E,N,6].
-        Advances p, dp, neighbor_index IN PLACE (timing leg), returns (obs[E,od,N], reward[E,N], a_prior[E,2,N])."""
+        Advances p, dp, neighbor_index IN PLACE (timing leg), returns (obs[E,od,N], reward[E,N], a_prior[E,2,N]);
+        indices=True appends (in_flags[E,N], sensed_index[E,N,G_MAX], occupied_index[E,N,OCC_MAX])."""
         E, _, n_a = p.shape
         od = obs_dim(with_self)
         obs = np.zeros((E, od, n_a)); rew = np.zeros((E, n_a)); ap = np.zeros((E, 2, n_a))
@@ -189,7 +190,7 @@ class Oracle:
                                 ctypes.c_double(VEL_MAX), ctypes.c_double(DT), ctypes.c_int(TOPO), ctypes.c_int(G_MAX),
                                 ctypes.c_int(OCC_MAX), ctypes.c_int(n_a), ctypes.c_int(od),
                                 ctypes.c_int(int(is_boundary)), _b(co), _b(cr))
-        return obs, rew, ap
+        return (obs, rew, ap, inf, sen, occ) if indices else (obs, rew, ap)
 
 
 class RefLib:

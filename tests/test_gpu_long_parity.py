@@ -1,0 +1,347 @@
+"""Long free-running trajectories, whole benchmarked batches and lattice-mode switches held to the oracle.
+
+test_gpu_parity.py checks the HIP step on short runs (<= 8 steps) and on samples of a synthetic state.  This module checks
+the state bench.py actually times and the paths that only show after hundreds of steps: assembled swarms (contacts carried
+between launches in sf_next, saturated occupied filters, many agents near the 0.05 reward threshold and the in-shape
+cut-off), the first agent count of every padded instantiation, the generic kernel at full size, and a batch whose kernel
+changes mid-trajectory.  The oracle runs on a thread pool (helpers.ThreadedOracle).
+
+Tolerances are test_gpu_parity.py's, unchanged: state, reward, done and every index / flag array bit-exact; obs and a_prior
+bit-exact with obs_dtype=float64 and equal to the oracle's double rounded once to float32 in the product dtype.  As in
+bench.py, the action of every step after the first (zero) one is the device's a_prior of the step before; the oracle gets
+the same float32 values, so its prior has to match first.
+
+A mismatch names the step, the output and the envs.  With SWARM_PARITY_DUMP=<dir> set, the first failing env's pre-step
+inputs (p, dp, neighbor_index, action, cells, n_g, l_cell, flags) are also written to <dir>/<case>_t<step>_e<env>.npz for
+arbitration against the oracle and the reference library on the CPU.
+"""
+import os
+
+import numpy as np
+import pytest
+
+from helpers import ThreadedOracle, fig_shapes
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+IDX = ("neighbor_index", "in_flags", "sensed_index", "occupied_index")
+SIZE_A, D_SEN = 0.035, 0.4
+IDX_EVERY = 25            # lockstep runs compare the four index arrays every IDX_EVERY steps and on the last step
+CHUNK = 512               # whole-batch checks copy outputs to the host this many envs at a time
+
+
+class Mismatch(AssertionError):
+    def __init__(self, what, envs):
+        super().__init__(f"{what}: {len(envs)} env(s) differ, first {list(envs[:8])}")
+        self.envs = envs
+
+
+def _same(dev, ref, what, env0=0):
+    """Exact equality of [E, ...] arrays; on failure name the envs (offset by env0) that differ."""
+    if dev.shape == ref.shape and np.array_equal(dev, ref):
+        return
+    if dev.shape != ref.shape:
+        raise AssertionError(f"{what}: shape {dev.shape} != {ref.shape}")
+    bad = np.nonzero(~(dev == ref).reshape(len(dev), -1).all(1))[0] + env0
+    raise Mismatch(what, bad)
+
+
+def _rows(x):
+    """oracle [E, D, N] -> device layout [E, N, D]."""
+    return np.ascontiguousarray(np.swapaxes(x, 1, 2))
+
+
+def _host(t):
+    return t.cpu().numpy()
+
+
+def _batch(n_env, n_a, sy, shapes, **kw):
+    from marl_llm_amd.batched import SwarmBatch
+    from marl_llm_amd.shapes import r_avoid_for
+    ra = r_avoid_for(n_a, shapes)
+    sb = SwarmBatch(n_env=n_env, n_agents=n_a, n_cells_max=sy["cells"].shape[2], r_avoid=ra, **kw)
+    sb.set_cells(sy["cells"], sy["n_g"], sy["l_cell"])
+    sb.set_state(sy["p"], sy["dp"])
+    return sb, ra
+
+
+def _dump(tag, t, e, pre, to, flags):
+    d = os.environ.get("SWARM_PARITY_DUMP")
+    if not d:
+        return
+    os.makedirs(d, exist_ok=True)
+    np.savez(os.path.join(d, f"{tag}_t{t}_e{e}.npz"), p=pre["p"][e], dp=pre["dp"][e], neighbor_index=pre["nei"][e],
+             action=pre["a"][e], cells=to.cells[e][:, : to.n_g[e]], n_g=to.n_g[e], l_cell=to.l_cell[e],
+             r_avoid=to.r_avoid, is_boundary=to.is_boundary, with_self=to.with_self, debug_flags=flags)
+
+
+def _compare_step(out, o, f32, with_idx, idx=None, env0=0):
+    """One step's device outputs (host copies: p, dp, obs, reward, done, prior) against the oracle's."""
+    cast = (lambda x: x.astype(np.float32)) if f32 else (lambda x: x)
+    _same(out["p"], o["p"], "p", env0)
+    _same(out["dp"], o["dp"], "dp", env0)
+    _same(out["reward"].astype(np.float64), o["reward"], "reward", env0)
+    _same(out["done"], np.zeros_like(out["done"]), "done", env0)
+    _same(out["obs"], cast(_rows(o["obs"])), "obs", env0)
+    _same(out["prior"], cast(_rows(o["a_prior"])), "a_prior", env0)
+    if with_idx:
+        for k in IDX:
+            _same(idx[k], o[k], k, env0)
+
+
+class Lockstep:
+    """A SwarmBatch and the threaded oracle run side by side from the same state, prior-policy actions."""
+
+    def __init__(self, oracle, sb, sy, ra, tag, is_boundary=True, with_self=True, flags=0):
+        self.sb, self.tag, self.flags = sb, tag, flags
+        self.f32 = sb.obs_dtype == torch.float32
+        self.to = ThreadedOracle(oracle, sy["cells"], sy["n_g"], sy["l_cell"], ra, is_boundary=is_boundary, with_self=with_self)
+        self.p, self.dp = sy["p"].copy(), sy["dp"].copy()
+        self.act = torch.zeros((sb.n_env, sb.n_agents, 2), dtype=torch.float32, device=sb.device)    # bench: zero first action
+        self.t = 0
+        self.max_contacts = 0          # most colliding pairs (centre distance < 2 size_a) seen in any one step
+        self.nei = None
+        self.observe()
+
+    def observe(self):
+        """sb.observe() (needed after set_state / set_cells) against the oracle's observation of the same state."""
+        obs = _host(self.sb.observe())
+        o = self.to.observe(self.p, self.dp)
+        cast = (lambda x: x.astype(np.float32)) if self.f32 else (lambda x: x)
+        _same(obs, cast(_rows(o["obs"])), f"{self.tag} observe t={self.t}: obs")
+        idx = {k: _host(v) for k, v in self.sb.indices().items()}
+        for k in IDX:
+            _same(idx[k], o[k], f"{self.tag} observe t={self.t}: {k}")
+        if self.nei is not None:       # the list depends on the agents only: the last step's, recomputed
+            _same(o["neighbor_index"], self.nei, f"{self.tag} observe t={self.t}: neighbor_index vs the last step's")
+        self.nei = o["neighbor_index"]
+        self.act = self.act.clone()    # the step writes its prior into a ping-pong buffer that observe() has shifted
+
+    def set_cells(self, cells, n_g, l_cell, env_begin):
+        self.sb.set_cells(cells, n_g, l_cell, env_begin=env_begin)
+        c = self.to.cells.copy(); g = self.to.n_g.copy(); lc = self.to.l_cell.copy()
+        c[env_begin: env_begin + len(n_g)] = cells; g[env_begin: env_begin + len(n_g)] = n_g
+        lc[env_begin: env_begin + len(n_g)] = l_cell
+        self.to.set_cells(c, g, lc)
+
+    def run(self, steps):
+        for s in range(steps):
+            self.t += 1
+            a = np.swapaxes(_host(self.act), 1, 2).astype(np.float64)              # [E,N,2] f32 -> [E,2,N] f64, exact
+            pre = dict(p=self.p, dp=self.dp, nei=self.nei, a=a)
+            obs, rew, done, pri = self.sb.step(self.act)
+            o = self.to.step(self.p, self.dp, a, self.nei)
+            pg, dpg = self.sb.get_state()
+            out = dict(p=_host(pg), dp=_host(dpg), obs=_host(obs), reward=_host(rew), done=_host(done), prior=_host(pri))
+            with_idx = self.t % IDX_EVERY == 0 or s == steps - 1
+            idx = {k: _host(v) for k, v in self.sb.indices().items()} if with_idx else None
+            try:
+                _compare_step(out, o, self.f32, with_idx, idx)
+            except Mismatch as ex:
+                _dump(self.tag, self.t, int(ex.envs[0]), pre, self.to, self.flags)
+                raise AssertionError(f"{self.tag} step {self.t}: {ex}") from None
+            self.p, self.dp, self.nei = o["p"], o["dp"], o["neighbor_index"]
+            self.act = pri
+            if self.to.is_boundary:
+                d = self.p[:, :, :, None] - self.p[:, :, None, :]
+                dc = np.sqrt(d[:, 0] ** 2 + d[:, 1] ** 2)
+                self.max_contacts = max(self.max_contacts, int(((dc < 2 * SIZE_A).sum() - dc[..., 0].size) // 2))
+            self.last = o
+
+    def close(self):
+        self.to.close()
+        self.sb.close()
+
+
+def _synth(n_env, n_a, shapes, seed, frac):
+    from marl_llm_amd.synth import synthetic_batch
+    return synthetic_batch(n_env, n_a, shapes, seed=seed, assembled_fraction=frac)
+
+
+# (id, N, envs, steps, shape set, synthetic seed, assembled fraction, SwarmBatch kwargs)
+LONG = [
+    ("headline", 64, 48, 800, "synthetic", 226, 0.0, {}),        # envs 0-47 of bench.py's seed-226 batch, its recipe
+    ("fig", 64, 24, 800, "fig", 226, 0.0, {}),                   # the reference's own tiled shapes (64-bit row masks)
+    ("n32_half", 32, 32, 400, "synthetic", 32, 0.3, {}),
+    ("n32_full", 32, 32, 400, "synthetic", 32, 0.3, {"debug_flags": 4}),
+    ("n128", 128, 8, 300, "synthetic", 128, 0.3, {}),
+    ("n256", 256, 4, 300, "synthetic", 256, 0.3, {}),
+    ("n9", 9, 6, 200, "synthetic", 9, 0.5, {}),                  # first agent count of each padded instantiation
+    ("n17", 17, 6, 200, "synthetic", 17, 0.5, {}),
+    ("n33", 33, 6, 200, "synthetic", 33, 0.5, {}),
+    ("n65", 65, 6, 200, "synthetic", 65, 0.5, {}),
+    ("n129", 129, 3, 200, "synthetic", 129, 0.5, {}),
+    ("periodic", 64, 12, 300, "synthetic", 641, 0.5, {"is_boundary": False}),
+    ("noself", 30, 12, 300, "synthetic", 30, 0.5, {"with_self": False}),
+    ("generic", 64, 16, 400, "synthetic", 642, 0.3, {"debug_flags": 2}),
+    ("f64", 64, 8, 300, "synthetic", 643, 0.3, {"obs_dtype": "f64"}),
+]
+
+
+@pytest.mark.parametrize("tag,n_a,n_env,steps,shape_set,seed,frac,kw", LONG, ids=[c[0] for c in LONG])
+def test_long_lockstep(oracle, shapes, tag, n_a, n_env, steps, shape_set, seed, frac, kw):
+    """Hundreds of free-running prior-policy steps, device and oracle in lockstep: p, dp, obs, reward, a_prior and done every
+    step, the four index arrays every 25 steps and on the last one."""
+    kw = dict(kw)
+    if kw.get("obs_dtype") == "f64":
+        kw["obs_dtype"] = torch.float64
+    sh = fig_shapes() if shape_set == "fig" else shapes
+    sy = _synth(n_env, n_a, sh, seed, frac)
+    sb, ra = _batch(n_env, n_a, sy, sh, **kw)
+    assert sb.lattice_envs() == (0 if kw.get("debug_flags", 0) & 2 else n_env)
+    ls = Lockstep(oracle, sb, sy, ra, tag, is_boundary=kw.get("is_boundary", True), with_self=kw.get("with_self", True),
+                  flags=kw.get("debug_flags", 0))
+    try:
+        ls.run(steps)
+        inf = ls.last["in_flags"]
+        if tag in ("headline", "fig"):         # the run reached the crowded state this module is about
+            assert inf.mean() >= 0.5, inf.mean()
+            assert (ls.last["reward"] == 1).any()
+            assert ls.max_contacts > 0
+        else:
+            assert inf.any()
+    finally:
+        ls.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Whole batches at the benchmarked state
+# ------------------------------------------------------------------------------------------------------------------------
+def _check_whole_batch(sb, to, pre, outs, f32, tag, t):
+    """Every env of one step, CHUNK envs at a time: pre = the step's inputs (host), outs = its device outputs."""
+    obs, rew, done, pri, p, dp = outs
+    idx = sb.indices()
+    E = sb.n_env
+    for b in range(0, E, CHUNK):
+        e = min(E, b + CHUNK)
+        envs = np.arange(b, e)
+        o = to.step(pre["p"][b:e], pre["dp"][b:e], pre["a"][b:e], pre["nei"][b:e], envs=envs)
+        out = dict(p=_host(p[b:e]), dp=_host(dp[b:e]), obs=_host(obs[b:e]), reward=_host(rew[b:e]), done=_host(done[b:e]),
+                   prior=_host(pri[b:e]))
+        ix = {k: _host(idx[k][b:e]) for k in IDX}
+        try:
+            _compare_step(out, o, f32, True, ix, env0=b)
+        except Mismatch as ex:
+            sub = {k: v[b:e] for k, v in pre.items()}
+            _dump(tag, t, int(ex.envs[0]) - b, sub, _Sub(to, envs), sb.cfg.debug_flags)
+            raise AssertionError(f"{tag} step {t}: {ex}") from None
+        del o, out, ix
+    return int(_host(idx["in_flags"]).sum())
+
+
+class _Sub:
+    """The cells of envs `envs` of a ThreadedOracle, for _dump."""
+
+    def __init__(self, to, envs):
+        self.cells, self.n_g, self.l_cell = to.cells[envs], to.n_g[envs], to.l_cell[envs]
+        self.r_avoid, self.is_boundary, self.with_self = to.r_avoid, to.is_boundary, to.with_self
+
+
+# (id, N, envs, env_offset, shape set, SwarmBatch kwargs, checked steps)
+WHOLE = [
+    ("64x4096", 64, 4096, 0, "synthetic", {}, (101, 320)),
+    ("64x4096_generic", 64, 4096, 0, "synthetic", {"debug_flags": 2}, (101,)),
+    ("64x4096_fig", 64, 4096, 0, "fig", {}, (320,)),
+    ("32x1024", 32, 1024, 0, "synthetic", {}, (320,)),
+    ("256x4096", 256, 4096, 0, "synthetic", {}, (101,)),
+    ("64x4096_shard3", 64, 4096, 3 * 4096, "synthetic", {}, (101,)),
+]
+
+
+@pytest.mark.parametrize("tag,n_a,n_env,env_offset,shape_set,kw,checks", WHOLE, ids=[c[0] for c in WHOLE])
+def test_whole_batch_at_bench_state(oracle, shapes, tag, n_a, n_env, env_offset, shape_set, kw, checks):
+    """bench.py's measure() recipe (bench.py:289-318, restated): seed-226 synthetic batch, observe, 100 prior-policy steps from
+    a zero action, then the prewarm detour (bench.py:340-360: more steps, set_state + observe back to the saved state, saved
+    action) before the 20 warmup and 200 timed steps.  On each checked step (101: the first warmup step; 320: the last timed
+    one, the step --dump-outputs writes) EVERY env is compared with one oracle step from the device's pre-step inputs.  A
+    second detour sits right before step 320, so the check there follows a restore as well."""
+    from marl_llm_amd.synth import synthetic_batch
+    sh = fig_shapes() if shape_set == "fig" else shapes
+    sy = synthetic_batch(n_env, n_a, sh, seed=226, env_offset=env_offset)
+    sb, ra = _batch(n_env, n_a, sy, sh, **kw)
+    assert sb.lattice_envs() == (0 if kw.get("debug_flags", 0) & 2 else n_env)
+    sb.observe()
+    to = ThreadedOracle(oracle, sy["cells"], sy["n_g"], sy["l_cell"], ra)
+    act = torch.zeros((n_env, n_a, 2), dtype=torch.float32, device=sb.device)
+    detours = {100, 319}
+    try:
+        for t in range(1, max(checks) + 1):
+            pre = None
+            if t in checks:                    # the step's inputs, taken BEFORE any detour: the restore must not show
+                p0, dp0 = sb.get_state()
+                pre = dict(p=_host(p0), dp=_host(dp0), nei=_host(sb.indices(False, False)["neighbor_index"]),
+                           a=np.swapaxes(_host(act), 1, 2).astype(np.float64))
+            if t - 1 in detours:
+                p0, dp0 = sb.get_state()
+                act0 = act.clone()
+                for _ in range(20):
+                    act = sb.step(act)[3]
+                sb.set_state(p0, dp0)
+                sb.observe()
+                act = act0
+                del p0, dp0
+            obs, rew, done, pri = sb.step(act)
+            if pre is not None:
+                p, dp = sb.get_state()
+                in_shape = _check_whole_batch(sb, to, pre, (obs, rew, done, pri, p, dp), True, tag, t)
+                assert in_shape > 0
+                del pre, p, dp
+            act = pri
+    finally:
+        to.close()
+        sb.close()
+    torch.cuda.empty_cache()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Lattice mode switching mid-trajectory
+# ------------------------------------------------------------------------------------------------------------------------
+def _lat_nrs(cells, n_g, d_sen=D_SEN):
+    """set_lattice_mode's window-row count for a batch of lattice cell sets (swarm_env.hip: detect_lattice fits the step as
+    the closest pair of consecutive cells, stored as float; swarm_set_cells takes R = d_sen / step; set_lattice_mode takes
+    floor(2 (max R + 0.01)) + 1 in float).  The lattice kernel runs while this is <= 15."""
+    rmax = np.float32(0)
+    for c, n in zip(cells, n_g):
+        d = np.diff(c[:, :n], axis=1)
+        step = np.float32(np.sqrt(np.min(d[0] * d[0] + d[1] * d[1])))
+        rmax = max(rmax, np.float32(d_sen / np.float64(step)))
+    return int(np.floor(np.float32(2) * (rmax + np.float32(0.01)))) + 1
+
+
+def test_lattice_mode_switches_mid_trajectory(oracle, shapes):
+    """One env's cells replaced by an off-lattice copy demotes the whole batch to the generic kernel, restoring them promotes
+    it back, and a lattice spacing on either side of the 15-window-row cap keeps or leaves the lattice kernel: the
+    trajectory stays oracle-exact across every switch."""
+    n_a, E, seg = 64, 16, 60
+    sy = _synth(E, n_a, shapes, 5150, 0.5)
+    sb, ra = _batch(E, n_a, sy, shapes)
+    ls = Lockstep(oracle, sb, sy, ra, "switch")
+    cells, n_g, l_cell = sy["cells"], sy["n_g"], sy["l_cell"]
+    try:
+        assert sb.lattice_envs() == E and _lat_nrs(cells, n_g) <= 15
+        ls.run(seg)
+        jit = cells[5:6].copy()
+        jit[0, :, : n_g[5]] += np.random.default_rng(5).normal(0, 0.004, (2, n_g[5]))
+        ls.set_cells(jit, n_g[5:6], l_cell[5:6], env_begin=5)
+        assert sb.lattice_envs() == E - 1          # one env off the lattice: the whole batch runs the generic kernel
+        ls.observe()
+        ls.run(seg)
+        ls.set_cells(cells[5:6], n_g[5:6], l_cell[5:6], env_begin=5)
+        assert sb.lattice_envs() == E
+        ls.observe()
+        ls.run(seg)
+        k = 9                                      # one env's lattice scaled about its centroid: spacing 0.054, then 0.053
+        g = cells[k, :, : n_g[k]]
+        ctr = g.mean(axis=1, keepdims=True)
+        for spacing, nrs in ((0.054, 15), (0.053, 16)):
+            sc = np.zeros_like(cells[k:k + 1])
+            sc[0, :, : n_g[k]] = ctr + (g - ctr) * (spacing / l_cell[k])
+            ls.set_cells(sc, n_g[k:k + 1], [spacing], env_begin=k)
+            assert sb.lattice_envs() == E          # still a lattice; only the window-row count decides the kernel
+            assert _lat_nrs(ls.to.cells, ls.to.n_g) == nrs
+            ls.observe()
+            ls.run(seg)
+        assert ls.last["in_flags"].any() and ls.max_contacts > 0
+    finally:
+        ls.close()

@@ -636,3 +636,98 @@ def test_half_occupied_geometry_equals_the_full_one(oracle, shapes, n_a, n_env, 
         assert np.array_equal(rews[-1][e].cpu().numpy().astype(np.float64), s["reward"][0])
         assert np.array_equal(pri[e].cpu().numpy(), _to_rows(s["a_prior"]))
         assert np.array_equal(sen[e].cpu().numpy(), s["sensed_index"]) and np.array_equal(occ[e].cpu().numpy(), s["occupied_index"])
+
+
+def _reward_threshold_case(oracle, rng, shapes, n_a, ra, d_sen=0.4):
+    """One env whose in-shape agents sit 1e-12 .. 1e-9 from the reward's `|v| < 0.05` decision: starting at a cell centre and
+    half a cell away with different oracle rewards, each is bisected along that segment down to adjacent doubles, then moved
+    that far off the crossing to either side at random -- far inside the fp32 sums' error (~1e-7), far outside the fp64
+    path's documented cos() deviation (~1e-16, test_gpu_parity.py docstring).  They start at least d_sen + r_avoid apart (nothing sensed, occupied or colliding in common,
+    so they are bisected together); the other agents wait in two arena corners out of everyone's range.  Zero velocity: a
+    zero-action step leaves every position as it is, so the step's reward is decided at these positions.
+    Returns (p, g, l_cell, number of agents whose crossing is the |v| test itself: same in-flag and sensed list both sides)."""
+    s = int(rng.integers(0, len(shapes["l_cell"])))
+    l_cell = float(shapes["l_cell"][s])
+    th = rng.uniform(-np.pi, np.pi)
+    rot = np.array([[np.cos(th), np.sin(th)], [-np.sin(th), np.cos(th)]])
+    g = shapes["grid_coords"][s].T
+    g = np.ascontiguousarray(rot @ (g - g.mean(axis=1, keepdims=True)))
+    cand = []
+    for c in rng.permutation(g.shape[1]):
+        if all(np.hypot(*(g[:, c] - g[:, k])) > d_sen + ra for k in cand):
+            cand.append(c)
+    park = np.array([(x, y) for x in np.arange(1.8, 2.35, 0.1) for y in np.arange(1.8, 2.35, 0.1)]).T
+    park = np.concatenate([park, -park], axis=1)
+    K = min(len(cand), n_a)
+    p = np.zeros((2, n_a))
+    p[:, :K] = g[:, cand[:K]]
+    p[:, K:] = park[:, : n_a - K]
+    assert np.hypot(*g).max() < 1.6 and n_a - K <= park.shape[1]       # corners >= 0.95 from every cell
+    zero = np.zeros((2, n_a))
+
+    def reward(q):
+        o = oracle.get_observation(q, zero, g, l_cell, ra, d_sen=d_sen)
+        return oracle.get_reward(q, g, o["neighbor_index"], o["in_flags"], o["sensed_index"], ra, d_sen=d_sen)[0], o
+
+    r0, o0 = reward(p)
+    lo, hi = p.copy(), p.copy()
+    live = np.zeros(n_a, bool)
+    for a in rng.permutation(8) * (np.pi / 4):
+        q = p.copy()
+        q[:, :K] += 0.5 * l_cell * np.array([[np.cos(a)], [np.sin(a)]])
+        r, o = reward(q)
+        new = (np.arange(n_a) < K) & ~live & (r != r0) & (o["in_flags"] == 1) & (o0["in_flags"] == 1)
+        hi[:, new] = q[:, new]
+        live |= new
+    u = hi - lo
+    u /= np.where(live, np.hypot(*u), 1.0)
+    for _ in range(64):
+        mid = lo.copy()
+        mid[:, live] = lo[:, live] + 0.5 * (hi[:, live] - lo[:, live])
+        r, _ = reward(mid)
+        same = r == r0
+        lo[:, live & same] = mid[:, live & same]
+        hi[:, live & ~same] = mid[:, live & ~same]
+    r_lo, o_lo = reward(lo)
+    r_hi, o_hi = reward(hi)
+    assert (r_lo[live] != r_hi[live]).all()
+    exact = live & (o_lo["in_flags"] == o_hi["in_flags"]) & (o_lo["sensed_index"] == o_hi["sensed_index"]).all(axis=1)
+    side = rng.uniform(size=n_a) < 0.5
+    off = u * 10.0 ** rng.uniform(-12, -9, n_a)
+    p = np.where(live, np.where(side, hi + off, lo - off), lo)
+    return np.ascontiguousarray(p), g, l_cell, int(exact.sum())
+
+
+@pytest.mark.parametrize("n_a,flags", [(64, 0), (64, 1), (64, 2), (32, 0)], ids=["64-lattice", "64-forced", "64-generic", "32-lattice"])
+def test_reward_threshold_placements(oracle, shapes, n_a, flags):
+    """Agents placed on the reward's 0.05 threshold to within an ulp: the fp32 sums of the lattice path and of the generic
+    scan can only decide outside their guard bands, so every one of these rewards must come out of the exact fp64 path and
+    equal the oracle's (a guard band that is missing or too narrow lets the fp32 verdict through for about half of them)."""
+    from marl_llm_amd.shapes import r_avoid_for
+    rng = np.random.default_rng(900 + n_a)
+    ra = r_avoid_for(n_a, shapes)
+    E = 48
+    cases = [_reward_threshold_case(oracle, rng, shapes, n_a, ra) for _ in range(E)]
+    assert sum(c[3] for c in cases) >= 16           # agents whose crossing is the |v| test itself (not in-flag / list)
+    cells, n_g = _pad_cells([c[1] for c in cases], max(c[1].shape[1] for c in cases))
+    sb = _batch(n_env=E, n_agents=n_a, n_cells_max=cells.shape[2], r_avoid=ra, obs_dtype=torch.float64, debug_flags=flags)
+    sb.set_cells(cells, n_g, [c[2] for c in cases])
+    assert sb.lattice_envs() == (0 if flags & 2 else E)
+    p = np.stack([c[0] for c in cases])
+    sb.set_state(p, np.zeros_like(p))
+    sb.observe()
+    nei = sb.indices(False, False)["neighbor_index"].cpu().numpy()
+    obs, rew, done, pri = sb.step(torch.zeros((E, n_a, 2), dtype=torch.float64, device=sb.device))
+    pg = sb.get_state()[0].cpu().numpy()
+    idx = sb.indices()
+    assert np.array_equal(pg, p)                         # nothing moved: the reward was decided at the placed positions
+    ones = 0
+    for e, (pe, g, l_cell, _) in enumerate(cases):
+        s = oracle.step(pe, np.zeros_like(pe), np.zeros_like(pe), g, nei[e], l_cell, ra)
+        assert np.array_equal(rew[e].cpu().numpy().astype(np.float64), s["reward"][0]), e
+        assert np.array_equal(obs[e].cpu().numpy(), _to_rows(s["obs"])), e
+        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
+            assert np.array_equal(idx[k][e].cpu().numpy(), s[k]), (e, k)
+        ones += int(s["reward"].sum())
+    assert ones > 0
+    sb.close()
