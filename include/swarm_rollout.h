@@ -63,7 +63,25 @@ int swarm_rollout(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *rin
                   const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset,
                   double *reward_stats, void *stream);
 
-/* Message of the last failing swarm_rollout on the calling thread. */
+/* Expert rollouts (the reference's collect_expert_data.py: agent_strategy 'rule' or 'llm' with is_collected, the data of
+ * train_assembly_airl.py).  Enqueues `steps` expert steps on `stream`; per step t, with c and n as above:
+ *   - SWARM_EXPERT_RULE: the rule-based expert of assembly.py:530-601 on the current state, in fp64 (the action of
+ *     swarm_rule_action, bit for bit); the env steps with that fp64 action (SWARM_F64) and act[c] = its f32 rounding.  The
+ *     trajectory is bit-identical to the eager loop `u = swarm_rule_action(); swarm_step(u, SWARM_F64)`.
+ *   - SWARM_EXPERT_LLM: the env steps with action = NULL (the library's prior-policy twin; the handle must be created with
+ *     llm_action) and act[c] = that applied action rounded to f32 (the `is_collected` fifth return value of the eager path).
+ *   - both: swarm_step writes obs[n], rew[c], done[c] and prior[c]; reward_stats as in swarm_rollout.
+ * Why f32 rows suffice: ReplayBufferExpert.sample hands its rows out through torch.Tensor, i.e. as fp32, and the step's f32
+ * observation is the f32 rounding of the fp64 one (the env's parity contract), so AIRL sees the same bits as from the
+ * reference's fp64 buffer.
+ * Checks as swarm_rollout minus the policy's; SWARM_EXPERT_RULE also needs num_obs_grid_max <= 128 (as swarm_rule_action).
+ * The first RULE call allocates the handle's list and fp64 action scratch (once); later calls allocate nothing.  A rejected
+ * call enqueues nothing; the message is in swarm_rollout_last_error. */
+enum { SWARM_EXPERT_RULE = 0, SWARM_EXPERT_LLM = 1 };
+int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t steps, int32_t source, double *reward_stats,
+                         void *stream);
+
+/* Message of the last failing swarm_rollout / swarm_rollout_expert on the calling thread. */
 const char *swarm_rollout_last_error(void);
 
 #ifdef __cplusplus

@@ -6,6 +6,7 @@ import os
 from .build import LIB
 
 F32, F64, BF16 = 0, 1, 2
+EXPERT_RULE, EXPERT_LLM = 0, 1      # include/swarm_rollout.h swarm_rollout_expert sources
 
 
 class SwarmConfig(ctypes.Structure):
@@ -47,7 +48,7 @@ BATCHED_SYMBOLS = ("swarm_abi_version", "swarm_default_config", "swarm_create", 
 POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_destroy", "swarm_policy_forward", "swarm_policy_forward_bf16",
                   "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_set_precision",
                   "swarm_policy_last_error")   # include/swarm_policy.h
-ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_last_error")   # include/swarm_rollout.h
+ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_expert", "swarm_rollout_last_error")   # include/swarm_rollout.h
 LEGACY_SYMBOLS = ("_get_observation", "_get_reward", "_sf_b2b_all", "_get_dist_b2w", "calculateActionPrior",
                   "swarm_legacy_status", "swarm_legacy_last_error")
 
@@ -92,6 +93,8 @@ def load():
     lib.swarm_rollout.argtypes = [vp, vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, vp, ctypes.c_float, ctypes.c_uint64,
                                   ctypes.c_uint64, ctypes.c_uint64, vp, vp]
     lib.swarm_rollout.restype = i32
+    lib.swarm_rollout_expert.argtypes = [vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, ctypes.c_int32, vp, vp]
+    lib.swarm_rollout_expert.restype = i32
     lib.swarm_rollout_last_error.argtypes = []; lib.swarm_rollout_last_error.restype = ctypes.c_char_p
     lib.swarm_policy_set_precision.argtypes = [vp, i32]; lib.swarm_policy_set_precision.restype = i32
     lib.swarm_policy_last_error.argtypes = []; lib.swarm_policy_last_error.restype = ctypes.c_char_p

@@ -2166,27 +2166,7 @@ k_metrics(const KP P, double *__restrict__ out)
 // capped sensed-cell list (`exp_sensed`, the same filter + round(i*step) selection as :544-572).  np.cos is numpy's
 // vectorised routine, so v_exp agrees to a few ulp, not bit for bit (tests: 1e-12 absolute on the clipped action).
 // -------------------------------------------------------------------------------------------------
-template <class F>
-__device__ double np_sum_stream(int n, F f)      // np.sum of f(0..n-1) for n <= 128, values generated on the fly
-{
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res += f(i);
-        return res;
-    }
-    double r[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = f(k);
-    const int n8 = n - (n % 8);
-    int i;
-    for (i = 8; i < n8; i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] += f(i + k);
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += f(i);
-    return res;
-}
+using swarm_internal::np_sum_stream;     // np.sum of f(0..n-1) for n <= 128 (swarm_internal.h)
 
 __global__ void __launch_bounds__(256)
 k_rule(const KP P, double *__restrict__ out)     // out [E][N][2]
@@ -2369,6 +2349,7 @@ struct swarm_env {
     double2 *d_sf;
     void *d_prior;
     double2 *d_act_next;           // [E][N] the 'llm' strategy's next action (cfg.llm_action)
+    double2 *d_act64;              // [E][N] fp64 action scratch of swarm_rollout_expert (first expert call)
     // reference-shaped host I/O (swarm_step_host): library-owned step outputs on the device, the export block on the
     // device, two pinned host copies of it (ping-pong: the previous step's arrays stay valid for one more step), a pinned
     // staging buffer for the action
@@ -2650,6 +2631,31 @@ int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out)
     if (!h || !out) return SWARM_ERR_INVALID;
     out->device = h->device; out->n_env = h->cfg.n_env; out->n_agents = h->cfg.n_agents; out->obs_dim = h->kp.obs_dim;
     out->obs_dtype = h->cfg.obs_dtype; out->with_prior = h->cfg.with_prior != 0; out->observed = h->observed;
+    out->g_max = h->kp.g_max; out->llm_action = h->cfg.llm_action != 0;
+    return SWARM_OK;
+}
+
+int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_expert_view *out)
+{
+    if (!h || !out) return SWARM_ERR_INVALID;
+    if (lists) {
+        const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
+        if (!h->d_exp_sensed) {
+            HIP_TRY(h, hipMalloc((void **)&h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4));
+            HIP_TRY(h, hipMalloc((void **)&h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4));
+        }
+        if (!h->d_act64) HIP_TRY(h, hipMalloc((void **)&h->d_act64, EN * sizeof(double2)));
+        // the observation pass of swarm_rule_action on the current state, index export on (idempotent, see swarm_get_indices)
+        h->kp.export_idx = 1; h->kp.export_small = 1; h->kp.exp_sensed = h->d_exp_sensed; h->kp.exp_occ = h->d_exp_occ;
+        const int rc = launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+        h->kp.export_idx = 0; h->kp.export_small = 0;
+        if (rc != SWARM_OK) return rc;
+    }
+    out->p = h->d_p; out->dp = h->d_dp; out->cells = h->d_cells;
+    out->near_cell = h->d_near; out->in_flag = h->d_inflag; out->exp_sensed = h->d_exp_sensed;
+    out->act_next = h->d_act_next; out->act64 = h->d_act64;
+    out->d_sen = h->kp.d_sen; out->r_avoid = h->kp.r_avoid;
+    out->n_env = h->cfg.n_env; out->n_agents = h->cfg.n_agents; out->g_max = h->kp.g_max; out->ng_max = h->kp.ng_max;
     return SWARM_OK;
 }
 
@@ -2710,7 +2716,7 @@ int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
     h->lat_ncols.assign((size_t)cfg->n_env, 0);
     h->lattice_disabled = (cfg->debug_flags & 2) != 0;
     h->d_nei = h->d_near = h->d_inflag = h->d_ng = h->d_exp_sensed = h->d_exp_occ = nullptr; h->d_sf = nullptr; h->d_prior = nullptr;
-    h->d_act_next = nullptr;
+    h->d_act_next = nullptr; h->d_act64 = nullptr;
     h->d_io_obs = h->d_io_prior = nullptr; h->d_io_rew = nullptr; h->d_io_done = nullptr;
     h->d_io_block = nullptr; h->h_io_block[0] = h->h_io_block[1] = nullptr; h->h_io_action = h->d_io_action = nullptr; h->io_block_bytes = 0;
     h->cells_set.assign((size_t)cfg->n_env, 0);
@@ -2836,7 +2842,7 @@ int swarm_destroy(swarm_env_t *h)
         (void)hipFree(h->d_ng); (void)hipFree(h->d_nei); (void)hipFree(h->d_near); (void)hipFree(h->d_inflag); (void)hipFree(h->d_sf);
         (void)hipFree(h->d_exp_sensed); (void)hipFree(h->d_exp_occ); (void)hipFree(h->d_lat); (void)hipFree(h->d_shape_idx); (void)hipFree(h->d_prior);
         (void)hipFree(h->d_shape_cells); (void)hipFree(h->d_shape_l); (void)hipFree(h->d_shape_cin); (void)hipFree(h->d_shape_ng); (void)hipFree(h->d_shape_lat);
-        (void)hipFree(h->d_act_next); (void)hipFree(h->d_io_obs); (void)hipFree(h->d_io_prior); (void)hipFree(h->d_io_rew); (void)hipFree(h->d_io_done);
+        (void)hipFree(h->d_act_next); (void)hipFree(h->d_act64); (void)hipFree(h->d_io_obs); (void)hipFree(h->d_io_prior); (void)hipFree(h->d_io_rew); (void)hipFree(h->d_io_done);
         (void)hipFree(h->d_io_block); (void)hipFree(h->d_io_action);
         if (h->h_io_block[0]) (void)hipHostFree(h->h_io_block[0]);
         if (h->h_io_block[1]) (void)hipHostFree(h->h_io_block[1]);

@@ -30,13 +30,55 @@ static inline unsigned long long swarm_noise_key(uint64_t seed, uint64_t step)
     return pmix64(pmix64(seed + 0x9E3779B97F4A7C15ull) ^ (0xD1B54A32D192ED03ull * (step + 1)));
 }
 
+// np.sum of f(0..n-1) for n <= 128, values generated on the fly: numpy's pairwise summation, which below its 128-element
+// block size is eight interleaved partial sums combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the tail
+template <class F>
+__device__ inline double np_sum_stream(int n, F f)
+{
+    if (n < 8) {
+        double res = 0.0;
+        for (int i = 0; i < n; ++i) res += f(i);
+        return res;
+    }
+    double r[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = f(k);
+    const int n8 = n - (n % 8);
+    int i;
+    for (i = 8; i < n8; i += 8) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] += f(i + k);
+    }
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res += f(i);
+    return res;
+}
+
 }  // namespace swarm_internal
 
 struct swarm_env_info {
-    int device, n_env, n_agents, obs_dim, obs_dtype;
-    bool with_prior, observed;
+    int device, n_env, n_agents, obs_dim, obs_dtype, g_max;
+    bool with_prior, observed, llm_action;
 };
 SWARM_HIDDEN int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out);
+
+// What the expert sources of swarm_rollout_expert read for the CURRENT state: the fp64 state, the target cells, the lists
+// the index-export observation pass leaves in HBM (nearest cell, in-shape flag, capped sensed-cell list), the 'llm'
+// strategy's next action and the handle's fp64 action scratch.  All device pointers of the handle's device.
+struct swarm_expert_view {
+    const double *p, *dp;               // [E][2][N]
+    const double *cells;                // [E][2][ng_max]
+    const int *near_cell, *in_flag;     // [E][N]
+    const int *exp_sensed;              // [E][N][g_max], -1 padded
+    const double2 *act_next;            // [E][N]: the 'llm' action (NULL unless the handle was created with llm_action)
+    double2 *act64;                     // [E][N]: fp64 action scratch (allocated by the first call with lists)
+    double d_sen, r_avoid;
+    int n_env, n_agents, g_max, ng_max;
+};
+// lists = true: allocate the list / action scratch on first use (never again) and ENQUEUE the index-export observation
+// pass of swarm_rule_action on the handle's stream (no host synchronisation); false: only fill `out`.  SWARM_OK or an error
+// code with the message in swarm_last_error(h).
+SWARM_HIDDEN int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_expert_view *out);
 
 struct swarm_policy_info {
     int device, in_dim, act_dim;

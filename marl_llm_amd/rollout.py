@@ -11,9 +11,13 @@ ring buffer (train_assembly.py:91-111, maddpg.py:72-87, agents.py:69-96, buffer_
 * `ChainedReplay` -- the same transitions stored as a ring of env steps that share observation rows (half the copy per push).
 * `rollout`       -- obs -> policy -> exploration noise (agents.py:82-96 continuous branch) -> env.step_tensor -> push.
 * `rollout_device`-- the same loop (fused policy, chained ring) as ONE library call per episode: swarm_rollout.
+* `rollout_expert`-- expert rollouts (rule-based expert or the prior's 'llm' twin) into the same ring, one library call per
+                     episode batch: swarm_rollout_expert (collect_expert_data.py's loop on the device).
+* `save_expert_data` -- a ring's transitions as the expert_data.npz that ReplayBufferExpert.load reads (train_assembly_airl.py).
 
 PyTorch is plumbing here (device memory, GEMMs); the environment step is the HIP library.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -349,53 +353,90 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
     import ctypes
     import numpy as np
     from . import _lib
-    from .batched import SwarmBatch
-    aenv = None
-    if isinstance(env, SwarmBatch):
-        sb = env
-    elif hasattr(env, "_flush_cells") and hasattr(env, "agent_strategy"):
-        if env.agent_strategy != "input" or env.is_collected:
-            raise ValueError("rollout_device drives the env with the policy's actions: needs agent_strategy 'input' and not is_collected")
-        if reset is not None:
-            raise ValueError("reset= needs a SwarmBatch; with an AssemblySwarmEnv call reset_tensor() and pass its obs")
-        aenv, sb = env, env._flush_cells()
-    else:
-        raise TypeError("env must be a SwarmBatch or an AssemblySwarmEnv")
+    aenv, sb = _device_env(env, "rollout_device", lambda e: e.agent_strategy == "input" and not e.is_collected,
+                           "rollout_device drives the env with the policy's actions: needs agent_strategy 'input' and not is_collected",
+                           reset)
     if not isinstance(policy, FusedPolicy):
         raise TypeError("rollout_device needs a FusedPolicy (the device loop runs the fused policy kernel)")
     steps = int(steps)
     if steps < 0:
         raise ValueError("steps must be >= 0")
     E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
-    n = E * N
-    if replay is None:
-        replay = getattr(sb, "_rollout_ring", None)
-        if replay is None:
-            replay = sb._rollout_ring = ChainedReplay(1, n, D, 2, sb.device, obs_dtype=sb.obs_dtype)
-    elif not isinstance(replay, ChainedReplay):
-        raise TypeError("replay must be a ChainedReplay (or None)")
+    replay = _device_ring(sb, replay)
     lib = _lib.load()
-    dt_code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float64: _lib.F64}[replay.obs.dtype]
     stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
 
     def call(k, coins, stats):
-        ring = _lib.SwarmRing(replay.obs.data_ptr(), replay.act.data_ptr(), replay.rew.data_ptr(), replay.done.data_ptr(),
-                              replay.act_prior.data_ptr() if sb.with_prior else None, replay.n, replay.obs.shape[-1], dt_code,
-                              replay.S, replay.cur)
+        ring = _ring_struct(sb, replay)
         rc = lib.swarm_rollout(sb.handle, policy.handle, ctypes.byref(ring), k,
                                coins.ctypes.data_as(ctypes.c_void_p) if coins is not None else None, float(noise_scale),
                                int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1),
                                ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, stream)
-        if rc != 0 and not (k == 0 and rc == 3 and reset is not None):    # SWARM_ERR_STATE (not observed): the reset observes
-            raise _lib.SwarmError(f"libswarmenv error {rc}: {lib.swarm_rollout_last_error().decode()}")
+        _check_rollout(lib, rc, k, reset)
 
+    _begin_chain(sb, replay, obs, reset, lambda: call(0, None, None), "rollout_device")
+    coins = None
+    if epsilon > 0:
+        coin = host_rng if host_rng is not None else np.random
+        coins = np.array([coin.random() < epsilon for _ in range(steps)], dtype=np.uint8)          # agents.py:89
+    stats = torch.empty((steps, 2), dtype=torch.float64, device=sb.device) if track_reward else None
+    call(steps, coins, stats)
+    _finish_chain(aenv, replay, steps)
+    return replay.obs[replay.cur].view(E, N, D), stats
+
+
+# ---- chain handling shared by rollout_device and rollout_expert
+def _device_env(env, who, strategy_ok, strategy_msg, reset):
+    """(AssemblySwarmEnv or None, SwarmBatch) of a device-loop call; the env's strategy is checked before anything runs."""
+    from .batched import SwarmBatch
+    if isinstance(env, SwarmBatch):
+        return None, env
+    if hasattr(env, "_flush_cells") and hasattr(env, "agent_strategy"):
+        if not strategy_ok(env):
+            raise ValueError(strategy_msg)
+        if reset is not None:
+            raise ValueError("reset= needs a SwarmBatch; with an AssemblySwarmEnv call reset_tensor() and pass its obs")
+        return env, env._flush_cells()
+    raise TypeError("env must be a SwarmBatch or an AssemblySwarmEnv")
+
+
+def _device_ring(sb, replay):
+    """The caller's ChainedReplay, or the private two-slot ring kept on the env."""
+    if replay is None:
+        replay = getattr(sb, "_rollout_ring", None)
+        if replay is None:
+            replay = sb._rollout_ring = ChainedReplay(1, sb.n_env * sb.n_agents, sb.obs_dim, 2, sb.device, obs_dtype=sb.obs_dtype)
+    elif not isinstance(replay, ChainedReplay):
+        raise TypeError("replay must be a ChainedReplay (or None)")
+    return replay
+
+
+def _ring_struct(sb, replay):
+    from . import _lib
+    dt_code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float64: _lib.F64}[replay.obs.dtype]
+    return _lib.SwarmRing(replay.obs.data_ptr(), replay.act.data_ptr(), replay.rew.data_ptr(), replay.done.data_ptr(),
+                          replay.act_prior.data_ptr() if sb.with_prior else None, replay.n, replay.obs.shape[-1], dt_code,
+                          replay.S, replay.cur)
+
+
+def _check_rollout(lib, rc, k, reset):
+    from . import _lib
+    if rc != 0 and not (k == 0 and rc == 3 and reset is not None):    # SWARM_ERR_STATE (not observed): the reset observes
+        raise _lib.SwarmError(f"libswarmenv error {rc}: {lib.swarm_rollout_last_error().decode()}")
+
+
+def _begin_chain(sb, replay, obs, reset, validate, who):
+    """Continue the ring's chain, or start a new one from `obs` / reset=(seed, episode[, env_offset]) through
+    replay.new_chain().  `validate()` (a zero-step library call) runs first: a rejected call leaves the ring as it was."""
+    E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
+    n = E * N
     cont = reset is None and (obs is None or _is_view_of(obs, replay.obs[replay.cur]))
     if cont and obs is None and not replay._chained:
-        raise ValueError("rollout_device: the ring holds no current observation; pass obs or reset=")
+        raise ValueError(f"{who}: the ring holds no current observation; pass obs or reset=")
     if not cont and obs is not None and (not isinstance(obs, torch.Tensor) or obs.device != sb.device or obs.dtype != sb.obs_dtype
                                          or obs.numel() != n * D):
         raise ValueError(f"obs must be a {sb.obs_dtype} tensor [{E}, {N}, {D}] on {sb.device}")
-    call(0, None, None)                     # validation only: a rejected call raises before the ring is touched
+    validate()                              # validation only: a rejected call raises before the ring is touched
     if not cont:
         kept = (replay.cur, replay.count, replay._chained, set(replay._sealed))
         try:
@@ -408,14 +449,93 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
         except Exception:
             replay.cur, replay.count, replay._chained, replay._sealed = kept
             raise
-    coins = None
-    if epsilon > 0:
-        coin = host_rng if host_rng is not None else np.random
-        coins = np.array([coin.random() < epsilon for _ in range(steps)], dtype=np.uint8)          # agents.py:89
-    stats = torch.empty((steps, 2), dtype=torch.float64, device=sb.device) if track_reward else None
-    call(steps, coins, stats)
+
+
+def _finish_chain(aenv, replay, steps):
     replay._advance(steps)
     if aenv is not None:
         aenv.simulation_time += aenv.dt * steps
         aenv._state_version += 1
+
+
+@torch.no_grad()
+def rollout_expert(env, steps, obs=None, replay=None, reset=None, source="rule", track_reward=True):
+    """`steps` expert steps in ONE library call (swarm_rollout_expert, include/swarm_rollout.h): the device counterpart of
+    collect_expert_data.py's loop (agent_strategy 'rule' / 'llm' with is_collected).  Enqueued on torch's current stream;
+    returns without a host synchronisation.
+
+    env    : a SwarmBatch, or an AssemblySwarmEnv whose agent_strategy is `source` (its float32 / bfloat16 backend).
+    source : "rule" -- the rule-based expert (assembly.py:530-601) computed on the device in fp64 (bit-identical to
+             SwarmBatch.rule_action()); the env steps with that fp64 action and the ring's act row holds its f32 rounding.
+             "llm"  -- the prior policy's twin (a batch created with llm_action): the ring's act row is the applied action,
+             what the eager path returns as its fifth value with is_collected.
+    replay / obs / reset : the chain, exactly as rollout_device (reset= seals the boundary slot through new_chain()).
+    Returns (obs [E,N,D] -- the ring slot of the last next_obs --, reward_stats [steps, 2] float64 or None).  On error
+    nothing is enqueued, the ring and the env state are unchanged, and SwarmError / ValueError raises."""
+    import ctypes
+    from . import _lib
+    if source not in ("rule", "llm"):
+        raise ValueError("source must be 'rule' or 'llm'")
+    aenv, sb = _device_env(env, "rollout_expert", lambda e: e.agent_strategy == source,
+                           f"rollout_expert(source={source!r}) needs an AssemblySwarmEnv with agent_strategy {source!r}", reset)
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("steps must be >= 0")
+    E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
+    replay = _device_ring(sb, replay)
+    lib = _lib.load()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
+    src = _lib.EXPERT_RULE if source == "rule" else _lib.EXPERT_LLM
+
+    def call(k, stats):
+        ring = _ring_struct(sb, replay)
+        rc = lib.swarm_rollout_expert(sb.handle, ctypes.byref(ring), k, src,
+                                      ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, stream)
+        _check_rollout(lib, rc, k, reset)
+
+    _begin_chain(sb, replay, obs, reset, lambda: call(0, None), "rollout_expert")
+    stats = torch.empty((steps, 2), dtype=torch.float64, device=sb.device) if track_reward else None
+    call(steps, stats)
+    _finish_chain(aenv, replay, steps)
     return replay.obs[replay.cur].view(E, N, D), stats
+
+
+EXPERT_KEYS = ("obs_buffs", "ac_buffs", "next_obs_buffs", "done_buffs")       # ReplayBufferExpert.save (buffer_expert.py)
+
+
+@torch.no_grad()
+def save_expert_data(replay, file_dir, dtype=np.float64):
+    """Write `file_dir`/expert_data.npz from a ChainedReplay, with exactly ReplayBufferExpert.save's keys: obs_buffs [L, D],
+    ac_buffs [L, 2], next_obs_buffs [L, D], done_buffs [L, 1], all in `dtype`.  ReplayBufferExpert.load reads it unchanged.
+
+    Rows are the ring's stored transitions, oldest step first; within a step env-major, then agent -- the order
+    ReplayBufferExpert.push produces from the numpy API, whose agent axis holds the envs side by side.  Sealed slots (the
+    last next_obs of a chain, see ChainedReplay.new_chain) start no transition and are skipped, so no row pairs one
+    episode's last observation with the next episode's first.
+
+    Differences from the reference's file: it holds only written rows (the reference saves its whole allocation, zero rows
+    included, once it is not yet full), and in chronological order (the reference's in ring order after a wrap-around).
+    train_assembly_airl.py sets total_length from the loaded shape, so it works unchanged.  The data streams to the file
+    one ring slot at a time (no host or device copy of the whole ring).  Returns the file's path."""
+    import os
+    import zipfile
+    starts = replay._valid_starts()[::-1]                           # oldest first
+    n, S, D = replay.n, replay.S, replay.obs.shape[-1]
+    L = len(starts) * n
+    dt = np.dtype(dtype)
+    src = {"obs_buffs": (lambda j: replay.obs[j], D), "ac_buffs": (lambda j: replay.act[j], 2),
+           "next_obs_buffs": (lambda j: replay.obs[(j + 1) % S], D), "done_buffs": (lambda j: replay.done[j], 1)}
+    os.makedirs(file_dir, exist_ok=True)
+    path = os.path.join(file_dir, "expert_data.npz")
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_STORED, allowZip64=True) as zf:    # np.savez's container
+        for key in EXPERT_KEYS:
+            rows, width = src[key]
+            with zf.open(key + ".npy", "w", force_zip64=True) as f:
+                np.lib.format.write_array_header_1_0(f, {"descr": np.lib.format.dtype_to_descr(dt), "fortran_order": False,
+                                                         "shape": (L, width)})
+                for j in starts:
+                    t = rows(j)
+                    if t.dtype == torch.bfloat16:
+                        t = t.float()                               # exact; numpy has no bfloat16
+                    f.write(np.ascontiguousarray(t.reshape(n, width).cpu().numpy().astype(dt, copy=False)).data)
+    return path
