@@ -5,7 +5,7 @@
  * called from /root/reference/marl_llm/algorithm/utils/agents.py:69-96 (DDPGAgent.step) on torch.Tensor(obs).
  * One HIP kernel (bf16 MFMA, fp32 accumulate) maps the env's observation rows [rows][in_dim] (fp32, device) to actions
  * [rows][act_dim] (fp32, device); weights are given once, in torch.nn.Linear layout ([out][in] row-major, fp32, host).
- * Same numerical contract as torch.autocast(bfloat16) on that module.  No CPU path: without a HIP device create fails.
+ * The arithmetic is stated exactly under swarm_policy_set_precision below.  No CPU path: without a HIP device create fails.
  */
 #ifndef SWARM_POLICY_H
 #define SWARM_POLICY_H
@@ -23,7 +23,9 @@ extern "C" {
 typedef struct swarm_policy swarm_policy_t;
 
 /* w1 [hidden][in_dim], w2 / w3 [hidden][hidden], w4 [act_dim][hidden], b* the biases; all fp32 HOST pointers.
- * Supported: in_dim <= 192 (multiple of 4), hidden <= 192, act_dim <= 4.  device < 0: the current device. */
+ * Supported: 4 <= in_dim <= 192 (multiple of 4), 1 <= hidden <= 191, 1 <= act_dim <= 4 (the padded hidden feature 191 at the
+ * most carries the constant one of the bias column).  Shapes and pointers are checked before any device call: a rejected
+ * create returns SWARM_POLICY_ERR_INVALID with a message.  device < 0: the current device. */
 int  swarm_policy_create(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
                          const float *w4, const float *b4, int in_dim, int hidden, int act_dim, int device, swarm_policy_t **out);
 void swarm_policy_destroy(swarm_policy_t *p);
@@ -42,17 +44,37 @@ int  swarm_policy_forward_bf16(swarm_policy_t *p, const void *obs_bf16, int64_t 
  * evaluated in the kernel's epilogue, nothing to store; noise_scale <= 0: plain forward.  row_offset is the global index of
  * the call's first row: a rank that passes the start of its shard draws exactly the noise the same rows get in one call over
  * the whole batch, and ranks that share (seed, step) draw different noise.  `act` may point anywhere on the device (e.g.
- * straight into a replay-buffer slot).  obs_is_bf16 as the two calls above. */
+ * straight into a replay-buffer slot).  obs_is_bf16 as the two calls above.
+ *
+ * Gaussian noise, counter-based, for global row g = row_offset + row (arithmetic mod 2^64, pmix64 as in swarm_rollout.h):
+ *   key = pmix64(pmix64(seed + 0x9E3779B97F4A7C15) ^ (0xD1B54A32D192ED03 * (step + 1)))
+ *   h   = pmix64(key ^ g)
+ *   for the component pairs (0, 1) and (2, 3), as far as act_dim reaches:
+ *     u1 = (float)((h >> 40) + 1) * 2^-24                 in (0, 1], exact in fp32
+ *     u2 = (float)((h >> 16) & 0xFFFFFF) * 2^-24         in [0, 1), exact in fp32
+ *     z[k] = sqrtf(-2 logf(u1)) * cosf(t),  z[k + 1] = sqrtf(-2 logf(u1)) * sinf(t),  t = 6.283185307179586f * u2 (fp32)
+ *     h = pmix64(h + 0x9E3779B97F4A7C15)                  (before the next pair)
+ *   act[g][k] = clamp(tanh(pre[k]) + noise_scale * z[k], -1, 1) in fp32. */
 int  swarm_policy_forward_explore_at(swarm_policy_t *p, const void *obs, int obs_is_bf16, int64_t rows, float *act,
                                      float noise_scale, uint64_t seed, uint64_t step, uint64_t row_offset, void *stream);
 /* The same with row_offset = 0: the noise is keyed by the call-local row index. */
 int  swarm_policy_forward_explore(swarm_policy_t *p, const void *obs, int obs_is_bf16, int64_t rows, float *act,
                                   float noise_scale, uint64_t seed, uint64_t step, void *stream);
 
-/* Arithmetic of the forward calls.  SWARM_POLICY_BF16 (default): operands rounded to bfloat16, fp32 sums -- the contract of
- * torch.autocast(bfloat16), ~4e-2 from the reference's fp32 actor on actions in [-1, 1].  SWARM_POLICY_BF16X3: operands split
- * into a high and a low bfloat16 part, three MFMAs per product (hi hi + hi lo + lo hi), fp32 sums -- within ~1e-4 of the fp32
- * actor (networks.py:6-44), about 1.9x the time. */
+/* Arithmetic of the forward calls, exactly (tests/helpers.py policy_model restates it in float64).  bf(v): v rounded to
+ * bfloat16, nearest-even.  Products of bf16 operands are exact in fp32; every sum is accumulated in fp32, in an order that
+ * is not part of the contract.
+ * SWARM_POLICY_BF16 (default):
+ *   layer 1:      h = bf(W1) . bf(x) + b1            b1 stays fp32 (it initialises the accumulators)
+ *   layers 2-4:   h = bf(Wl) . a + bf(bl)            the bias rides in the weights' constant-one column, as bf16
+ *   activation:   a = bf(fmaxf(v, 0.01f * v))        v = the fp32 sum, the product rounded in fp32
+ *   output:       tanhf of the fp32 sum of layer 4   (no bf16 rounding before the tanh)
+ *   Close to torch.autocast(bfloat16), not equal to it: autocast also rounds b1 and the pre-tanh sum to bf16.  About 4e-2 from
+ *   the reference's fp32 actor on actions in [-1, 1].
+ * SWARM_POLICY_BF16X3: every operand v (weights on the host, layer inputs and activations in the kernel) is split into
+ *   hi = bf(v) and lo = bf(v - hi) (v - hi is exact in fp32); a product is Whi.xhi + Whi.xlo + Wlo.xhi (lo.lo dropped), three
+ *   MFMAs, fp32 sums.  Layer 1's bias is fp32, the biases of layers 2-4 are hi + lo; bf16 observation rows have lo = 0.
+ *   Within ~1e-4 of the fp32 actor (networks.py:6-44), about 1.9x the time. */
 #define SWARM_POLICY_BF16   0
 #define SWARM_POLICY_BF16X3 1
 int  swarm_policy_set_precision(swarm_policy_t *p, int precision);

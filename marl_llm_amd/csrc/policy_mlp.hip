@@ -13,8 +13,9 @@
 // Fragment maps (cdna_hip_programming.md section 3): A[row = l & 31][k = 8 (l >> 5) + j], B[k = 8 (l >> 5) + j][col = l & 31],
 // C/D col = l & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).
 //
-// Numerics: weights and layer inputs are rounded to bf16 (round-to-nearest-even), sums and biases are fp32: the same
-// contract as torch.autocast(bfloat16) on the reference module.  tests/test_gpu_policy.py states the tolerance.
+// Numerics: weights and layer inputs are rounded to bf16 (round-to-nearest-even), sums are fp32, layer 1's bias is fp32 and
+// the biases of layers 2-4 are bf16 (the constant-one column); include/swarm_policy.h states the contract exactly and
+// tests/test_gpu_policy_contract.py holds the kernel to a float64 model of it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>

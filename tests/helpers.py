@@ -122,3 +122,198 @@ class ThreadedOracle:
                                                      self.r_avoid, is_periodic=not self.is_boundary, with_self=self.with_self)
         self._map(work, len(envs))
         return {k: np.stack([r[k] for r in res]) for k in res[0]}
+
+
+# ---- counter-based generators of the policy and rollout kernels (include/swarm_policy.h, include/swarm_rollout.h) ----
+M64 = (1 << 64) - 1
+GOLD = 0x9E3779B97F4A7C15
+
+
+def mix64(z):
+    """pmix64 (splitmix64's finaliser) on a Python int, mod 2^64."""
+    z &= M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    return z ^ (z >> 31)
+
+
+def mix64_np(z):
+    """pmix64 elementwise on a uint64 array (numpy's uint64 arithmetic wraps mod 2^64)."""
+    z = np.asarray(z).astype(np.uint64)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def noise_key(seed, step):
+    """swarm_noise_key: the key of a (seed, step)'s exploration generators."""
+    return mix64(mix64(seed + GOLD) ^ ((0xD1B54A32D192ED03 * (step + 1)) & M64))
+
+
+def policy_normals(seed, step, rows, act_dim, row_offset=0):
+    """include/swarm_policy.h 'Gaussian noise', restated: the normals z [rows, act_dim] of global rows row_offset + row, in
+    float64 from the kernel's float32 uniforms (u1, u2 and the argument 2 pi u2 are formed exactly as the kernel forms them),
+    and the Box-Muller radius [rows, act_dim] of each component (the scale of its rounding error)."""
+    g = np.arange(rows, dtype=np.uint64) + np.uint64(row_offset)
+    h = mix64_np(np.uint64(noise_key(seed, step)) ^ g)
+    z = np.empty((rows, act_dim)); rad = np.empty((rows, act_dim))
+    for k in range(0, act_dim, 2):
+        u1 = ((h >> np.uint64(40)) + np.uint64(1)).astype(np.float32) * np.float32(2.0 ** -24)          # (0, 1], exact
+        u2 = ((h >> np.uint64(16)) & np.uint64(0xFFFFFF)).astype(np.float32) * np.float32(2.0 ** -24)   # [0, 1), exact
+        arg = np.float32(6.283185307179586) * u2                                                        # rounded in fp32
+        r = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
+        z[:, k] = r * np.cos(arg.astype(np.float64)); rad[:, k] = r
+        if k + 1 < act_dim:
+            z[:, k + 1] = r * np.sin(arg.astype(np.float64)); rad[:, k + 1] = r
+        h = mix64_np(h + np.uint64(GOLD))
+    return z, rad
+
+
+# ---- float64 model of the fused policy kernel's arithmetic (csrc/policy_mlp.hip, include/swarm_policy.h) ----
+U32 = 2.0 ** -24            # unit roundoff of fp32
+SLOPE = 0.01                # leaky-ReLU slope, applied as the fp32 product 0.01f * v
+
+
+def _bf(t):
+    """Round float32-representable values (held in float64) to bfloat16, nearest-even, and widen back."""
+    import torch
+    return t.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+
+
+def _lrelu32(h):
+    """The kernel's activation of a float64 pre-activation h: v = fp32(h), r = fmaxf(v, 0.01f * v) (product rounded in
+    fp32).  Returns r in float64.  Monotone non-decreasing in h."""
+    import torch
+    v = h.to(torch.float32)
+    return torch.maximum(v, v * torch.tensor(SLOPE, dtype=torch.float32, device=h.device)).to(torch.float64)
+
+
+def _split(t):
+    """hi = bf(v), lo = bf(v - hi) of float32-representable values (v - hi is exact in fp32)."""
+    hi = _bf(t)
+    return hi, _bf(t - hi)
+
+
+def _lowbit(t):
+    """Exponent of the lowest set bit of every nonzero element (float64, exact); +inf for zeros."""
+    import torch
+    a = t.abs()
+    m, e = torch.frexp(a)
+    mi = (m * 2.0 ** 53).to(torch.int64)
+    low = torch.log2((mi & -mi).to(torch.float64)) + e.to(torch.float64) - 53.0
+    return torch.where(a > 0, low, torch.full_like(low, float("inf")))
+
+
+def policy_weights(module):
+    """fc1..fc4 weights and biases of a PolicyMLP-like module as fp32 values held in float64 (what swarm_policy_create
+    reads)."""
+    import torch
+    return [t.detach().to("cpu", torch.float32).to(torch.float64) for fc in (module.fc1, module.fc2, module.fc3, module.fc4)
+            for t in (fc.weight, fc.bias)]
+
+
+def policy_model(module, x, precision, device=None, quantum=False):
+    """csrc/policy_mlp.hip restated in float64 (include/swarm_policy.h 'Arithmetic').  x [rows, in_dim] float32 or bfloat16
+    (the values the kernel reads); precision "bf16" or "bf16x3".
+
+    bf16:   layer 1  h = bf(W1) . bf(x) + b1                  (b1 fp32: it initialises the accumulators)
+            layer l  h = bf(Wl) . a + bf(bl)                   (the bias rides in the constant-one column), l = 2..4
+            a = bf(fp32(max(v, 0.01f * v))), v = fp32(h);    output tanh(h4)
+    bf16x3: every operand v split as hi = bf(v), lo = bf(v - hi); a product is Whi.xhi + Whi.xlo + Wlo.xhi (lo.lo dropped);
+            biases of layers 2-4 are hi + lo, layer 1's fp32; bf16 input rows have lo = 0; a = hi + lo of the activation r.
+
+    The sums h are exact up to float64 rounding.  Returns a dict (float64 tensors on `device`, default x's):
+      out [rows, act]    tanh(h4)
+      h   list of the four pre-activations [rows, width]
+      r   list of the three fp32 activations r (before the bf16 rounding / split)
+      S   list of the four sums of |terms| (the bias included) per row and feature
+      n   list of the four term counts per sum (bias included)
+      q   (quantum=True) list of the four per-row exponents q such that every term of the row's sums is a multiple of 2^q
+    """
+    import torch
+    dev = torch.device(device) if device is not None else x.device
+    x3 = precision == "bf16x3"
+    if precision not in ("bf16", "bf16x3"):
+        raise ValueError(precision)
+    w1, b1, w2, b2, w3, b3, w4, b4 = [t.to(dev) for t in policy_weights(module)]
+    xin = x.to(dev).to(torch.float64)
+    res = dict(h=[], r=[], S=[], n=[], q=[])
+    # layer inputs: a list of (operand, weight part) pairs whose products are the terms
+    if x3:
+        if x.dtype == torch.bfloat16:
+            ah, al = xin, torch.zeros_like(xin)
+        else:
+            ah, al = _split(xin)
+    else:
+        ah, al = _bf(xin), None
+    layers = ((w1, b1, True), (w2, b2, False), (w3, b3, False), (w4, b4, False))
+    for li, (w, b, first) in enumerate(layers):
+        if x3:
+            wh, wl = _split(w)
+            pairs = [(ah, wh), (al, wh), (ah, wl)]
+            bias_terms = [b] if first else list(_split(b))
+        else:
+            pairs = [(ah, _bf(w))]
+            bias_terms = [b] if first else [_bf(b)]
+        h = sum(a @ wt.T for a, wt in pairs) + sum(bias_terms)
+        S = sum(a.abs() @ wt.abs().T for a, wt in pairs) + sum(t.abs() for t in bias_terms)
+        res["h"].append(h); res["S"].append(S)
+        res["n"].append(len(pairs) * w.shape[1] + len(bias_terms))
+        if quantum:
+            qa = torch.stack([_lowbit(a).amin(dim=1) for a, _ in pairs], 1)             # [rows, pairs]
+            qw = torch.stack([_lowbit(wt).amin() for _, wt in pairs])                    # [pairs]
+            qb = torch.stack([_lowbit(t).amin() for t in bias_terms]).amin()
+            res["q"].append(torch.minimum((qa + qw).amin(dim=1), qb))
+        if li < 3:
+            r = _lrelu32(h)
+            res["r"].append(r)
+            if x3:
+                ah, al = _split(r)
+            else:
+                ah = _bf(r)
+    res["out"] = torch.tanh(res["h"][3])
+    return res
+
+
+def gamma(n):
+    """Rigorous relative factor of an fp32 sum of n exact terms in any order, against the exact sum rounded once:
+    |fl(sum) - sum| <= n 2^-24 sum|terms| (first order; n u covers the (n - 1) u of the additions and the model's own
+    float64 rounding with room to spare)."""
+    return n * U32
+
+
+def decided_rows(model, slack=1.0):
+    """bf16 mode: rows whose every hidden activation is the same bf16 value for any pre-activation within gamma(n) S of the
+    model's (the rounding function is monotone in h, so comparing both ends of the interval decides it).  On such a row the
+    kernel's bf16 activations equal the model's whatever its summation order.  Returns a bool [rows] tensor."""
+    ok = None
+    for h, S, n in zip(model["h"][:3], model["S"][:3], model["n"][:3]):
+        rho = slack * gamma(n) * S
+        same = (_bf(_lrelu32(h - rho)) == _bf(_lrelu32(h + rho))).all(dim=1)
+        ok = same if ok is None else ok & same
+    return ok
+
+
+def output_bound(model, precision, module):
+    """Bound on |kernel pre-tanh - model h4| per output.  bf16: gamma(n4) S4, valid on decided rows (identical activations).
+    bf16x3: propagated through the layers -- the sum's own gamma(n) S, plus the effect of the previous layer's activation
+    error on this layer's terms (fp32 rounding of v and of 0.01f v, the re-split of a moved activation into hi + lo)."""
+    import torch
+    if precision == "bf16":
+        return gamma(model["n"][3]) * model["S"][3]
+    ws = [t.to(model["h"][0].device) for t in policy_weights(module)][0::2]
+    E = gamma(model["n"][0]) * model["S"][0]
+    for li in range(1, 4):
+        h, r = model["h"][li - 1], model["r"][li - 1]
+        Dr = E * (1 + 2 * SLOPE * U32) + 2 * U32 * h.abs()              # |r' - r|: the kernel's fp32 v and the product 0.01f v
+        Da = Dr * (1 + 2.0 ** -18) + 2.0 ** -17 * r.abs()               # |(hi + lo)' - (hi + lo)|, each within 2^-18 |r| of r
+        Dhi = Dr * (1 + 2.0 ** -8) + 2.0 ** -8 * r.abs()                # |hi' - hi|
+        wh, wl = _split(ws[li])
+        prop = Da @ wh.abs().T + Dhi @ wl.abs().T
+        E = prop + gamma(model["n"][li]) * (model["S"][li] + prop + 2 * Dhi @ wh.abs().T)      # the kernel's own S
+    return E
+
+
+def tanh_tol(y):
+    """Accuracy of the kernel's tanhf (device libm: within 2 ulp) plus the fp32 rounding of the result: 4 ulp."""
+    return 8 * U32 * y.abs() + 2.0 ** -30

@@ -3,8 +3,8 @@
 Tolerances (stated here as the brief requires for floating-point kernels):
   * against the fp32 torch forward: |d action| <= 3e-2 -- weights and layer inputs are rounded to bf16 (2^-9 relative each),
     four layers of 180..192 terms with fp32 accumulation; the tanh output is in [-1, 1];
-  * against a torch emulation of the kernel's contract (bf16-rounded weights and layer inputs, fp32 sums; the kernel also
-    carries the biases of layers 2-4 in bf16, as torch.autocast does): <= 8e-3
+  * against a torch emulation of the kernel's contract (bf16-rounded weights and layer inputs, fp32 sums, layer 1's bias in
+    fp32 and the biases of layers 2-4 rounded to bf16, as the kernel carries them; include/swarm_policy.h): <= 8e-3
     (only the summation order differs, which flips the bf16 rounding of near-tie hidden activations: one bf16 ulp, 2^-8
     relative, at a time; the maximum over 5e5 outputs was 4e-3);
   * integer data (everything exactly representable, sums < 2^24): the pre-activation path is exact, which pins the MFMA
@@ -21,7 +21,7 @@ def _emulate(module, x):
     bf = lambda t: t.to(torch.bfloat16).to(torch.float32)
     h = bf(x)
     for k, fc in enumerate((module.fc1, module.fc2, module.fc3, module.fc4)):
-        h = F.linear(h, bf(fc.weight), fc.bias)
+        h = F.linear(h, bf(fc.weight), fc.bias if k == 0 else bf(fc.bias))
         if k < 3:
             h = bf(F.leaky_relu(h))
     return torch.tanh(h)

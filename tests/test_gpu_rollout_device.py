@@ -7,31 +7,15 @@ import ctypes
 import numpy as np
 import pytest
 
+from helpers import mix64, mix64_np, noise_key
+
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-M64 = (1 << 64) - 1
-GOLD = 0x9E3779B97F4A7C15
-
-
-def mix64(z):
-    z &= M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    return z ^ (z >> 31)
-
-
-def mix64_np(z):
-    z = z.astype(np.uint64)
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return z ^ (z >> np.uint64(31))
 
 
 def uniform_actions(seed, step, rows, row_offset=0):
     """include/swarm_rollout.h 'Uniform actions', restated: [rows, 2] float32."""
-    key = mix64(mix64(seed + GOLD) ^ ((0xD1B54A32D192ED03 * (step + 1)) & M64))
-    ukey = mix64(key ^ 0x5851F42D4C957F2D)
+    ukey = mix64(noise_key(seed, step) ^ 0x5851F42D4C957F2D)
     g = np.arange(rows, dtype=np.uint64) + np.uint64(row_offset)
     h = mix64_np(np.uint64(ukey) ^ g)
     out = np.empty((rows, 2), np.float32)
