@@ -54,12 +54,24 @@ int  swarm_policy_forward_bf16(swarm_policy_t *p, const void *obs_bf16, int64_t 
  *     u2 = (float)((h >> 16) & 0xFFFFFF) * 2^-24         in [0, 1), exact in fp32
  *     z[k] = sqrtf(-2 logf(u1)) * cosf(t),  z[k + 1] = sqrtf(-2 logf(u1)) * sinf(t),  t = 6.283185307179586f * u2 (fp32)
  *     h = pmix64(h + 0x9E3779B97F4A7C15)                  (before the next pair)
- *   act[g][k] = clamp(tanh(pre[k]) + noise_scale * z[k], -1, 1) in fp32. */
+ *   act[g][k] = clamp(tanh(pre[k]) + noise_scale * z[k], -1, 1) in fp32.
+ *
+ * Log-probability of the noise (swarm_policy_forward_explore_logpi; GaussianNoise.log_prob of utils/noise.py on the noise
+ * before the clamp, the log_pi of agents.py:93-95), in fp32 from the same z[k], with noise_scale the fp32 value passed:
+ *   c  = (float)((double)act_dim * log((double)noise_scale * sqrt(2.0 * M_PI)))     once per call, on the host, in double
+ *   s  = z[0]*z[0] + z[1]*z[1] + ... + z[act_dim-1]*z[act_dim-1]                   fp32, left to right, no fused multiply-add
+ *   log_pi[g] = -(0.5f * s) - c                                                     fp32
+ * noise_scale <= 0 (plain forward): log_pi[g] = -0.0f, the reference's -act_dim * log(1).  The actions are the same bits
+ * whether log_pi is requested or not. */
 int  swarm_policy_forward_explore_at(swarm_policy_t *p, const void *obs, int obs_is_bf16, int64_t rows, float *act,
                                      float noise_scale, uint64_t seed, uint64_t step, uint64_t row_offset, void *stream);
 /* The same with row_offset = 0: the noise is keyed by the call-local row index. */
 int  swarm_policy_forward_explore(swarm_policy_t *p, const void *obs, int obs_is_bf16, int64_t rows, float *act,
                                   float noise_scale, uint64_t seed, uint64_t step, void *stream);
+/* swarm_policy_forward_explore_at that also writes log_pi[rows] (fp32, DEVICE, required: NULL is rejected with
+ * SWARM_POLICY_ERR_INVALID), the log-probability of each row's exploration noise stated above. */
+int  swarm_policy_forward_explore_logpi(swarm_policy_t *p, const void *obs, int obs_is_bf16, int64_t rows, float *act, float *log_pi,
+                                        float noise_scale, uint64_t seed, uint64_t step, uint64_t row_offset, void *stream);
 
 /* Arithmetic of the forward calls, exactly (tests/helpers.py policy_model restates it in float64).  bf(v): v rounded to
  * bfloat16, nearest-even.  Products of bf16 operands are exact in fp32; every sum is accumulated in fp32, in an order that

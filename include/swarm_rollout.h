@@ -63,6 +63,17 @@ int swarm_rollout(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *rin
                   const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset,
                   double *reward_stats, void *stream);
 
+/* swarm_rollout that also records the log-probability of each exploring action (the log_pi of agents.py:78-96 that
+ * train_assembly_airl.py:134-143 stores with every transition): log_pi is a DEVICE fp32 array [n_slots][rows], indexed by the
+ * same slot c as act, and per step t
+ *   - a policy step writes log_pi[c] as swarm_policy_forward_explore_logpi does (swarm_policy.h; -0.0f if noise_scale <= 0);
+ *   - a uniform (epsilon) step writes log_pi[c][row] = (float)(-2 * ln 2), i.e. -act_dim * log(2).
+ * Everything else -- the actions, the env step, the ring, reward_stats -- is bit for bit what swarm_rollout computes with the
+ * same arguments.  log_pi = NULL is rejected (SWARM_ERR_INVALID); validation comes first, as in swarm_rollout. */
+int swarm_rollout_logpi(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, float *log_pi, int32_t steps,
+                        const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset,
+                        double *reward_stats, void *stream);
+
 /* Expert rollouts (the reference's collect_expert_data.py: agent_strategy 'rule' or 'llm' with is_collected, the data of
  * train_assembly_airl.py).  Enqueues `steps` expert steps on `stream`; per step t, with c and n as above:
  *   - SWARM_EXPERT_RULE: the rule-based expert of assembly.py:530-601 on the current state, in fp64 (the action of
@@ -81,7 +92,7 @@ enum { SWARM_EXPERT_RULE = 0, SWARM_EXPERT_LLM = 1 };
 int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t steps, int32_t source, double *reward_stats,
                          void *stream);
 
-/* Message of the last failing swarm_rollout / swarm_rollout_expert on the calling thread. */
+/* Message of the last failing swarm_rollout / swarm_rollout_logpi / swarm_rollout_expert on the calling thread. */
 const char *swarm_rollout_last_error(void);
 
 #ifdef __cplusplus

@@ -46,9 +46,10 @@ BATCHED_SYMBOLS = ("swarm_abi_version", "swarm_default_config", "swarm_create", 
                    "swarm_step_algorithmic_bytes", "swarm_timer_start", "swarm_timer_stop", "swarm_lattice_envs", "swarm_set_shapes", "swarm_reset", "swarm_get_cells", "swarm_get_shape_index", "swarm_metrics", "swarm_rule_action",
                    "swarm_host_outputs", "swarm_observe_host", "swarm_step_host", "swarm_get_llm_action")
 POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_destroy", "swarm_policy_forward", "swarm_policy_forward_bf16",
-                  "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_set_precision",
+                  "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_forward_explore_logpi",
+                  "swarm_policy_set_precision",
                   "swarm_policy_last_error")   # include/swarm_policy.h
-ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_expert", "swarm_rollout_last_error")   # include/swarm_rollout.h
+ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_logpi", "swarm_rollout_expert", "swarm_rollout_last_error")   # include/swarm_rollout.h
 LEGACY_SYMBOLS = ("_get_observation", "_get_reward", "_sf_b2b_all", "_get_dist_b2w", "calculateActionPrior",
                   "swarm_legacy_status", "swarm_legacy_last_error")
 
@@ -90,9 +91,15 @@ def load():
     lib.swarm_policy_forward_explore_at.argtypes = [vp, vp, i32, ctypes.c_int64, vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
                                                     ctypes.c_uint64, vp]
     lib.swarm_policy_forward_explore_at.restype = i32
+    lib.swarm_policy_forward_explore_logpi.argtypes = [vp, vp, i32, ctypes.c_int64, vp, vp, ctypes.c_float, ctypes.c_uint64,
+                                                       ctypes.c_uint64, ctypes.c_uint64, vp]
+    lib.swarm_policy_forward_explore_logpi.restype = i32
     lib.swarm_rollout.argtypes = [vp, vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, vp, ctypes.c_float, ctypes.c_uint64,
                                   ctypes.c_uint64, ctypes.c_uint64, vp, vp]
     lib.swarm_rollout.restype = i32
+    lib.swarm_rollout_logpi.argtypes = [vp, vp, ctypes.POINTER(SwarmRing), vp, ctypes.c_int32, vp, ctypes.c_float, ctypes.c_uint64,
+                                        ctypes.c_uint64, ctypes.c_uint64, vp, vp]
+    lib.swarm_rollout_logpi.restype = i32
     lib.swarm_rollout_expert.argtypes = [vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, ctypes.c_int32, vp, vp]
     lib.swarm_rollout_expert.restype = i32
     lib.swarm_rollout_last_error.argtypes = []; lib.swarm_rollout_last_error.restype = ctypes.c_char_p

@@ -80,9 +80,11 @@ constexpr int kSmemBytes = 2 * kChunkFrags * 64 * 16;                       // 7
 // product is three MFMAs, w_hi x_hi + w_hi x_lo + w_lo x_hi, accumulated in fp32 -- the rollout then follows the reference's
 // fp32 actor to ~1e-4 instead of bf16's 4e-2.  The weight stream alternates high and low chunks (same chunk size, same two
 // LDS buffers: twice as many chunk steps); a high chunk meets both activation parts, a low chunk the high part only.
-template <bool IN_BF16, int TPW, bool X3>
+// LOGPI: also write log_pi[row], the log-density of the row's Gaussian exploration noise (include/swarm_policy.h).  A template
+// parameter rather than a run-time test, so that the instantiations without it compile exactly as before (218 VGPRs).
+template <bool IN_BF16, int TPW, bool X3, bool LOGPI>
 __global__ void __launch_bounds__(64 * waves_of(X3), (TPW == 1 && !X3) ? 2 : 1)
-k_policy_mlp(const MlpParams P, const void *__restrict__ obs_, float *__restrict__ act)
+k_policy_mlp(const MlpParams P, const void *__restrict__ obs_, float *__restrict__ act, float *__restrict__ log_pi, float logpi_c)
 {
     constexpr int kWaves = waves_of(X3), kPre = pre_of(kWaves);
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -243,6 +245,17 @@ k_policy_mlp(const MlpParams P, const void *__restrict__ obs_, float *__restrict
                                 if (P.noise_scale > 0.0f) v = fminf(fmaxf(v + P.noise_scale * z[k], -1.0f), 1.0f);
                                 y[k] = v;
                             }
+                        if constexpr (LOGPI) {                              // -(0.5 sum_k z_k^2) - c, the sum in k order
+                            float lp = -0.0f;                               // no noise: -act_dim log(1) = -0.0
+                            if (P.noise_scale > 0.0f) {
+                                float s = z[0] * z[0];
+#pragma unroll
+                                for (int k = 1; k < 4; ++k)
+                                    if (k < P.act_dim) s = s + z[k] * z[k];
+                                lp = -(0.5f * s) - logpi_c;
+                            }
+                            log_pi[row] = lp;
+                        }
                     }
                 }
             }
@@ -264,6 +277,22 @@ uint16_t bf16_rne(float f)
 }
 
 thread_local std::string g_policy_error;
+
+// The instantiations a (precision, TPW) choice launches, with and without log-pi.
+template <bool IN_BF16, int TPW, bool X3>
+void launch_policy(const dim3 &g, const dim3 &b, hipStream_t st, const MlpParams &q, const void *obs, float *act, float *log_pi,
+                   float logpi_c)
+{
+    if (log_pi) hipLaunchKernelGGL((k_policy_mlp<IN_BF16, TPW, X3, true>), g, b, kSmemBytes, st, q, obs, act, log_pi, logpi_c);
+    else hipLaunchKernelGGL((k_policy_mlp<IN_BF16, TPW, X3, false>), g, b, kSmemBytes, st, q, obs, act, nullptr, 0.0f);
+}
+
+template <bool IN_BF16, int TPW, bool X3>
+void set_smem()
+{
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<IN_BF16, TPW, X3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<IN_BF16, TPW, X3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
+}
 
 }  // namespace
 
@@ -380,8 +409,10 @@ void swarm_policy_destroy(swarm_policy_t *p)
     delete p;
 }
 
+// log_pi != NULL: the LOGPI instantiation writes log_pi[rows] (the caller has checked the pointer).
 static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int64_t rows, float *act, void *stream,
-                          float noise_scale = 0.0f, uint64_t seed = 0, uint64_t step = 0, uint64_t row_offset = 0)
+                          float noise_scale = 0.0f, uint64_t seed = 0, uint64_t step = 0, uint64_t row_offset = 0,
+                          float *log_pi = nullptr)
 {
     if (!p || !obs || !act || rows < 0) { g_policy_error = "swarm_policy_forward: bad argument"; return SWARM_POLICY_ERR_INVALID; }
     if (in_bf16 && (p->in_dim & 7)) { g_policy_error = "swarm_policy_forward_bf16: in_dim must be a multiple of 8"; return SWARM_POLICY_ERR_INVALID; }
@@ -394,6 +425,8 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
     q.noise_scale = noise_scale > 0.0f ? noise_scale : 0.0f;
     q.noise_key = swarm_noise_key(seed, step);
     q.row_offset = row_offset;
+    // log-pi's constant act_dim * log(noise_scale * sqrt(2 pi)), in double from the fp32 scale the kernel uses (swarm_policy.h)
+    const float logpi_c = q.noise_scale > 0.0f ? (float)((double)p->act_dim * std::log((double)q.noise_scale * std::sqrt(2.0 * M_PI))) : 0.0f;
     // one row tile per wave; the two-tile instantiation (SWARM_POLICY_TPW=2, measurement knob) is slower: 98 vs 87 us on
     // 262144 bf16 rows, 118 vs 106 us on fp32 rows -- one wave per SIMD costs more than the halved LDS reads give back
     int tpw = 1;
@@ -403,25 +436,22 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
     const long long per_block = (long long)n_waves * 32 * tpw;
     const unsigned grid = (unsigned)((rows + per_block - 1) / per_block);
     if (!p->smem_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<false, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<true, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<false, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<true, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<false, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<true, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
+        set_smem<false, 1, false>(); set_smem<true, 1, false>();
+        set_smem<false, 2, false>(); set_smem<true, 2, false>();
+        set_smem<false, 1, true>(); set_smem<true, 1, true>();
         p->smem_set = true;
     }
     const dim3 g(grid), b(64 * n_waves);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (p->precision == 1) {
-        if (in_bf16) hipLaunchKernelGGL((k_policy_mlp<true, 1, true>), g, b, kSmemBytes, st, q, obs, act);
-        else hipLaunchKernelGGL((k_policy_mlp<false, 1, true>), g, b, kSmemBytes, st, q, obs, act);
+        if (in_bf16) launch_policy<true, 1, true>(g, b, st, q, obs, act, log_pi, logpi_c);
+        else launch_policy<false, 1, true>(g, b, st, q, obs, act, log_pi, logpi_c);
     } else if (tpw == 2) {
-        if (in_bf16) hipLaunchKernelGGL((k_policy_mlp<true, 2, false>), g, b, kSmemBytes, st, q, obs, act);
-        else hipLaunchKernelGGL((k_policy_mlp<false, 2, false>), g, b, kSmemBytes, st, q, obs, act);
+        if (in_bf16) launch_policy<true, 2, false>(g, b, st, q, obs, act, log_pi, logpi_c);
+        else launch_policy<false, 2, false>(g, b, st, q, obs, act, log_pi, logpi_c);
     } else {
-        if (in_bf16) hipLaunchKernelGGL((k_policy_mlp<true, 1, false>), g, b, kSmemBytes, st, q, obs, act);
-        else hipLaunchKernelGGL((k_policy_mlp<false, 1, false>), g, b, kSmemBytes, st, q, obs, act);
+        if (in_bf16) launch_policy<true, 1, false>(g, b, st, q, obs, act, log_pi, logpi_c);
+        else launch_policy<false, 1, false>(g, b, st, q, obs, act, log_pi, logpi_c);
     }
     const hipError_t e = hipGetLastError();
     (void)hipSetDevice(prev);
@@ -456,6 +486,13 @@ int swarm_policy_forward_explore_at(swarm_policy_t *p, const void *obs, int obs_
                                     float noise_scale, uint64_t seed, uint64_t step, uint64_t row_offset, void *stream)
 {
     return policy_forward(p, obs, obs_is_bf16 != 0, rows, act, stream, noise_scale, seed, step, row_offset);
+}
+
+int swarm_policy_forward_explore_logpi(swarm_policy_t *p, const void *obs, int obs_is_bf16, int64_t rows, float *act, float *log_pi,
+                                      float noise_scale, uint64_t seed, uint64_t step, uint64_t row_offset, void *stream)
+{
+    if (!log_pi) { g_policy_error = "swarm_policy_forward_explore_logpi: null log_pi (a [rows] fp32 device array is required)"; return SWARM_POLICY_ERR_INVALID; }
+    return policy_forward(p, obs, obs_is_bf16 != 0, rows, act, stream, noise_scale, seed, step, row_offset, log_pi);
 }
 
 }  // extern "C"

@@ -62,9 +62,14 @@ std::string check_ring_slots(const swarm_env_info &ei, const swarm_ring_t *ring)
     return "";
 }
 
+// log-pi of a uniform action on [-1, 1]^2 (agents.py:91: -act_dim * log(2)), rounded to fp32
+constexpr float kLogPiUniform = (float)(-2.0 * 0.69314718055994530942);
+
 // The epsilon branch of agents.py:89-91 (np.random.uniform(-1, 1) per component), counter-based: formula in swarm_rollout.h.
+// LOGPI: also log_pi[row] = kLogPiUniform (a template parameter: the instantiation without it compiles as before).
+template <bool LOGPI>
 __global__ void __launch_bounds__(kThreads) k_uniform_actions(float2 *__restrict__ act, long long rows, unsigned long long ukey,
-                                                              unsigned long long row_offset)
+                                                              unsigned long long row_offset, float *__restrict__ log_pi)
 {
     const long long row = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (row >= rows) return;
@@ -73,6 +78,7 @@ __global__ void __launch_bounds__(kThreads) k_uniform_actions(float2 *__restrict
     a.x = (float)(unsigned)((h >> 40) & 0xFFFFFFull) * 1.1920928955078125e-07f - 1.0f;      // 2^-23
     a.y = (float)(unsigned)((h >> 16) & 0xFFFFFFull) * 1.1920928955078125e-07f - 1.0f;
     act[row] = a;
+    if constexpr (LOGPI) log_pi[row] = kLogPiUniform;
 }
 
 // Number of nonzero rewards of one step, added (one 64-bit atomic per workgroup) to the zeroed counter that shares the
@@ -240,56 +246,55 @@ struct DeviceScope {
 
 }  // namespace
 
-extern "C" {
-
-const char *swarm_rollout_last_error(void) { return g_rollout_error.c_str(); }
-
-int swarm_rollout(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps, const uint8_t *uniform_steps,
-                  float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset, double *reward_stats, void *stream)
+// swarm_rollout (want_logpi = false, log_pi = NULL) and swarm_rollout_logpi (log_pi [n_slots][rows], written per step like act).
+static int rollout_impl(const char *who, bool want_logpi, swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring,
+                        float *log_pi, int32_t steps, const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0,
+                        uint64_t row_offset, double *reward_stats, void *stream)
 {
     // ---- validation: nothing is enqueued before all of it passed
-    if (!env || !pol || !ring) return fail(SWARM_ERR_INVALID, "null env, policy or ring");
+    if (!env || !pol || !ring) return fail(SWARM_ERR_INVALID, "null env, policy or ring", who);
+    if (want_logpi && !log_pi) return fail(SWARM_ERR_INVALID, "null log_pi (a [n_slots][rows] fp32 device array is required)", who);
     swarm_env_info ei;
     swarm_policy_info pi;
     if (swarm_internal_env_info(env, &ei) != SWARM_OK || swarm_internal_policy_info(pol, &pi) != SWARM_POLICY_OK)
-        return fail(SWARM_ERR_INVALID, "bad handle");
+        return fail(SWARM_ERR_INVALID, "bad handle", who);
     char msg[256];
-    if (steps < 0) return fail(SWARM_ERR_INVALID, "steps < 0");
+    if (steps < 0) return fail(SWARM_ERR_INVALID, "steps < 0", who);
     if (ei.device != pi.device) {
         std::snprintf(msg, sizeof msg, "env handle on device %d, policy on device %d", ei.device, pi.device);
-        return fail(SWARM_ERR_INVALID, msg);
+        return fail(SWARM_ERR_INVALID, msg, who);
     }
     if (ei.obs_dtype != SWARM_F32 && ei.obs_dtype != SWARM_BF16)
-        return fail(SWARM_ERR_INVALID, "the env handle's obs dtype must be SWARM_F32 or SWARM_BF16 (the policy reads no fp64 rows)");
+        return fail(SWARM_ERR_INVALID, "the env handle's obs dtype must be SWARM_F32 or SWARM_BF16 (the policy reads no fp64 rows)", who);
     {
         const std::string m = check_ring_shape(ei, ring);
-        if (!m.empty()) return fail(SWARM_ERR_INVALID, m);
+        if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
     }
     const long long rows = (long long)ei.n_env * ei.n_agents;
     if (pi.in_dim != ei.obs_dim) {
         std::snprintf(msg, sizeof msg, "policy in_dim %d != env obs_dim %d", pi.in_dim, ei.obs_dim);
-        return fail(SWARM_ERR_INVALID, msg);
+        return fail(SWARM_ERR_INVALID, msg, who);
     }
-    if (pi.act_dim != 2) return fail(SWARM_ERR_INVALID, "policy act_dim must be 2 (the env's action)");
-    if (ei.obs_dtype == SWARM_BF16 && (pi.in_dim & 7)) return fail(SWARM_ERR_INVALID, "bf16 observation rows need obs_dim % 8 == 0");
+    if (pi.act_dim != 2) return fail(SWARM_ERR_INVALID, "policy act_dim must be 2 (the env's action)", who);
+    if (ei.obs_dtype == SWARM_BF16 && (pi.in_dim & 7)) return fail(SWARM_ERR_INVALID, "bf16 observation rows need obs_dim % 8 == 0", who);
     {
         const std::string m = check_ring_slots(ei, ring);
-        if (!m.empty()) return fail(SWARM_ERR_INVALID, m);
+        if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
     }
-    if (!ei.observed) return fail(SWARM_ERR_STATE, "the env handle is not observed (swarm_observe / swarm_reset first)");
+    if (!ei.observed) return fail(SWARM_ERR_STATE, "the env handle is not observed (swarm_observe / swarm_reset first)", who);
     if (steps == 0) return SWARM_OK;
 
     // ---- enqueue
     DeviceScope dev(ei.device);
-    if (!dev.ok) return fail(SWARM_ERR_HIP, "hipSetDevice failed");
+    if (!dev.ok) return fail(SWARM_ERR_HIP, "hipSetDevice failed", who);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (swarm_set_stream(env, stream) != SWARM_OK) return fail(SWARM_ERR_INVALID, "swarm_set_stream failed");
+    if (swarm_set_stream(env, stream) != SWARM_OK) return fail(SWARM_ERR_INVALID, "swarm_set_stream failed", who);
     const bool bf16 = ei.obs_dtype == SWARM_BF16;
     const size_t obs_slot = (size_t)rows * ei.obs_dim * (bf16 ? 2 : 4), pri_slot = (size_t)rows * 2 * (bf16 ? 2 : 4);
     char *const obs = static_cast<char *>(ring->obs), *const pri = static_cast<char *>(ring->prior);
     if (reward_stats) {
         const hipError_t e = hipMemsetAsync(reward_stats, 0, (size_t)steps * 2 * sizeof(double), st);
-        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e), who);
     }
     const unsigned act_grid = (unsigned)((rows + kThreads - 1) / kThreads);
     const unsigned cnt_grid = (unsigned)std::min<long long>((rows + kThreads * kCountPerThread - 1) / (kThreads * kCountPerThread),
@@ -297,32 +302,58 @@ int swarm_rollout(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *rin
     for (int t = 0; t < steps; ++t) {
         const int c = (int)(((long long)ring->cur + t) % ring->n_slots), n = (c + 1) % ring->n_slots;
         float *const act = ring->act + (size_t)c * rows * 2;
+        float *const lp = log_pi ? log_pi + (size_t)c * rows : nullptr;
         if (uniform_steps && uniform_steps[t]) {
             const unsigned long long ukey = pmix64(swarm_noise_key(seed, step0 + t) ^ kUniformSalt);
-            hipLaunchKernelGGL(k_uniform_actions, dim3(act_grid), dim3(kThreads), 0, st, reinterpret_cast<float2 *>(act), rows, ukey,
-                               (unsigned long long)row_offset);
+            if (lp)
+                hipLaunchKernelGGL(k_uniform_actions<true>, dim3(act_grid), dim3(kThreads), 0, st, reinterpret_cast<float2 *>(act), rows,
+                                   ukey, (unsigned long long)row_offset, lp);
+            else
+                hipLaunchKernelGGL(k_uniform_actions<false>, dim3(act_grid), dim3(kThreads), 0, st, reinterpret_cast<float2 *>(act), rows,
+                                   ukey, (unsigned long long)row_offset, nullptr);
             const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_uniform_actions: ") + hipGetErrorString(e));
-        } else if (swarm_policy_forward_explore_at(pol, obs + c * obs_slot, bf16, rows, act, noise_scale, seed, step0 + t, row_offset,
-                                                   stream) != SWARM_POLICY_OK) {
-            return fail(SWARM_ERR_HIP, swarm_policy_last_error());
+            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_uniform_actions: ") + hipGetErrorString(e), who);
+        } else if ((lp ? swarm_policy_forward_explore_logpi(pol, obs + c * obs_slot, bf16, rows, act, lp, noise_scale, seed, step0 + t,
+                                                            row_offset, stream)
+                       : swarm_policy_forward_explore_at(pol, obs + c * obs_slot, bf16, rows, act, noise_scale, seed, step0 + t,
+                                                         row_offset, stream)) != SWARM_POLICY_OK) {
+            return fail(SWARM_ERR_HIP, swarm_policy_last_error(), who);
         }
         const int rc = swarm_step(env, act, SWARM_F32, obs + n * obs_slot, ring->rew + (size_t)c * rows, ring->done + (size_t)c * rows,
                                   pri ? pri + c * pri_slot : nullptr);
-        if (rc != SWARM_OK) return fail(rc, swarm_last_error(env));
+        if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
         if (reward_stats) {
             hipLaunchKernelGGL(k_reward_count, dim3(cnt_grid), dim3(kThreads), 0, st, ring->rew + (size_t)c * rows, rows,
                                reinterpret_cast<unsigned long long *>(reward_stats + 2 * t));
             const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_count: ") + hipGetErrorString(e));
+            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_count: ") + hipGetErrorString(e), who);
         }
     }
     if (reward_stats) {
         hipLaunchKernelGGL(k_reward_stats, dim3((steps + kThreads - 1) / kThreads), dim3(kThreads), 0, st, reward_stats, (int)steps, rows);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_stats: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_stats: ") + hipGetErrorString(e), who);
     }
     return SWARM_OK;
+}
+
+extern "C" {
+
+const char *swarm_rollout_last_error(void) { return g_rollout_error.c_str(); }
+
+int swarm_rollout(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps, const uint8_t *uniform_steps,
+                  float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset, double *reward_stats, void *stream)
+{
+    return rollout_impl("swarm_rollout", false, env, pol, ring, nullptr, steps, uniform_steps, noise_scale, seed, step0, row_offset,
+                        reward_stats, stream);
+}
+
+int swarm_rollout_logpi(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, float *log_pi, int32_t steps,
+                        const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset,
+                        double *reward_stats, void *stream)
+{
+    return rollout_impl("swarm_rollout_logpi", true, env, pol, ring, log_pi, steps, uniform_steps, noise_scale, seed, step0, row_offset,
+                        reward_stats, stream);
 }
 
 int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t steps, int32_t source, double *reward_stats, void *stream)

@@ -10,7 +10,8 @@ ring buffer (train_assembly.py:91-111, maddpg.py:72-87, agents.py:69-96, buffer_
 * `DeviceReplay`  -- the ring buffer of buffer_agent.py:13-128 with one row per (env, agent) transition, as device tensors.
 * `ChainedReplay` -- the same transitions stored as a ring of env steps that share observation rows (half the copy per push).
 * `rollout`       -- obs -> policy -> exploration noise (agents.py:82-96 continuous branch) -> env.step_tensor -> push.
-* `rollout_device`-- the same loop (fused policy, chained ring) as ONE library call per episode: swarm_rollout.
+* `rollout_device`-- the same loop (fused policy, chained ring) as ONE library call per episode: swarm_rollout; with
+                     log_pi=True also each action's log-probability (swarm_rollout_logpi), the AIRL agent side's log_pi.
 * `rollout_expert`-- expert rollouts (rule-based expert or the prior's 'llm' twin) into the same ring, one library call per
                      episode batch: swarm_rollout_expert (collect_expert_data.py's loop on the device).
 * `save_expert_data` -- a ring's transitions as the expert_data.npz that ReplayBufferExpert.load reads (train_assembly_airl.py).
@@ -79,11 +80,14 @@ class FusedPolicy:
         if self.lib.swarm_policy_set_precision(self.handle, 1 if self.precision == "bf16x3" else 0) != 0:
             raise RuntimeError("swarm_policy_set_precision failed: " + self.lib.swarm_policy_last_error().decode())
 
-    def __call__(self, obs, out=None, noise_scale=0.0, seed=0, step=0):
+    def __call__(self, obs, out=None, noise_scale=0.0, seed=0, step=0, log_pi=None, row_offset=0):
         """obs [rows, in_dim] float32 or bfloat16 on the device (contiguous) -> actions [rows, act_dim] float32.
         noise_scale > 0: the exploring actor of agents.py:93-96 in the same launch -- clamp(action + noise_scale * N(0, 1),
-        -1, 1) with a counter-based generator keyed by (seed, step, row).  out: where to write (a contiguous float32
-        tensor of rows * act_dim elements, e.g. a replay-ring slot)."""
+        -1, 1) with a counter-based generator keyed by (seed, step, row_offset + row).  out: where to write (a contiguous
+        float32 tensor of rows * act_dim elements, e.g. a replay-ring slot).
+        log_pi: a contiguous float32 tensor of `rows` elements on the device, or True to allocate one -- the kernel also
+        writes each row's log-probability of its noise (GaussianNoise.log_prob, include/swarm_policy.h; -0.0 without
+        noise) and the call returns (actions, log_pi [rows]).  The actions are the same bits either way."""
         if (obs.dtype not in (torch.float32, torch.bfloat16) or not obs.is_contiguous() or obs.device != self.device
                 or obs.shape[-1] != self.in_dim):
             raise ValueError("FusedPolicy expects a contiguous float32 / bfloat16 [rows, %d] tensor on %s" % (self.in_dim, self.device))
@@ -92,12 +96,24 @@ class FusedPolicy:
             out = torch.empty((rows, self.act_dim), dtype=torch.float32, device=self.device)
         elif (out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or out.numel() != rows * self.act_dim):
             raise ValueError("out must be a contiguous float32 tensor of %d elements on %s" % (rows * self.act_dim, self.device))
+        if log_pi is True:
+            log_pi = torch.empty(rows, dtype=torch.float32, device=self.device)
+        elif log_pi is not None and (not isinstance(log_pi, torch.Tensor) or log_pi.dtype != torch.float32 or log_pi.device != self.device
+                                     or not log_pi.is_contiguous() or log_pi.numel() != rows):
+            raise ValueError("log_pi must be True or a contiguous float32 tensor of %d elements on %s" % (rows, self.device))
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self.lib.swarm_policy_forward_explore(self.handle, obs.data_ptr(), int(obs.dtype == torch.bfloat16), rows, out.data_ptr(),
-                                                   float(noise_scale), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), stream)
+        m64 = 2 ** 64 - 1
+        args = (float(noise_scale), int(seed) & m64, int(step) & m64, int(row_offset) & m64, stream)
+        if log_pi is None:
+            rc = self.lib.swarm_policy_forward_explore_at(self.handle, obs.data_ptr(), int(obs.dtype == torch.bfloat16), rows,
+                                                          out.data_ptr(), *args)
+        else:
+            rc = self.lib.swarm_policy_forward_explore_logpi(self.handle, obs.data_ptr(), int(obs.dtype == torch.bfloat16), rows,
+                                                             out.data_ptr(), log_pi.data_ptr(), *args)
         if rc != 0:
             raise RuntimeError("swarm_policy_forward failed: " + self.lib.swarm_policy_last_error().decode())
-        return out.view(rows, self.act_dim)
+        act = out.view(rows, self.act_dim)
+        return act if log_pi is None else (act, log_pi.view(rows))
 
     def close(self):
         if self.handle is not None:
@@ -177,27 +193,32 @@ class ChainedReplay:
 
     Episode boundaries without loss: `new_chain()` SEALS the ring instead -- the slot that holds the last next_obs of the
     previous chain is kept, marked as no transition start (sample() and len() skip it), and the new chain starts in the
-    slot after it (rollout_device does this on every reset).  A ring that was never sealed samples exactly as before."""
+    slot after it (rollout_device does this on every reset).  A ring that was never sealed samples exactly as before.
 
-    def __init__(self, n_steps, rows_per_step, obs_dim, act_dim, device, obs_dtype=torch.float32):
+    log_pi=True adds a [S, n, 1] float32 column: the log-probability of each transition's exploring action (the
+    log_pi_orig of buffer_agent.py's push, what AIRL's discriminator subtracts), returned by sample(is_log_pi=True)."""
+
+    def __init__(self, n_steps, rows_per_step, obs_dim, act_dim, device, obs_dtype=torch.float32, log_pi=False):
         self.K, self.S, self.n = int(n_steps), int(n_steps) + 1, int(rows_per_step)
         z = lambda d, dt=torch.float32: torch.zeros((self.S, self.n, d), dtype=dt, device=device)
         self.obs = z(obs_dim, obs_dtype)
         # act_prior in the env's output dtype and done as the env's uint8, so that a step can write them in place
         self.act, self.act_prior = z(act_dim), z(act_dim, obs_dtype)
         self.rew, self.done = z(1), z(1, torch.uint8)
+        self.log_pi = z(1) if log_pi else None
         self.cur, self.count, self._chained = 0, 0, False
         self._sealed = set()        # slots that hold a chain's last next_obs but start no transition (new_chain)
 
     # zero-copy use (rollout's fused path): the policy writes its action and the env step its outputs straight into the slots
     def begin_step(self, obs):
         """Slots of the transition about to be taken: dict(obs_in = observation rows of the current slot (copied from
-        `obs` unless the chain already holds them), act, rew, done, prior, next_obs).  Follow with end_step()."""
+        `obs` unless the chain already holds them), act, rew, done, prior, next_obs, log_pi (None without the column)).
+        Follow with end_step()."""
         c, nx = self.cur, (self.cur + 1) % self.S
         if not self._chained:
             self.obs[c].copy_(obs.reshape(self.n, -1))
         return dict(obs_in=self.obs[c], act=self.act[c], rew=self.rew[c], done=self.done[c], prior=self.act_prior[c],
-                    next_obs=self.obs[nx])
+                    next_obs=self.obs[nx], log_pi=self.log_pi[c] if self.log_pi is not None else None)
 
     def end_step(self):
         self._sealed.discard(self.cur)
@@ -237,10 +258,13 @@ class ChainedReplay:
         w = [(self.cur - 1 - b) % self.S for b in range(self.count)]
         return [j for j in w if j not in self._sealed]
 
-    def push(self, obs, act, rew, next_obs, done, act_prior=None):
+    def push(self, obs, act, rew, next_obs, done, act_prior=None, log_pi=None):
+        """log_pi [E,N] / [E,N,1] (or any shape of n elements): stored in the log-pi column (the ring must have one)."""
         n = self.n
         if obs.shape[0] * obs.shape[1] != n:
             raise ValueError("ChainedReplay takes whole env steps of %d rows" % n)
+        if log_pi is not None and (self.log_pi is None or log_pi.numel() != n):
+            raise ValueError("push(log_pi=): the ring needs log_pi=True and %d values per step" % n)
         c, nx = self.cur, (self.cur + 1) % self.S
         self._sealed.discard(c)
         if not self._chained:
@@ -250,9 +274,15 @@ class ChainedReplay:
         self.rew[c] = rew.reshape(n, 1); self.done[c] = done.reshape(n, 1).to(self.done.dtype)
         if act_prior is not None:
             self.act_prior[c] = act_prior.reshape(n, -1).to(self.act_prior.dtype)
+        if log_pi is not None:
+            self.log_pi[c] = log_pi.reshape(n, 1)
         self.cur, self.count, self._chained = nx, min(self.count + 1, self.K), True
 
-    def sample(self, batch, generator=None):
+    def sample(self, batch, generator=None, is_log_pi=False):
+        """(obs, act, rew, next_obs, done, act_prior) of `batch` uniform transitions; is_log_pi=True appends their log-pi
+        [batch, 1] float32 -- the 7-tuple of buffer_agent.py's sample(..., is_log_pi=True)."""
+        if is_log_pi and self.log_pi is None:
+            raise ValueError("sample(is_log_pi=True) needs a ChainedReplay built with log_pi=True")
         dev = self.obs.device
         valid = self._valid_starts() if self._sealed else None
         if valid is None or len(valid) == self.count:
@@ -265,13 +295,34 @@ class ChainedReplay:
             j = torch.tensor(valid, device=dev)[pick]
         r = torch.randint(0, self.n, (batch,), device=dev, generator=generator)
         jn = (j + 1) % self.S
-        return (self.obs[j, r], self.act[j, r], self.rew[j, r], self.obs[jn, r], self.done[j, r].to(torch.float32),
-                self.act_prior[j, r].to(torch.float32))
+        out = (self.obs[j, r], self.act[j, r], self.rew[j, r], self.obs[jn, r], self.done[j, r].to(torch.float32),
+               self.act_prior[j, r].to(torch.float32))
+        return out + (self.log_pi[j, r],) if is_log_pi else out
+
+
+# log-pi of a uniform action on [-1, 1]^2 (agents.py:91: -act_dim * log(2)) in fp32: what a coin step records
+LOG_PI_UNIFORM = float(np.float32(-2.0 * np.log(2.0)))
+
+
+def gaussian_log_pi(z, noise_scale):
+    """GaussianNoise.log_prob (utils/noise.py) of the noise noise_scale * z, as include/swarm_policy.h states it for the fused
+    kernel: z [rows, act_dim] float32 normals -> [rows] float32 -(0.5 * sum_k z_k^2) - c, the sum in k order, c the fp32
+    rounding of act_dim * log(fp32(noise_scale) * sqrt(2 pi)) evaluated in double; noise_scale <= 0: -0.0."""
+    import math
+    rows, act_dim = z.shape
+    if not noise_scale > 0:
+        return torch.full((rows,), -0.0, dtype=torch.float32, device=z.device)
+    c = float(np.float32(act_dim * math.log(float(np.float32(noise_scale)) * math.sqrt(2.0 * math.pi))))
+    z = z.float()
+    s = z[:, 0] * z[:, 0]
+    for k in range(1, act_dim):
+        s = s + z[:, k] * z[:, k]
+    return -(0.5 * s) - c
 
 
 @torch.no_grad()
 def rollout(env, policy, steps, obs, replay=None, noise_scale=0.0, epsilon=0.0, generator=None, host_rng=None,
-            track_reward=True, seed=0, step0=0):
+            track_reward=True, seed=0, step0=0, log_pi=False):
     """Run `steps` env steps entirely on the device.
 
     env   : object with step_tensor(action[E,N,2]) -> (obs[E,N,D], rew[E,N], done[E,N], a_prior[E,N,2]|None)
@@ -286,9 +337,14 @@ def rollout(env, policy, steps, obs, replay=None, noise_scale=0.0, epsilon=0.0, 
     and writes the action into the replay slot; the env step writes next_obs / reward / done / prior into the ring.
     Everywhere else: the policy's action + torch noise, then `replay.push`.
     track_reward: also return the mean reward of every step ([steps] tensor; one small reduction per step).
+    log_pi: also store each transition's log-probability of its exploring action (agents.py:78-96's log_pi) in the ring's
+            log-pi column -- the fused kernel's (FusedPolicy), gaussian_log_pi of the torch normals (any other module), or
+            LOG_PI_UNIFORM on a coin step.  Needs a ChainedReplay built with log_pi=True.
     Returns (last obs, mean reward per step tensor [steps] or None)."""
     import numpy as np
     from .batched import SwarmBatch
+    if log_pi and not (isinstance(replay, ChainedReplay) and replay.log_pi is not None):
+        raise ValueError("rollout(log_pi=True) needs a ChainedReplay built with log_pi=True")
     step = env.step_tensor if hasattr(env, "step_tensor") else env.step
     E, N, D = obs.shape
     rews = torch.zeros(steps, device=obs.device) if track_reward else None
@@ -300,8 +356,11 @@ def rollout(env, policy, steps, obs, replay=None, noise_scale=0.0, epsilon=0.0, 
             sl = replay.begin_step(obs)
             if explore_uniform:
                 sl["act"].copy_(torch.rand((E * N, policy.act_dim), device=obs.device, generator=generator) * 2 - 1)
+                if log_pi:
+                    sl["log_pi"].fill_(LOG_PI_UNIFORM)
             else:
-                policy(sl["obs_in"], out=sl["act"], noise_scale=noise_scale, seed=seed, step=step0 + t)
+                policy(sl["obs_in"], out=sl["act"], noise_scale=noise_scale, seed=seed, step=step0 + t,
+                       log_pi=sl["log_pi"].view(-1) if log_pi else None)
             next_obs, rew, done, pri = env.step(sl["act"].view(E, N, 2),
                                                 out=dict(obs=sl["next_obs"], rew=sl["rew"], done=sl["done"], prior=sl["prior"]))
             replay.end_step()
@@ -309,18 +368,30 @@ def rollout(env, policy, steps, obs, replay=None, noise_scale=0.0, epsilon=0.0, 
             x = obs.reshape(E * N, D)
             if x.dtype != torch.float32 and not (x.dtype == torch.bfloat16 and isinstance(policy, FusedPolicy)):
                 x = x.float()
+            lp = None
             if explore_uniform:
                 act = torch.rand((E * N, 2), device=obs.device, generator=generator) * 2 - 1
+                if log_pi:
+                    lp = torch.full((E * N,), LOG_PI_UNIFORM, device=obs.device)
             elif isinstance(policy, FusedPolicy):
-                act = policy(x, noise_scale=noise_scale, seed=seed, step=step0 + t)                   # noise in the kernel's epilogue
+                act = policy(x, noise_scale=noise_scale, seed=seed, step=step0 + t, log_pi=True if log_pi else None)  # noise in the kernel's epilogue
+                if log_pi:
+                    act, lp = act
             else:
                 act = policy(x)
+                z = None
                 if noise_scale > 0:                                                                    # agents.py:93-96
-                    act = (act + noise_scale * torch.randn(act.shape, device=obs.device, generator=generator)).clamp_(-1, 1)
+                    z = torch.randn(act.shape, device=obs.device, generator=generator)
+                    act = (act + noise_scale * z).clamp_(-1, 1)
+                if log_pi:
+                    lp = gaussian_log_pi(z if z is not None else act, noise_scale)
             act = act.reshape(E, N, 2)
             next_obs, rew, done, pri = step(act)
             if replay is not None:
-                replay.push(obs, act, rew, next_obs, done, pri)
+                if log_pi:
+                    replay.push(obs, act, rew, next_obs, done, pri, log_pi=lp)
+                else:
+                    replay.push(obs, act, rew, next_obs, done, pri)
         if track_reward:
             rews[t] = rew.mean()
         obs = next_obs
@@ -334,7 +405,7 @@ def _is_view_of(t, slot):
 
 @torch.no_grad()
 def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, epsilon=0.0, host_rng=None, seed=0, step0=0,
-                   row_offset=0, reset=None, track_reward=True):
+                   row_offset=0, reset=None, track_reward=True, log_pi=False):
     """`steps` exploring-actor + env steps in ONE library call (swarm_rollout, include/swarm_rollout.h): the launches are
     enqueued on torch's current stream and the call returns without a host synchronisation.
 
@@ -348,8 +419,13 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
                starts a new chain through replay.new_chain(): the stored transitions keep their true next_obs.
     epsilon  : the coin of agents.py:89-91, drawn on the host before the call, one host_rng.random() per step (the order and
                count rollout() uses); a coin step takes counter-based uniform actions instead of the policy.
+    log_pi   : also record each transition's log-probability of its exploring action (swarm_rollout_logpi) in the ring's
+               log-pi column: the policy kernel's (include/swarm_policy.h) or LOG_PI_UNIFORM on a coin step -- what
+               train_assembly_airl.py pushes as log_pi_orig.  The ring must be built with log_pi=True (the private ring
+               gets the column on request); the actions and the rest of the ring are the same bits as without it.
     Returns (obs [E,N,D] -- the ring slot of the last next_obs --, reward_stats [steps, 2] float64 (mean, population std
-    per step; train_assembly.py:109-110) or None).  On error nothing is enqueued, the ring is unchanged, SwarmError raises."""
+    per step; train_assembly.py:109-110) or None).  On error nothing is enqueued, the ring is unchanged, SwarmError raises
+    (ValueError for a ring without the log-pi column)."""
     import ctypes
     import numpy as np
     from . import _lib
@@ -362,16 +438,21 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
     if steps < 0:
         raise ValueError("steps must be >= 0")
     E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
-    replay = _device_ring(sb, replay)
+    replay = _device_ring(sb, replay, log_pi)
+    if log_pi and replay.log_pi is None:
+        raise ValueError("rollout_device(log_pi=True) needs a ChainedReplay built with log_pi=True")
     lib = _lib.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
 
     def call(k, coins, stats):
         ring = _ring_struct(sb, replay)
-        rc = lib.swarm_rollout(sb.handle, policy.handle, ctypes.byref(ring), k,
-                               coins.ctypes.data_as(ctypes.c_void_p) if coins is not None else None, float(noise_scale),
-                               int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1),
-                               ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, stream)
+        tail = (k, coins.ctypes.data_as(ctypes.c_void_p) if coins is not None else None, float(noise_scale),
+                int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1),
+                ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, stream)
+        if log_pi:
+            rc = lib.swarm_rollout_logpi(sb.handle, policy.handle, ctypes.byref(ring), ctypes.c_void_p(replay.log_pi.data_ptr()), *tail)
+        else:
+            rc = lib.swarm_rollout(sb.handle, policy.handle, ctypes.byref(ring), *tail)
         _check_rollout(lib, rc, k, reset)
 
     _begin_chain(sb, replay, obs, reset, lambda: call(0, None, None), "rollout_device")
@@ -400,12 +481,14 @@ def _device_env(env, who, strategy_ok, strategy_msg, reset):
     raise TypeError("env must be a SwarmBatch or an AssemblySwarmEnv")
 
 
-def _device_ring(sb, replay):
-    """The caller's ChainedReplay, or the private two-slot ring kept on the env."""
+def _device_ring(sb, replay, log_pi=False):
+    """The caller's ChainedReplay, or the private two-slot ring kept on the env (given a log-pi column if log_pi)."""
     if replay is None:
         replay = getattr(sb, "_rollout_ring", None)
         if replay is None:
             replay = sb._rollout_ring = ChainedReplay(1, sb.n_env * sb.n_agents, sb.obs_dim, 2, sb.device, obs_dtype=sb.obs_dtype)
+        if log_pi and replay.log_pi is None:
+            replay.log_pi = torch.zeros((replay.S, replay.n, 1), dtype=torch.float32, device=sb.device)
     elif not isinstance(replay, ChainedReplay):
         raise TypeError("replay must be a ChainedReplay (or None)")
     return replay
