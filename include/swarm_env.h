@@ -129,10 +129,19 @@ int  swarm_set_state(swarm_env_t *h, const double *p, const double *dp);   /* [E
  * env range reproducible on any rank -- and runs the observation pass (obs may be NULL). */
 int  swarm_set_shapes(swarm_env_t *h, int n_shapes, const double *shape_cells, const int32_t *n_g, const double *l_cell);
 int  swarm_reset(swarm_env_t *h, uint64_t seed, uint64_t episode, int64_t env_offset, void *obs);
+/* Device-side shape switch (what eval_assembly.py:34-57 process_shape does in mid-episode, with its rotation 0 and offset 0):
+ * every env takes shape `shape_index` of the set uploaded by swarm_set_shapes, at the set's own pose -- the env's cells are the
+ * shape's cells, the same doubles.  One kernel on the handle's stream writes the cells, n_g, the in-shape cut-off, the lattice
+ * record and the shape index of every env; p / dp are untouched.  Then the observation pass runs (obs may be NULL: the carried
+ * prior and the neighbour caches are refreshed, no observation is written).  Afterwards the handle is bit for bit in the state
+ * that swarm_set_cells with E copies of that shape followed by swarm_observe leaves (swarm_get_shape_index then reports
+ * shape_index instead of -1).  No host synchronisation, no host-to-device copy, no allocation.
+ * SWARM_ERR_STATE without a shape set or a state, SWARM_ERR_INVALID for an index outside [0, n_shapes): nothing is enqueued. */
+int  swarm_select_shape(swarm_env_t *h, int32_t shape_index, void *obs);
 int  swarm_get_state(swarm_env_t *h, double *p, double *dp);
 int  swarm_get_cells(swarm_env_t *h, double *cells, int32_t *n_g);        /* [E][2][n_cells_max], [E]; host or device */
-/* Shape index each env drew in the last swarm_reset (assembly.py:160 `rand_shape_index`), [E] host or device; -1 for envs whose
- * cells were set through swarm_set_cells.  The host needs it for l_cell / shape_frequency (assembly.py:161-163). */
+/* Shape index each env drew in the last swarm_reset (assembly.py:160 `rand_shape_index`) or was given by swarm_select_shape,
+ * [E] host or device; -1 for envs whose cells were set through swarm_set_cells.  The host needs it for l_cell / shape_frequency (assembly.py:161-163). */
 int  swarm_get_shape_index(swarm_env_t *h, int32_t *shape_index);
 
 /* Recompute observations and the obs-derived caches (neighbor_index, in_flags, nearest cell) from the
@@ -190,8 +199,9 @@ int  swarm_get_indices(swarm_env_t *h, int32_t *neighbor_index, int32_t *in_flag
                        int32_t *sensed_index, int32_t *occupied_index);
 
 /* How many environments currently have target cells that are a row-major subset of a square lattice (the reference's
- * tiled shapes always are, its seven fig PNGs included).  When ALL do (and n_agents <= 64), the sensed / occupied bit sets are built by a row walk
- * over the lattice instead of the all-cells scan; results are identical.  debug_flags bit 1 disables that path. */
+ * tiled shapes always are, its seven fig PNGs included).  When ALL do (any n_agents up to 256; the sensing window must span at most 15
+ * lattice rows), the sensed / occupied bit sets are built by a row walk over the lattice instead of the all-cells scan; results are
+ * identical.  debug_flags bit 1 disables that path. */
 int  swarm_lattice_envs(const swarm_env_t *h);
 
 /* Roofline helper: bytes one swarm_step moves by SURVEY.md section 8d's accounting IN THIS BUILD'S DTYPES (fp64 state and

@@ -92,7 +92,34 @@ enum { SWARM_EXPERT_RULE = 0, SWARM_EXPERT_LLM = 1 };
 int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t steps, int32_t source, double *reward_stats,
                          void *stream);
 
-/* Message of the last failing swarm_rollout / swarm_rollout_logpi / swarm_rollout_expert on the calling thread. */
+/* Evaluation rollouts (the reference's eval_assembly.py:119-205: the deterministic actor, the three wrapper metrics and the
+ * state trace every step, target-shape switches in mid-episode).  Enqueues `steps` evaluation steps on `stream`; per step t,
+ * in the script's order (:145-186), with c and n as above:
+ *   1. p / dp given: p[t], dp[t] = the env's state BEFORE the step (:150-151; device-to-device copies);
+ *   2. switch_to[t] >= 0: swarm_select_shape(env, switch_to[t], NULL) (:154-157).  The ring slot obs[c] is NOT rewritten: the
+ *      reference's actor at a switch step sees the observation the previous env.step returned, computed against the old
+ *      shape (:177-185);
+ *   3. metrics given: metrics[t] = swarm_metrics of the current state against the cells now in force (:160-162);
+ *   4. act[c] = the policy on obs[c] without noise (explore=False, :178: swarm_policy_forward_explore_at with noise_scale 0),
+ *      at the precision the policy handle is set to;
+ *   5. swarm_step writes obs[n], rew[c], done[c] and prior[c]; reward_stats[t] as in swarm_rollout.
+ * Without switches, metrics and trace the ring is bit for bit what swarm_rollout writes with noise_scale 0 and no uniform
+ * steps.  A two-slot ring is enough for evaluation; a long ring records the evaluation transitions.
+ * switch_to: HOST [steps], -1 = keep, s >= 0 = every env switches to shape s of the uploaded set; NULL = no switch.
+ * out: the optional outputs, all DEVICE pointers (NULL = all off).
+ * Checks as swarm_rollout, plus: every switch_to[t] in [-1, n_shapes) (SWARM_ERR_INVALID), a shape set if any entry is >= 0
+ * (SWARM_ERR_STATE), p and dp given together.  A rejected call enqueues nothing and leaves the handle as it was; the message
+ * is in swarm_rollout_last_error.  No host synchronisation, no allocation, no graph capture. */
+typedef struct swarm_eval_out {
+    double *metrics;        /* [steps][E][3]: coverage_rate, distribution_uniformity, voronoi_based_uniformity; NULL = off */
+    double *p, *dp;         /* [steps][E][2][N]: the state before step t; both or neither */
+    double *reward_stats;   /* [steps][2] as swarm_rollout; NULL = off */
+} swarm_eval_out_t;
+int swarm_rollout_eval(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps, const int32_t *switch_to,
+                       const swarm_eval_out_t *out, void *stream);
+
+/* Message of the last failing swarm_rollout / swarm_rollout_logpi / swarm_rollout_expert / swarm_rollout_eval on the calling
+ * thread. */
 const char *swarm_rollout_last_error(void);
 
 #ifdef __cplusplus

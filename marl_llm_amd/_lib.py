@@ -33,6 +33,10 @@ class SwarmRing(ctypes.Structure):               # include/swarm_rollout.h swarm
                 ("n_slots", ctypes.c_int32), ("cur", ctypes.c_int32)]
 
 
+class SwarmEvalOut(ctypes.Structure):            # include/swarm_rollout.h swarm_eval_out_t
+    _fields_ = [("metrics", ctypes.c_void_p), ("p", ctypes.c_void_p), ("dp", ctypes.c_void_p), ("reward_stats", ctypes.c_void_p)]
+
+
 class SwarmError(RuntimeError):
     pass
 
@@ -44,12 +48,13 @@ BATCHED_SYMBOLS = ("swarm_abi_version", "swarm_default_config", "swarm_create", 
                    "swarm_set_stream", "swarm_synchronize", "swarm_obs_dim", "swarm_set_cells", "swarm_set_state",
                    "swarm_get_state", "swarm_observe", "swarm_step", "swarm_get_indices",
                    "swarm_step_algorithmic_bytes", "swarm_timer_start", "swarm_timer_stop", "swarm_lattice_envs", "swarm_set_shapes", "swarm_reset", "swarm_get_cells", "swarm_get_shape_index", "swarm_metrics", "swarm_rule_action",
-                   "swarm_host_outputs", "swarm_observe_host", "swarm_step_host", "swarm_get_llm_action")
+                   "swarm_host_outputs", "swarm_observe_host", "swarm_step_host", "swarm_get_llm_action", "swarm_select_shape")
 POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_destroy", "swarm_policy_forward", "swarm_policy_forward_bf16",
                   "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_forward_explore_logpi",
                   "swarm_policy_set_precision",
                   "swarm_policy_last_error")   # include/swarm_policy.h
-ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_logpi", "swarm_rollout_expert", "swarm_rollout_last_error")   # include/swarm_rollout.h
+ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_logpi", "swarm_rollout_expert", "swarm_rollout_eval",
+                   "swarm_rollout_last_error")   # include/swarm_rollout.h
 LEGACY_SYMBOLS = ("_get_observation", "_get_reward", "_sf_b2b_all", "_get_dist_b2w", "calculateActionPrior",
                   "swarm_legacy_status", "swarm_legacy_last_error")
 
@@ -102,6 +107,9 @@ def load():
     lib.swarm_rollout_logpi.restype = i32
     lib.swarm_rollout_expert.argtypes = [vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, ctypes.c_int32, vp, vp]
     lib.swarm_rollout_expert.restype = i32
+    lib.swarm_rollout_eval.argtypes = [vp, vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, vp, ctypes.POINTER(SwarmEvalOut), vp]
+    lib.swarm_rollout_eval.restype = i32
+    lib.swarm_select_shape.argtypes = [vp, ctypes.c_int32, vp]; lib.swarm_select_shape.restype = i32
     lib.swarm_rollout_last_error.argtypes = []; lib.swarm_rollout_last_error.restype = ctypes.c_char_p
     lib.swarm_policy_set_precision.argtypes = [vp, i32]; lib.swarm_policy_set_precision.restype = i32
     lib.swarm_policy_last_error.argtypes = []; lib.swarm_policy_last_error.restype = ctypes.c_char_p

@@ -65,6 +65,8 @@ class SwarmBatch:
         self._pri = [torch.empty((E, N, 2), dtype=obs_dtype, device=self.device) for _ in range(2)]
         self._done = torch.zeros((E, N), dtype=torch.uint8, device=self.device)
         self._flip = 0
+        self.n_shapes = 0                # shapes of the uploaded set (set_shapes)
+        self.shape_in_force = -1         # the shape every env was switched to (select_shape / rollout_eval), else -1
 
     # -- plumbing -----------------------------------------------------------------------------------
     def _sync_stream(self):
@@ -102,6 +104,7 @@ class SwarmBatch:
         check(self.lib, self.handle, self.lib.swarm_set_cells(self.handle, int(env_begin), count, cptr,
                                                               n_g.ctypes.data_as(ctypes.c_void_p),
                                                               l_cell.ctypes.data_as(ctypes.c_void_p)))
+        self.shape_in_force = -1
 
     def set_shapes(self, results):
         """Upload a shape set (the reference's results.pkl layout: 'grid_coords' list of (n_g, 2), 'l_cell' list)
@@ -118,6 +121,23 @@ class SwarmBatch:
         check(self.lib, self.handle, self.lib.swarm_set_shapes(self.handle, S, cells.ctypes.data_as(ctypes.c_void_p),
                                                                n_g.ctypes.data_as(ctypes.c_void_p),
                                                                l_cell.ctypes.data_as(ctypes.c_void_p)))
+        self.n_shapes = S
+
+    def select_shape(self, index, out=None):
+        """Device-side shape switch (swarm_select_shape): every env takes shape `index` of the uploaded set at the set's own
+        pose, the state stays, and the observation pass runs -- the handle is then in the state
+        `set_cells(E copies of the shape); observe()` leaves, without a host upload or a synchronisation.  Returns the
+        observation tensor (the batch's own buffer, or `out`, a caller-owned obs tensor as in reset())."""
+        if out is not None:
+            obs = self._out_ptrs(dict(obs=out))["obs"].view(self.n_env, self.n_agents, self.obs_dim)
+        else:
+            obs = self._obs[self._flip ^ 1]
+        self._sync_stream()
+        check(self.lib, self.handle, self.lib.swarm_select_shape(self.handle, int(index), _ptr(obs)))
+        if out is None:
+            self._flip ^= 1
+        self.shape_in_force = int(index)
+        return obs
 
     def reset(self, seed, episode=0, env_offset=0, out=None):
         """Batched device-side reset (swarm_reset): returns the first observation tensor.  out: a caller-owned obs tensor
@@ -129,6 +149,7 @@ class SwarmBatch:
             obs = self._obs[self._flip]
         self._sync_stream()
         check(self.lib, self.handle, self.lib.swarm_reset(self.handle, int(seed), int(episode), int(env_offset), _ptr(obs)))
+        self.shape_in_force = -1         # every env drew its own shape
         return obs
 
     def get_cells(self):

@@ -3,7 +3,8 @@
 // policy kernel (policy_mlp.hip) or the uniform-action kernel below, the env step (swarm_env.hip) and, optionally, the
 // reward-count kernel below, all on one stream; the reward statistics are finished by one launch after the loop.
 // swarm_rollout_expert is the same loop with an expert in place of the policy: the rule-based expert kernel below (after the
-// env's index-export observation pass) or a copy of the env's own 'llm' action.
+// env's index-export observation pass) or a copy of the env's own 'llm' action.  swarm_rollout_eval is the evaluation loop:
+// the actor without noise, and per step a state trace, an optional device-side shape switch and the wrapper metrics.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -423,6 +424,107 @@ int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t ste
     }
     if (reward_stats) {
         hipLaunchKernelGGL(k_reward_stats, dim3((steps + kThreads - 1) / kThreads), dim3(kThreads), 0, st, reward_stats, (int)steps, rows);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_stats: ") + hipGetErrorString(e), who);
+    }
+    return SWARM_OK;
+}
+
+int swarm_rollout_eval(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps, const int32_t *switch_to,
+                       const swarm_eval_out_t *out, void *stream)
+{
+    static const char *const who = "swarm_rollout_eval";
+    // ---- validation: nothing is enqueued before all of it passed
+    if (!env || !pol || !ring) return fail(SWARM_ERR_INVALID, "null env, policy or ring", who);
+    swarm_env_info ei;
+    swarm_policy_info pi;
+    if (swarm_internal_env_info(env, &ei) != SWARM_OK || swarm_internal_policy_info(pol, &pi) != SWARM_POLICY_OK)
+        return fail(SWARM_ERR_INVALID, "bad handle", who);
+    char msg[256];
+    if (steps < 0) return fail(SWARM_ERR_INVALID, "steps < 0", who);
+    if (ei.device != pi.device) {
+        std::snprintf(msg, sizeof msg, "env handle on device %d, policy on device %d", ei.device, pi.device);
+        return fail(SWARM_ERR_INVALID, msg, who);
+    }
+    {
+        std::string m = check_ring_shape(ei, ring);
+        if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
+    }
+    const long long rows = (long long)ei.n_env * ei.n_agents;
+    if (pi.in_dim != ei.obs_dim) {
+        std::snprintf(msg, sizeof msg, "policy in_dim %d != env obs_dim %d", pi.in_dim, ei.obs_dim);
+        return fail(SWARM_ERR_INVALID, msg, who);
+    }
+    if (pi.act_dim != 2) return fail(SWARM_ERR_INVALID, "policy act_dim must be 2 (the env's action)", who);
+    if (ei.obs_dtype == SWARM_BF16 && (pi.in_dim & 7)) return fail(SWARM_ERR_INVALID, "bf16 observation rows need obs_dim % 8 == 0", who);
+    {
+        const std::string m = check_ring_slots(ei, ring);
+        if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
+    }
+    const swarm_eval_out_t none = {nullptr, nullptr, nullptr, nullptr};
+    const swarm_eval_out_t &o = out ? *out : none;
+    if ((o.p == nullptr) != (o.dp == nullptr)) return fail(SWARM_ERR_INVALID, "the state trace needs p and dp together", who);
+    bool switches = false;
+    if (switch_to) {
+        for (int t = 0; t < steps; ++t) {
+            if (switch_to[t] < -1 || (switch_to[t] >= 0 && ei.n_shapes >= 1 && switch_to[t] >= ei.n_shapes)) {
+                std::snprintf(msg, sizeof msg, "switch_to[%d] = %d outside [-1, n_shapes = %d)", t, (int)switch_to[t], ei.n_shapes);
+                return fail(SWARM_ERR_INVALID, msg, who);
+            }
+            switches = switches || switch_to[t] >= 0;
+        }
+    }
+    if (switches && ei.n_shapes < 1) return fail(SWARM_ERR_STATE, "switch_to needs a shape set (swarm_set_shapes)", who);
+    if (!ei.observed) return fail(SWARM_ERR_STATE, "the env handle is not observed (swarm_observe / swarm_reset first)", who);
+    if (steps == 0) return SWARM_OK;
+
+    // ---- enqueue
+    DeviceScope dev(ei.device);
+    if (!dev.ok) return fail(SWARM_ERR_HIP, "hipSetDevice failed", who);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (swarm_set_stream(env, stream) != SWARM_OK) return fail(SWARM_ERR_INVALID, "swarm_set_stream failed", who);
+    const bool bf16 = ei.obs_dtype == SWARM_BF16;
+    const size_t obs_slot = (size_t)rows * ei.obs_dim * (bf16 ? 2 : 4), pri_slot = (size_t)rows * 2 * (bf16 ? 2 : 4);
+    char *const obs = static_cast<char *>(ring->obs), *const pri = static_cast<char *>(ring->prior);
+    swarm_expert_view v;                                                 // the handle's p / dp (no lists: nothing is enqueued)
+    if (swarm_internal_expert_view(env, false, &v) != SWARM_OK) return fail(SWARM_ERR_INVALID, "bad handle", who);
+    if (o.reward_stats) {
+        const hipError_t e = hipMemsetAsync(o.reward_stats, 0, (size_t)steps * 2 * sizeof(double), st);
+        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e), who);
+    }
+    const size_t state_elems = (size_t)rows * 2, state_bytes = state_elems * sizeof(double);
+    const unsigned cnt_grid = (unsigned)std::min<long long>((rows + kThreads * kCountPerThread - 1) / (kThreads * kCountPerThread),
+                                                            kCountMaxBlocks);
+    for (int t = 0; t < steps; ++t) {
+        const int c = (int)(((long long)ring->cur + t) % ring->n_slots), n = (c + 1) % ring->n_slots;
+        float *const act = ring->act + (size_t)c * rows * 2;
+        if (o.p) {
+            hipError_t e = hipMemcpyAsync(o.p + (size_t)t * state_elems, v.p, state_bytes, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(o.dp + (size_t)t * state_elems, v.dp, state_bytes, hipMemcpyDeviceToDevice, st);
+            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("state trace copy: ") + hipGetErrorString(e), who);
+        }
+        if (switch_to && switch_to[t] >= 0) {
+            const int rc = swarm_select_shape(env, switch_to[t], nullptr);
+            if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
+        }
+        if (o.metrics) {
+            const int rc = swarm_internal_metrics_step(env, o.metrics + (size_t)t * ei.n_env * 3);
+            if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
+        }
+        if (swarm_policy_forward_explore_at(pol, obs + c * obs_slot, bf16, rows, act, 0.0f, 0, (uint64_t)t, 0, stream) != SWARM_POLICY_OK)
+            return fail(SWARM_ERR_HIP, swarm_policy_last_error(), who);
+        const int rc = swarm_step(env, act, SWARM_F32, obs + n * obs_slot, ring->rew + (size_t)c * rows, ring->done + (size_t)c * rows,
+                                  pri ? pri + c * pri_slot : nullptr);
+        if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
+        if (o.reward_stats) {
+            hipLaunchKernelGGL(k_reward_count, dim3(cnt_grid), dim3(kThreads), 0, st, ring->rew + (size_t)c * rows, rows,
+                               reinterpret_cast<unsigned long long *>(o.reward_stats + 2 * t));
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_count: ") + hipGetErrorString(e), who);
+        }
+    }
+    if (o.reward_stats) {
+        hipLaunchKernelGGL(k_reward_stats, dim3((steps + kThreads - 1) / kThreads), dim3(kThreads), 0, st, o.reward_stats, (int)steps, rows);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_stats: ") + hipGetErrorString(e), who);
     }

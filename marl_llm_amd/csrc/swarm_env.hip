@@ -2157,6 +2157,166 @@ k_metrics(const KP P, double *__restrict__ out)
     if (tid == 0) out[(size_t)e * 3 + 2] = np_var_metric(val, tmp, N);
 }
 
+// -------------------------------------------------------------------------------------------------
+// The per-step metrics kernel of the evaluation loop (swarm_rollout_eval): the same bits as k_metrics, which stays the
+// in-repo reference, at a fraction of its work.  WPE waves per env in a 256-thread workgroup: one (four envs per workgroup)
+// when the batch alone fills the chip, four (one env per workgroup, the cells and agents dealt over 256 lanes) for a small
+// batch, where one wave per env would leave most SIMDs idle and the launch would be latency-bound.
+//
+// Where k_metrics spends its time and why the cheaper form is exact.  With s = dx*dx + dy*dy (the same fp64 expression,
+// no contraction) every distance k_metrics uses is d = sqrt(s), and fp64 sqrt is correctly rounded, hence monotone:
+// s_a <= s_b implies d_a <= d_b.
+//   * coverage of a cell: any_j (d_j < r/2)  ==  (min_j d_j < r/2)  ==  (sqrt(min_j s_j) < r/2).  So only the minimum of
+//     the squared distances is needed, and with h2 = (r/2)^2 the verdict is read off it: s_min < h2 (1 - 2^-40) means
+//     sqrt(s_min) is more than 2^-42 relative (thousands of ulps) below r/2, s_min > h2 (1 + 2^-40) the same above; only
+//     inside that band is the exact sqrt compared.  This minimum skips NaN, as `d < r/2` does; the argmin's running
+//     minimum is seeded with agent 0 whatever it is, as np.argmin's loop in k_metrics is, so NaN states give the same bits.
+//   * Voronoi owner: np.argmin over the ROUNDED norms = the lowest index j with d_j == d_min.  The scan keeps the running
+//     minimum of s and the first index that reached it.  An earlier agent can share the rounded norm only if its s lies
+//     within a few 2^-52 of s_min; at the last update of the minimum the previous minimum (the smallest s of all earlier
+//     agents) is compared with s_new (1 + 2^-40): above it, every earlier sqrt is more than 2^-42 relative larger, so the
+//     index stands; otherwise (or for s below 1e-270, where the spacing of s is coarse) the cell is redone with k_metrics'
+//     own sqrt loop.  A later agent never wins a tie, in either form.
+//   * minimum non-zero distance of an agent: d != 0 iff s != 0, and the minimum commutes with sqrt: one sqrt per agent.
+//   * np.var: numpy's pairwise sum has eight independent accumulators per block of <= 128 elements; eight lanes run one
+//     each (the same additions in the same order), the ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) tree, the tail and the
+//     recursive halves above 128 elements are as in np_pairwise_sum.  Minimum and maximum do not depend on the order.
+// Per (cell, agent) pair that leaves two subtractions, two multiplications, one addition and a compare in fp64; the agents'
+// (x, y) are read as one 16-byte LDS broadcast.
+// -------------------------------------------------------------------------------------------------
+constexpr int kMsEnvs = 4;                                   // envs (= waves) per workgroup
+
+__device__ inline double wave_get(double v, int lane) { return __shfl(v, lane); }
+
+// np_pairwise_sum(a, n) by one whole wave (every lane calls with the same arguments and gets the same value); a in LDS
+__device__ double wave_pairwise_sum(const double *a, int n, int lane)
+{
+    if (n < 8) {
+        double res = 0.0;
+        for (int i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    if (n <= 128) {
+        const int n8 = n - (n % 8);
+        double r = 0.0;
+        if (lane < 8) {
+            r = a[lane];
+            for (int i = 8 + lane; i < n8; i += 8) r += a[i];
+        }
+        const double r0 = wave_get(r, 0), r1 = wave_get(r, 1), r2 = wave_get(r, 2), r3 = wave_get(r, 3);
+        const double r4 = wave_get(r, 4), r5 = wave_get(r, 5), r6 = wave_get(r, 6), r7 = wave_get(r, 7);
+        double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+        for (int i = n8; i < n; ++i) res += a[i];
+        return res;
+    }
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    const double lo = wave_pairwise_sum(a, n2, lane);
+    return lo + wave_pairwise_sum(a + n2, n - n2, lane);
+}
+
+template <int WPE>
+__global__ void __launch_bounds__(64 * kMsEnvs)
+k_metrics_step(const KP P, double *__restrict__ out, const int stride)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int T = 64 * WPE, EPBK = kMsEnvs / WPE;         // lanes per env, envs per workgroup
+    const int N = P.n_a, lane = threadIdx.x & 63, w = threadIdx.x / T, t = threadIdx.x % T;
+    const bool first = (threadIdx.x >> 6) % WPE == 0;         // the env's first wave runs the np.var tails
+    const int e_raw = blockIdx.x * EPBK + w;
+    const bool active = e_raw < P.n_env;                     // a surplus wave does no work but meets every barrier
+    const int e = active ? e_raw : P.n_env - 1;
+    unsigned char *base = smem + (size_t)w * stride;
+    double2 *xy = reinterpret_cast<double2 *>(base);                    // [N]
+    double *val = reinterpret_cast<double *>(base + (size_t)16 * N);   // [N] per-agent values
+    double *tmp = val + N;                                              // [N] scratch
+    int *cnt = reinterpret_cast<int *>(tmp + N);                        // [N] Voronoi counts, then [1] coverage count
+    const int ng = P.n_g[e];
+    const double *gx = P.cells + (size_t)e * 2 * P.ng_max, *gy = gx + P.ng_max;
+    for (int i = t; i < N; i += T) {
+        double2 q; q.x = P.p[(size_t)e * 2 * N + i]; q.y = P.p[(size_t)e * 2 * N + N + i];
+        xy[i] = q; cnt[i] = 0;
+    }
+    if (t == 0) cnt[N] = 0;
+    __syncthreads();
+    const double half = P.r_avoid / 2, h2 = half * half;
+    const double band = 1.0 + 0x1p-40, h2_lo = h2 * (1.0 - 0x1p-40), h2_hi = h2 * band;
+    int covered = 0;
+    for (int c = t; c < ng; c += T) {
+        const double cx = gx[c], cy = gy[c];
+        double best = 0.0, cmin = INFINITY; int owner = 0; bool amb = false;
+        for (int j = 0; j < N; ++j) {
+            const double2 q = xy[j];
+            const double dx = q.x - cx, dy = q.y - cy;
+            const double s2 = dx * dx + dy * dy;
+            cmin = s2 < cmin ? s2 : cmin;                     // a NaN never covers (d < r/2 is false), but it does seed argmin
+            if (j == 0) { best = s2; amb = s2 < 1e-270; }
+            else if (s2 < best) { amb = (best <= s2 * band) || (s2 < 1e-270); best = s2; owner = j; }
+        }
+        if (amb) {                                            // a tie after rounding is possible: k_metrics' own loop
+            double bd = 0.0; owner = 0;
+            for (int j = 0; j < N; ++j) {
+                const double2 q = xy[j];
+                const double dx = q.x - cx, dy = q.y - cy;
+                const double d = sqrt(dx * dx + dy * dy);
+                if (j == 0 || d < bd) { bd = d; owner = j; }
+            }
+        }
+        const bool cov = cmin < h2_lo ? true : (cmin > h2_hi ? false : sqrt(cmin) < half);
+        covered += cov ? 1 : 0;
+        atomicAdd(&cnt[owner], 1);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) covered += __shfl_xor(covered, o);
+    if (lane == 0) atomicAdd(&cnt[N], covered);                // an integer sum: the order does not matter
+    for (int i = t; i < N; i += T) {                           // minimum non-zero distance of every agent
+        const double2 a = xy[i];
+        double m = INFINITY;
+        for (int j = 0; j < N; ++j) {
+            const double2 q = xy[j];
+            const double dx = q.x - a.x, dy = q.y - a.y;
+            const double s2 = dx * dx + dy * dy;
+            if (s2 != 0 && s2 < m) m = s2;
+        }
+        val[i] = sqrt(m);
+    }
+    __syncthreads();
+    double res[2] = {0.0, 0.0};
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {                     // np_var_metric of val, by the env's first wave
+        double mean = 0.0, mn = 0.0, mx = 0.0;
+        if (first) {
+            mean = wave_pairwise_sum(val, N, lane) / N;
+            mn = val[0]; mx = val[0];
+            for (int i = lane; i < N; i += 64) {
+                const double v = val[i], d = v - mean;
+                tmp[i] = d * d;
+                mn = v < mn ? v : mn; mx = v > mx ? v : mx;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
+                mn = a < mn ? a : mn; mx = b > mx ? b : mx;
+            }
+        }
+        __syncthreads();
+        if (first) {
+            const double var = wave_pairwise_sum(tmp, N, lane) / N;
+            res[pass] = (var - mn) / (mx - mn);
+        }
+        __syncthreads();
+        if (pass == 0) {
+            for (int i = t; i < N; i += T) val[i] = (double)cnt[i];
+            __syncthreads();
+        }
+    }
+    if (active && first && lane == 0) {
+        out[(size_t)e * 3 + 0] = (double)cnt[N] / ng;
+        out[(size_t)e * 3 + 1] = res[0];
+        out[(size_t)e * 3 + 2] = res[1];
+    }
+}
+
 
 // -------------------------------------------------------------------------------------------------
 // rule-based expert controller: agent_strategy == 'rule',
@@ -2235,6 +2395,22 @@ k_interleave(const double *__restrict__ cells, double2 *__restrict__ out, int ng
         double2 g; g.x = cells[e * 2 * ng_max + c]; g.y = cells[e * 2 * ng_max + ng_max + c];
         out[e * ng_max + c] = g;
     }
+}
+
+// The device-side shape switch (swarm_select_shape; eval_assembly.py:34-57 process_shape with its rotation 0 and offset 0):
+// every env takes shape `s` of the uploaded set as it stands -- the whole cell row (the same doubles, padding included) into
+// both cell layouts, and the per-env scalars k_reset writes.  p / dp are not touched.
+__global__ void __launch_bounds__(256)
+k_select_shape(const ShapeSet S, const int s, const int ng_max, double *__restrict__ cells_out, double2 *__restrict__ cells_xy,
+               int *__restrict__ ng_out, double *__restrict__ cin_out, LatEnv *__restrict__ lat_out, int *__restrict__ shape_out)
+{
+    const int e = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;         // grid (ceil(ng_max / 256), n_env)
+    if (c < ng_max) {
+        double2 g; g.x = S.cells[(size_t)s * 2 * ng_max + c]; g.y = S.cells[(size_t)s * 2 * ng_max + ng_max + c];
+        cells_out[(size_t)e * 2 * ng_max + c] = g.x; cells_out[(size_t)e * 2 * ng_max + ng_max + c] = g.y;
+        cells_xy[(size_t)e * ng_max + c] = g;
+    }
+    if (c == 0) { ng_out[e] = S.n_g[s]; cin_out[e] = S.c_in[s]; shape_out[e] = s; lat_out[e] = S.lat[s]; }
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -2341,6 +2517,9 @@ struct swarm_env {
     int *d_shape_idx;              // [E] shape index drawn by the last swarm_reset (-1 before / after swarm_set_cells)
     LatEnv *d_shape_lat;
     bool shapes_lattice; float shapes_rmax, shapes_cmax; int shapes_ncols;
+    std::vector<char> shape_lat_ok;            // per shape of the set: a lattice subset (swarm_select_shape)
+    std::vector<float> shape_R, shape_Rc;
+    std::vector<int> shape_ncols;
     std::vector<char> lat_ok;      // per env: cells are a lattice subset
     std::vector<float> lat_R, lat_Rc;
     std::vector<int> lat_ncols;
@@ -2631,7 +2810,24 @@ int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out)
     if (!h || !out) return SWARM_ERR_INVALID;
     out->device = h->device; out->n_env = h->cfg.n_env; out->n_agents = h->cfg.n_agents; out->obs_dim = h->kp.obs_dim;
     out->obs_dtype = h->cfg.obs_dtype; out->with_prior = h->cfg.with_prior != 0; out->observed = h->observed;
-    out->g_max = h->kp.g_max; out->llm_action = h->cfg.llm_action != 0;
+    out->g_max = h->kp.g_max; out->llm_action = h->cfg.llm_action != 0; out->n_shapes = h->n_shapes;
+    return SWARM_OK;
+}
+
+int swarm_internal_metrics_step(swarm_env_t *h, double *out)
+{
+    if (!h || !out) return SWARM_ERR_INVALID;
+    if (!h->have_cells || !h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_rollout_eval: cells / state not set");
+    DeviceGuard g(h->device);
+    const int stride = (36 * h->cfg.n_agents + 4 + 15) & ~15;             // per env: xy[N], val[N], tmp[N], cnt[N + 1]
+    // one wave per env needs about two waves per SIMD (4 SIMDs per CU) to hide its latencies; below that, four waves per env
+    if ((long long)h->cfg.n_env >= 8LL * h->n_cu)
+        hipLaunchKernelGGL(k_metrics_step<1>, dim3((unsigned)((h->cfg.n_env + kMsEnvs - 1) / kMsEnvs)), dim3(64 * kMsEnvs),
+                           (size_t)stride * kMsEnvs, h->stream, h->kp, out, stride);
+    else
+        hipLaunchKernelGGL(k_metrics_step<kMsEnvs>, dim3((unsigned)h->cfg.n_env), dim3(64 * kMsEnvs), (size_t)stride, h->stream,
+                           h->kp, out, stride);
+    HIP_TRY(h, hipGetLastError());
     return SWARM_OK;
 }
 
@@ -2935,6 +3131,9 @@ int swarm_set_shapes(swarm_env_t *h, int n_shapes, const double *shape_cells, co
     const size_t row = (size_t)2 * h->kp.ng_max;
     std::vector<double> cin((size_t)n_shapes);
     std::vector<LatEnv> lat((size_t)n_shapes);
+    std::vector<char> s_ok((size_t)n_shapes, 0);
+    std::vector<float> s_R((size_t)n_shapes, 0.0f), s_Rc((size_t)n_shapes, 0.0f);
+    std::vector<int> s_nc((size_t)n_shapes, 0);
     bool all = true; float rmax = 0.0f, cmax = 0.0f; int ncmax = 0;
     for (int k = 0; k < n_shapes; ++k) {
         if (n_g[k] < 1 || n_g[k] > h->cfg.n_cells_max) return fail(h, SWARM_ERR_INVALID, "swarm_set_shapes: n_g must be in [1, n_cells_max]");
@@ -2947,6 +3146,7 @@ int swarm_set_shapes(swarm_env_t *h, int n_shapes, const double *shape_cells, co
             const double l = L.R;
             L.R = (float)(h->kp.d_sen / l); L.Rc = (float)((h->kp.r_avoid / 2.0) / l);
             rmax = std::max(rmax, L.R); cmax = std::max(cmax, L.Rc); ncmax = std::max(ncmax, L.ncols);
+            s_ok[(size_t)k] = 1; s_R[(size_t)k] = L.R; s_Rc[(size_t)k] = L.Rc; s_nc[(size_t)k] = L.ncols;
         } else { std::memset(&L, 0, sizeof(L)); all = false; }
     }
     DeviceGuard g(h->device);
@@ -2963,6 +3163,7 @@ int swarm_set_shapes(swarm_env_t *h, int n_shapes, const double *shape_cells, co
     HIP_TRY(h, hipMemcpy(h->d_shape_ng, n_g, (size_t)n_shapes * 4, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_shape_lat, lat.data(), (size_t)n_shapes * sizeof(LatEnv), hipMemcpyHostToDevice));
     h->n_shapes = n_shapes; h->shapes_lattice = all; h->shapes_rmax = rmax; h->shapes_cmax = cmax; h->shapes_ncols = ncmax;
+    h->shape_lat_ok = s_ok; h->shape_R = s_R; h->shape_Rc = s_Rc; h->shape_ncols = s_nc;
     return SWARM_OK;
 }
 
@@ -2990,6 +3191,34 @@ int swarm_reset(swarm_env_t *h, uint64_t seed, uint64_t episode, int64_t env_off
     std::fill(h->lat_ncols.begin(), h->lat_ncols.end(), h->shapes_ncols);
     h->have_cells = h->have_state = true;
     set_lattice_mode(h, h->shapes_lattice, h->shapes_rmax, h->shapes_cmax, h->shapes_ncols);
+    h->observed = false;
+    return swarm_observe(h, obs);
+}
+
+int swarm_select_shape(swarm_env_t *h, int32_t shape_index, void *obs)
+{
+    if (!h) return SWARM_ERR_INVALID;
+    if (h->n_shapes < 1) return fail(h, SWARM_ERR_STATE, "swarm_select_shape: no shape set (swarm_set_shapes)");
+    if (shape_index < 0 || shape_index >= h->n_shapes) return fail(h, SWARM_ERR_INVALID, "swarm_select_shape: shape_index outside [0, n_shapes)");
+    if (!h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_select_shape: state not set (swarm_set_state / swarm_reset)");
+    DeviceGuard g(h->device);
+    ShapeSet S;
+    S.n_shapes = h->n_shapes; S.cells = h->d_shape_cells; S.n_g = h->d_shape_ng; S.l_cell = h->d_shape_l;
+    S.c_in = h->d_shape_cin; S.lat = h->d_shape_lat;
+    hipLaunchKernelGGL(k_select_shape, dim3((unsigned)((h->kp.ng_max + 255) / 256), (unsigned)h->cfg.n_env), dim3(256), 0, h->stream, S,
+                       (int)shape_index, h->kp.ng_max, h->d_cells, h->d_cells_xy, h->d_ng, h->d_cin, h->d_lat, h->d_shape_idx);
+    HIP_TRY(h, hipGetLastError());
+    // the host bookkeeping swarm_set_cells would leave for E copies of this shape
+    const size_t s = (size_t)shape_index;
+    const bool ok = h->shape_lat_ok[s] != 0;
+    std::fill(h->cells_set.begin(), h->cells_set.end(), 1);
+    std::fill(h->lat_ok.begin(), h->lat_ok.end(), ok ? 1 : 0);
+    if (ok) {
+        std::fill(h->lat_R.begin(), h->lat_R.end(), h->shape_R[s]); std::fill(h->lat_Rc.begin(), h->lat_Rc.end(), h->shape_Rc[s]);
+        std::fill(h->lat_ncols.begin(), h->lat_ncols.end(), h->shape_ncols[s]);
+    }
+    h->have_cells = true;
+    set_lattice_mode(h, ok, ok ? h->shape_R[s] : 0.0f, ok ? h->shape_Rc[s] : 0.0f, ok ? h->shape_ncols[s] : 0);
     h->observed = false;
     return swarm_observe(h, obs);
 }

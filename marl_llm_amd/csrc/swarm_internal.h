@@ -57,7 +57,7 @@ __device__ inline double np_sum_stream(int n, F f)
 }  // namespace swarm_internal
 
 struct swarm_env_info {
-    int device, n_env, n_agents, obs_dim, obs_dtype, g_max;
+    int device, n_env, n_agents, obs_dim, obs_dtype, g_max, n_shapes;
     bool with_prior, observed, llm_action;
 };
 SWARM_HIDDEN int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out);
@@ -79,6 +79,10 @@ struct swarm_expert_view {
 // pass of swarm_rule_action on the handle's stream (no host synchronisation); false: only fill `out`.  SWARM_OK or an error
 // code with the message in swarm_last_error(h).
 SWARM_HIDDEN int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_expert_view *out);
+
+// The evaluation loop's per-step metrics launch: out[E][3] (DEVICE), bit for bit what swarm_metrics writes (k_metrics_step in
+// swarm_env.hip).  Enqueued on the handle's stream; no host synchronisation.
+SWARM_HIDDEN int swarm_internal_metrics_step(swarm_env_t *h, double *out);
 
 struct swarm_policy_info {
     int device, in_dim, act_dim;

@@ -15,6 +15,11 @@ ring buffer (train_assembly.py:91-111, maddpg.py:72-87, agents.py:69-96, buffer_
 * `rollout_expert`-- expert rollouts (rule-based expert or the prior's 'llm' twin) into the same ring, one library call per
                      episode batch: swarm_rollout_expert (collect_expert_data.py's loop on the device).
 * `save_expert_data` -- a ring's transitions as the expert_data.npz that ReplayBufferExpert.load reads (train_assembly_airl.py).
+* `rollout_eval`  -- evaluation rollouts (eval_assembly.py's loop on the device), one library call: swarm_rollout_eval -- the
+                     actor without noise, per step the three wrapper metrics of every env, a state trace and target-shape
+                     switches that never return to the host.
+* `save_eval_results` -- a rollout_eval trace as the metrics.pkl / state_data.npz eval_assembly.py writes, plus the batch's
+                     per-step mean / std over envs.
 
 PyTorch is plumbing here (device memory, GEMMs); the environment step is the HIP library.
 """
@@ -622,3 +627,163 @@ def save_expert_data(replay, file_dir, dtype=np.float64):
                         t = t.float()                               # exact; numpy has no bfloat16
                     f.write(np.ascontiguousarray(t.reshape(n, width).cpu().numpy().astype(dt, copy=False)).data)
     return path
+
+
+# ---- evaluation (eval_assembly.py:119-205)
+METRIC_KEYS = ("coverage_rate", "uniformity_degree", "voronoi_uniformity")     # eval_assembly.py:168-174, trace.metrics[..., k]
+
+
+class EvalTrace:
+    """What rollout_eval recorded: metrics [steps, E, 3] float64 (coverage_rate, distribution_uniformity,
+    voronoi_based_uniformity of the state BEFORE step t against the cells in force at step t), p / dp [steps, E, 2, N]
+    float64 (that state) or None, reward_stats [steps, 2] float64 or None -- device tensors, valid once the stream has run --
+    and shape [steps], a host int array: the shape index every env was switched to and that is in force at step t, or -1
+    while no switch has happened (cells set by hand, or drawn per env by a reset)."""
+
+    def __init__(self, metrics, p=None, dp=None, reward_stats=None, shape=None):
+        self.metrics, self.p, self.dp, self.reward_stats = metrics, p, dp, reward_stats
+        self.shape = np.full(len(metrics), -1, np.int64) if shape is None else np.asarray(shape, dtype=np.int64)
+
+
+def _switch_schedule(switch, steps):
+    """switch= of rollout_eval as the int32 [steps] array swarm_rollout_eval takes (-1 = keep), or None without a switch:
+    a {step: shape_index} dict, or a sequence of length `steps` (-1 / None = keep)."""
+    if switch is None:
+        return None
+    sched = np.full(steps, -1, np.int32)
+    if isinstance(switch, dict):
+        for t, sh in switch.items():
+            if int(t) != t or not 0 <= int(t) < steps:
+                raise ValueError("switch: step %r outside [0, %d)" % (t, steps))
+            sched[int(t)] = _shape_entry(sh)
+    else:
+        seq = list(switch)
+        if len(seq) != steps:
+            raise ValueError("switch: a sequence must have one entry per step (%d), got %d" % (steps, len(seq)))
+        for t, sh in enumerate(seq):
+            sched[t] = -1 if sh is None else _shape_entry(sh, keep_ok=True)
+    return sched if (sched >= 0).any() else None
+
+
+def _shape_entry(sh, keep_ok=False):
+    if int(sh) != sh or int(sh) < (-1 if keep_ok else 0) or int(sh) >= 2 ** 31:
+        raise ValueError("switch: shape index %r is not a valid index" % (sh,))
+    return int(sh)
+
+
+@torch.no_grad()
+def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=None, trace_state=False, track_reward=True):
+    """`steps` evaluation steps in ONE library call (swarm_rollout_eval, include/swarm_rollout.h): the device counterpart of
+    eval_assembly.py:145-186 for every env of the batch.  Per step: the state trace, an optional target-shape switch on the
+    device, the three wrapper metrics, the actor WITHOUT noise (explore=False) at the policy's precision, the env step.
+    Enqueued on torch's current stream; returns without waiting for the GPU.
+
+    env / policy / replay / obs / reset : exactly as rollout_device (the ring records the evaluation transitions; the
+             private two-slot ring is enough for evaluation).
+    switch : {step: shape_index} or a sequence of length `steps` (-1 / None = keep): at that step every env takes that shape
+             of the uploaded set (SwarmBatch.set_shapes) at the set's own pose, before the step's metrics -- process_shape of
+             eval_assembly.py:34-57.  The actor at a switch step still sees the observation the previous step returned
+             (computed against the old shape), as the reference's does.  Needs a SwarmBatch; ValueError with an
+             AssemblySwarmEnv (assign its grid_center / n_g / l_cell between calls instead).
+    trace_state : also record p / dp before every step.
+    Returns (obs [E,N,D] -- the ring slot of the last next_obs --, EvalTrace).  On error nothing is enqueued, the ring and
+    the env are unchanged, and SwarmError / ValueError raises."""
+    import ctypes
+    from . import _lib
+    if switch is not None and not hasattr(env, "select_shape"):
+        if hasattr(env, "_flush_cells"):
+            raise ValueError("switch= needs a SwarmBatch with a shape set; an AssemblySwarmEnv switches through its grid_center / "
+                             "n_g / l_cell attributes between calls")
+    aenv, sb = _device_env(env, "rollout_eval", lambda e: e.agent_strategy == "input" and not e.is_collected,
+                           "rollout_eval drives the env with the policy's actions: needs agent_strategy 'input' and not is_collected",
+                           reset)
+    if not isinstance(policy, FusedPolicy):
+        raise TypeError("rollout_eval needs a FusedPolicy (the device loop runs the fused policy kernel)")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("steps must be >= 0")
+    sched = _switch_schedule(switch, steps)
+    if sched is not None:
+        if sb.n_shapes < 1:
+            raise _lib.SwarmError("rollout_eval: switch= needs a shape set (SwarmBatch.set_shapes)")
+        if int(sched.max()) >= sb.n_shapes:
+            raise ValueError("switch: shape index %d outside [0, %d)" % (int(sched.max()), sb.n_shapes))
+    E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
+    replay = _device_ring(sb, replay)
+    lib = _lib.load()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
+
+    def call(k, sw, out):
+        ring = _ring_struct(sb, replay)
+        rc = lib.swarm_rollout_eval(sb.handle, policy.handle, ctypes.byref(ring), k,
+                                    sw.ctypes.data_as(ctypes.c_void_p) if sw is not None else None,
+                                    ctypes.byref(out) if out is not None else None, stream)
+        _check_rollout(lib, rc, k, reset)
+
+    _begin_chain(sb, replay, obs, reset, lambda: call(0, None, None), "rollout_eval")
+    f64 = dict(dtype=torch.float64, device=sb.device)
+    metrics = torch.empty((steps, E, 3), **f64)
+    p = torch.empty((steps, E, 2, N), **f64) if trace_state else None
+    dp = torch.empty((steps, E, 2, N), **f64) if trace_state else None
+    stats = torch.empty((steps, 2), **f64) if track_reward else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    call(steps, sched, _lib.SwarmEvalOut(ptr(metrics), ptr(p), ptr(dp), ptr(stats)))
+    shape = np.full(steps, sb.shape_in_force, np.int64)
+    if sched is not None:
+        for t in np.nonzero(sched >= 0)[0]:
+            shape[t:] = sched[t]
+        sb.shape_in_force = int(shape[-1])
+    _finish_chain(aenv, replay, steps)
+    return replay.obs[replay.cur].view(E, N, D), EvalTrace(metrics, p, dp, stats, shape)
+
+
+def _host_array(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def save_eval_results(trace, file_dir, env=0):
+    """Write a rollout_eval trace as the files eval_assembly.py:168-174,195-205 writes, for env `env` of the batch, and the
+    batch statistics; returns their paths (metrics.pkl, state_data.npz, metrics_batch.npz).
+
+    metrics.pkl      : the reference's list, one dict per step: coverage_rate, uniformity_degree, voronoi_uniformity (floats),
+                       et_index, shape_count.  The reference logs shape_count after its increment, so shape_count = the
+                       shape index in force + 1 (0 while no switch has happened).
+    state_data.npz   : pos, vel [2, N, T] float64 and t_step = T - 1 (the reference saves its loop variable).  Needs a trace
+                       recorded with trace_state=True (ValueError otherwise, before anything is written).
+    metrics_batch.npz: what the batch adds -- mean, std [T, 3] over the envs, NaN-aware (distribution_uniformity is 0/0 when
+                       all minimum distances are equal; a step whose envs are all NaN stays NaN), nan_count [T, 3], and the
+                       raw metrics [T, E, 3].
+    Waits for the GPU (it reads the trace back)."""
+    import os
+    import pickle
+    import warnings
+    if trace.p is None or trace.dp is None:
+        raise ValueError("save_eval_results: state_data.npz needs a trace recorded with trace_state=True")
+    m = _host_array(trace.metrics).astype(np.float64, copy=False)
+    if m.ndim != 3 or m.shape[2] != 3:
+        raise ValueError("trace.metrics must be [steps, E, 3]")
+    T, E, _ = m.shape
+    e = int(env)
+    if not 0 <= e < E:
+        raise ValueError("env %d outside [0, %d)" % (e, E))
+    shape = np.asarray(trace.shape).reshape(-1)
+    if shape.shape[0] != T:
+        raise ValueError("trace.shape must have one entry per step")
+    p, dp = _host_array(trace.p), _host_array(trace.dp)
+    os.makedirs(file_dir, exist_ok=True)
+    rows = []
+    for t in range(T):
+        d = {k: float(m[t, e, j]) for j, k in enumerate(METRIC_KEYS)}
+        d["et_index"] = t
+        d["shape_count"] = int(shape[t]) + 1
+        rows.append(d)
+    paths = [os.path.join(file_dir, f) for f in ("metrics.pkl", "state_data.npz", "metrics_batch.npz")]
+    with open(paths[0], "wb") as f:
+        pickle.dump(rows, f)
+    np.savez(paths[1], pos=np.ascontiguousarray(p[:, e].transpose(1, 2, 0)), vel=np.ascontiguousarray(dp[:, e].transpose(1, 2, 0)),
+             t_step=T - 1)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)            # all-NaN steps: the mean / std stay NaN
+        mean, std = np.nanmean(m, axis=1), np.nanstd(m, axis=1)
+    np.savez(paths[2], mean=mean, std=std, nan_count=np.isnan(m).sum(axis=1), metrics=m)
+    return tuple(paths)

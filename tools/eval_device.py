@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Device counterpart of the reference's eval_assembly.py: one rollout_eval call evaluates a given actor on `--envs`
+environments at once, with mid-episode target-shape switches, and save_eval_results writes the reference's metrics.pkl and
+state_data.npz for one env plus metrics_batch.npz (mean / std of the three metrics over the envs per step).
+
+  python tools/eval_device.py --random-actor --envs 64 --episode_length 300 --switch 0:0,150:1
+  python tools/eval_device.py --model models/run/model.pt --results_file results.pkl --switch 0:4,300:5 --episode_length 600
+
+--model reads the actor's fc1..fc4 tensors from a MADDPG checkpoint (torch.save of {'init_dict', 'agent_params': [{'policy':
+state_dict, ...}]}; a bare state dict works too) into a PolicyMLP.  The file is read with torch.load(weights_only=True): tensors
+and plain containers only."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+from marl_llm_amd.batched import SwarmBatch
+from marl_llm_amd.rollout import FusedPolicy, PolicyMLP, rollout_eval, save_eval_results
+from marl_llm_amd.shapes import load_results, r_avoid_for, synthetic_shape_set
+
+FC = ("fc1", "fc2", "fc3", "fc4")
+
+
+def parse_switch(text):
+    """'0:4,300:5' -> {0: 4, 300: 5}."""
+    sched = {}
+    for item in filter(None, (text or "").split(",")):
+        t, s = item.split(":")
+        sched[int(t)] = int(s)
+    return sched
+
+
+def actor_state(ckpt):
+    """The fc1..fc4 weight / bias tensors of the actor in a checkpoint dict."""
+    sd = ckpt
+    if isinstance(sd, dict) and "agent_params" in sd:
+        sd = sd["agent_params"][0]
+    if isinstance(sd, dict) and "policy" in sd:
+        sd = sd["policy"]
+    out = {}
+    for fc in FC:
+        for part in ("weight", "bias"):
+            keys = [k for k in sd if k == f"{fc}.{part}" or k.endswith(f".{fc}.{part}")]
+            if len(keys) != 1:
+                raise KeyError(f"checkpoint: expected exactly one {fc}.{part}, found {keys}")
+            out[f"{fc}.{part}"] = sd[keys[0]].detach().to(torch.float32)
+    return out
+
+
+def load_actor(path):
+    sd = actor_state(torch.load(path, map_location="cpu", weights_only=True))
+    hidden, obs_dim = sd["fc1.weight"].shape
+    module = PolicyMLP(obs_dim, sd["fc4.weight"].shape[0], hidden)
+    module.load_state_dict(sd)
+    return module
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--n_a", type=int, default=30)
+    ap.add_argument("--envs", type=int, default=64)
+    ap.add_argument("--episode_length", type=int, default=300)
+    ap.add_argument("--switch", default="0:0", help="step:shape pairs, e.g. 0:4,300:5")
+    ap.add_argument("--model", default=None, help="MADDPG checkpoint (model.pt)")
+    ap.add_argument("--random-actor", action="store_true", help="a randomly initialised actor instead of --model")
+    ap.add_argument("--precision", default="bf16x3", choices=("bf16", "bf16x3"),
+                    help="bf16x3 follows the reference's fp32 actor to ~1e-4")
+    ap.add_argument("--results_file", default=None, help="shape set in the reference's results.pkl layout (default: synthetic)")
+    ap.add_argument("--seed", type=int, default=226)
+    ap.add_argument("--env", type=int, default=0, help="the env metrics.pkl / state_data.npz are written for")
+    ap.add_argument("--out", default="eval_results")
+    args = ap.parse_args()
+    if (args.model is None) == (not args.random_actor):
+        ap.error("give exactly one of --model and --random-actor")
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_device: no HIP device (the evaluation loop has no CPU path)")
+    shapes = load_results(args.results_file) if args.results_file else synthetic_shape_set()
+    ng_max = max(np.asarray(g).shape[0] for g in shapes["grid_coords"])
+    sb = SwarmBatch(n_env=args.envs, n_agents=args.n_a, n_cells_max=ng_max, r_avoid=r_avoid_for(args.n_a, shapes))
+    sb.set_shapes(shapes)
+    if args.random_actor:
+        torch.manual_seed(args.seed)
+        module = PolicyMLP(sb.obs_dim, 2, 180)
+    else:
+        module = load_actor(args.model)
+    policy = FusedPolicy(module.to(sb.device), device=sb.device, precision=args.precision)
+    _, trace = rollout_eval(sb, policy, args.episode_length, reset=(args.seed, 0, 0), switch=parse_switch(args.switch),
+                            trace_state=True)
+    paths = save_eval_results(trace, args.out, env=args.env)
+    m = trace.metrics[-1].cpu().numpy()
+    with np.errstate(all="ignore"):
+        print("last step over %d envs: coverage %.4f, distribution uniformity %.4f, voronoi uniformity %.4f | mean reward %.4f"
+              % (args.envs, np.nanmean(m[:, 0]), np.nanmean(m[:, 1]), np.nanmean(m[:, 2]), float(trace.reward_stats[:, 0].mean())))
+    for p in paths:
+        print(p)
+    sb.close()
+    policy.close()
+
+
+if __name__ == "__main__":
+    main()
