@@ -189,7 +189,20 @@ int  swarm_metrics(swarm_env_t *h, double *out);
  * state: action[E][N][2] (DEVICE pointer, double), clipped to [-1, 1]; feed it to swarm_step with SWARM_F64 to reproduce
  * a rule-mode step (with is_collected the reference returns it as the fifth element, assembly.py:663-664).  Runs the
  * observation pass with the index export switched on, then a one-thread-per-agent kernel.  fp64 in numpy's operation
- * order; np.cos differs from the device cos by a few ulp, so parity is 1e-12 absolute, not bit-exact. */
+ * order; np.cos differs from the device cos by a few ulp, so parity is 1e-12 absolute, not bit-exact.
+ * The clip is np.clip: a NaN sum stays NaN (it is not turned into a bound).  Two agents at the same position give
+ * r_avoid / 0 * 0 = NaN in both components of both; a NaN coordinate makes that agent's action NaN and removes it from
+ * everybody's neighbourhood (NaN compares false), a NaN velocity makes NaN the action of every agent that has it within
+ * d_sen.  Every finite state gives a finite action.  (The observation pass is memory-safe for such states: DESIGN.md,
+ * "Non-finite positions in the observation pass".)
+ * The n_s > num_obs_grid_max selection of the sensed cells rounds i * step as the controller does, np.round (a tie goes to
+ * the even index, assembly.py:564); the observation (swarm_observe / swarm_step / swarm_get_indices) keeps std::round
+ * (AssemblyEnv.cpp:223).  Ties exist only when num_obs_grid_max - 1 is even, so not for the default 80; for those caps the
+ * list the expert reads differs from the one swarm_get_indices returns.
+ * Periodic handles (is_boundary == 0): the controller takes no wrap, as assembly.py:530-601 takes none -- its distances to
+ * agents and cells, the in-shape flag, the nearest cell and the sensed-cell list with its occupied-cell filter all use the
+ * plain differences of the stored positions (the observation pass wraps only the topological-neighbour rows).
+ * tests/test_gpu_rule_contract.py holds this call and swarm_rollout_expert's rule source to the numpy restatement. */
 int  swarm_rule_action(swarm_env_t *h, double *action);
 
 /* Index scratch of the CURRENT state (device pointers, any may be NULL).  The step keeps neighbor_index / in_flags / the

@@ -18,6 +18,7 @@
 namespace {
 
 using swarm_internal::np_sum_stream;
+using swarm_internal::np_clip1;
 using swarm_internal::pmix64;
 using swarm_internal::swarm_noise_key;
 
@@ -205,8 +206,8 @@ __global__ void __launch_bounds__(256) k_rule_ring(const swarm_expert_view V, do
         }
         const double ax = (ent_x + exp_x) + int_x, ay = (ent_y + exp_y) + int_y;
         double2 a;
-        a.x = fmin(fmax(ax, -1.0), 1.0);                                       // np.clip :601
-        a.y = fmin(fmax(ay, -1.0), 1.0);
+        a.x = np_clip1(ax);                                                    // np.clip :601
+        a.y = np_clip1(ay);
         act64[(size_t)e * N + i] = a;
         act32[(size_t)e * N + i] = make_float2((float)a.x, (float)a.y);
     }

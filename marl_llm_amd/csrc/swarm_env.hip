@@ -82,6 +82,8 @@ struct KP {
     int force_exact;           // debug: take every exact fallback path
     int cap_int;               // G-1 odd: the cap's round(i*step) is an exact integer division by 2(G-1)
     unsigned cap_magic; int cap_shift;
+    int cap_even;              // the expert's export pass: ties of round(i*step) go to even, as np.round sends them (assembly.py:564);
+                               // the observation itself rounds them away from zero (std::round, CPP:223).  Ties need G-1 even.
     int dbg_phase, dbg_extra;  // diagnostics only (tools/ablate.py): run phase dbg_phase dbg_extra EXTRA times; the
                                // phases are idempotent, so results are unchanged and the extra cost is the phase's cost
     int off_cxyf, off_partc, off_lat, off_cov, off_flag;
@@ -1520,7 +1522,8 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
                 const unsigned hq_ = __umulhi(x, P.cap_magic);
                 return (int)((((x - hq_) >> 1) + hq_) >> P.cap_shift);
             }
-            return (int)round(q * ((double)nm1 / (G - 1)));
+            const double v = q * ((double)nm1 / (G - 1));
+            return (int)(P.cap_even ? rint(v) : round(v));
         };
         auto walk_range = [&](auto capped) {
             constexpr bool CAP = decltype(capped)::value;
@@ -1774,7 +1777,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
                         const unsigned hq = __umulhi(x, P.cap_magic);
                         r = (((x - hq) >> 1) + hq) >> P.cap_shift;                 // x / (2 (G-1)), Granlund-Montgomery
                     } else {
-                        r = (unsigned)(int)round(q * step);
+                        r = (unsigned)(int)(P.cap_even ? rint(q * step) : round(q * step));
                     }
                     atomicOr(&rl[(r >> 5) * AG], 1u << (r & 31));
                 }
@@ -2327,6 +2330,7 @@ k_metrics_step(const KP P, double *__restrict__ out, const int stride)
 // vectorised routine, so v_exp agrees to a few ulp, not bit for bit (tests: 1e-12 absolute on the clipped action).
 // -------------------------------------------------------------------------------------------------
 using swarm_internal::np_sum_stream;     // np.sum of f(0..n-1) for n <= 128 (swarm_internal.h)
+using swarm_internal::np_clip1;          // np.clip(v, -1, 1): a NaN stays NaN (swarm_internal.h)
 
 __global__ void __launch_bounds__(256)
 k_rule(const KP P, double *__restrict__ out)     // out [E][N][2]
@@ -2379,8 +2383,8 @@ k_rule(const KP P, double *__restrict__ out)     // out [E][N][2]
             int_x += 5 * (vx[j] - ui) / n_near; int_y += 5 * (vy[j] - wi) / n_near;
         }
         const double ax = (ent_x + exp_x) + int_x, ay = (ent_y + exp_y) + int_y;
-        out[((size_t)e * N + i) * 2 + 0] = fmin(fmax(ax, -1.0), 1.0);          // np.clip :601
-        out[((size_t)e * N + i) * 2 + 1] = fmin(fmax(ay, -1.0), 1.0);
+        out[((size_t)e * N + i) * 2 + 0] = np_clip1(ax);                       // np.clip :601
+        out[((size_t)e * N + i) * 2 + 1] = np_clip1(ay);
     }
 }
 
@@ -2843,8 +2847,9 @@ int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_expert_view *ou
         if (!h->d_act64) HIP_TRY(h, hipMalloc((void **)&h->d_act64, EN * sizeof(double2)));
         // the observation pass of swarm_rule_action on the current state, index export on (idempotent, see swarm_get_indices)
         h->kp.export_idx = 1; h->kp.export_small = 1; h->kp.exp_sensed = h->d_exp_sensed; h->kp.exp_occ = h->d_exp_occ;
+        h->kp.cap_even = 1;
         const int rc = launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-        h->kp.export_idx = 0; h->kp.export_small = 0;
+        h->kp.export_idx = 0; h->kp.export_small = 0; h->kp.cap_even = 0;
         if (rc != SWARM_OK) return rc;
     }
     out->p = h->d_p; out->dp = h->d_dp; out->cells = h->d_cells;
@@ -3451,8 +3456,9 @@ int swarm_rule_action(swarm_env_t *h, double *action)
     }
     // observation pass on the current state with the index export switched on (idempotent, see swarm_get_indices)
     h->kp.export_idx = 1; h->kp.export_small = 1; h->kp.exp_sensed = h->d_exp_sensed; h->kp.exp_occ = h->d_exp_occ;
+    h->kp.cap_even = 1;
     int rc = launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-    h->kp.export_idx = 0; h->kp.export_small = 0;
+    h->kp.export_idx = 0; h->kp.export_small = 0; h->kp.cap_even = 0;
     if (rc != SWARM_OK) return rc;
     hipLaunchKernelGGL(k_rule, dim3(h->cfg.n_env), dim3(h->cfg.n_agents <= 64 ? 64 : 256), 0, h->stream, h->kp, action);
     HIP_TRY(h, hipGetLastError());

@@ -54,6 +54,10 @@ __device__ inline double np_sum_stream(int n, F f)
     return res;
 }
 
+// np.clip(v, -1, 1): NaN compares false both ways and passes through (fmin / fmax would return the bound); every other
+// value, -0.0 included, is what fmin(fmax(v, -1.0), 1.0) gives.
+__device__ inline double np_clip1(double v) { return v < -1.0 ? -1.0 : (v > 1.0 ? 1.0 : v); }
+
 }  // namespace swarm_internal
 
 struct swarm_env_info {

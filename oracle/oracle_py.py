@@ -355,11 +355,22 @@ def wrapper_metrics(p, grid, r_avoid):
     return np.array([m1, m2, m3])
 
 
-def rule_action(p, dp, grid, l_cell, r_avoid, d_sen=D_SEN, g_max=G_MAX):
+RULE_DETAIL_KEYS = ("raw", "in_flag", "n_sensed", "n_filtered", "subsampled", "n_near", "n_avoid")
+
+
+def rule_action(p, dp, grid, l_cell, r_avoid, d_sen=D_SEN, g_max=G_MAX, detail=False):
     """The rule-based expert controller, agent_strategy == 'rule' (assembly.py:530-601), restated with the same numpy
-    calls in the same order.  Returns a (2, n_a) clipped to [-1, 1]."""
+    calls in the same order.  Returns a (2, n_a) clipped to [-1, 1].
+
+    detail=True returns (a, info) with a unchanged and info a dict of what the controller decided per agent
+    (RULE_DETAIL_KEYS): raw (2, n_a) the sum before np.clip; in_flag; n_sensed the cells with |cell - p_i| < d_sen;
+    n_filtered what the occupied-cell filter left of them (== n_sensed where it did not run); subsampled whether
+    n_filtered > g_max sent the list through the round(i * step) selection; n_near the neighbours with |p_j - p_i| < d_sen;
+    n_avoid those of them inside r_avoid.  Tests use it to know which components np.clip saturated and which branches
+    their inputs reached."""
     n_a = p.shape[1]
     a = np.zeros((2, n_a))
+    info = dict(raw=np.zeros((2, n_a)), **{k: np.zeros(n_a, np.int64) for k in RULE_DETAIL_KEYS[1:]}) if detail else None
     k_1, k_2, k_3 = 1, 15, 17                                                   # :532
     for i in range(n_a):
         rel_pos = grid - p[:, [i]]                                              # _get_trgt_grid_state :828-844
@@ -370,6 +381,7 @@ def rule_action(p, dp, grid, l_cell, r_avoid, d_sen=D_SEN, g_max=G_MAX):
         else:
             in_flag, target_pos, target_vel = 0, grid[:, min_index], np.array([0, 0])
         sensed_indices = np.where(rel_pos_norm < d_sen)[0]
+        n_sensed = len(sensed_indices)
         target_pos_rel = target_pos - p[:, i]; target_vel_rel = target_vel - dp[:, i]
         if in_flag == 1:                                                        # :538-541
             v_ent = np.zeros(2)
@@ -410,4 +422,9 @@ def rule_action(p, dp, grid, l_cell, r_avoid, d_sen=D_SEN, g_max=G_MAX):
                 v_int += -k_3 * (r_avoid / nrm[nb] - 1) * agent_pos_rel[:, nb]
             v_int += 5 * agent_vel_rel[:, nb] / len(nearby)
         a[:, i] = np.clip(v_ent + v_exp + v_int, -1, 1)                         # :600-601
-    return a
+        if detail:
+            info["raw"][:, i] = v_ent + v_exp + v_int
+            for k, v in (("in_flag", in_flag), ("n_sensed", n_sensed), ("n_filtered", n_s), ("subsampled", n_s > g_max),
+                         ("n_near", len(nearby)), ("n_avoid", np.count_nonzero(nrm[nearby] < r_avoid))):
+                info[k][i] = v
+    return (a, info) if detail else a

@@ -317,3 +317,127 @@ def output_bound(model, precision, module):
 def tanh_tol(y):
     """Accuracy of the kernel's tanhf (device libm: within 2 ulp) plus the fp32 rounding of the result: 4 ulp."""
     return 8 * U32 * y.abs() + 2.0 ** -30
+
+
+# ---- inputs and bookkeeping of the rule-expert contract tests (test_gpu_rule_contract.py, test_rule_contract_host.py) ----
+def calm_case(rng, shapes, n_a, r_avoid, shape=None, off_shape=0.125, jitter=0.1, speed=0.05, spacing=1.0, away=0.0):
+    """One env on which the rule expert's sum mostly stays inside (-1, 1): a rotated / offset target shape as in make_case,
+    the agents on cells picked greedily at pairwise distance >= spacing * r_avoid (when the shape runs out of such cells the
+    rest go on any free cell), a jitter of `jitter` * l_cell, `off_shape` of the agents pushed 1 to 3 cells outside the
+    shape's nearest cell (so in_flag == 0 and v_ent acts) and velocities within +-speed.  `away` of the agents are taken off
+    the shape altogether (>= 0.8 from every cell where the arena has room): the others then keep long sensed lists, so the
+    n_s > g_max subsample runs.  Returns p, dp, grid, l_cell."""
+    s = int(rng.integers(0, len(shapes["l_cell"]))) if shape is None else shape
+    g = np.asarray(shapes["grid_coords"][s], np.float64).T.copy()
+    l_cell = float(shapes["l_cell"][s])
+    th = rng.uniform(-np.pi, np.pi)
+    rot = np.array([[np.cos(th), np.sin(th)], [-np.sin(th), np.cos(th)]])
+    g = np.ascontiguousarray(rot @ g + rng.uniform(-1.4, 1.4, (2, 1)))
+    n_g = g.shape[1]
+    order = rng.permutation(n_g)
+    chosen = []
+    for c in order:                                                    # greedy packing at the avoidance distance
+        if len(chosen) == n_a:
+            break
+        if not chosen or np.linalg.norm(g[:, chosen] - g[:, [c]], axis=0).min() >= spacing * r_avoid:
+            chosen.append(int(c))
+    if len(chosen) < n_a:
+        rest = [int(c) for c in order if int(c) not in set(chosen)]
+        chosen += rest[: n_a - len(chosen)]
+    chosen += [int(c) for c in rng.integers(0, n_g, max(0, n_a - len(chosen)))]           # n_a > n_g: share cells
+    p = g[:, chosen] + rng.uniform(-jitter, jitter, (2, n_a)) * l_cell
+    centre = g.mean(axis=1, keepdims=True)
+    for i in rng.permutation(n_a)[: int(round(off_shape * n_a))]:      # off the shape: outward, beyond its nearest cell
+        out = p[:, [i]] - centre
+        out = out / (np.linalg.norm(out) + 1e-12)
+        for k in range(1, 400):
+            q = p[:, [i]] + out * k * 0.5 * l_cell
+            if np.linalg.norm(g - q, axis=0).min() > rng.uniform(1.0, 3.0) * l_cell:
+                break
+        p[:, [i]] = q
+    for i in rng.permutation(n_a)[: int(round(away * n_a))]:
+        for _ in range(200):
+            q = rng.uniform(-2.3, 2.3, (2, 1))
+            if np.linalg.norm(g - q, axis=0).min() >= 0.8:
+                break
+        p[:, [i]] = q
+    dp = rng.uniform(-speed, speed, (2, n_a))
+    return np.ascontiguousarray(p), np.ascontiguousarray(dp), g, l_cell
+
+
+def rule_details(cases, r_avoid, g_max=80, d_sen=0.4, workers=None):
+    """oracle_py.rule_action(detail=True) of every (p, dp, grid, l_cell) of `cases` on a pool of oracle_threads() processes
+    (the restatement is Python loops: threads would share one interpreter lock).  Returns (a [E,2,N], info dict of stacked
+    per-env arrays, RULE_DETAIL_KEYS)."""
+    jobs = [(np.asarray(p), np.asarray(dp), np.asarray(g), float(l), float(r_avoid), float(d_sen), int(g_max)) for p, dp, g, l in cases]
+    n = oracle_threads() if workers is None else int(workers)
+    if n <= 1 or len(jobs) == 1:
+        res = [_rule_detail_job(j) for j in jobs]
+    else:
+        res = list(_rule_pool(n).map(_rule_detail_job, jobs, chunksize=max(1, len(jobs) // (4 * n))))
+    a = np.stack([r[0] for r in res])
+    return a, {k: np.stack([r[1][k] for r in res]) for k in res[0][1]}
+
+
+_RULE_POOL = {}
+
+
+def _rule_pool(n):
+    """One pool of spawned workers per process (spawn: the parent may hold a GPU context, which must not be forked), shut
+    down at exit."""
+    if n not in _RULE_POOL:
+        import atexit
+        import multiprocessing as mp
+        from concurrent.futures import ProcessPoolExecutor
+        _RULE_POOL[n] = ProcessPoolExecutor(max_workers=n, mp_context=mp.get_context("spawn"))
+        atexit.register(_RULE_POOL[n].shutdown)
+    return _RULE_POOL[n]
+
+
+def _rule_detail_job(job):
+    import os as _os
+    import sys as _sys
+    root = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
+    if root not in _sys.path:
+        _sys.path.insert(0, root)
+    from oracle.oracle_py import rule_action
+    p, dp, g, l_cell, r_avoid, d_sen, g_max = job
+    with np.errstate(all="ignore"):
+        return rule_action(p, dp, g, l_cell, r_avoid, d_sen=d_sen, g_max=g_max, detail=True)
+
+
+def rule_branch_counts(info):
+    """Of the agents with at least one component of |raw| < 1 (NaN excluded): how many have a neighbour in d_sen, one inside
+    r_avoid, in_flag == 0, a non-empty filtered sensed list, a subsampled list; and the share of components with |raw| < 1."""
+    with np.errstate(invalid="ignore"):
+        free = np.abs(info["raw"]) < 1                                 # [E, 2, N]
+    ag = free.any(axis=1)                                              # [E, N]
+    return dict(share=float(free.mean()), near=int((ag & (info["n_near"] >= 1)).sum()), avoid=int((ag & (info["n_avoid"] >= 1)).sum()),
+                outside=int((ag & (info["in_flag"] == 0)).sum()), sensed=int((ag & (info["n_filtered"] >= 1)).sum()),
+                subsampled=int((ag & (info["subsampled"] != 0)).sum()), agents=int(ag.size))
+
+
+RULE_NS = (1, 2, 7, 8, 9, 30, 63, 64, 65, 127, 128, 129, 191, 192, 193, 200, 255, 256)
+RULE_SUBSAMPLE_NS = tuple(n for n in RULE_NS if n >= 30)    # below, an agent's own r_avoid / 2 disc leaves <= g_max cells
+
+
+def calm_batch(shapes, n_a, r_avoid, seed=0, agents=6144):
+    """The calm envs of one agent count: a third packed on the shape (neighbours inside r_avoid, the occupied-cell filter),
+    two thirds with most agents away from it (v_ent, and long filtered lists: the subsample), about `agents` agents in all."""
+    rng = np.random.default_rng([seed, n_a])
+    n_env = max(6, -(-agents // n_a)) if n_a >= 8 else 64
+    return [calm_case(rng, shapes, n_a, r_avoid) if e % 3 == 0 else
+            calm_case(rng, shapes, n_a, r_avoid, away=0.7, off_shape=0.05, spacing=2.0) for e in range(n_env)]
+
+
+def assert_calm_conditions(n_a, info):
+    """The conditions the unsaturated comparison puts on its inputs, from the restatement's detail output alone; returns
+    the counts (rule_branch_counts)."""
+    c = rule_branch_counts(info)
+    if n_a < 8:
+        assert c["share"] > 0, (n_a, c)
+        return c
+    assert c["share"] >= 1 / 3, (n_a, c)
+    for k in ("near", "avoid", "outside", "sensed") + (("subsampled",) if n_a in RULE_SUBSAMPLE_NS else ()):
+        assert c[k] >= 100, (n_a, k, c)
+    return c

@@ -3,7 +3,10 @@ actions (tests/golden/g5_rule_*.npz) and vs the numpy restatement on synthetic b
 
 Tolerance: 1e-12 absolute on the clipped action -- every term is fp64 in numpy's operation order, but np.cos is numpy's
 vectorised routine and the device uses its own fp64 cos (a few ulp apart), and np.linalg.norm of a 1-D vector goes through
-BLAS dot (FMA).  The step that consumes the action is the bit-exact path of test_gpu_parity.py."""
+BLAS dot (FMA).  The step that consumes the action is the bit-exact path of test_gpu_parity.py.
+
+Most components of these inputs are saturated by the clip (exactly +-1), where the tolerance checks a sign only:
+test_gpu_rule_contract.py compares on unsaturated inputs, at every launch shape, on the thresholds and on NaN states."""
 import numpy as np
 import pytest
 
