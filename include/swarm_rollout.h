@@ -76,8 +76,9 @@ int swarm_rollout_logpi(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_
 
 /* Expert rollouts (the reference's collect_expert_data.py: agent_strategy 'rule' or 'llm' with is_collected, the data of
  * train_assembly_airl.py).  Enqueues `steps` expert steps on `stream`; per step t, with c and n as above:
- *   - SWARM_EXPERT_RULE: the rule-based expert of assembly.py:530-601 on the current state, in fp64 (the action of
- *     swarm_rule_action, bit for bit); the env steps with that fp64 action (SWARM_F64) and act[c] = its f32 rounding.  The
+ *   - SWARM_EXPERT_RULE: the rule-based expert of assembly.py:530-601 on the current state, in fp64 (swarm_rule_action's
+ *     kernel after swarm_rule_action's observation pass: its action bit for bit); the env steps with that fp64 action
+ *     (SWARM_F64) and act[c] = its f32 rounding.  The
  *     trajectory is bit-identical to the eager loop `u = swarm_rule_action(); swarm_step(u, SWARM_F64)`.
  *   - SWARM_EXPERT_LLM: the env steps with action = NULL (the library's prior-policy twin; the handle must be created with
  *     llm_action) and act[c] = that applied action rounded to f32 (the `is_collected` fifth return value of the eager path).
@@ -86,7 +87,8 @@ int swarm_rollout_logpi(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_
  * observation is the f32 rounding of the fp64 one (the env's parity contract), so AIRL sees the same bits as from the
  * reference's fp64 buffer.
  * Checks as swarm_rollout minus the policy's; SWARM_EXPERT_RULE also needs num_obs_grid_max <= 128 (as swarm_rule_action).
- * The first RULE call allocates the handle's list and fp64 action scratch (once); later calls allocate nothing.  A rejected
+ * The first RULE call allocates the handle's fp64 action scratch and, unless swarm_rule_action or swarm_get_indices already
+ * did, its list scratch (once each); later calls allocate nothing.  A rejected
  * call enqueues nothing; the message is in swarm_rollout_last_error. */
 enum { SWARM_EXPERT_RULE = 0, SWARM_EXPERT_LLM = 1 };
 int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t steps, int32_t source, double *reward_stats,

@@ -10,7 +10,8 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SRCS = [os.path.join(PKG, "csrc", "swarm_env.hip"), os.path.join(PKG, "csrc", "legacy_shim.hip"),
-        os.path.join(PKG, "csrc", "policy_mlp.hip"), os.path.join(PKG, "csrc", "rollout.hip")]
+        os.path.join(PKG, "csrc", "policy_mlp.hip"), os.path.join(PKG, "csrc", "rollout.hip"),
+        os.path.join(PKG, "csrc", "rule_expert.hip")]
 INC = os.path.join(ROOT, "include")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libswarmenv.so")

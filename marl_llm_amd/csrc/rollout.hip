@@ -2,8 +2,8 @@
 // transitions written straight into a chained replay ring.  The loop itself is host code that only enqueues: per step the
 // policy kernel (policy_mlp.hip) or the uniform-action kernel below, the env step (swarm_env.hip) and, optionally, the
 // reward-count kernel below, all on one stream; the reward statistics are finished by one launch after the loop.
-// swarm_rollout_expert is the same loop with an expert in place of the policy: the rule-based expert kernel below (after the
-// env's index-export observation pass) or a copy of the env's own 'llm' action.  swarm_rollout_eval is the evaluation loop:
+// swarm_rollout_expert is the same loop with an expert in place of the policy: the rule-based expert kernel (rule_expert.hip,
+// after the env's index-export observation pass) or a copy of the env's own 'llm' action.  swarm_rollout_eval is the evaluation loop:
 // the actor without noise, and per step a state trace, an optional device-side shape switch and the wrapper metrics.
 #include <hip/hip_runtime.h>
 
@@ -126,113 +126,15 @@ __global__ void __launch_bounds__(kThreads) k_reward_stats(double *__restrict__ 
     stats[2 * t + 1] = sqrt((cd * (a * a) + (nd - cd) * (m * m)) / nd);
 }
 
-// ---- expert sources of swarm_rollout_expert
+// ---- expert sources of swarm_rollout_expert: the rule-expert kernel (rule_expert.hip) and
 
-constexpr int kRuleMaxAgents = 256;                                     // swarm_create's n_agents cap
-
-// The rule-based expert (assembly.py:530-601) of every agent of one env per workgroup, for the current state: the same
-// fp64 operations in the same order as swarm_env.hip's k_rule (bit-identical output), restructured for the batched
-// collection loop.  The env's p / dp are staged in LDS once (k_rule reads every neighbour's from HBM twice); the
-// `|r| < d_sen` neighbour test runs once per pair into a per-agent bit mask of W 64-bit words (k_rule evaluates it twice);
-// the interaction sum then visits the set bits in ascending j, i.e. k_rule's order.  Writes the fp64 action (the step's
-// input) and its f32 rounding (the ring's act row) in the same pass.
-template <int W>
-__global__ void __launch_bounds__(256) k_rule_ring(const swarm_expert_view V, double2 *__restrict__ act64, float2 *__restrict__ act32)
-{
-    __shared__ double s_p[2 * kRuleMaxAgents], s_v[2 * kRuleMaxAgents];
-    const int N = V.n_agents, e = blockIdx.x, G = V.g_max;
-    {
-        const double *gp = V.p + (size_t)e * 2 * N, *gv = V.dp + (size_t)e * 2 * N;
-        for (int k = threadIdx.x; k < 2 * N; k += blockDim.x) { s_p[k] = gp[k]; s_v[k] = gv[k]; }
-    }
-    __syncthreads();
-    const double *px = s_p, *py = s_p + N, *vx = s_v, *vy = s_v + N;
-    const double *gx = V.cells + (size_t)e * 2 * V.ng_max, *gy = gx + V.ng_max;
-    const double d_sen = V.d_sen, r_avoid = V.r_avoid;
-    const double k_1 = 1, k_2 = 15, k_3 = 17;                                  // :532
-    for (int i = threadIdx.x; i < N; i += blockDim.x) {
-        const double xi = px[i], yi = py[i], ui = vx[i], wi = vy[i];
-        const bool in_shape = V.in_flag[(size_t)e * N + i] != 0;
-        double ent_x = 0.0, ent_y = 0.0;                                       // :538-541
-        if (!in_shape) {
-            const int bc = V.near_cell[(size_t)e * N + i];
-            const double rx = gx[bc] - xi, ry = gy[bc] - yi;
-            const double nr = sqrt(rx * rx + ry * ry) + 1e-8;
-            ent_x = k_1 * (rx / nr) + (0.0 - ui);
-            ent_y = k_1 * (ry / nr) + (0.0 - wi);
-        }
-        const int *sel = V.exp_sensed + ((size_t)e * N + i) * G;               // capped list, -1 padded (:561-572)
-        int n = 0;
-        while (n < G && sel[n] >= 0) ++n;
-        double exp_x = 0.0, exp_y = 0.0;                                       // :574-584
-        if (n > 0) {
-            auto psi = [&](double rx, double ry) {                             // _rho_cos_dec(z, 0, d_sen) :846-850
-                const double z = sqrt(rx * rx + ry * ry);
-                return z < d_sen ? 0.5 * (1.0 + cos(M_PI * (z / d_sen - 0) / (1.0 - 0))) : 0.0;
-            };
-            const double sx = np_sum_stream(n, [&](int q) { const int c = sel[q]; const double rx = gx[c] - xi, ry = gy[c] - yi; return psi(rx, ry) * rx; });
-            const double sy = np_sum_stream(n, [&](int q) { const int c = sel[q]; const double rx = gx[c] - xi, ry = gy[c] - yi; return psi(rx, ry) * ry; });
-            double den = np_sum_stream(n, [&](int q) { const int c = sel[q]; return psi(gx[c] - xi, gy[c] - yi); });
-            if (den == 0) den = 1e-8;
-            exp_x = k_2 * sx / den; exp_y = k_2 * sy / den;
-        }
-        unsigned long long near[W];                                            // :587-598, neighbours j != i with |r| < d_sen
-        int n_near = 0;
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-            unsigned long long m = 0;
-            const int jn = min(64, N - 64 * w);
-            for (int b = 0; b < jn; ++b) {
-                const int j = 64 * w + b;
-                const double rx = px[j] - xi, ry = py[j] - yi;
-                m |= (unsigned long long)(j != i && sqrt(rx * rx + ry * ry) < d_sen) << b;
-            }
-            near[w] = m;
-            n_near += __popcll(m);
-        }
-        double int_x = 0.0, int_y = 0.0;
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-            for (unsigned long long m = near[w]; m; m &= m - 1) {
-                const int j = 64 * w + __ffsll((long long)m) - 1;
-                const double rx = px[j] - xi, ry = py[j] - yi;
-                const double nr = sqrt(rx * rx + ry * ry);
-                if (nr < r_avoid) {
-                    const double c = -k_3 * (r_avoid / nr - 1);
-                    int_x += c * rx; int_y += c * ry;
-                }
-                int_x += 5 * (vx[j] - ui) / n_near; int_y += 5 * (vy[j] - wi) / n_near;
-            }
-        }
-        const double ax = (ent_x + exp_x) + int_x, ay = (ent_y + exp_y) + int_y;
-        double2 a;
-        a.x = np_clip1(ax);                                                    // np.clip :601
-        a.y = np_clip1(ay);
-        act64[(size_t)e * N + i] = a;
-        act32[(size_t)e * N + i] = make_float2((float)a.x, (float)a.y);
-    }
-}
-
-// The 'llm' source: the action the step is about to apply (the env's own d_act_next, fp64) rounded to f32 into act[c].
+// the 'llm' source: the action the step is about to apply (the env's own d_act_next, fp64) rounded to f32 into act[c].
 __global__ void __launch_bounds__(kThreads) k_act_f32(const double2 *__restrict__ src, float2 *__restrict__ dst, long long rows)
 {
     const long long row = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (row >= rows) return;
     const double2 a = src[row];
     dst[row] = make_float2((float)a.x, (float)a.y);
-}
-
-int launch_rule_ring(const swarm_expert_view &v, float2 *act32, hipStream_t st)
-{
-    const dim3 grid(v.n_env), block(v.n_agents <= 64 ? 64 : 256);          // k_rule's launch shape
-    switch ((v.n_agents + 63) / 64) {
-    case 1: hipLaunchKernelGGL(k_rule_ring<1>, grid, block, 0, st, v, v.act64, act32); break;
-    case 2: hipLaunchKernelGGL(k_rule_ring<2>, grid, block, 0, st, v, v.act64, act32); break;
-    case 3: hipLaunchKernelGGL(k_rule_ring<3>, grid, block, 0, st, v, v.act64, act32); break;
-    default: hipLaunchKernelGGL(k_rule_ring<4>, grid, block, 0, st, v, v.act64, act32); break;
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
 }
 
 struct DeviceScope {
@@ -246,98 +148,176 @@ struct DeviceScope {
     ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-}  // namespace
+// ---- validation shared by the entry points: each returns SWARM_OK or fail()'s code, in the order the callers document
+
+// The handles' infos (pol, pi: NULL for an entry point without a policy), steps and the devices.
+int check_handles(const char *who, const swarm_env_t *env, int32_t steps, swarm_env_info &ei, const swarm_policy_t *pol = nullptr,
+                  swarm_policy_info *pi = nullptr)
+{
+    if (swarm_internal_env_info(env, &ei) != SWARM_OK || (pol && swarm_internal_policy_info(pol, pi) != SWARM_POLICY_OK))
+        return fail(SWARM_ERR_INVALID, "bad handle", who);
+    if (steps < 0) return fail(SWARM_ERR_INVALID, "steps < 0", who);
+    if (pol && ei.device != pi->device) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "env handle on device %d, policy on device %d", ei.device, pi->device);
+        return fail(SWARM_ERR_INVALID, msg, who);
+    }
+    return SWARM_OK;
+}
+
+// A policy's loop: the ring's shape, the policy's dimensions against the env's, the ring's slots.
+int check_policy_ring(const char *who, const swarm_env_info &ei, const swarm_policy_info &pi, const swarm_ring_t *ring)
+{
+    std::string m = check_ring_shape(ei, ring);
+    if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
+    if (pi.in_dim != ei.obs_dim) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "policy in_dim %d != env obs_dim %d", pi.in_dim, ei.obs_dim);
+        return fail(SWARM_ERR_INVALID, msg, who);
+    }
+    if (pi.act_dim != 2) return fail(SWARM_ERR_INVALID, "policy act_dim must be 2 (the env's action)", who);
+    if (ei.obs_dtype == SWARM_BF16 && (pi.in_dim & 7)) return fail(SWARM_ERR_INVALID, "bf16 observation rows need obs_dim % 8 == 0", who);
+    m = check_ring_slots(ei, ring);
+    return m.empty() ? SWARM_OK : fail(SWARM_ERR_INVALID, m, who);
+}
+
+int check_observed(const char *who, const swarm_env_info &ei)
+{
+    return ei.observed ? SWARM_OK : fail(SWARM_ERR_STATE, "the env handle is not observed (swarm_observe / swarm_reset first)", who);
+}
+
+int hip_check(const char *who, hipError_t e, const char *what)
+{
+    return e == hipSuccess ? SWARM_OK : fail(SWARM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e), who);
+}
+
+// ---- the loop shared by the entry points
+
+// One call's context, built after validation: the device and the stream in force, and where slot t of the ring lives.
+struct Loop {
+    const char *const who;
+    swarm_env_t *const env;
+    DeviceScope dev;
+    void *const stream;                                                     // as the libraries' entry points take it
+    const hipStream_t st;
+    const long long rows;
+    const bool bf16;
+    const size_t obs_slot, pri_slot;
+    char *const obs_base, *const pri_base;
+    float *const act_base, *const rew_base;
+    uint8_t *const done_base;
+    const int cur, n_slots;
+    int rc;                                                                 // SWARM_OK, or why nothing may be enqueued
+
+    Loop(const char *who_, swarm_env_t *env_, const swarm_env_info &ei, const swarm_ring_t *ring, void *stream_)
+        : who(who_), env(env_), dev(ei.device), stream(stream_), st(static_cast<hipStream_t>(stream_)), rows(ring->rows),
+          bf16(ei.obs_dtype == SWARM_BF16), obs_slot((size_t)rows * ei.obs_dim * (bf16 ? 2 : 4)), pri_slot((size_t)rows * 2 * (bf16 ? 2 : 4)),
+          obs_base(static_cast<char *>(ring->obs)), pri_base(static_cast<char *>(ring->prior)), act_base(ring->act), rew_base(ring->rew),
+          done_base(ring->done), cur(ring->cur), n_slots(ring->n_slots), rc(SWARM_OK)
+    {
+        if (!dev.ok) rc = fail(SWARM_ERR_HIP, "hipSetDevice failed", who);
+        else if (swarm_set_stream(env, stream) != SWARM_OK) rc = fail(SWARM_ERR_INVALID, "swarm_set_stream failed", who);
+    }
+
+    int c(int t) const { return (int)(((long long)cur + t) % n_slots); }   // the slot step t writes; its next obs goes to n(t)
+    int n(int t) const { return (c(t) + 1) % n_slots; }
+    float *act(int t) const { return act_base + (size_t)c(t) * rows * 2; }
+    void *obs(int slot) const { return obs_base + slot * obs_slot; }
+    float *rew(int t) const { return rew_base + (size_t)c(t) * rows; }
+    uint8_t *done(int t) const { return done_base + (size_t)c(t) * rows; }
+    void *prior(int t) const { return pri_base ? pri_base + c(t) * pri_slot : nullptr; }
+    unsigned row_grid() const { return (unsigned)((rows + kThreads - 1) / kThreads); }
+
+    int step(const void *action, int dtype, int t) const
+    {
+        const int r = swarm_step(env, action, dtype, obs(n(t)), rew(t), done(t), prior(t));
+        return r == SWARM_OK ? SWARM_OK : fail(r, swarm_last_error(env), who);
+    }
+    int check(hipError_t e, const char *what) const { return hip_check(who, e, what); }
+    int launched(const char *kernel) const { return check(hipGetLastError(), kernel); }
+};
+
+// reward_stats [steps][2] (DEVICE) of a loop; every member is a no-op when stats is NULL.
+struct RewardStats {
+    const Loop &L;
+    double *const stats;
+    const int steps;
+
+    int begin() const { return stats ? L.check(hipMemsetAsync(stats, 0, (size_t)steps * 2 * sizeof(double), L.st), "hipMemsetAsync") : SWARM_OK; }
+    int count(int t) const
+    {
+        if (!stats) return SWARM_OK;
+        const unsigned grid = (unsigned)std::min<long long>((L.rows + kThreads * kCountPerThread - 1) / (kThreads * kCountPerThread),
+                                                            kCountMaxBlocks);
+        hipLaunchKernelGGL(k_reward_count, dim3(grid), dim3(kThreads), 0, L.st, L.rew(t), L.rows,
+                           reinterpret_cast<unsigned long long *>(stats + 2 * t));
+        return L.launched("k_reward_count");
+    }
+    int finish() const
+    {
+        if (!stats) return SWARM_OK;
+        hipLaunchKernelGGL(k_reward_stats, dim3((steps + kThreads - 1) / kThreads), dim3(kThreads), 0, L.st, stats, steps, L.rows);
+        return L.launched("k_reward_stats");
+    }
+};
+
+// `steps` times: the entry point's own work for step t (`act_and_step(t)`: whatever precedes the action, the action into
+// L.act(t), and L.step), then the reward count.  Enqueues only; stops at the first error.
+template <class F>
+int run_loop(const Loop &L, int steps, double *reward_stats, F &&act_and_step)
+{
+    const RewardStats rs{L, reward_stats, steps};
+    int rc = rs.begin();
+    for (int t = 0; rc == SWARM_OK && t < steps; ++t) {
+        rc = act_and_step(t);
+        if (rc == SWARM_OK) rc = rs.count(t);
+    }
+    return rc == SWARM_OK ? rs.finish() : rc;
+}
 
 // swarm_rollout (want_logpi = false, log_pi = NULL) and swarm_rollout_logpi (log_pi [n_slots][rows], written per step like act).
-static int rollout_impl(const char *who, bool want_logpi, swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring,
-                        float *log_pi, int32_t steps, const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0,
-                        uint64_t row_offset, double *reward_stats, void *stream)
+int rollout_impl(const char *who, bool want_logpi, swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, float *log_pi,
+                 int32_t steps, const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset,
+                 double *reward_stats, void *stream)
 {
     // ---- validation: nothing is enqueued before all of it passed
     if (!env || !pol || !ring) return fail(SWARM_ERR_INVALID, "null env, policy or ring", who);
     if (want_logpi && !log_pi) return fail(SWARM_ERR_INVALID, "null log_pi (a [n_slots][rows] fp32 device array is required)", who);
     swarm_env_info ei;
     swarm_policy_info pi;
-    if (swarm_internal_env_info(env, &ei) != SWARM_OK || swarm_internal_policy_info(pol, &pi) != SWARM_POLICY_OK)
-        return fail(SWARM_ERR_INVALID, "bad handle", who);
-    char msg[256];
-    if (steps < 0) return fail(SWARM_ERR_INVALID, "steps < 0", who);
-    if (ei.device != pi.device) {
-        std::snprintf(msg, sizeof msg, "env handle on device %d, policy on device %d", ei.device, pi.device);
-        return fail(SWARM_ERR_INVALID, msg, who);
-    }
+    if (int rc = check_handles(who, env, steps, ei, pol, &pi)) return rc;
     if (ei.obs_dtype != SWARM_F32 && ei.obs_dtype != SWARM_BF16)
         return fail(SWARM_ERR_INVALID, "the env handle's obs dtype must be SWARM_F32 or SWARM_BF16 (the policy reads no fp64 rows)", who);
-    {
-        const std::string m = check_ring_shape(ei, ring);
-        if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
-    }
-    const long long rows = (long long)ei.n_env * ei.n_agents;
-    if (pi.in_dim != ei.obs_dim) {
-        std::snprintf(msg, sizeof msg, "policy in_dim %d != env obs_dim %d", pi.in_dim, ei.obs_dim);
-        return fail(SWARM_ERR_INVALID, msg, who);
-    }
-    if (pi.act_dim != 2) return fail(SWARM_ERR_INVALID, "policy act_dim must be 2 (the env's action)", who);
-    if (ei.obs_dtype == SWARM_BF16 && (pi.in_dim & 7)) return fail(SWARM_ERR_INVALID, "bf16 observation rows need obs_dim % 8 == 0", who);
-    {
-        const std::string m = check_ring_slots(ei, ring);
-        if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
-    }
-    if (!ei.observed) return fail(SWARM_ERR_STATE, "the env handle is not observed (swarm_observe / swarm_reset first)", who);
+    if (int rc = check_policy_ring(who, ei, pi, ring)) return rc;
+    if (int rc = check_observed(who, ei)) return rc;
     if (steps == 0) return SWARM_OK;
 
     // ---- enqueue
-    DeviceScope dev(ei.device);
-    if (!dev.ok) return fail(SWARM_ERR_HIP, "hipSetDevice failed", who);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (swarm_set_stream(env, stream) != SWARM_OK) return fail(SWARM_ERR_INVALID, "swarm_set_stream failed", who);
-    const bool bf16 = ei.obs_dtype == SWARM_BF16;
-    const size_t obs_slot = (size_t)rows * ei.obs_dim * (bf16 ? 2 : 4), pri_slot = (size_t)rows * 2 * (bf16 ? 2 : 4);
-    char *const obs = static_cast<char *>(ring->obs), *const pri = static_cast<char *>(ring->prior);
-    if (reward_stats) {
-        const hipError_t e = hipMemsetAsync(reward_stats, 0, (size_t)steps * 2 * sizeof(double), st);
-        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e), who);
-    }
-    const unsigned act_grid = (unsigned)((rows + kThreads - 1) / kThreads);
-    const unsigned cnt_grid = (unsigned)std::min<long long>((rows + kThreads * kCountPerThread - 1) / (kThreads * kCountPerThread),
-                                                            kCountMaxBlocks);
-    for (int t = 0; t < steps; ++t) {
-        const int c = (int)(((long long)ring->cur + t) % ring->n_slots), n = (c + 1) % ring->n_slots;
-        float *const act = ring->act + (size_t)c * rows * 2;
-        float *const lp = log_pi ? log_pi + (size_t)c * rows : nullptr;
+    const Loop L(who, env, ei, ring, stream);
+    if (L.rc != SWARM_OK) return L.rc;
+    return run_loop(L, steps, reward_stats, [&](int t) {
+        float *const act = L.act(t);
+        float *const lp = log_pi ? log_pi + (size_t)L.c(t) * L.rows : nullptr;
         if (uniform_steps && uniform_steps[t]) {
             const unsigned long long ukey = pmix64(swarm_noise_key(seed, step0 + t) ^ kUniformSalt);
             if (lp)
-                hipLaunchKernelGGL(k_uniform_actions<true>, dim3(act_grid), dim3(kThreads), 0, st, reinterpret_cast<float2 *>(act), rows,
-                                   ukey, (unsigned long long)row_offset, lp);
+                hipLaunchKernelGGL(k_uniform_actions<true>, dim3(L.row_grid()), dim3(kThreads), 0, L.st, reinterpret_cast<float2 *>(act),
+                                   L.rows, ukey, (unsigned long long)row_offset, lp);
             else
-                hipLaunchKernelGGL(k_uniform_actions<false>, dim3(act_grid), dim3(kThreads), 0, st, reinterpret_cast<float2 *>(act), rows,
-                                   ukey, (unsigned long long)row_offset, nullptr);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_uniform_actions: ") + hipGetErrorString(e), who);
-        } else if ((lp ? swarm_policy_forward_explore_logpi(pol, obs + c * obs_slot, bf16, rows, act, lp, noise_scale, seed, step0 + t,
+                hipLaunchKernelGGL(k_uniform_actions<false>, dim3(L.row_grid()), dim3(kThreads), 0, L.st, reinterpret_cast<float2 *>(act),
+                                   L.rows, ukey, (unsigned long long)row_offset, nullptr);
+            if (int rc = L.launched("k_uniform_actions")) return rc;
+        } else if ((lp ? swarm_policy_forward_explore_logpi(pol, L.obs(L.c(t)), L.bf16, L.rows, act, lp, noise_scale, seed, step0 + t,
                                                             row_offset, stream)
-                       : swarm_policy_forward_explore_at(pol, obs + c * obs_slot, bf16, rows, act, noise_scale, seed, step0 + t,
+                       : swarm_policy_forward_explore_at(pol, L.obs(L.c(t)), L.bf16, L.rows, act, noise_scale, seed, step0 + t,
                                                          row_offset, stream)) != SWARM_POLICY_OK) {
             return fail(SWARM_ERR_HIP, swarm_policy_last_error(), who);
         }
-        const int rc = swarm_step(env, act, SWARM_F32, obs + n * obs_slot, ring->rew + (size_t)c * rows, ring->done + (size_t)c * rows,
-                                  pri ? pri + c * pri_slot : nullptr);
-        if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
-        if (reward_stats) {
-            hipLaunchKernelGGL(k_reward_count, dim3(cnt_grid), dim3(kThreads), 0, st, ring->rew + (size_t)c * rows, rows,
-                               reinterpret_cast<unsigned long long *>(reward_stats + 2 * t));
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_count: ") + hipGetErrorString(e), who);
-        }
-    }
-    if (reward_stats) {
-        hipLaunchKernelGGL(k_reward_stats, dim3((steps + kThreads - 1) / kThreads), dim3(kThreads), 0, st, reward_stats, (int)steps, rows);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_stats: ") + hipGetErrorString(e), who);
-    }
-    return SWARM_OK;
+        return L.step(act, SWARM_F32, t);
+    });
 }
+
+}  // namespace
 
 extern "C" {
 
@@ -366,69 +346,35 @@ int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t ste
         return fail(SWARM_ERR_INVALID, "source must be SWARM_EXPERT_RULE (0) or SWARM_EXPERT_LLM (1)", who);
     if (!env || !ring) return fail(SWARM_ERR_INVALID, "null env or ring", who);
     swarm_env_info ei;
-    if (swarm_internal_env_info(env, &ei) != SWARM_OK) return fail(SWARM_ERR_INVALID, "bad handle", who);
-    if (steps < 0) return fail(SWARM_ERR_INVALID, "steps < 0", who);
+    if (int rc = check_handles(who, env, steps, ei)) return rc;
     {
         std::string m = check_ring_shape(ei, ring);
         if (m.empty()) m = check_ring_slots(ei, ring);
         if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
     }
-    if (ei.n_agents > kRuleMaxAgents) return fail(SWARM_ERR_INVALID, "n_agents > 256", who);
+    if (ei.n_agents > 256) return fail(SWARM_ERR_INVALID, "n_agents > 256", who);
     if (source == SWARM_EXPERT_RULE && ei.g_max > 128)
         return fail(SWARM_ERR_INVALID, "the rule expert needs num_obs_grid_max <= 128 (as swarm_rule_action)", who);
     if (source == SWARM_EXPERT_LLM && !ei.llm_action)
         return fail(SWARM_ERR_INVALID, "the llm source needs a handle created with llm_action", who);
-    if (!ei.observed) return fail(SWARM_ERR_STATE, "the env handle is not observed (swarm_observe / swarm_reset first)", who);
+    if (int rc = check_observed(who, ei)) return rc;
     if (steps == 0) return SWARM_OK;
 
     // ---- enqueue
-    DeviceScope dev(ei.device);
-    if (!dev.ok) return fail(SWARM_ERR_HIP, "hipSetDevice failed", who);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (swarm_set_stream(env, stream) != SWARM_OK) return fail(SWARM_ERR_INVALID, "swarm_set_stream failed", who);
-    const long long rows = ring->rows;
-    const bool bf16 = ei.obs_dtype == SWARM_BF16;
-    const size_t obs_slot = (size_t)rows * ei.obs_dim * (bf16 ? 2 : 4), pri_slot = (size_t)rows * 2 * (bf16 ? 2 : 4);
-    char *const obs = static_cast<char *>(ring->obs), *const pri = static_cast<char *>(ring->prior);
-    if (reward_stats) {
-        const hipError_t e = hipMemsetAsync(reward_stats, 0, (size_t)steps * 2 * sizeof(double), st);
-        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e), who);
-    }
-    const unsigned act_grid = (unsigned)((rows + kThreads - 1) / kThreads);
-    const unsigned cnt_grid = (unsigned)std::min<long long>((rows + kThreads * kCountPerThread - 1) / (kThreads * kCountPerThread),
-                                                            kCountMaxBlocks);
-    for (int t = 0; t < steps; ++t) {
-        const int c = (int)(((long long)ring->cur + t) % ring->n_slots), n = (c + 1) % ring->n_slots;
-        float2 *const act = reinterpret_cast<float2 *>(ring->act + (size_t)c * rows * 2);
-        swarm_expert_view v;
-        int rc = swarm_internal_expert_view(env, source == SWARM_EXPERT_RULE, &v);
+    const Loop L(who, env, ei, ring, stream);
+    if (L.rc != SWARM_OK) return L.rc;
+    return run_loop(L, steps, reward_stats, [&](int t) {
+        swarm_expert_view v;                                             // RULE: after the index-export pass it enqueues
+        const int rc = swarm_internal_expert_view(env, source == SWARM_EXPERT_RULE, &v);
         if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
-        const void *step_act = nullptr;                                  // LLM: NULL = the handle's own action
         if (source == SWARM_EXPERT_RULE) {
-            const int e = launch_rule_ring(v, act, st);
-            if (e) return fail(SWARM_ERR_HIP, std::string("k_rule_ring: ") + hipGetErrorString((hipError_t)e), who);
-            step_act = v.act64;
-        } else {
-            hipLaunchKernelGGL(k_act_f32, dim3(act_grid), dim3(kThreads), 0, st, v.act_next, act, rows);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_act_f32: ") + hipGetErrorString(e), who);
+            if (int e = L.check(swarm_internal_launch_rule(v, reinterpret_cast<double *>(v.act64), L.act(t), L.st), "k_rule")) return e;
+            return L.step(v.act64, SWARM_F64, t);
         }
-        rc = swarm_step(env, step_act, SWARM_F64, obs + n * obs_slot, ring->rew + (size_t)c * rows, ring->done + (size_t)c * rows,
-                        pri ? pri + c * pri_slot : nullptr);
-        if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
-        if (reward_stats) {
-            hipLaunchKernelGGL(k_reward_count, dim3(cnt_grid), dim3(kThreads), 0, st, ring->rew + (size_t)c * rows, rows,
-                               reinterpret_cast<unsigned long long *>(reward_stats + 2 * t));
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_count: ") + hipGetErrorString(e), who);
-        }
-    }
-    if (reward_stats) {
-        hipLaunchKernelGGL(k_reward_stats, dim3((steps + kThreads - 1) / kThreads), dim3(kThreads), 0, st, reward_stats, (int)steps, rows);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_stats: ") + hipGetErrorString(e), who);
-    }
-    return SWARM_OK;
+        hipLaunchKernelGGL(k_act_f32, dim3(L.row_grid()), dim3(kThreads), 0, L.st, v.act_next, reinterpret_cast<float2 *>(L.act(t)), L.rows);
+        if (int e = L.launched("k_act_f32")) return e;
+        return L.step(nullptr, SWARM_F64, t);                            // NULL = the handle's own 'llm' action
+    });
 }
 
 int swarm_rollout_eval(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps, const int32_t *switch_to,
@@ -439,29 +385,8 @@ int swarm_rollout_eval(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t
     if (!env || !pol || !ring) return fail(SWARM_ERR_INVALID, "null env, policy or ring", who);
     swarm_env_info ei;
     swarm_policy_info pi;
-    if (swarm_internal_env_info(env, &ei) != SWARM_OK || swarm_internal_policy_info(pol, &pi) != SWARM_POLICY_OK)
-        return fail(SWARM_ERR_INVALID, "bad handle", who);
-    char msg[256];
-    if (steps < 0) return fail(SWARM_ERR_INVALID, "steps < 0", who);
-    if (ei.device != pi.device) {
-        std::snprintf(msg, sizeof msg, "env handle on device %d, policy on device %d", ei.device, pi.device);
-        return fail(SWARM_ERR_INVALID, msg, who);
-    }
-    {
-        std::string m = check_ring_shape(ei, ring);
-        if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
-    }
-    const long long rows = (long long)ei.n_env * ei.n_agents;
-    if (pi.in_dim != ei.obs_dim) {
-        std::snprintf(msg, sizeof msg, "policy in_dim %d != env obs_dim %d", pi.in_dim, ei.obs_dim);
-        return fail(SWARM_ERR_INVALID, msg, who);
-    }
-    if (pi.act_dim != 2) return fail(SWARM_ERR_INVALID, "policy act_dim must be 2 (the env's action)", who);
-    if (ei.obs_dtype == SWARM_BF16 && (pi.in_dim & 7)) return fail(SWARM_ERR_INVALID, "bf16 observation rows need obs_dim % 8 == 0", who);
-    {
-        const std::string m = check_ring_slots(ei, ring);
-        if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
-    }
+    if (int rc = check_handles(who, env, steps, ei, pol, &pi)) return rc;
+    if (int rc = check_policy_ring(who, ei, pi, ring)) return rc;
     const swarm_eval_out_t none = {nullptr, nullptr, nullptr, nullptr};
     const swarm_eval_out_t &o = out ? *out : none;
     if ((o.p == nullptr) != (o.dp == nullptr)) return fail(SWARM_ERR_INVALID, "the state trace needs p and dp together", who);
@@ -469,6 +394,7 @@ int swarm_rollout_eval(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t
     if (switch_to) {
         for (int t = 0; t < steps; ++t) {
             if (switch_to[t] < -1 || (switch_to[t] >= 0 && ei.n_shapes >= 1 && switch_to[t] >= ei.n_shapes)) {
+                char msg[256];
                 std::snprintf(msg, sizeof msg, "switch_to[%d] = %d outside [-1, n_shapes = %d)", t, (int)switch_to[t], ei.n_shapes);
                 return fail(SWARM_ERR_INVALID, msg, who);
             }
@@ -476,33 +402,20 @@ int swarm_rollout_eval(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t
         }
     }
     if (switches && ei.n_shapes < 1) return fail(SWARM_ERR_STATE, "switch_to needs a shape set (swarm_set_shapes)", who);
-    if (!ei.observed) return fail(SWARM_ERR_STATE, "the env handle is not observed (swarm_observe / swarm_reset first)", who);
+    if (int rc = check_observed(who, ei)) return rc;
     if (steps == 0) return SWARM_OK;
 
     // ---- enqueue
-    DeviceScope dev(ei.device);
-    if (!dev.ok) return fail(SWARM_ERR_HIP, "hipSetDevice failed", who);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (swarm_set_stream(env, stream) != SWARM_OK) return fail(SWARM_ERR_INVALID, "swarm_set_stream failed", who);
-    const bool bf16 = ei.obs_dtype == SWARM_BF16;
-    const size_t obs_slot = (size_t)rows * ei.obs_dim * (bf16 ? 2 : 4), pri_slot = (size_t)rows * 2 * (bf16 ? 2 : 4);
-    char *const obs = static_cast<char *>(ring->obs), *const pri = static_cast<char *>(ring->prior);
+    const Loop L(who, env, ei, ring, stream);
+    if (L.rc != SWARM_OK) return L.rc;
     swarm_expert_view v;                                                 // the handle's p / dp (no lists: nothing is enqueued)
     if (swarm_internal_expert_view(env, false, &v) != SWARM_OK) return fail(SWARM_ERR_INVALID, "bad handle", who);
-    if (o.reward_stats) {
-        const hipError_t e = hipMemsetAsync(o.reward_stats, 0, (size_t)steps * 2 * sizeof(double), st);
-        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e), who);
-    }
-    const size_t state_elems = (size_t)rows * 2, state_bytes = state_elems * sizeof(double);
-    const unsigned cnt_grid = (unsigned)std::min<long long>((rows + kThreads * kCountPerThread - 1) / (kThreads * kCountPerThread),
-                                                            kCountMaxBlocks);
-    for (int t = 0; t < steps; ++t) {
-        const int c = (int)(((long long)ring->cur + t) % ring->n_slots), n = (c + 1) % ring->n_slots;
-        float *const act = ring->act + (size_t)c * rows * 2;
+    const size_t state_elems = (size_t)L.rows * 2, state_bytes = state_elems * sizeof(double);
+    return run_loop(L, steps, o.reward_stats, [&](int t) {
         if (o.p) {
-            hipError_t e = hipMemcpyAsync(o.p + (size_t)t * state_elems, v.p, state_bytes, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.dp + (size_t)t * state_elems, v.dp, state_bytes, hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("state trace copy: ") + hipGetErrorString(e), who);
+            hipError_t e = hipMemcpyAsync(o.p + (size_t)t * state_elems, v.p, state_bytes, hipMemcpyDeviceToDevice, L.st);
+            if (e == hipSuccess) e = hipMemcpyAsync(o.dp + (size_t)t * state_elems, v.dp, state_bytes, hipMemcpyDeviceToDevice, L.st);
+            if (int rc = L.check(e, "state trace copy")) return rc;
         }
         if (switch_to && switch_to[t] >= 0) {
             const int rc = swarm_select_shape(env, switch_to[t], nullptr);
@@ -512,24 +425,10 @@ int swarm_rollout_eval(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t
             const int rc = swarm_internal_metrics_step(env, o.metrics + (size_t)t * ei.n_env * 3);
             if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
         }
-        if (swarm_policy_forward_explore_at(pol, obs + c * obs_slot, bf16, rows, act, 0.0f, 0, (uint64_t)t, 0, stream) != SWARM_POLICY_OK)
+        if (swarm_policy_forward_explore_at(pol, L.obs(L.c(t)), L.bf16, L.rows, L.act(t), 0.0f, 0, (uint64_t)t, 0, stream) != SWARM_POLICY_OK)
             return fail(SWARM_ERR_HIP, swarm_policy_last_error(), who);
-        const int rc = swarm_step(env, act, SWARM_F32, obs + n * obs_slot, ring->rew + (size_t)c * rows, ring->done + (size_t)c * rows,
-                                  pri ? pri + c * pri_slot : nullptr);
-        if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
-        if (o.reward_stats) {
-            hipLaunchKernelGGL(k_reward_count, dim3(cnt_grid), dim3(kThreads), 0, st, ring->rew + (size_t)c * rows, rows,
-                               reinterpret_cast<unsigned long long *>(o.reward_stats + 2 * t));
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_count: ") + hipGetErrorString(e), who);
-        }
-    }
-    if (o.reward_stats) {
-        hipLaunchKernelGGL(k_reward_stats, dim3((steps + kThreads - 1) / kThreads), dim3(kThreads), 0, st, o.reward_stats, (int)steps, rows);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SWARM_ERR_HIP, std::string("k_reward_stats: ") + hipGetErrorString(e), who);
-    }
-    return SWARM_OK;
+        return L.step(L.act(t), SWARM_F32, t);
+    });
 }
 
 }  // extern "C"

@@ -2321,73 +2321,6 @@ k_metrics_step(const KP P, double *__restrict__ out, const int stride)
 }
 
 
-// -------------------------------------------------------------------------------------------------
-// rule-based expert controller: agent_strategy == 'rule',
-// /root/reference/cus_gym/gym/envs/customized_envs/assembly.py:530-601, for the CURRENT state.  Not a hot path (expert
-// data collection, collect_expert_data.py): one thread per agent, fp64 in numpy's operation order (np.sum's pairwise
-// blocks of 8 included).  It consumes what the observation pass left in HBM: nearest cell / in-shape flag and the
-// capped sensed-cell list (`exp_sensed`, the same filter + round(i*step) selection as :544-572).  np.cos is numpy's
-// vectorised routine, so v_exp agrees to a few ulp, not bit for bit (tests: 1e-12 absolute on the clipped action).
-// -------------------------------------------------------------------------------------------------
-using swarm_internal::np_sum_stream;     // np.sum of f(0..n-1) for n <= 128 (swarm_internal.h)
-using swarm_internal::np_clip1;          // np.clip(v, -1, 1): a NaN stays NaN (swarm_internal.h)
-
-__global__ void __launch_bounds__(256)
-k_rule(const KP P, double *__restrict__ out)     // out [E][N][2]
-{
-    const int N = P.n_a, e = blockIdx.x, G = P.g_max;
-    const double *px = P.p + (size_t)e * 2 * N, *py = px + N;
-    const double *vx = P.dp + (size_t)e * 2 * N, *vy = vx + N;
-    const double *gx = P.cells + (size_t)e * 2 * P.ng_max, *gy = gx + P.ng_max;
-    const double k_1 = 1, k_2 = 15, k_3 = 17;                                  // :532
-    for (int i = threadIdx.x; i < N; i += blockDim.x) {
-        const double xi = px[i], yi = py[i], ui = vx[i], wi = vy[i];
-        const bool in_shape = P.in_flag[(size_t)e * N + i] != 0;
-        double ent_x = 0.0, ent_y = 0.0;                                       // :538-541
-        if (!in_shape) {
-            const int bc = P.near_cell[(size_t)e * N + i];
-            const double rx = gx[bc] - xi, ry = gy[bc] - yi;
-            const double nr = sqrt(rx * rx + ry * ry) + 1e-8;
-            ent_x = k_1 * (rx / nr) + (0.0 - ui);
-            ent_y = k_1 * (ry / nr) + (0.0 - wi);
-        }
-        const int *sel = P.exp_sensed + ((size_t)e * N + i) * G;               // capped list, -1 padded (:561-572)
-        int n = 0;
-        while (n < G && sel[n] >= 0) ++n;
-        double exp_x = 0.0, exp_y = 0.0;                                       // :574-584
-        if (n > 0) {
-            auto psi = [&](double rx, double ry) {                             // _rho_cos_dec(z, 0, d_sen) :846-850
-                const double z = sqrt(rx * rx + ry * ry);
-                return z < P.d_sen ? 0.5 * (1.0 + cos(M_PI * (z / P.d_sen - 0) / (1.0 - 0))) : 0.0;
-            };
-            const double sx = np_sum_stream(n, [&](int q) { const int c = sel[q]; const double rx = gx[c] - xi, ry = gy[c] - yi; return psi(rx, ry) * rx; });
-            const double sy = np_sum_stream(n, [&](int q) { const int c = sel[q]; const double rx = gx[c] - xi, ry = gy[c] - yi; return psi(rx, ry) * ry; });
-            double den = np_sum_stream(n, [&](int q) { const int c = sel[q]; return psi(gx[c] - xi, gy[c] - yi); });
-            if (den == 0) den = 1e-8;
-            exp_x = k_2 * sx / den; exp_y = k_2 * sy / den;
-        }
-        int n_near = 0;                                                        // :587-598
-        for (int j = 0; j < N; ++j) {
-            const double rx = px[j] - xi, ry = py[j] - yi;
-            n_near += (j != i && sqrt(rx * rx + ry * ry) < P.d_sen) ? 1 : 0;
-        }
-        double int_x = 0.0, int_y = 0.0;
-        for (int j = 0; j < N; ++j) {
-            const double rx = px[j] - xi, ry = py[j] - yi;
-            const double nr = sqrt(rx * rx + ry * ry);
-            if (j == i || !(nr < P.d_sen)) continue;
-            if (nr < P.r_avoid) {
-                const double c = -k_3 * (P.r_avoid / nr - 1);
-                int_x += c * rx; int_y += c * ry;
-            }
-            int_x += 5 * (vx[j] - ui) / n_near; int_y += 5 * (vy[j] - wi) / n_near;
-        }
-        const double ax = (ent_x + exp_x) + int_x, ay = (ent_y + exp_y) + int_y;
-        out[((size_t)e * N + i) * 2 + 0] = np_clip1(ax);                       // np.clip :601
-        out[((size_t)e * N + i) * 2 + 1] = np_clip1(ay);
-    }
-}
-
 // (x, y)-interleaved copy of the target cells of envs [e0, e0 + count): the step kernel gathers cells per lane, and one
 // 16-byte load per cell costs half the address-unit work of two 8-byte loads from the ABI's [2][ng_max] layout.
 __global__ void __launch_bounds__(256)
@@ -2807,6 +2740,24 @@ int launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *ob
     return fail(h, SWARM_ERR_INVALID, "unsupported agent count");
 }
 
+// Re-run the observation pass on the current state with the export switched on (the step keeps the index scratch in LDS and
+// writes none of it to HBM); it recomputes the same caches from the same state, so it is idempotent.  Always leaves nearest
+// cell / in-shape flag / neighbours in HBM; lists: also the sensed / occupied cell lists (allocated on first use); cap_even:
+// the expert's rounding of the sensed-list subsample (KP::cap_even).  Enqueued on the handle's stream, no synchronisation.
+int export_pass(swarm_env *h, bool lists, bool cap_even)
+{
+    if (lists && !h->d_exp_sensed) {
+        const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
+        HIP_TRY(h, hipMalloc((void **)&h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4));
+        HIP_TRY(h, hipMalloc((void **)&h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4));
+    }
+    h->kp.export_small = 1; h->kp.cap_even = cap_even;
+    if (lists) { h->kp.export_idx = 1; h->kp.exp_sensed = h->d_exp_sensed; h->kp.exp_occ = h->d_exp_occ; }
+    const int rc = launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+    h->kp.export_idx = 0; h->kp.export_small = 0; h->kp.cap_even = 0;
+    return rc;
+}
+
 }  // namespace
 
 int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out)
@@ -2839,17 +2790,8 @@ int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_expert_view *ou
 {
     if (!h || !out) return SWARM_ERR_INVALID;
     if (lists) {
-        const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
-        if (!h->d_exp_sensed) {
-            HIP_TRY(h, hipMalloc((void **)&h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4));
-            HIP_TRY(h, hipMalloc((void **)&h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4));
-        }
-        if (!h->d_act64) HIP_TRY(h, hipMalloc((void **)&h->d_act64, EN * sizeof(double2)));
-        // the observation pass of swarm_rule_action on the current state, index export on (idempotent, see swarm_get_indices)
-        h->kp.export_idx = 1; h->kp.export_small = 1; h->kp.exp_sensed = h->d_exp_sensed; h->kp.exp_occ = h->d_exp_occ;
-        h->kp.cap_even = 1;
-        const int rc = launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-        h->kp.export_idx = 0; h->kp.export_small = 0; h->kp.cap_even = 0;
+        if (!h->d_act64) HIP_TRY(h, hipMalloc((void **)&h->d_act64, (size_t)h->cfg.n_env * h->cfg.n_agents * sizeof(double2)));
+        const int rc = export_pass(h, true, true);
         if (rc != SWARM_OK) return rc;
     }
     out->p = h->d_p; out->dp = h->d_dp; out->cells = h->d_cells;
@@ -3420,23 +3362,10 @@ int swarm_get_indices(swarm_env_t *h, int32_t *neighbor_index, int32_t *in_flags
     if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_get_indices: nothing observed yet");
     DeviceGuard g(h->device);
     const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
-    const bool lists = sensed_index || occupied_index;
-    if (lists && !h->d_exp_sensed) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4));
-        HIP_TRY(h, hipMalloc((void **)&h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4));
-    }
-    {
-        // re-run the observation pass on the current state with the export switched on (the step keeps the index
-        // scratch in LDS and writes none of it to HBM); it recomputes the same caches from the same state, so it is
-        // idempotent.
-        h->kp.export_small = 1;
-        if (lists) { h->kp.export_idx = 1; h->kp.exp_sensed = h->d_exp_sensed; h->kp.exp_occ = h->d_exp_occ; }
-        int rc = launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-        h->kp.export_idx = 0; h->kp.export_small = 0;
-        if (rc != SWARM_OK) return rc;
-        if (sensed_index) HIP_TRY(h, hipMemcpyAsync(sensed_index, h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4, hipMemcpyDefault, h->stream));
-        if (occupied_index) HIP_TRY(h, hipMemcpyAsync(occupied_index, h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4, hipMemcpyDefault, h->stream));
-    }
+    const int rc = export_pass(h, sensed_index || occupied_index, false);
+    if (rc != SWARM_OK) return rc;
+    if (sensed_index) HIP_TRY(h, hipMemcpyAsync(sensed_index, h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4, hipMemcpyDefault, h->stream));
+    if (occupied_index) HIP_TRY(h, hipMemcpyAsync(occupied_index, h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4, hipMemcpyDefault, h->stream));
     if (neighbor_index) HIP_TRY(h, hipMemcpyAsync(neighbor_index, h->d_nei, EN * (size_t)h->kp.topo * 4, hipMemcpyDefault, h->stream));
     if (in_flags) HIP_TRY(h, hipMemcpyAsync(in_flags, h->d_inflag, EN * 4, hipMemcpyDefault, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -3449,19 +3378,12 @@ int swarm_rule_action(swarm_env_t *h, double *action)
     if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_rule_action: nothing observed yet");
     if (h->kp.g_max > 128) return fail(h, SWARM_ERR_INVALID, "swarm_rule_action: num_obs_grid_max > 128 not supported");
     DeviceGuard g(h->device);
-    const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
-    if (!h->d_exp_sensed) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4));
-        HIP_TRY(h, hipMalloc((void **)&h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4));
-    }
-    // observation pass on the current state with the index export switched on (idempotent, see swarm_get_indices)
-    h->kp.export_idx = 1; h->kp.export_small = 1; h->kp.exp_sensed = h->d_exp_sensed; h->kp.exp_occ = h->d_exp_occ;
-    h->kp.cap_even = 1;
-    int rc = launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-    h->kp.export_idx = 0; h->kp.export_small = 0; h->kp.cap_even = 0;
+    int rc = export_pass(h, true, true);
     if (rc != SWARM_OK) return rc;
-    hipLaunchKernelGGL(k_rule, dim3(h->cfg.n_env), dim3(h->cfg.n_agents <= 64 ? 64 : 256), 0, h->stream, h->kp, action);
-    HIP_TRY(h, hipGetLastError());
+    swarm_expert_view v;
+    rc = swarm_internal_expert_view(h, false, &v);
+    if (rc != SWARM_OK) return rc;
+    HIP_TRY(h, swarm_internal_launch_rule(v, action, nullptr, h->stream));       // k_rule (rule_expert.hip)
     return SWARM_OK;
 }
 

@@ -1,7 +1,7 @@
 // Internal interface between the translation units of libswarmenv.so: what the device rollout loop (rollout.hip) needs to
-// know about the two opaque handles, and the counter-based hash every in-kernel generator is built from.  Not installed,
-// not exported: the accessors have hidden visibility, so the public ABI (swarm_env.h, swarm_policy.h, swarm_rollout.h)
-// does not change.
+// know about the two opaque handles, the rule-expert kernel's launcher (rule_expert.hip; called by swarm_env.hip and
+// rollout.hip) and the counter-based hash every in-kernel generator is built from.  Not installed, not exported: the
+// accessors have hidden visibility, so the public ABI (swarm_env.h, swarm_policy.h, swarm_rollout.h) does not change.
 #ifndef SWARM_INTERNAL_H
 #define SWARM_INTERNAL_H
 
@@ -66,9 +66,9 @@ struct swarm_env_info {
 };
 SWARM_HIDDEN int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out);
 
-// What the expert sources of swarm_rollout_expert read for the CURRENT state: the fp64 state, the target cells, the lists
-// the index-export observation pass leaves in HBM (nearest cell, in-shape flag, capped sensed-cell list), the 'llm'
-// strategy's next action and the handle's fp64 action scratch.  All device pointers of the handle's device.
+// What the rule-expert kernel and the expert sources of swarm_rollout_expert read for the CURRENT state: the fp64 state, the
+// target cells, the lists the index-export observation pass leaves in HBM (nearest cell, in-shape flag, capped sensed-cell
+// list), the 'llm' strategy's next action and the handle's fp64 action scratch.  All device pointers of the handle's device.
 struct swarm_expert_view {
     const double *p, *dp;               // [E][2][N]
     const double *cells;                // [E][2][ng_max]
@@ -83,6 +83,11 @@ struct swarm_expert_view {
 // pass of swarm_rule_action on the handle's stream (no host synchronisation); false: only fill `out`.  SWARM_OK or an error
 // code with the message in swarm_last_error(h).
 SWARM_HIDDEN int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_expert_view *out);
+
+// Enqueue the rule-expert kernel (rule_expert.hip) on `st` for the lists in `v`: the fp64 action into act64 [E][N][2] (8-byte
+// aligned; 16-byte aligned when act32 is given, as v.act64 is) and, act32 != NULL, its f32 rounding into act32 [E][N][2].
+// Returns the launch's hipGetLastError().
+SWARM_HIDDEN hipError_t swarm_internal_launch_rule(const swarm_expert_view &v, double *act64, float *act32, hipStream_t st);
 
 // The evaluation loop's per-step metrics launch: out[E][3] (DEVICE), bit for bit what swarm_metrics writes (k_metrics_step in
 // swarm_env.hip).  Enqueued on the handle's stream; no host synchronisation.

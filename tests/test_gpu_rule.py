@@ -69,6 +69,59 @@ def test_rule_action_matches_restatement_on_synthetic_batches(n_a, n_env):
     sb.close()
 
 
+@pytest.mark.parametrize("n_a", [3, 65])      # 64-thread launch, one mask word; 256-thread launch, one agent in the second word
+def test_rule_action_into_a_destination_that_is_only_8_byte_aligned(n_a):
+    """swarm_rule_action takes a `double *`: 8 bytes into a larger buffer is a valid destination.  The rollout's instantiation
+    of the same kernel stores 16 bytes per agent into the handle's own scratch; this entry point must not.  Also the two
+    orders in which a handle can first meet the two entry points (the action scratch is allocated by the rollout only)."""
+    import ctypes
+    import torch
+    from marl_llm_amd._lib import check
+    from marl_llm_amd.batched import SwarmBatch
+    from marl_llm_amd.rollout import ChainedReplay, rollout_expert
+    from marl_llm_amd.shapes import r_avoid_for, synthetic_shape_set
+    from marl_llm_amd.synth import synthetic_batch
+    n_env, sentinel = 2, 7.5
+    shapes = synthetic_shape_set()
+    sy = synthetic_batch(n_env, n_a, shapes, seed=77)
+
+    def handle():
+        sb = SwarmBatch(n_env=n_env, n_agents=n_a, n_cells_max=sy["cells"].shape[2], r_avoid=r_avoid_for(n_a, shapes), device="cuda:0")
+        sb.set_cells(sy["cells"], sy["n_g"], sy["l_cell"])
+        sb.set_state(sy["p"], sy["dp"])
+        return sb, sb.observe()
+
+    def expert_step(sb, obs):
+        ring = ChainedReplay(1, n_env * n_a, sb.obs_dim, 2, sb.device)
+        rollout_expert(sb, 1, obs=obs, replay=ring, track_reward=False)
+        return ring.act[0].view(n_env, n_a, 2)
+
+    sb, obs = handle()
+    n = n_env * n_a * 2
+    buf = torch.full((n + 4,), sentinel, dtype=torch.float64, device=sb.device)
+    dst = buf[1: 1 + n]
+    assert dst.data_ptr() % 16 == 8
+    sb._sync_stream()
+    check(sb.lib, sb.handle, sb.lib.swarm_rule_action(sb.handle, ctypes.c_void_p(dst.data_ptr())))
+    u = sb.rule_action()
+    assert torch.equal(dst.view(torch.int64), u.view(-1).view(torch.int64))
+    assert bool((buf[:1] == sentinel).all()) and bool((buf[1 + n:] == sentinel).all())
+    assert bool((u.abs() < 1).any())                                   # not only clipped components
+
+    # swarm_rule_action first, then the handle's first expert rollout: against an eager twin
+    assert torch.equal(expert_step(sb, obs), u.float())
+    twin, _ = handle()
+    twin.step(u)
+    for a, b in zip(sb.get_state(), twin.get_state()):
+        assert torch.equal(a.view(torch.int64), b.view(torch.int64))
+    # the opposite order: a handle whose first expert call is the rollout, then swarm_rule_action on the state it left
+    rev, obs = handle()
+    assert torch.equal(expert_step(rev, obs), u.float())
+    assert torch.equal(rev.rule_action().view(torch.int64), twin.rule_action().view(torch.int64))
+    for h in (sb, twin, rev):
+        h.close()
+
+
 def test_env_rule_mode_returns_the_applied_action():
     """AssemblySwarmEnv(agent_strategy='rule', is_collected=True): step ignores the passed action and returns u."""
     from marl_llm_amd.env import AssemblySwarmWrapper, AssemblySwarmEnv, make_args

@@ -11,8 +11,8 @@ for K in "ILi64EfLb1ELb1ELb0E" "ILi64EfLb1ELb0ELb0E" "ILi64EfLb0ELb1ELb0E" "ILi3
   E=$(awk -v L=$L 'NR>L && /\.end_amdhsa_kernel/{print NR; exit}' $S)
   echo "k_env<$K>" $(awk -v L=$L 'NR>L && /; (NumVgprs|ScratchSize|Occupancy|codeLenInByte)/{printf "%s ", $0; n++} n>=4{exit}' $S) "; spill instructions:" $(sed -n "${L},${E}p" $S | grep -c "Folded Spill\|Folded Reload")
 done
-# the policy kernel (VGPRs must not move: 218 for the bf16 instantiations) and the rollout loop's kernels (no scratch)
-for F in policy_mlp rollout; do
+# the policy kernel (VGPRs must not move: 218 for the bf16 instantiations), the rollout loop's kernels and the rule expert (no scratch)
+for F in policy_mlp rollout rule_expert; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -I$R/include -c $R/marl_llm_amd/csrc/$F.hip -o $T/$F.o \
       -Rpass-analysis=kernel-resource-usage 2>&1 | sed -n 's/.*remark: *//p' | sed 's/ \[-Rpass-analysis.*//' |
     awk '/^Function Name:/{if (l) print l; l=$3; next} /^(VGPRs|AGPRs|ScratchSize|Occupancy)/{l=l" ; "$0} END{if (l) print l}'
