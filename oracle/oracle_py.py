@@ -34,6 +34,7 @@ VEL_MAX = 0.8
 DT = 0.1
 D_SEN = 0.4
 BOUNDARY = np.array([-2.4, 2.4, 2.4, -2.4], dtype=np.float64)
+PRIOR_GAIN = (2.0, 3.0, 2.0)        # attraction, repulsion, alignment (AssemblyEnv.cpp:1128-1132)
 
 
 def build_oracle(force=False):
@@ -73,7 +74,8 @@ class Oracle:
         build_oracle()
         self.lib = ctypes.CDLL(ORACLE_SO)
         for name in ("orc_get_observation", "orc_get_reward", "orc_get_dist_b2b", "orc_sf_b2b_all",
-                     "orc_get_dist_b2w", "orc_action_prior", "orc_step", "orc_step_batch"):
+                     "orc_get_dist_b2w", "orc_action_prior", "orc_action_prior_g", "orc_step", "orc_step_g",
+                     "orc_step_batch", "orc_step_batch_g"):
             getattr(self.lib, name).restype = None
 
     def get_observation(self, p, dp, grid, l_cell, r_avoid, d_sen=D_SEN, boundary=BOUNDARY,
@@ -134,62 +136,66 @@ class Oracle:
                                   _d(np.ascontiguousarray(boundary, np.float64)))
         return d, c.astype(bool)
 
-    def action_prior(self, p, dp, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN):
+    def action_prior(self, p, dp, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN, prior_gain=PRIOR_GAIN):
         p = np.ascontiguousarray(p, np.float64); dp = np.ascontiguousarray(dp, np.float64)
         grid = np.ascontiguousarray(grid, np.float64)
         n_a, n_g = p.shape[1], grid.shape[1]
         ap = np.zeros((2, n_a))
         nei = np.ascontiguousarray(neighbor_index, np.int32)
-        self.lib.orc_action_prior(_d(p), _d(dp), _d(ap), _d(grid), _i(nei), ctypes.c_double(d_sen),
-                                  ctypes.c_double(r_avoid), ctypes.c_double(l_cell), ctypes.c_int(nei.shape[1]),
-                                  ctypes.c_int(n_a), ctypes.c_int(n_g))
+        self.lib.orc_action_prior_g(_d(p), _d(dp), _d(ap), _d(grid), _i(nei), ctypes.c_double(d_sen),
+                                    ctypes.c_double(r_avoid), ctypes.c_double(l_cell), ctypes.c_int(nei.shape[1]),
+                                    ctypes.c_int(n_a), ctypes.c_int(n_g), _d(np.array(prior_gain, np.float64)))
         return ap
 
     def step(self, p, dp, a, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN, boundary=BOUNDARY,
-             is_boundary=True, with_self=True, with_prior=True):
-        """One env step.  Returns a dict with the NEW p, dp and every output (inputs are not modified)."""
+             is_boundary=True, with_self=True, with_prior=True, *, size_a=SIZE_A, k_ball=K_BALL, k_wall=K_WALL,
+             c_wall=C_WALL, vel_max=VEL_MAX, dt=DT, topo=TOPO, g_max=G_MAX, occ_max=OCC_MAX, prior_gain=PRIOR_GAIN):
+        """One env step.  Returns a dict with the NEW p, dp and every output (inputs are not modified).  The keyword-only
+        constants default to the reference's; prior_gain = (attraction, repulsion, alignment)."""
         p = np.array(p, np.float64, order="C"); dp = np.array(dp, np.float64, order="C")
         a = np.ascontiguousarray(a, np.float64); grid = np.ascontiguousarray(grid, np.float64)
         n_a, n_g = p.shape[1], grid.shape[1]
         nei = np.array(neighbor_index, np.int32, order="C")
-        od = obs_dim(with_self)
+        od = 2 * 2 * (topo + 1 + (1 if with_self else 0)) + 2 * g_max
         obs = np.zeros((od, n_a)); rew = np.zeros((1, n_a)); ap = np.zeros((2, n_a))
-        inf = np.empty(n_a, np.int32); sen = np.empty((n_a, G_MAX), np.int32); occ = np.empty((n_a, OCC_MAX), np.int32)
+        inf = np.empty(n_a, np.int32); sen = np.empty((n_a, g_max), np.int32); occ = np.empty((n_a, occ_max), np.int32)
         co = np.array([not is_boundary, True, with_self, False], np.uint8)
         cr = np.array([not is_boundary, True, True, True, True], np.uint8)
-        self.lib.orc_step(_d(p), _d(dp), _d(a), _d(obs), _d(rew), _d(ap) if with_prior else None,
+        self.lib.orc_step_g(_d(p), _d(dp), _d(a), _d(obs), _d(rew), _d(ap) if with_prior else None,
                           _d(np.ascontiguousarray(boundary, np.float64)), _d(grid), _i(nei), _i(inf), _i(sen), _i(occ),
                           ctypes.c_double(d_sen), ctypes.c_double(r_avoid), ctypes.c_double(l_cell),
-                          ctypes.c_double(SIZE_A), ctypes.c_double(K_BALL), ctypes.c_double(K_WALL),
-                          ctypes.c_double(C_WALL), ctypes.c_double(VEL_MAX), ctypes.c_double(DT),
-                          ctypes.c_int(TOPO), ctypes.c_int(G_MAX), ctypes.c_int(OCC_MAX),
+                          ctypes.c_double(size_a), ctypes.c_double(k_ball), ctypes.c_double(k_wall),
+                          ctypes.c_double(c_wall), ctypes.c_double(vel_max), ctypes.c_double(dt),
+                          ctypes.c_int(topo), ctypes.c_int(g_max), ctypes.c_int(occ_max),
                           ctypes.c_int(n_a), ctypes.c_int(n_g), ctypes.c_int(od), ctypes.c_int(int(is_boundary)),
-                          _b(co), _b(cr))
+                          _b(co), _b(cr), _d(np.array(prior_gain, np.float64)))
         return dict(p=p, dp=dp, obs=obs, reward=rew, a_prior=ap if with_prior else None,
                     neighbor_index=nei, in_flags=inf, sensed_index=sen, occupied_index=occ,
                     done=np.zeros((1, n_a), bool))
 
     def step_batch(self, p, dp, a, grid, n_g, l_cell, neighbor_index, r_avoid, d_sen=D_SEN, boundary=BOUNDARY,
-                   is_boundary=True, with_self=True, indices=False):
-        """E envs: p, dp, a [E,2,N]; grid [E,2,NG_MAX]; n_g, l_cell [E]; neighbor_index [E,N,6].
+                   is_boundary=True, with_self=True, indices=False, *, size_a=SIZE_A, k_ball=K_BALL, k_wall=K_WALL,
+                   c_wall=C_WALL, vel_max=VEL_MAX, dt=DT, topo=TOPO, g_max=G_MAX, occ_max=OCC_MAX, prior_gain=PRIOR_GAIN):
+        """E envs: p, dp, a [E,2,N]; grid [E,2,NG_MAX]; n_g, l_cell [E]; neighbor_index [E,N,topo].
         Advances p, dp, neighbor_index IN PLACE (timing leg), returns (obs[E,od,N], reward[E,N], a_prior[E,2,N]);
-        indices=True appends (in_flags[E,N], sensed_index[E,N,G_MAX], occupied_index[E,N,OCC_MAX])."""
+        indices=True appends (in_flags[E,N], sensed_index[E,N,g_max], occupied_index[E,N,occ_max]).
+        The keyword-only constants are Oracle.step's."""
         E, _, n_a = p.shape
-        od = obs_dim(with_self)
+        od = 2 * 2 * (topo + 1 + (1 if with_self else 0)) + 2 * g_max
         obs = np.zeros((E, od, n_a)); rew = np.zeros((E, n_a)); ap = np.zeros((E, 2, n_a))
-        inf = np.empty((E, n_a), np.int32); sen = np.empty((E, n_a, G_MAX), np.int32)
-        occ = np.empty((E, n_a, OCC_MAX), np.int32)
+        inf = np.empty((E, n_a), np.int32); sen = np.empty((E, n_a, g_max), np.int32)
+        occ = np.empty((E, n_a, occ_max), np.int32)
         co = np.array([not is_boundary, True, with_self, False], np.uint8)
         cr = np.array([not is_boundary, True, True, True, True], np.uint8)
         n_g = np.ascontiguousarray(n_g, np.int32); l_cell = np.ascontiguousarray(l_cell, np.float64)
-        self.lib.orc_step_batch(ctypes.c_int(E), _d(p), _d(dp), _d(a), _d(obs), _d(rew), _d(ap),
+        self.lib.orc_step_batch_g(ctypes.c_int(E), _d(p), _d(dp), _d(a), _d(obs), _d(rew), _d(ap),
                                 _d(np.ascontiguousarray(boundary, np.float64)), _d(grid), _i(n_g), _d(l_cell),
                                 ctypes.c_int(grid.shape[2]), _i(neighbor_index), _i(inf), _i(sen), _i(occ),
-                                ctypes.c_double(d_sen), ctypes.c_double(r_avoid), ctypes.c_double(SIZE_A),
-                                ctypes.c_double(K_BALL), ctypes.c_double(K_WALL), ctypes.c_double(C_WALL),
-                                ctypes.c_double(VEL_MAX), ctypes.c_double(DT), ctypes.c_int(TOPO), ctypes.c_int(G_MAX),
-                                ctypes.c_int(OCC_MAX), ctypes.c_int(n_a), ctypes.c_int(od),
-                                ctypes.c_int(int(is_boundary)), _b(co), _b(cr))
+                                ctypes.c_double(d_sen), ctypes.c_double(r_avoid), ctypes.c_double(size_a),
+                                ctypes.c_double(k_ball), ctypes.c_double(k_wall), ctypes.c_double(c_wall),
+                                ctypes.c_double(vel_max), ctypes.c_double(dt), ctypes.c_int(topo), ctypes.c_int(g_max),
+                                ctypes.c_int(occ_max), ctypes.c_int(n_a), ctypes.c_int(od),
+                                ctypes.c_int(int(is_boundary)), _b(co), _b(cr), _d(np.array(prior_gain, np.float64)))
         return (obs, rew, ap, inf, sen, occ) if indices else (obs, rew, ap)
 
 
@@ -302,24 +308,26 @@ def numpy_dist_b2b(p, is_periodic=False, w_half=2.4, h_half=2.4, size_a=SIZE_A):
 
 
 def ref_step(ref, p, dp, a, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN, boundary=BOUNDARY,
-             is_boundary=True, with_self=True):
+             is_boundary=True, with_self=True, *, size_a=SIZE_A, k_ball=K_BALL, k_wall=K_WALL, c_wall=C_WALL,
+             vel_max=VEL_MAX, dt=DT):
     """AssemblySwarmEnv.step (assembly.py:487-666; 'input' strategy, 'llm_rl' method) restated with the
-    five native calls going to the REAL reference library `ref` (a RefLib).  Inputs are not modified."""
+    five native calls going to the REAL reference library `ref` (a RefLib).  Inputs are not modified.  The keyword-only
+    constants are the env's attributes of the same names (assembly.py:44-79), defaulting to the reference's values."""
     p = np.array(p, np.float64, order="C"); dp = np.array(dp, np.float64, order="C")
     is_periodic = not is_boundary
     w_half = (boundary[2] - boundary[0]) / 2; h_half = (boundary[1] - boundary[3]) / 2
-    d_center, d_edge, collide = numpy_dist_b2b(p, is_periodic, w_half, h_half)
-    sf_b2b = ref.sf_b2b_all(p, d_edge, collide, d_center, boundary, is_periodic)
+    d_center, d_edge, collide = numpy_dist_b2b(p, is_periodic, w_half, h_half, size_a)
+    sf_b2b = ref.sf_b2b_all(p, d_edge, collide, d_center, boundary, is_periodic, k_ball)
     if is_boundary:
-        d_b2w, c_b2w = ref.dist_b2w(p, boundary)
-        sf_b2w = np.array([[1, 0, -1, 0], [0, -1, 0, 1]]).dot(c_b2w * d_b2w) * 100
-        df_b2w = np.array([[-1, 0, -1, 0], [0, -1, 0, -1]]).dot(c_b2w * np.concatenate((dp, dp), axis=0)) * 5
+        d_b2w, c_b2w = ref.dist_b2w(p, boundary, size_a)
+        sf_b2w = np.array([[1, 0, -1, 0], [0, -1, 0, 1]]).dot(c_b2w * d_b2w) * k_wall
+        df_b2w = np.array([[-1, 0, -1, 0], [0, -1, 0, -1]]).dot(c_b2w * np.concatenate((dp, dp), axis=0)) * c_wall
     a_prior = ref.action_prior(p, dp, grid, neighbor_index, l_cell, r_avoid, d_sen)
     F = 1 * a + sf_b2b + sf_b2w + df_b2w if is_boundary else 1 * a + sf_b2b
     ddp = F / np.ones(p.shape[1], dtype=int)
-    dp += ddp * DT
-    dp = np.clip(dp, -VEL_MAX, VEL_MAX)
-    p += dp * DT
+    dp += ddp * dt
+    dp = np.clip(dp, -vel_max, vel_max)
+    p += dp * dt
     if is_periodic:
         p[0, p[0, :] < boundary[0]] += 2 * w_half
         p[0, p[0, :] > boundary[2]] -= 2 * w_half

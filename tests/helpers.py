@@ -42,6 +42,162 @@ def make_case(rng, shapes, n_a, cluster, shape=None):
     return np.ascontiguousarray(p), np.ascontiguousarray(dp), g, l_cell
 
 
+def adversarial_case(rng, shapes, n_a, ra, d_sen=0.4, contact=0.07, shift=None):
+    """Agents placed (almost) exactly ON the decision thresholds the fp32 pre-filter has to resolve:
+    distance to a cell ~ d_sen and ~ r_avoid/2 (sensed / occupied bits), the midpoint between two cells
+    (nearest-cell ties), the in-shape radius, and agent pairs ~ d_sen, r_avoid and `contact` (= 2 size_a) apart.
+    shift (2, 1): the whole case is translated by it BEFORE the placements, so they sit on the thresholds at that offset."""
+    p, dp, g, l_cell = make_case(rng, shapes, n_a, 1)
+    if shift is not None:
+        g = np.ascontiguousarray(g + shift); p = p + shift
+    eps = [0.0, 1e-16, -1e-16, 1e-13, -1e-13, 1e-10, -1e-10, 1e-8, -1e-8, 3e-7, -3e-7, 2e-6, -2e-6]
+    k = 0
+    for i in range(n_a):
+        c = int(rng.integers(0, g.shape[1]))
+        th = rng.uniform(0, 2 * np.pi)
+        u = np.array([np.cos(th), np.sin(th)])
+        mode = i % 6
+        e = eps[k % len(eps)]; k += 1
+        if mode == 0:
+            p[:, i] = g[:, c] + u * d_sen * (1 + e)
+        elif mode == 1:
+            p[:, i] = g[:, c] + u * (ra / 2) * (1 + e)
+        elif mode == 2:
+            c2 = (c + 1) % g.shape[1]
+            mid = 0.5 * (g[:, c] + g[:, c2]); d = g[:, c2] - g[:, c]
+            p[:, i] = mid + d * e + np.array([-d[1], d[0]]) * rng.uniform(-0.3, 0.3)
+        elif mode == 3:
+            p[:, i] = g[:, c] + u * (np.sqrt(2) * l_cell / 2) * (1 + e)
+        elif mode == 4 and i > 0:
+            p[:, i] = p[:, i - 1] + u * [d_sen, ra, contact, d_sen + ra / 2][k % 4] * (1 + e)
+        elif mode == 5:
+            # nearest-cell ties across lattice rows: the midpoint of two vertically adjacent cells, the common vertex
+            # of a 2x2 block (four-way tie -> lowest index wins), and the same from far outside the shape
+            dd = np.linalg.norm(g - g[:, [c]], axis=0)
+            nb = np.where((dd > 0) & (dd < 1.01 * l_cell))[0]
+            if len(nb):
+                d = g[:, nb[int(rng.integers(0, len(nb)))]] - g[:, c]
+                perp = np.array([-d[1], d[0]])
+                sub = k % 3
+                if sub == 0:
+                    p[:, i] = g[:, c] + 0.5 * d + d * e
+                elif sub == 1:
+                    p[:, i] = g[:, c] + 0.5 * d + 0.5 * perp + u * abs(e)
+                else:
+                    p[:, i] = g[:, c] + 0.5 * d + perp * (rng.integers(3, 12) + 0.5) + d * e
+    return np.ascontiguousarray(p), dp, g, l_cell
+
+
+# ---- non-default configurations of the env step (test_gpu_config_parity.py, test_oracle_vs_reference.py) ----
+DEFAULT_BOX = (-2.4, 2.4, 2.4, -2.4)            # [x_min, y_max, x_max, y_min]
+OFF_BOX = (-1.5, 2.0, 3.0, -1.0)                # non-square, off-centre: w_half = 2.25, h_half = 1.5
+BIG_BOX = (-6.0, 6.0, 6.0, -6.0)
+DEFAULT_PHYS = dict(size_a=0.035, k_ball=30.0, k_wall=100.0, c_wall=5.0, vel_max=0.8, dt=0.1)
+# one constant at a time, then all together; none a power-of-two multiple of its default, no two fields equal
+DYNAMICS_ROWS = [("size_a", dict(size_a=0.05)), ("size_a_small", dict(size_a=0.02)), ("k_ball", dict(k_ball=45.0)),
+                 ("k_wall", dict(k_wall=60.0)), ("c_wall", dict(c_wall=2.5)), ("vel_max", dict(vel_max=0.5)),
+                 ("dt", dict(dt=0.05)), ("dt_long", dict(dt=0.13)),
+                 ("all", dict(size_a=0.05, k_ball=45.0, k_wall=60.0, c_wall=2.5, vel_max=0.5, dt=0.13))]
+
+
+def physics(**over):
+    """The six dynamics constants, the reference's values unless overridden."""
+    d = dict(DEFAULT_PHYS); d.update(over)
+    return d
+
+
+def config_case(rng, shapes, n_a, boundary=DEFAULT_BOX, size_a=0.035, vel_max=0.8, dt=0.1, cluster=1):
+    """One env (n_a >= 8) whose state reaches every term of the dynamics in the box `boundary`.  make_case's shape and
+    agents, translated so that the shape's bounding box is centred in the box, then
+      agents 0..3  at the left, top, right and bottom edge, closer than size_a (a wall contact) and closer than one step
+                   (a periodic wrap), moving outward = into the wall; 0 and 2 share their y, 1 and 3 their x, so in periodic
+                   mode each pair is a neighbour pair through the wrap of one axis only, and 0 -- the one row the
+                   reference's numpy distance matrix wraps -- is in contact with 2 through it;
+      agents 4, 5  1.2 size_a apart: in contact for this size_a;
+      agents 6, 7  between 2 size_a and the default 0.07 apart (0.08 at the default size): a contact for exactly one of
+                   this size_a and the default one;
+      agents 4..7  move at 0.995 vel_max per component, so a small push clips them.
+    Returns p, dp, grid, l_cell."""
+    p, dp, g, l_cell = make_case(rng, shapes, n_a, cluster)
+    x0, y1, x2, y3 = boundary
+    shift = np.array([[0.5 * (x0 + x2)], [0.5 * (y1 + y3)]]) - 0.5 * (g.min(axis=1, keepdims=True) + g.max(axis=1, keepdims=True))
+    g = np.ascontiguousarray(g + shift); p = p + shift
+    if not cluster:
+        p = np.stack([rng.uniform(x0, x2, n_a), rng.uniform(y3, y1, n_a)])
+    v = 0.6 * vel_max
+    gap = min(0.4 * size_a, 0.4 * v * dt)
+    ym, xm = rng.uniform(y3 + 0.3, y1 - 0.3), rng.uniform(x0 + 0.3, x2 - 0.3)
+    p[:, 0] = (x0 + gap, ym); dp[:, 0] = (-v, 0.01)
+    p[:, 1] = (xm, y1 - gap); dp[:, 1] = (0.02, v)
+    p[:, 2] = (x2 - gap, ym); dp[:, 2] = (v, -0.015)
+    p[:, 3] = (xm, y3 + gap); dp[:, 3] = (-0.025, -v)
+    th = rng.uniform(0, 2 * np.pi, 2)
+    u = np.stack([np.cos(th), np.sin(th)])
+    p[:, 5] = p[:, 4] + u[:, 0] * 1.2 * size_a
+    band = 0.08 if size_a == 0.035 else 0.5 * (2 * size_a + 0.07)
+    p[:, 7] = p[:, 6] + u[:, 1] * band
+    dp[:, 4:8] = 0.995 * vel_max * rng.choice([-1.0, 1.0], (2, 4))
+    return np.ascontiguousarray(p), np.ascontiguousarray(dp), g, l_cell
+
+
+def pad_cells(grids, ng_max):
+    """[E] lists of (2, n_g) cells -> SwarmBatch.set_cells' cells [E, 2, ng_max] and n_g [E]."""
+    cells = np.zeros((len(grids), 2, ng_max))
+    n_g = np.zeros(len(grids), np.int32)
+    for e, g in enumerate(grids):
+        n_g[e] = g.shape[1]
+        cells[e, :, : g.shape[1]] = g
+    return cells, n_g
+
+
+def oracle_run(oracle, cases, acts, r_avoid, d_sen=0.4, boundary=DEFAULT_BOX, periodic=False, prior_gain=(2.0, 3.0, 2.0), **phys):
+    """The oracle's trajectory of every case (p, dp, grid, l_cell) of `cases`: get_observation, then one step per entry of
+    `acts` ([E, N, 2] float32 actions; None = the previous step's prior rounded to float32, as a float32 policy would feed it
+    back).  Returns (first [E] observation dicts, steps [T][E] oracle.step dicts each with the float32 action it took under
+    "act" ([N, 2]), counts) where counts holds what the trajectory reached, from the oracle's own functions: agent-agent
+    contacts, contacts with each wall [left, top, right, bottom], velocity components clipped at +-vel_max, absolute wraps
+    at each edge [left, top, right, bottom] and neighbour-list entries that exist only through the periodic wrap."""
+    ph = physics(**phys)
+    b = np.array(boundary, np.float64)
+    w_half, h_half = (b[2] - b[0]) / 2, (b[1] - b[3]) / 2
+    first = [oracle.get_observation(p, dp, g, l, r_avoid, d_sen=d_sen, boundary=b, is_periodic=periodic) for p, dp, g, l in cases]
+    state = [(c[0], c[1], o["neighbor_index"]) for c, o in zip(cases, first)]
+    counts = dict(contact=0, wall=np.zeros(4, int), clip=0, wrap=np.zeros(4, int), wrap_only=0)
+
+    def wrap_only(p, dp, g, l, nei):
+        plain = oracle.get_observation(p, dp, g, l, r_avoid, d_sen=d_sen, boundary=b, is_periodic=False)["neighbor_index"]
+        return sum(len(set(a[a >= 0]) - set(q[q >= 0])) for a, q in zip(nei, plain))
+
+    if periodic:
+        counts["wrap_only"] += sum(wrap_only(c[0], c[1], c[2], c[3], o["neighbor_index"]) for c, o in zip(cases, first))
+    steps = []
+    for t, act in enumerate(acts):
+        row = []
+        for e, (p, dp, nei) in enumerate(state):
+            a = np.ascontiguousarray(act[e] if act is not None else steps[-1][e]["a_prior"].T.astype(np.float32))
+            g, l = cases[e][2], cases[e][3]
+            counts["contact"] += int(oracle.dist_b2b(p, b, periodic, ph["size_a"])[2].sum())
+            if not periodic:
+                counts["wall"] += oracle.dist_b2w(p, b, ph["size_a"])[1].sum(axis=1)
+            s = oracle.step(p, dp, np.ascontiguousarray(a.T), g, nei, l, r_avoid, d_sen=d_sen, boundary=b, is_boundary=not periodic,
+                            prior_gain=prior_gain, **ph)
+            counts["clip"] += int((np.abs(s["dp"]) == ph["vel_max"]).sum())
+            if periodic:
+                d = s["p"] - p
+                counts["wrap"] += [int((d[0] > w_half).sum()), int((d[1] < -h_half).sum()), int((d[0] < -w_half).sum()), int((d[1] > h_half).sum())]
+                counts["wrap_only"] += wrap_only(s["p"], s["dp"], g, l, s["neighbor_index"])
+            s["act"] = a
+            row.append(s)
+            state[e] = (s["p"], s["dp"], s["neighbor_index"])
+        steps.append(row)
+    return first, steps, counts
+
+
+def random_actions(rng, steps, n_env, n_a):
+    """The action schedule of the free-running parity tests: random float32 actions alternating with the fed-back prior."""
+    return [rng.uniform(-1, 1, (n_env, n_a, 2)).astype(np.float32) if t % 2 == 0 else None for t in range(steps)]
+
+
 def oracle_threads(n_items=None):
     """Worker count of the threaded oracle: at most 16 and at most the CPUs this process may run on (the machine's CPU count
     can be many times that), and no more than there are items to share out."""

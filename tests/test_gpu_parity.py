@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from helpers import GOLDEN_DIR, golden_files, load_golden, make_case
+from helpers import adversarial_case as _adversarial_case
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -282,49 +283,6 @@ def test_error_behaviour(shapes):
     with pytest.raises(SwarmError):                  # wrong action shape
         sb.step(torch.zeros((2, 7, 2), device=sb.device))
     sb.close()
-
-
-def _adversarial_case(rng, shapes, n_a, ra, d_sen=0.4):
-    """Agents placed (almost) exactly ON the decision thresholds the fp32 pre-filter has to resolve:
-    distance to a cell ~ d_sen and ~ r_avoid/2 (sensed / occupied bits), the midpoint between two cells
-    (nearest-cell ties), the in-shape radius, and agent pairs ~ d_sen, r_avoid and 0.07 apart."""
-    p, dp, g, l_cell = make_case(rng, shapes, n_a, 1)
-    eps = [0.0, 1e-16, -1e-16, 1e-13, -1e-13, 1e-10, -1e-10, 1e-8, -1e-8, 3e-7, -3e-7, 2e-6, -2e-6]
-    k = 0
-    for i in range(n_a):
-        c = int(rng.integers(0, g.shape[1]))
-        th = rng.uniform(0, 2 * np.pi)
-        u = np.array([np.cos(th), np.sin(th)])
-        mode = i % 6
-        e = eps[k % len(eps)]; k += 1
-        if mode == 0:
-            p[:, i] = g[:, c] + u * d_sen * (1 + e)
-        elif mode == 1:
-            p[:, i] = g[:, c] + u * (ra / 2) * (1 + e)
-        elif mode == 2:
-            c2 = (c + 1) % g.shape[1]
-            mid = 0.5 * (g[:, c] + g[:, c2]); d = g[:, c2] - g[:, c]
-            p[:, i] = mid + d * e + np.array([-d[1], d[0]]) * rng.uniform(-0.3, 0.3)
-        elif mode == 3:
-            p[:, i] = g[:, c] + u * (np.sqrt(2) * l_cell / 2) * (1 + e)
-        elif mode == 4 and i > 0:
-            p[:, i] = p[:, i - 1] + u * [d_sen, ra, 0.07, d_sen + ra / 2][k % 4] * (1 + e)
-        elif mode == 5:
-            # nearest-cell ties across lattice rows: the midpoint of two vertically adjacent cells, the common vertex
-            # of a 2x2 block (four-way tie -> lowest index wins), and the same from far outside the shape
-            dd = np.linalg.norm(g - g[:, [c]], axis=0)
-            nb = np.where((dd > 0) & (dd < 1.01 * l_cell))[0]
-            if len(nb):
-                d = g[:, nb[int(rng.integers(0, len(nb)))]] - g[:, c]
-                perp = np.array([-d[1], d[0]])
-                sub = k % 3
-                if sub == 0:
-                    p[:, i] = g[:, c] + 0.5 * d + d * e
-                elif sub == 1:
-                    p[:, i] = g[:, c] + 0.5 * d + 0.5 * perp + u * abs(e)
-                else:
-                    p[:, i] = g[:, c] + 0.5 * d + perp * (rng.integers(3, 12) + 0.5) + d * e
-    return np.ascontiguousarray(p), dp, g, l_cell
 
 
 @pytest.mark.parametrize("n_a,n_env,force", [(64, 24, 0), (64, 8, 1), (64, 12, 2), (64, 6, 3), (32, 16, 0), (32, 8, 2), (8, 16, 0),
