@@ -58,6 +58,38 @@ def _b(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte))
 
 
+def _chk(a, shape, dtype):
+    """A caller's pre-allocated output array: it is written in place, so it has to be exactly what the library expects."""
+    if not (isinstance(a, np.ndarray) and a.shape == tuple(shape) and a.dtype == dtype and a.flags.c_contiguous and a.flags.writeable):
+        raise ValueError("output array must be C-contiguous %s%s" % (np.dtype(dtype).name, tuple(shape)))
+    return a
+
+
+def _obs_out(out, od, n_a, topo, g_max, occ_max):
+    return (_chk(out["obs"], (od, n_a), np.float64), _chk(out["neighbor_index"], (n_a, topo), np.int32),
+            _chk(out["in_flags"], (n_a,), np.int32), _chk(out["sensed_index"], (n_a, g_max), np.int32),
+            _chk(out["occupied_index"], (n_a, occ_max), np.int32))
+
+
+def obs_out_arrays(n_a, topo=None, g_max=None, occ_max=None, with_self=True, fill=(0.0, -1)):
+    """The five caller-owned output arrays of _get_observation, pre-filled with fill = (obs value, index value)."""
+    topo = TOPO if topo is None else topo; g_max = G_MAX if g_max is None else g_max
+    occ_max = OCC_MAX if occ_max is None else occ_max
+    od = 2 * 2 * (topo + 1 + (1 if with_self else 0)) + 2 * g_max
+    return dict(obs=np.full((od, n_a), float(fill[0])), neighbor_index=np.full((n_a, topo), fill[1], np.int32),
+                in_flags=np.full(n_a, fill[1], np.int32), sensed_index=np.full((n_a, g_max), fill[1], np.int32),
+                occupied_index=np.full((n_a, occ_max), fill[1], np.int32))
+
+
+def _radius(radius, size_a, n_a):
+    if radius is None:
+        return np.full(n_a, size_a, np.float64)
+    r = np.ascontiguousarray(radius, np.float64)
+    if r.shape != (n_a,):
+        raise ValueError("radius must have shape (n_a,)")
+    return r
+
+
 def obs_dim(with_self=True):
     return 2 * 2 * (TOPO + 1 + (1 if with_self else 0)) + 2 * G_MAX
 
@@ -79,28 +111,34 @@ class Oracle:
             getattr(self.lib, name).restype = None
 
     def get_observation(self, p, dp, grid, l_cell, r_avoid, d_sen=D_SEN, boundary=BOUNDARY,
-                        is_periodic=False, with_self=True, topo=TOPO, g_max=G_MAX, occ_max=OCC_MAX):
+                        is_periodic=False, with_self=True, topo=TOPO, g_max=G_MAX, occ_max=OCC_MAX, *, vel_max=VEL_MAX,
+                        out=None):
+        """vel_max is accepted for RefLib's signature and unused (the Cartesian branch never reads Vel_max).  out: the five
+        output arrays (obs_out_arrays) to write into instead of fresh ones."""
         p = np.ascontiguousarray(p, np.float64); dp = np.ascontiguousarray(dp, np.float64)
         grid = np.ascontiguousarray(grid, np.float64)
         n_a, n_g = p.shape[1], grid.shape[1]
         od = 2 * 2 * (topo + 1 + (1 if with_self else 0)) + 2 * g_max
-        obs = np.zeros((od, n_a)); nei = np.empty((n_a, topo), np.int32)
-        inf = np.empty(n_a, np.int32); sen = np.empty((n_a, g_max), np.int32)
-        occ = np.empty((n_a, occ_max), np.int32)
+        if out is None:
+            out = dict(obs=np.zeros((od, n_a)), neighbor_index=np.empty((n_a, topo), np.int32), in_flags=np.empty(n_a, np.int32),
+                       sensed_index=np.empty((n_a, g_max), np.int32), occupied_index=np.empty((n_a, occ_max), np.int32))
+        obs, nei, inf, sen, occ = _obs_out(out, od, n_a, topo, g_max, occ_max)
         cond = np.array([is_periodic, True, with_self, False], np.uint8)
         self.lib.orc_get_observation(_d(p), _d(dp), _d(obs), _d(np.ascontiguousarray(boundary, np.float64)), _d(grid),
                                      _i(nei), _i(inf), _i(sen), _i(occ),
                                      ctypes.c_double(d_sen), ctypes.c_double(r_avoid), ctypes.c_double(l_cell),
                                      ctypes.c_int(topo), ctypes.c_int(g_max), ctypes.c_int(occ_max),
                                      ctypes.c_int(n_a), ctypes.c_int(n_g), ctypes.c_int(od), _b(cond))
-        return dict(obs=obs, neighbor_index=nei, in_flags=inf, sensed_index=sen, occupied_index=occ)
+        return out
 
     def get_reward(self, p, grid, neighbor_index, in_flags, sensed_index, r_avoid, d_sen=D_SEN,
-                   boundary=BOUNDARY, is_periodic=False):
+                   boundary=BOUNDARY, is_periodic=False, occupied_index=None, *, cond3=True, cond4=True, coef=0.05, out=None):
+        """cond3 / cond4: condition[3] (penalise interaction) and condition[4] (penalise exploration).  occupied_index and
+        coef are RefLib's: the reference copies them in and reads neither.  out: a (1, n_a) float64 array to write into."""
         p = np.ascontiguousarray(p, np.float64); grid = np.ascontiguousarray(grid, np.float64)
         n_a, n_g = p.shape[1], grid.shape[1]
-        rew = np.zeros((1, n_a))
-        cond = np.array([is_periodic, True, True, True, True], np.uint8)
+        rew = np.zeros((1, n_a)) if out is None else _chk(out, (1, n_a), np.float64)
+        cond = np.array([is_periodic, True, True, cond3, cond4], np.uint8)
         self.lib.orc_get_reward(_d(p), _d(rew), _d(np.ascontiguousarray(boundary, np.float64)), _d(grid),
                                 _i(np.ascontiguousarray(neighbor_index, np.int32)),
                                 _i(np.ascontiguousarray(in_flags, np.int32)),
@@ -119,28 +157,33 @@ class Oracle:
                                   ctypes.c_int(int(is_periodic)), _d(dc), _d(de), _b(col))
         return dc, de, col.astype(bool)
 
-    def sf_b2b_all(self, p, d_edge, collide, d_center, boundary=BOUNDARY, is_periodic=False, k_ball=K_BALL):
+    def sf_b2b_all(self, p, d_edge, collide, d_center, boundary=BOUNDARY, is_periodic=False, k_ball=K_BALL, *, out=None):
         p = np.ascontiguousarray(p, np.float64)
         n_a = p.shape[1]
-        sf = np.zeros((2, n_a))
+        sf = np.zeros((2, n_a)) if out is None else _chk(out, (2, n_a), np.float64)
         self.lib.orc_sf_b2b_all(_d(p), _d(sf), _d(np.ascontiguousarray(d_edge)), _b(np.ascontiguousarray(collide, np.uint8)),
                                 _d(np.ascontiguousarray(boundary, np.float64)), _d(np.ascontiguousarray(d_center)),
                                 ctypes.c_int(n_a), ctypes.c_double(k_ball), ctypes.c_int(int(is_periodic)))
         return sf
 
-    def dist_b2w(self, p, boundary=BOUNDARY, size_a=SIZE_A):
+    def dist_b2w(self, p, boundary=BOUNDARY, size_a=SIZE_A, *, radius=None, out=None):
+        """radius: per-agent radii [n_a] (default: size_a for everyone).  out: (d_b2w (4, n_a) float64, collide (4, n_a) bool)
+        to write into."""
         p = np.ascontiguousarray(p, np.float64)
         n_a = p.shape[1]
-        d = np.empty((4, n_a)); c = np.empty((4, n_a), np.uint8)
-        self.lib.orc_get_dist_b2w(_d(p), _d(np.full(n_a, size_a)), _d(d), _b(c), ctypes.c_int(n_a),
+        r = _radius(radius, size_a, n_a)
+        if out is None:
+            out = (np.empty((4, n_a)), np.empty((4, n_a), bool))
+        d, c = _chk(out[0], (4, n_a), np.float64), _chk(out[1], (4, n_a), np.bool_)
+        self.lib.orc_get_dist_b2w(_d(p), _d(r), _d(d), _b(c.view(np.uint8)), ctypes.c_int(n_a),
                                   _d(np.ascontiguousarray(boundary, np.float64)))
-        return d, c.astype(bool)
+        return d, c
 
-    def action_prior(self, p, dp, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN, prior_gain=PRIOR_GAIN):
+    def action_prior(self, p, dp, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN, prior_gain=PRIOR_GAIN, *, out=None):
         p = np.ascontiguousarray(p, np.float64); dp = np.ascontiguousarray(dp, np.float64)
         grid = np.ascontiguousarray(grid, np.float64)
         n_a, n_g = p.shape[1], grid.shape[1]
-        ap = np.zeros((2, n_a))
+        ap = np.zeros((2, n_a)) if out is None else _chk(out, (2, n_a), np.float64)
         nei = np.ascontiguousarray(neighbor_index, np.int32)
         self.lib.orc_action_prior_g(_d(p), _d(dp), _d(ap), _d(grid), _i(nei), ctypes.c_double(d_sen),
                                     ctypes.c_double(r_avoid), ctypes.c_double(l_cell), ctypes.c_int(nei.shape[1]),
@@ -218,26 +261,34 @@ class RefLib:
         return a.ctypes.data_as(ctypes.POINTER(ctypes.c_bool))
 
     def get_observation(self, p, dp, grid, l_cell, r_avoid, d_sen=D_SEN, boundary=BOUNDARY,
-                        is_periodic=False, with_self=True, topo=TOPO, g_max=G_MAX, occ_max=OCC_MAX):
+                        is_periodic=False, with_self=True, topo=TOPO, g_max=G_MAX, occ_max=OCC_MAX, *, vel_max=VEL_MAX,
+                        out=None, dim=2, cartesian=True):
+        """vel_max: the Vel_max argument.  out: the five output arrays (obs_out_arrays) to write into.  dim and cartesian
+        (condition[1]) are for callers bound to a library that refuses the other values; the reference reads dim rows of
+        every (2, n_a) input, so dim must stay 2 with it."""
         p = np.ascontiguousarray(p, np.float64); dp = np.ascontiguousarray(dp, np.float64)
         grid = np.ascontiguousarray(grid, np.float64)
         n_a, n_g = p.shape[1], grid.shape[1]
         od = 2 * 2 * (topo + 1 + (1 if with_self else 0)) + 2 * g_max
         heading = np.zeros((2, n_a))
-        obs = np.zeros((od, n_a)); nei = -np.ones((n_a, topo), np.int32)       # assembly.py:227-231
-        inf = np.zeros(n_a, np.int32); sen = -np.ones((n_a, g_max), np.int32)
-        occ = -np.ones((n_a, occ_max), np.int32)
-        cond = np.array([is_periodic, True, with_self, False])
+        if out is None:
+            out = dict(obs=np.zeros((od, n_a)), neighbor_index=-np.ones((n_a, topo), np.int32),       # assembly.py:227-231
+                       in_flags=np.zeros(n_a, np.int32), sensed_index=-np.ones((n_a, g_max), np.int32),
+                       occupied_index=-np.ones((n_a, occ_max), np.int32))
+        obs, nei, inf, sen, occ = _obs_out(out, od, n_a, topo, g_max, occ_max)
+        cond = np.array([is_periodic, cartesian, with_self, False])
         self.lib._get_observation(_d(p), _d(dp), _d(heading), _d(obs), _d(np.ascontiguousarray(boundary, np.float64)),
                                   _d(grid), _i(nei), _i(inf), _i(sen), _i(occ),
                                   ctypes.c_double(d_sen), ctypes.c_double(r_avoid), ctypes.c_double(l_cell),
-                                  ctypes.c_double(VEL_MAX), ctypes.c_int(topo), ctypes.c_int(g_max),
+                                  ctypes.c_double(vel_max), ctypes.c_int(topo), ctypes.c_int(g_max),
                                   ctypes.c_int(occ_max), ctypes.c_int(n_a), ctypes.c_int(n_g), ctypes.c_int(od),
-                                  ctypes.c_int(2), self._bb(cond))
-        return dict(obs=obs, neighbor_index=nei, in_flags=inf, sensed_index=sen, occupied_index=occ)
+                                  ctypes.c_int(dim), self._bb(cond))
+        return out
 
     def get_reward(self, p, grid, neighbor_index, in_flags, sensed_index, r_avoid, d_sen=D_SEN,
-                   boundary=BOUNDARY, is_periodic=False, occupied_index=None):
+                   boundary=BOUNDARY, is_periodic=False, occupied_index=None, *, cond3=True, cond4=True, coef=0.05, out=None,
+                   dim=2):
+        """cond3 / cond4: condition[3] / condition[4]; coef: coefficients[0]; out: a (1, n_a) float64 array to write into."""
         p = np.ascontiguousarray(p, np.float64); grid = np.ascontiguousarray(grid, np.float64)
         n_a, n_g = p.shape[1], grid.shape[1]
         nei = np.ascontiguousarray(neighbor_index, np.int32)
@@ -245,44 +296,51 @@ class RefLib:
         if occupied_index is None:
             occupied_index = -np.ones((n_a, OCC_MAX), np.int32)
         occ = np.ascontiguousarray(occupied_index, np.int32)
-        rew = np.zeros((1, n_a)); zeros = np.zeros((2, n_a))
-        coef = np.array([0.05]); cond = np.array([is_periodic, True, True, True, True], dtype=bool)
+        rew = np.zeros((1, n_a)) if out is None else _chk(out, (1, n_a), np.float64)
+        zeros = np.zeros((2, n_a))
+        coef = np.array([coef], np.float64); cond = np.array([is_periodic, True, True, cond3, cond4], dtype=bool)
         cb2b = np.zeros((n_a, n_a), bool); cb2w = np.zeros((4, n_a), bool)
         self.lib._get_reward(_d(p), _d(zeros), _d(zeros.copy()), _d(zeros.copy()), _d(rew),
                              _d(np.ascontiguousarray(boundary, np.float64)), _d(grid), _i(nei),
                              _i(np.ascontiguousarray(in_flags, np.int32)), _i(sen), _i(occ),
                              ctypes.c_double(d_sen), ctypes.c_double(r_avoid), ctypes.c_double(0.0),
                              ctypes.c_int(nei.shape[1]), ctypes.c_int(sen.shape[1]), ctypes.c_int(occ.shape[1]),
-                             ctypes.c_int(n_a), ctypes.c_int(n_g), ctypes.c_int(2), self._bb(cond),
+                             ctypes.c_int(n_a), ctypes.c_int(n_g), ctypes.c_int(dim), self._bb(cond),
                              self._bb(cb2b), self._bb(cb2w), _d(coef))
         return rew
 
-    def sf_b2b_all(self, p, d_edge, collide, d_center, boundary=BOUNDARY, is_periodic=False, k_ball=K_BALL):
+    def sf_b2b_all(self, p, d_edge, collide, d_center, boundary=BOUNDARY, is_periodic=False, k_ball=K_BALL, *, out=None,
+                   dim=2):
         p = np.ascontiguousarray(p, np.float64)
         n_a = p.shape[1]
-        sf = np.zeros((2, n_a))
+        sf = np.zeros((2, n_a)) if out is None else _chk(out, (2, n_a), np.float64)
         self.lib._sf_b2b_all(_d(p), _d(sf), _d(np.ascontiguousarray(d_edge)), self._bb(np.ascontiguousarray(collide, bool)),
                              _d(np.ascontiguousarray(boundary, np.float64)), _d(np.ascontiguousarray(d_center)),
-                             ctypes.c_int(n_a), ctypes.c_int(2), ctypes.c_double(k_ball), ctypes.c_bool(bool(is_periodic)))
+                             ctypes.c_int(n_a), ctypes.c_int(dim), ctypes.c_double(k_ball), ctypes.c_bool(bool(is_periodic)))
         return sf
 
-    def dist_b2w(self, p, boundary=BOUNDARY, size_a=SIZE_A):
+    def dist_b2w(self, p, boundary=BOUNDARY, size_a=SIZE_A, *, radius=None, out=None, dim=2):
+        """radius: per-agent radii [n_a] (default: size_a for everyone).  out: (d_b2w (4, n_a) float64, collide (4, n_a) bool)
+        to write into."""
         p = np.ascontiguousarray(p, np.float64)
         n_a = p.shape[1]
-        d = np.ones((4, n_a)); c = np.zeros((4, n_a), bool)
-        self.lib._get_dist_b2w(_d(p), _d(np.full(n_a, size_a)), _d(d), self._bb(c), ctypes.c_int(2), ctypes.c_int(n_a),
+        r = _radius(radius, size_a, n_a)
+        if out is None:
+            out = (np.ones((4, n_a)), np.zeros((4, n_a), bool))
+        d, c = _chk(out[0], (4, n_a), np.float64), _chk(out[1], (4, n_a), np.bool_)
+        self.lib._get_dist_b2w(_d(p), _d(r), _d(d), self._bb(c), ctypes.c_int(dim), ctypes.c_int(n_a),
                                _d(np.ascontiguousarray(boundary, np.float64)))
         return d, c
 
-    def action_prior(self, p, dp, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN):
+    def action_prior(self, p, dp, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN, *, out=None, dim=2):
         p = np.ascontiguousarray(p, np.float64); dp = np.ascontiguousarray(dp, np.float64)
         grid = np.ascontiguousarray(grid, np.float64)
         n_a, n_g = p.shape[1], grid.shape[1]
         nei = np.ascontiguousarray(neighbor_index, np.int32)
-        ap = np.zeros((2, n_a))
+        ap = np.zeros((2, n_a)) if out is None else _chk(out, (2, n_a), np.float64)
         self.lib.calculateActionPrior(_d(p), _d(dp), _d(ap), _d(grid), _i(nei), ctypes.c_double(d_sen),
                                       ctypes.c_double(r_avoid), ctypes.c_double(l_cell), ctypes.c_int(nei.shape[1]),
-                                      ctypes.c_int(n_a), ctypes.c_int(n_g), ctypes.c_int(2))
+                                      ctypes.c_int(n_a), ctypes.c_int(n_g), ctypes.c_int(dim))
         return ap
 
 

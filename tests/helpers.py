@@ -597,3 +597,458 @@ def assert_calm_conditions(n_a, info):
     for k in ("near", "avoid", "outside", "sensed") + (("subsampled",) if n_a in RULE_SUBSAMPLE_NS else ()):
         assert c[k] >= 100, (n_a, k, c)
     return c
+
+
+# ---- hand-built inputs of the five legacy symbols (test_gpu_legacy_contract.py, test_oracle_vs_reference.py) ----
+# A case is dict(id, fn, kw, meta): fn the RefLib / Oracle method, kw its keyword arguments (what the caller hands the symbol),
+# meta what the builder placed on purpose.  legacy_call() runs one through any of the three libraries with the outputs
+# pre-filled with junk; the restatements below (legacy_reward_v, ...) say from the inputs alone what a case reaches.
+LEGACY_NS = (1, 2, 5, 63, 64, 65, 256)          # _get_observation stops at 256 agents; the four small symbols have no cap
+LEGACY_L = 0.0625                               # lattice spacing 2^-4: cell coordinates and their differences are exact
+LEGACY_NX, LEGACY_NY = 24, 16
+OBS_JUNK, IDX_JUNK = 7.0, -7
+
+
+def lattice(nx, ny, l, centre=None, theta=0.0):
+    """(2, nx * ny) cell centres, index = iy * nx + ix, cell (0, 0) at the origin; or rotated by theta about the lattice's
+    middle and moved so that the middle lies at `centre`."""
+    ix, iy = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")
+    g = np.stack([ix.ravel() * l, iy.ravel() * l]).astype(np.float64)
+    if centre is not None:
+        g = g - g.mean(axis=1, keepdims=True)
+        rot = np.array([[np.cos(theta), np.sin(theta)], [-np.sin(theta), np.cos(theta)]])
+        g = rot @ g + np.asarray(centre, np.float64).reshape(2, 1)
+    return np.ascontiguousarray(g)
+
+
+def legacy_obs_case(n_a, topo, g_max, d_sen, with_self, periodic, box, occ_max=None, vel_max=0.8, n_g=324, seed=0):
+    """_get_observation: an 18 x 18 rotated lattice (cut to its first n_g cells) whose spacing puts about 1.5 g_max cells
+    (at least; the spacing is capped at 0.08) inside d_sen, agent 0 in its middle, 60 % of the others scattered over it and
+    the rest over the box; in periodic mode up to four pairs straddle an edge (x and y alternating), 0.02 to 0.1 apart through
+    the wrap and a box apart without it.  With two agents in periodic mode the lattice sits on the left edge instead and the
+    two agents straddle it.  meta: pairs."""
+    rng = np.random.default_rng([seed, n_a, topo, g_max, int(d_sen * 10), periodic])
+    x0, y1, x2, y3 = box
+    l = min(0.08, d_sen * np.sqrt(np.pi / (1.5 * g_max)))
+    mid = np.array([0.5 * (x0 + x2), 0.5 * (y1 + y3)]) + rng.uniform(-0.2, 0.2, 2)
+    two = periodic and n_a == 2
+    if two:
+        mid = np.array([x0 + 0.04, 0.5 * (y1 + y3)])
+    g = lattice(18, 18, l, mid, rng.uniform(-np.pi, np.pi))[:, :n_g]
+    g = np.ascontiguousarray(g)
+    p = np.empty((2, n_a))
+    k_cl = int(round(0.6 * n_a))
+    p[:, :k_cl] = g[:, rng.integers(0, g.shape[1], k_cl)] + rng.normal(0, 0.4 * l, (2, k_cl))
+    p[:, k_cl:] = np.stack([rng.uniform(x0 + 0.25, x2 - 0.25, n_a - k_cl), rng.uniform(y3 + 0.25, y1 - 0.25, n_a - k_cl)])
+    p[:, 0] = mid + rng.uniform(-0.3, 0.3, 2) * l
+    pairs = 0
+    if two:
+        p[:, 1] = (x2 - 0.04, mid[1] + 0.01); pairs = 1
+    elif periodic:
+        pairs = min((n_a - 1) // 2, 4)
+        for k in range(pairs):
+            d1, d2, off = rng.uniform(0.01, 0.04), rng.uniform(0.01, 0.04), rng.uniform(-0.02, 0.02)
+            if k % 2 == 0:
+                ym = y3 + (k + 1) * (y1 - y3) / (pairs + 1) + 0.013
+                p[:, 1 + 2 * k] = (x0 + d1, ym); p[:, 2 + 2 * k] = (x2 - d2, ym + off)
+            else:
+                xm = x0 + (k + 1) * (x2 - x0) / (pairs + 1) + 0.017
+                p[:, 1 + 2 * k] = (xm, y3 + d1); p[:, 2 + 2 * k] = (xm + off, y1 - d2)
+    dp = rng.uniform(-0.5, 0.5, (2, n_a))
+    kw = dict(p=np.ascontiguousarray(p), dp=dp, grid=g, l_cell=float(l), r_avoid=float(2 * l), d_sen=d_sen,
+              boundary=np.array(box, np.float64), is_periodic=periodic, with_self=with_self, topo=topo, g_max=g_max,
+              occ_max=g.shape[1] if occ_max is None else occ_max, vel_max=vel_max)
+    return dict(fn="get_observation", kw=kw, meta=dict(pairs=pairs))
+
+
+_NEI_PATTERNS = ("MNFFMF", "FMNDMM", "FFMFMF", "SMMMMM", "MMMMMM", "FNSDFM")
+_SYM_OFFSETS = sorted(((a, b) for a in range(-3, 4) for b in range(0, 4) if (b > 0 or a > 0)), key=lambda o: (o[0] ** 2 + o[1] ** 2, o))
+
+
+def legacy_hand_state(n_a, topo, g_max, d_sen, box=OFF_BOX, seed=0):
+    """The caller-built inputs of _get_reward and calculateActionPrior; nothing here is any library's output.
+
+    Cells: the 24 x 16 lattice of spacing 2^-4 with cell (0, 0) at the origin, plus (n_a >= 16) two cells either side of each
+    of the four edge agents.  Agent i sits on interior cell (1 + i % 22, 1 + i // 22), odd i 0.0036 off it, so agent i + 1 is
+    one cell away and agent i + 3 three.  Placed on purpose:
+      agent 3 (n_a >= 5)     half a cell off in x: two cells equidistant;
+      agent 4 (n_a >= 5)     half a cell off in x and y: four cells at sqrt(2) * 2^-4 / 2 exactly;
+      agents 6..11 (n_a >= 16)  three pairs along x from x = 0: 0.125 apart, one step of nextafter less, one more;
+      agents 12..15 (n_a >= 16) one pair straddling the x edges of `box`, one the y edges, 0.06 apart through the wrap.
+    neighbor_index rows cycle through _NEI_PATTERNS (rotated by i // 6, cut to topo): M = -1, N = agent i + 1, F = agents
+    i + 3 + 2 k, S = i itself, D = the entry before repeated; so -1 comes first, in the middle and last, a far agent before a
+    near one, duplicates and the own index all occur.  in_flags cycles through (1, 1, 0, 1, 2, 1, -1).  sensed_index rows
+    cycle through five kinds: 0 pairs of cells mirrored about the agent with -1 between them (|v| ~ the agent's offset);
+    1 cells on the +x side only; 2 all -1; 3 only cells at z >= d_sen (den == 0); 4 -1, then the agent's own cell (z == 0
+    for even i).  The placed agents get in_flag 1 and kind 0.  Returns dict(p, grid, neighbor_index, in_flags, sensed_index,
+    r_avoid = 0.125, l_cell = 2^-4, boundary)."""
+    l, nx, ny = LEGACY_L, LEGACY_NX, LEGACY_NY
+    g = lattice(nx, ny, l)
+    x0, y1, x2, y3 = box
+    p = np.empty((2, n_a)); base = np.empty(n_a, np.int64)
+    for i in range(n_a):
+        ix, iy = 1 + i % 22, 1 + (i // 22) % 14
+        base[i] = iy * nx + ix
+        p[:, i] = g[:, base[i]] + ((0.003, -0.002) if i % 2 else (0.0, 0.0))
+    placed = {}
+    if n_a >= 5:
+        p[:, 3] = g[:, base[3]] + (l / 2, 0.0)
+        p[:, 4] = g[:, base[4]] + (l / 2, l / 2)
+    extra = []
+    if n_a >= 16:
+        for k, d in enumerate((0.125, np.nextafter(0.125, 0.0), np.nextafter(0.125, 1.0))):
+            row = 8 + 2 * k
+            a, b = 6 + 2 * k, 7 + 2 * k
+            p[:, a] = (0.0, row * l); base[a] = row * nx
+            p[:, b] = (d, row * l); base[b] = row * nx + 2
+            placed[a] = b; placed[b] = a
+        edge = [(x0 + 0.03, 0.5), (x2 - 0.03, 0.5), (0.75, y3 + 0.03), (0.75, y1 - 0.03)]
+        for k, q in enumerate(edge):
+            a = 12 + k
+            p[:, a] = q; base[a] = -1
+            extra += [(q[0] + l, q[1]), (q[0] - l, q[1])]
+            placed[a] = 12 + (k ^ 1)
+        g = np.ascontiguousarray(np.concatenate([g, np.array(extra).T], axis=1))
+    nei = np.full((n_a, topo), -1, np.int32)
+    for i in range(n_a):
+        pat = _NEI_PATTERNS[i % 6]
+        r = (i // 6) % 6
+        pat = (pat[r:] + pat[:r])[:topo]
+        for k, t in enumerate(pat):
+            nei[i, k] = {"M": -1, "N": (i + 1) % n_a, "F": (i + 3 + 2 * k) % n_a, "S": i, "D": nei[i, k - 1] if k else (i + 1) % n_a}[t]
+    for a, b in placed.items():
+        nei[a] = -1
+        nei[a, min(1, topo - 1)] = b                   # after a leading -1 where topo allows
+    inf = np.array([(1, 1, 0, 1, 2, 1, -1)[i % 7] for i in range(n_a)], np.int32)
+    sen = np.full((n_a, g_max), -1, np.int32)
+
+    def fit(cells, gap):
+        """cells with a -1 after every `gap` of them, as many whole groups of `gap` as g_max holds"""
+        row = []
+        for k in range(0, len(cells) - gap + 1, gap):
+            grp = list(cells[k:k + gap]) + ([-1] if g_max >= 7 else [])
+            if len(row) + gap > g_max:
+                break
+            row += grp
+        return row[:g_max]
+
+    for i in range(n_a):
+        kind = 0 if i in placed else i % 5
+        if i in placed:
+            inf[i] = 1
+        if base[i] < 0:                                 # an edge agent: its own two cells
+            c = nx * ny + 2 * (i - 12)
+            row = [c, c + 1]
+        else:
+            ix, iy = base[i] % nx, base[i] // nx
+            ok = lambda a, b: 0 <= ix + a < nx and 0 <= iy + b < ny
+            cid = lambda a, b: (iy + b) * nx + ix + a
+            if kind == 0:
+                row = fit([c for a, b in _SYM_OFFSETS if ok(a, b) and ok(-a, -b) for c in (cid(a, b), cid(-a, -b))], 2)
+            elif kind == 1:
+                row = fit([cid(a, b) for a in (1, 2, 3) for b in (0, 1, -1) if ok(a, b)], 1)
+            elif kind == 2:
+                row = []
+            elif kind == 3:
+                z = np.linalg.norm(g[:, :nx * ny] - p[:, [i]], axis=0)
+                far = np.argsort(-z, kind="stable")[:5]
+                row = fit([int(c) for c in far if z[c] >= d_sen + 1e-6], 1)
+            else:
+                row = ([-1] + [int(base[i])] + ([cid(1, 0), cid(-1, 0)] if g_max >= 4 else []))[:g_max]
+        sen[i, :len(row)] = row
+    return dict(p=np.ascontiguousarray(p), grid=g, neighbor_index=nei, in_flags=inf, sensed_index=sen, r_avoid=0.125,
+                l_cell=l, boundary=np.array(box, np.float64))
+
+
+def legacy_reward_case(n_a, topo, g_max, d_sen, periodic, cond3, cond4, r_avoid=0.125):
+    s = legacy_hand_state(n_a, topo, g_max, d_sen)
+    kw = dict(p=s["p"], grid=s["grid"], neighbor_index=s["neighbor_index"], in_flags=s["in_flags"], sensed_index=s["sensed_index"],
+              r_avoid=r_avoid, d_sen=d_sen, boundary=s["boundary"], is_periodic=periodic,
+              occupied_index=np.full((n_a, 3), -1, np.int32), cond3=cond3, cond4=cond4, coef=0.05)
+    return dict(fn="get_reward", kw=kw, meta={})
+
+
+def legacy_reward_v(kw):
+    """|v| of AssemblyEnv.cpp:506-545 restated in numpy float64 for every agent that reaches it (in_flag == 1 and a sensed
+    cell), NaN for the others; and the agents whose list is non-empty but has den == 0."""
+    p, g, d_sen = kw["p"], kw["grid"], kw["d_sen"]
+    n_a = p.shape[1]
+    v = np.full(n_a, np.nan); den0 = np.zeros(n_a, bool)
+    for i in range(n_a):
+        cells = kw["sensed_index"][i][kw["sensed_index"][i] != -1]
+        if kw["in_flags"][i] != 1 or len(cells) == 0:
+            continue
+        rel = g[:, cells] - p[:, [i]]
+        z = np.sqrt(rel[0] ** 2 + rel[1] ** 2)
+        psi = np.where(z < d_sen, 0.5 * (1.0 + np.cos(np.pi * (z / d_sen))), 0.0)
+        den = psi.sum()
+        den0[i] = den == 0
+        den = 1e-8 if den == 0 else den
+        v[i] = np.hypot((psi * rel[0]).sum() / den, (psi * rel[1]).sum() / den)
+    return v, den0
+
+
+def legacy_collisions(kw, wrap):
+    """Per agent: does any listed neighbour lie inside r_avoid (AssemblyEnv.cpp:459-491), with or without the periodic wrap;
+    and the distance of every listed neighbour (NaN for -1), for the tests that need one to sit exactly at r_avoid."""
+    p, nei, b = kw["p"], kw["neighbor_index"], kw["boundary"]
+    wh, hh = (b[2] - b[0]) / 2, (b[1] - b[3]) / 2
+    hit = np.zeros(p.shape[1], bool); dist = np.full(nei.shape, np.nan)
+    for i in range(p.shape[1]):
+        for k, j in enumerate(nei[i]):
+            if j == -1:
+                continue
+            x, y = p[0, j] - p[0, i], p[1, j] - p[1, i]
+            if wrap:
+                x = x + 2 * wh if x < -wh else (x - 2 * wh if x > wh else x)
+                y = y + 2 * hh if y < -hh else (y - 2 * hh if y > hh else y)
+            dist[i, k] = np.sqrt(x * x + y * y)
+            hit[i] |= kw["r_avoid"] > dist[i, k]
+    return hit, dist
+
+
+def legacy_prior_case(n_a, topo, r_avoid, dp_scale, l_cell=LEGACY_L, one_cell=False, coincide=False, seed=0):
+    """calculateActionPrior on legacy_hand_state's positions and neighbour lists.  l_cell is the caller's number: below the
+    lattice's own spacing it puts agents outside the in-shape threshold sqrt(2) l_cell / 2 without moving anything.
+    one_cell: n_g = 1.  coincide (n_a >= 6): agent 5 lies exactly on agent 2 and each lists the other first."""
+    s = legacy_hand_state(n_a, topo, 2, 0.4)
+    rng = np.random.default_rng([seed, n_a, topo])
+    p, nei = s["p"].copy(), s["neighbor_index"].copy()
+    if coincide:
+        p[:, 5] = p[:, 2]; nei[5, 0] = 2; nei[2, 0] = 5
+    g = s["grid"][:, [LEGACY_NX * 3 + 5]].copy() if one_cell else s["grid"]
+    kw = dict(p=p, dp=rng.uniform(-1, 1, (2, n_a)) * dp_scale, grid=np.ascontiguousarray(g), neighbor_index=nei, l_cell=l_cell,
+              r_avoid=r_avoid, d_sen=0.4)
+    return dict(fn="action_prior", kw=kw, meta={})
+
+
+def legacy_sf_case(n_a, k_ball, periodic, mode, box=OFF_BOX, seed=0):
+    """_sf_b2b_all on matrices that are nobody's function of p: d_edge normal (negatives included), d_center uniform in
+    [0.05, 1], collide 0/1 bytes, all three asymmetric.  mode "rand": a third of the pairs collide; "dense": all of them;
+    "coincident": rand, with agent 1 on agent 0 and d_center[1][0] = 0."""
+    rng = np.random.default_rng([seed, n_a, int(k_ball * 10), periodic])
+    x0, y1, x2, y3 = box
+    p = np.stack([rng.uniform(x0, x2, n_a), rng.uniform(y3, y1, n_a)])
+    d_edge = rng.normal(0, 0.05, (n_a, n_a))
+    d_center = rng.uniform(0.05, 1.0, (n_a, n_a))
+    collide = np.ones((n_a, n_a), bool) if mode == "dense" else rng.random((n_a, n_a)) < 1 / 3
+    if mode == "coincident":
+        p[:, 1] = p[:, 0]; d_center[1, 0] = 0.0; collide[1, 0] = True
+    kw = dict(p=p, d_edge=d_edge, collide=collide, d_center=d_center, boundary=np.array(box, np.float64), is_periodic=periodic,
+              k_ball=k_ball)
+    return dict(fn="sf_b2b_all", kw=kw, meta=dict(mode=mode))
+
+
+def legacy_sf_terms(kw):
+    """Per agent, the number of nonzero terms its sum has, from the inputs: pairs (a > b) with collide[a][b] set, d_edge[a][b]
+    nonzero and the two agents apart."""
+    n_a = kw["p"].shape[1]
+    lo = np.tril(np.ones((n_a, n_a), bool), -1)
+    apart = (kw["p"][:, :, None] != kw["p"][:, None, :]).any(axis=0)
+    live = lo & kw["collide"].astype(bool) & (kw["d_edge"] != 0) & apart
+    return (live | live.T).sum(axis=1)
+
+
+def legacy_b2w_case(n_a, box=OFF_BOX, seed=0):
+    """_get_dist_b2w with a radius of its own for every agent, agents inside the box, and (n_a >= 8) agents 0..3 with their
+    edge exactly on the left, top, right and bottom wall (radius 0.25; d == 0 in exact arithmetic) and 4..7 beyond them."""
+    rng = np.random.default_rng([seed, n_a])
+    x0, y1, x2, y3 = box
+    p = np.stack([rng.uniform(x0 + 0.2, x2 - 0.2, n_a), rng.uniform(y3 + 0.2, y1 - 0.2, n_a)])
+    r = 0.02 + 0.1 * (rng.permutation(n_a) + 1) / (n_a + 1)
+    if n_a >= 8:
+        p[:, 0] = (x0 + 0.25, 0.3); p[:, 1] = (0.4, y1 - 0.25); p[:, 2] = (x2 - 0.25, 0.6); p[:, 3] = (0.9, y3 + 0.25)
+        r[:4] = 0.25
+        p[:, 4] = (x0 - 0.3, 0.1); p[:, 5] = (0.2, y1 + 0.3); p[:, 6] = (x2 + 0.3, 0.7); p[:, 7] = (1.1, y3 - 0.3)
+    elif n_a == 1:
+        p[:, 0] = (x0 + 0.25, y1 + 0.5); r[0] = 0.25            # on the left wall, beyond the top one
+    return dict(fn="dist_b2w", kw=dict(p=p, boundary=np.array(box, np.float64), radius=r), meta={})
+
+
+def legacy_call(lib, case, **over):
+    """Run a case through RefLib, a RefLib bound to libswarmenv.so, or Oracle, the caller's output buffers pre-filled with
+    junk (doubles 7.0, indices -7, bools True).  Returns {name: array}."""
+    from oracle.oracle_py import obs_out_arrays
+    kw = dict(case["kw"]); kw.update(over)
+    fn, n_a = case["fn"], case["kw"]["p"].shape[1]
+    if fn == "get_observation":
+        out = obs_out_arrays(n_a, kw["topo"], kw["g_max"], kw["occ_max"], kw["with_self"], fill=(OBS_JUNK, IDX_JUNK))
+        return lib.get_observation(**kw, out=out)
+    if fn == "dist_b2w":
+        d, c = lib.dist_b2w(**kw, out=(np.full((4, n_a), OBS_JUNK), np.ones((4, n_a), bool)))
+        return dict(d_b2w=d, collide=c)
+    rows = 1 if fn == "get_reward" else 2
+    return {fn: getattr(lib, fn)(**kw, out=np.full((rows, n_a), OBS_JUNK))}
+
+
+def assert_same(a, b, what=""):
+    """Every output of two legacy_call results equal bit for bit (NaN == NaN)."""
+    assert a.keys() == b.keys()
+    for k in a:
+        assert a[k].shape == b[k].shape and a[k].dtype == b[k].dtype, (what, k)
+        assert np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == "f"), (what, k, int((a[k] != b[k]).sum()))
+
+
+# the rows of each symbol: every n_a, topo, g_max, d_sen and flag value the contract names occurs in at least one
+LEGACY_OBS_ROWS = [                       # n_a, topo, g_max, d_sen, with_self, periodic, box, occ_max, vel_max
+    (1, 1, 2, 0.2, True, False, OFF_BOX, None, 0.8), (2, 3, 7, 0.4, False, True, OFF_BOX, None, 0.8),
+    (5, 6, 45, 0.7, True, False, DEFAULT_BOX, None, 0.3), (5, 3, 80, 0.4, True, True, OFF_BOX, None, 0.8),
+    (63, 6, 80, 0.4, True, True, OFF_BOX, None, 0.8), (64, 3, 45, 0.4, False, False, OFF_BOX, None, 0.8),
+    (65, 1, 7, 0.7, True, True, OFF_BOX, None, 2.5), (256, 6, 80, 0.7, True, False, OFF_BOX, None, 0.8),
+    (256, 3, 2, 0.2, False, True, OFF_BOX, None, 0.8), (64, 6, 45, 0.7, True, True, OFF_BOX, 20, 0.8)]
+LEGACY_REWARD_ROWS = [                    # n_a, topo, g_max, d_sen, periodic, cond3, cond4
+    (1, 1, 2, 0.2, False, True, True), (2, 3, 7, 0.4, True, True, True), (5, 6, 80, 0.7, False, False, True),
+    (63, 6, 128, 0.4, True, True, True), (64, 3, 7, 0.4, False, True, False), (65, 1, 2, 0.7, True, False, False),
+    (256, 6, 80, 0.2, False, True, True), (300, 6, 128, 0.4, True, True, True), (300, 3, 7, 0.7, False, False, True),
+    (64, 6, 80, 0.4, True, False, True)]
+LEGACY_SF_ROWS = [                        # n_a, k_ball, periodic, mode
+    (1, 30.0, False, "rand"), (2, 7.5, True, "rand"), (5, 30.0, True, "dense"), (5, 30.0, False, "coincident"),
+    (63, 7.5, False, "rand"), (64, 30.0, True, "dense"), (65, 7.5, True, "rand"), (256, 30.0, False, "rand"),
+    (300, 7.5, True, "dense")]
+LEGACY_B2W_ROWS = [(n,) for n in LEGACY_NS + (300,)]
+LEGACY_PRIOR_ROWS = [                     # n_a, topo, r_avoid, dp_scale, l_cell, one_cell, coincide, calm
+    (5, 6, 0.07, 0.05, LEGACY_L, False, False, True), (64, 3, 0.07, 0.05, LEGACY_L, False, False, True),
+    (300, 6, 0.07, 0.05, LEGACY_L, False, False, True), (256, 1, 0.07, 0.05, LEGACY_L, False, False, True),
+    (1, 1, 0.125, 0.5, LEGACY_L, False, False, False), (2, 3, 0.125, 0.5, 0.03, False, False, False),
+    (63, 6, 0.125, 0.5, LEGACY_L, False, True, False), (65, 6, 0.125, 0.5, 0.03, False, True, False),
+    (256, 6, 0.125, 0.5, LEGACY_L / 2, False, False, False), (300, 3, 0.125, 0.5, 0.03, True, False, False),
+    (5, 6, 0.125, 0.05, float(np.nextafter(LEGACY_L, 0.0)), False, False, False),
+    (5, 6, 0.125, 0.05, float(np.nextafter(LEGACY_L, 1.0)), False, False, False),
+    (5, 3, 0.125, 0.05, 0.0, False, False, False), (64, 6, 0.07, 0.05, LEGACY_L, True, False, False)]
+
+
+def legacy_specs():
+    """[(id, builder, args)] of every case; legacy_case(spec) builds one."""
+    def tag(*a):
+        return "-".join("%g" % x if isinstance(x, (int, float)) and not isinstance(x, bool) else ("T" if x is True else "F" if x is False
+                        else "off" if x == OFF_BOX else "def" if x == DEFAULT_BOX else "n" if x is None else str(x)) for x in a)
+    s = [("obs-" + tag(*r), "obs", r) for r in LEGACY_OBS_ROWS]
+    s += [("reward-" + tag(*r), "reward", r) for r in LEGACY_REWARD_ROWS]
+    s += [("reward-ravoid-%s" % k, "reward", (64, 6, 7, 0.4, True, True, True, v)) for k, v in
+          (("below", float(np.nextafter(0.125, 0.0))), ("above", float(np.nextafter(0.125, 1.0))))]
+    s += [("sf-" + tag(*r), "sf", r) for r in LEGACY_SF_ROWS]
+    s += [("b2w-" + tag(*r), "b2w", r) for r in LEGACY_B2W_ROWS]
+    s += [("prior%d-" % k + tag(*r[:4]), "prior", r) for k, r in enumerate(LEGACY_PRIOR_ROWS)]
+    return s
+
+
+_LEGACY_CACHE = {}
+
+
+def legacy_case(spec):
+    """The case of one legacy_specs() entry, built once per process; the arrays are shared, so nobody writes to them."""
+    cid, kind, r = spec
+    if cid not in _LEGACY_CACHE:
+        if kind == "obs":
+            c = legacy_obs_case(*r)
+        elif kind == "reward":
+            c = legacy_reward_case(*r)
+        elif kind == "sf":
+            c = legacy_sf_case(*r)
+        elif kind == "b2w":
+            c = legacy_b2w_case(*r)
+        else:
+            c = legacy_prior_case(*r[:7])
+            c["meta"]["calm"] = r[7]
+        c["id"] = cid
+        for v in c["kw"].values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+        _LEGACY_CACHE[cid] = c
+    return _LEGACY_CACHE[cid]
+
+
+def legacy_reach(case, ref):
+    """What a case has to reach, asserted from its inputs and from `ref`'s outputs alone (ref: the reference library, or the
+    oracle where that was not built); never from the library under test.  Returns the counts."""
+    kw, fn, meta = case["kw"], case["fn"], case["meta"]
+    n_a = kw["p"].shape[1]
+    c = {}
+    if fn == "get_observation":
+        n_g = kw["grid"].shape[1]
+        full = legacy_call(ref, case, g_max=max(n_g, 2), occ_max=n_g)
+        c["over_g_max"] = int(((full["sensed_index"] >= 0).sum(axis=1) > kw["g_max"]).sum())
+        assert c["over_g_max"] >= 1, c
+        c["occupied_max"] = int((full["occupied_index"] >= 0).sum(axis=1).max())
+        if kw["occ_max"] < n_g:              # the reference bounds the list by the same round(i * step) pick (AssemblyEnv.cpp:218-228)
+            assert c["occupied_max"] > kw["occ_max"], c
+        got = legacy_call(ref, case)
+        if n_a - 1 < kw["topo"]:
+            assert (got["neighbor_index"][:, n_a - 1:] == -1).all()
+        if kw["is_periodic"]:
+            plain = legacy_call(ref, case, is_periodic=False)["neighbor_index"]
+            c["wrap_only"] = sum(len(set(a[a >= 0]) - set(q[q >= 0])) for a, q in zip(got["neighbor_index"], plain))
+            assert meta["pairs"] >= 1 and c["wrap_only"] >= 2 * meta["pairs"], (c, meta)
+        if kw["vel_max"] != 0.8:             # the Cartesian branch never reads Vel_max
+            assert_same(got, legacy_call(ref, case, vel_max=0.8), "vel_max")
+    elif fn == "get_reward":
+        v, den0 = legacy_reward_v(kw)
+        c["margin"] = float(np.nanmin(np.abs(v - 0.05))) if np.isfinite(v).any() else np.inf
+        assert c["margin"] >= 1e-9, c
+        c["uniform"], c["not_uniform"], c["den0"] = int((v < 0.05).sum()), int((v >= 0.05).sum()), int(den0.sum())
+        hit_w, dist = legacy_collisions(kw, True)
+        hit_p, _ = legacy_collisions(kw, False)
+        c["wrap_only_collisions"] = int((hit_w & ~hit_p).sum())
+        nei = kw["neighbor_index"]
+        first = np.array([np.argmax(kw["r_avoid"] > np.nan_to_num(d, nan=np.inf)) if h else -1 for d, h in zip(dist, hit_p)])
+        c["hit_after_gap"] = int(sum(f > 0 and (nei[i, :f] == -1).any() for i, f in enumerate(first)))
+        c["hit_after_far"] = int(sum(f > 0 and (nei[i, :f] >= 0).any() for i, f in enumerate(first)))
+        if n_a >= 16:
+            k = min(1, nei.shape[1] - 1)
+            assert (dist[6, k], dist[8, k], dist[10, k]) == (0.125, np.nextafter(0.125, 0.0), np.nextafter(0.125, 1.0))
+            assert c["wrap_only_collisions"] == 4
+            assert c["den0"] >= 1 and c["uniform"] >= 8 and c["not_uniform"] >= 1, c
+            if nei.shape[1] >= 3:
+                assert c["hit_after_gap"] >= 1 and c["hit_after_far"] >= 1, c
+            sen = kw["sensed_index"]
+            if sen.shape[1] >= 7:
+                inner = [(r[:np.max(np.nonzero(r >= 0)[0])] == -1).any() for r in sen if (r >= 0).any()]
+                assert sum(inner) >= n_a // 4
+            assert ((sen == -1).all(axis=1) & (kw["in_flags"] == 1)).any()
+            assert set(np.unique(kw["in_flags"])) == {-1, 0, 1, 2}
+            own = [i for i in range(n_a) if any((kw["grid"][:, s] == kw["p"][:, i]).all() for s in sen[i][sen[i] >= 0])]
+            assert len(own) >= 1                     # a sensed cell exactly at the agent: z == 0
+    elif fn == "sf_b2b_all":
+        terms = legacy_sf_terms(kw)
+        c["three_terms"] = float((terms >= 3).mean())
+        if meta["mode"] == "dense":
+            assert c["three_terms"] >= 0.9, c
+        if n_a >= 5:                                 # nothing here is symmetric, and d_edge has both signs
+            assert not np.array_equal(kw["d_edge"], kw["d_edge"].T) and not np.array_equal(kw["d_center"], kw["d_center"].T)
+            assert (kw["d_edge"] < 0).any() and (kw["d_edge"] > 0).any()
+            assert meta["mode"] == "dense" or not np.array_equal(kw["collide"], kw["collide"].T)
+        assert set(np.unique(kw["collide"].view(np.uint8))) <= {0, 1}
+    elif fn == "dist_b2w":
+        d, col = legacy_call(ref, case).values()
+        assert len(np.unique(kw["radius"])) >= min(n_a, max(1, n_a - 3))
+        if n_a >= 8:
+            for w in range(4):
+                assert d[w, w] == 0 and not col[w, w] and col[w, 4 + w], w
+        c["collisions"] = int(col.sum())
+    else:
+        out = legacy_call(ref, case)["action_prior"]
+        if n_a >= 5 and kw["grid"].shape[1] > 1:     # agent 3: two cells equidistant; agent 4: four at sqrt(2) 2^-4 / 2 exactly
+            z = [np.sort(np.sqrt(((kw["grid"] - kw["p"][:, [i]]) ** 2).sum(axis=0))) for i in (3, 4)]
+            assert z[0][0] == z[0][1] == LEGACY_L / 2 and z[1][0] == z[1][3] == np.sqrt(2) * LEGACY_L / 2
+            assert np.sqrt(2) * np.nextafter(LEGACY_L, 0.0) / 2 < z[1][0] < np.sqrt(2) * np.nextafter(LEGACY_L, 1.0) / 2
+        c["free_share"] = float((np.abs(out) < 1).mean())
+        if meta.get("calm"):
+            assert c["free_share"] >= 0.4, c
+        elif n_a >= 5:
+            assert (np.abs(out) == 1).any(), c
+    return c
+
+
+def legacy_cache_configs():
+    """The _get_observation calls of the cache test: A, then B (A with seven cells fewer), C (A in a box 0.3 wider on every
+    side, so the pairs straddling A's edges are no neighbours), D (A without the self state).  Each differs from A in
+    exactly one argument."""
+    a = legacy_obs_case(64, 6, 45, 0.4, True, True, OFF_BOX)
+    def variant(**over):
+        kw = dict(a["kw"]); kw.update(over)
+        return dict(fn="get_observation", kw=kw, meta=a["meta"])
+    b = variant(grid=np.ascontiguousarray(a["kw"]["grid"][:, :-7]))
+    b["kw"]["occ_max"] = a["kw"]["occ_max"]
+    c = variant(boundary=np.array(OFF_BOX) + np.array([-0.3, 0.3, 0.3, -0.3]))
+    d = variant(with_self=False)
+    return dict(A=a, B=b, C=c, D=d)

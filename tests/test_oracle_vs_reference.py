@@ -1,11 +1,18 @@
 """Pin the oracle (oracle/assembly_oracle.c) against the reference's own C++ compiled unmodified
 (oracle/_ref/libAssemblyEnv.so, built by oracle/Makefile from
 /root/reference/cus_gym/gym/envs/customized_envs/envs_cplus/src/AssemblyEnv.cpp).
-Both are IEEE double with the same operation order, so equality is exact (==), not a tolerance."""
+Both are IEEE double with the same operation order, so equality is exact (==), not a tolerance.
+
+The hand-built cases of the legacy symbols (helpers.legacy_specs, what tests/test_gpu_legacy_contract.py feeds the HIP shim) run
+here first: every named input is defined in the reference, and the oracle -- the witness where oracle/_ref was not built --
+agrees with it bit for bit.  No input had to be dropped.  Two things the cases stay clear of because the reference leaves
+them open: agents at equal distance from an agent in _get_observation (std::sort's order of equal keys, AssemblyEnv.cpp:641)
+and dim != 2 (the reference reads dim rows of every two-row input), which only the shim's refusal path is given."""
 import numpy as np
 import pytest
 
-from helpers import BIG_BOX, DEFAULT_BOX, DYNAMICS_ROWS, OFF_BOX, config_case, make_case, physics
+from helpers import (BIG_BOX, DEFAULT_BOX, DYNAMICS_ROWS, OFF_BOX, assert_same, config_case, legacy_cache_configs, legacy_call,
+                     legacy_case, legacy_reach, legacy_specs, make_case, physics)
 from marl_llm_amd.shapes import r_avoid_for
 from oracle.oracle_py import numpy_dist_b2b, ref_step
 
@@ -123,3 +130,28 @@ def test_functions_match_reference_on_the_off_centre_box(oracle, reflib, shapes,
     wa, wb = oracle.dist_b2w(p, b, size_a), reflib.dist_b2w(p, b, size_a)
     assert np.array_equal(wa[0], wb[0]) and np.array_equal(wa[1], wb[1])
     assert wa[1][:, :4].diagonal().all()                             # agent w touches wall w
+
+
+# ---- the hand-built inputs of the five legacy symbols (helpers.legacy_specs) ----
+LEGACY = legacy_specs()
+
+
+@pytest.mark.parametrize("spec", LEGACY, ids=[s[0] for s in LEGACY])
+def test_legacy_cases_are_defined_in_the_reference_and_the_oracle_agrees(oracle, reflib, spec):
+    """Each case reaches what it was built for, by the reference's outputs and by the oracle's alike, and the two libraries
+    return the same bits in every output buffer, none of which keeps the junk it was handed with."""
+    case = legacy_case(spec)
+    assert legacy_reach(case, reflib) == legacy_reach(case, oracle)
+    a, b = legacy_call(reflib, case), legacy_call(oracle, case)
+    assert_same(a, b, spec[0])
+    assert_same(a, legacy_call(reflib, case), spec[0])                 # the same call twice: nothing undefined was read
+    for k, v in a.items():
+        assert v.dtype == bool or not (v == (7.0 if v.dtype.kind == "f" else -7)).any(), k
+
+
+def test_legacy_cache_configurations_differ_in_the_reference(oracle, reflib):
+    res = {k: legacy_call(reflib, c) for k, c in legacy_cache_configs().items()}
+    for k, c in legacy_cache_configs().items():
+        assert_same(res[k], legacy_call(oracle, c), k)
+    for k in "BCD":
+        assert res[k]["obs"].shape != res["A"]["obs"].shape or not np.array_equal(res[k]["obs"], res["A"]["obs"]), k
