@@ -253,6 +253,12 @@ __device__ __forceinline__ double clamp_ref(double v, double lo, double hi)
 // serial chain, not by throughput: shorter chains on more workgroups.
 template <int NPAD, bool HALF = false> struct Geo {
     static_assert(!HALF || NPAD < 64, "the half-occupied geometry is for N < 64");
+    static constexpr int NPAD_ = NPAD; static constexpr bool HALF_ = HALF;
+    // lattice launches address LDS through LatMap's compile-time offsets.  Not the full-occupancy geometries of N < 64 (several
+    // environments per wavefront): measured at 32 x 8192 the constants LOSE 0.8 % there (97.25 -> 98.01 us, three alternating
+    // rounds, spread 0.5; fewer VGPRs and less code, the same occupancy -- the schedule that comes out is the slower one).  N = 8 and 16 run the
+    // same code shape and were not measured with the constants, so all three keep the run-time offsets and the code they had.
+    static constexpr bool CT_MAP = NPAD >= 64 || HALF;
     static constexpr int AG = NPAD < 64 ? 64 : NPAD;
     static constexpr int EPB = NPAD < 64 ? (64 / NPAD) / (HALF ? 2 : 1) : 1;
     static constexpr int ACTW = NPAD < 64 ? EPB * NPAD : 64;     // agent threads of a 64-group that hold agents
@@ -278,6 +284,61 @@ template <int NPAD, bool HALF = false> struct Geo {
 #endif
     static constexpr int WPS_LAT = NPAD == 64 ? SWARM_WPS : (NPAD < 64 ? SWARM_WPS_SMALL : (NPAD == 128 ? SWARM_WPS_128 : 1));
     static constexpr int WPS_GEN = NPAD == 64 ? 6 : (NPAD < 64 ? 5 : 1);
+};
+
+// LDS map of the lattice (row-space) launches, shared by the kernel and by the host's layout_t: every region but the last
+// has a size that depends on the geometry alone, so its offset is a compile-time constant (folded into the ds_*
+// instructions' immediate offsets: no scalar base, no vector add per region).  The sensed lists `sidx` come LAST: their size
+// depends on g_max (KP::g_stride); the export-only `orow` follows them at a run-time offset (KP::off_orow).  Regions that
+// share bytes, and why they may:
+//   pm   over sidx   the partial pair masks are consumed two barriers before the first list slot is written
+//   perm over part_d written two barriers after the walking splits' distances were consumed
+//   prk  over part_c the partial ranks: the nearest-cell candidates are consumed by the merge, a barrier earlier
+//   the exact reward's scratch (N > 64) over srow
+template <int NPAD, bool HALF> struct LatMap {
+    typedef Geo<NPAD, HALF> G_;
+    static constexpr int AG = G_::AG, EPB = G_::EPB, NW = G_::NW, WPE = G_::WPE, T = G_::T;
+    static constexpr int NRC = 16;                                        // window rows stored per agent (lat_nrs <= 15)
+    static constexpr int al(int bytes) { return (bytes + 15) & ~15; }
+    static constexpr int mx(int a, int b) { return a > b ? a : b; }
+    static constexpr int sp_bytes = 4 * AG * 8;
+    static constexpr int hdr_bytes = AG * 16;
+    static constexpr int rew_scratch_bytes = NW * 1536;
+    static constexpr int srow_bytes = mx((NRC - 1) * AG * 4, rew_scratch_bytes);
+    static constexpr int pcr_bytes = AG * NRC;
+    static constexpr int partc_bytes = WPE * AG * 2;
+    static constexpr int partd_bytes = (WPE - 1) * AG * 8;
+    static constexpr int lat_bytes = EPB * 64 * (8 + 2);
+    static constexpr int cov_bytes = EPB * 64 * 8;
+    static constexpr int flag_bytes = AG;                                 // one byte per agent thread
+    static constexpr int snei_bytes = AG * kNeiStride * 2;
+    static constexpr int sncf_bytes = AG * 4;
+    static constexpr int snear_bytes = NW > 1 ? NW * AG * 8 : 0;          // (N <= 64: the nearby mask stays in a register)
+    static constexpr int orow_bytes = NRC * AG * 4;
+    static constexpr int pm_bytes = (NW == 1 ? WPE * 4 : 5) * NW * AG * 8;   // partial pair masks (per-split copies for N <= 64, one accumulator set above)
+    static constexpr int sp = 0;
+    static constexpr int hdr = sp + al(sp_bytes);
+    static constexpr int srow = hdr + al(hdr_bytes);
+    static constexpr int pcr = srow + al(srow_bytes);
+    static constexpr int partc = pcr + al(pcr_bytes);
+    static constexpr int partd = partc + al(partc_bytes);
+    static constexpr int lat = partd + al(partd_bytes);
+    static constexpr int cov = lat + al(lat_bytes);
+    static constexpr int flag = cov + al(cov_bytes);
+    static constexpr int snei = flag + al(flag_bytes);
+    static constexpr int sncf = snei + al(snei_bytes);
+    static constexpr int snear = sncf + al(sncf_bytes);
+    static constexpr int sidx = snear + al(snear_bytes);
+    static constexpr int perm = partd;
+    static constexpr int perm_bytes = T, prk_bytes = WPE * AG * 2;
+    static constexpr int sidx_bytes(int g_stride) { return al(mx(AG * g_stride * 2, pm_bytes)); }
+    static constexpr int total(int g_stride) { return sidx + sidx_bytes(g_stride); }                  // a step launch
+    static constexpr int orow_off(int g_stride) { return total(g_stride); }
+    static constexpr int total_export(int g_stride) { return orow_off(g_stride) + al(orow_bytes); }   // a launch that exports the lists
+    static_assert(perm_bytes <= partd_bytes, "perm must fit the distance array it reuses");
+    static_assert(prk_bytes <= partc_bytes, "the partial ranks must fit the nearest-cell candidates they reuse");
+    static_assert(rew_scratch_bytes <= srow_bytes, "the exact reward's scratch must fit the window rows it reuses");
+    static_assert(pm_bytes <= sidx_bytes(0), "the pair masks must fit the list region they reuse");
 };
 
 constexpr double kSentinel = 1.0e200;     // coordinates of padding cells: d2 overflows to +inf
@@ -348,33 +409,37 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
     typedef typename Pair<OT>::type OT2;
 
     extern __shared__ __align__(16) unsigned char smem[];
+    // offset of LDS region r: the compile-time map (LatMap) on lattice launches of the geometries that gain from it
+    // (Geo::CT_MAP), else layout_t's run-time offsets -- on lattice launches the same map, handed over in KP
+    typedef LatMap<NPAD, HALF> LM;
+#define LO(r) ((LAT && G_::CT_MAP) ? LM::r : P.off_##r)
     float *cxq = reinterpret_cast<float *>(smem + P.off_cxyf);          // fp32 cells, per PAIR {xa, xb, ya, yb} (pre-filter)
-    double *sp = reinterpret_cast<double *>(smem + P.off_sp);            // [4][AG]: px, py, vx, vy
+    double *sp = reinterpret_cast<double *>(smem + LO(sp));            // [4][AG]: px, py, vx, vy
     u64 *cmask = reinterpret_cast<u64 *>(smem + P.off_cmask);            // [cell][NW]
     float *rsum = reinterpret_cast<float *>(smem + P.off_cmask);         // [WPE][3][AG]  (aliases cmask, later phase)
     unsigned *sbits = reinterpret_cast<unsigned *>(smem + P.off_sbits);  // [word][AG]
     unsigned *obits = reinterpret_cast<unsigned *>(smem + P.off_obits);  // [word][AG] (export launches only)
-    short *sidx = reinterpret_cast<short *>(smem + P.off_sidx);          // [AG][g_stride]
+    short *sidx = reinterpret_cast<short *>(smem + LO(sidx));          // [AG][g_stride]
     typedef std::conditional_t<LAT, short, int> pc_t;                    // (lattice launches: 16-bit -- the kernel's LDS budget is seven workgroups per CU)
-    pc_t *part_c = reinterpret_cast<pc_t *>(smem + P.off_partc);         // [WPE][AG] per-split nearest-cell candidates (cell index < 2^15)
-    u64 *pm = reinterpret_cast<u64 *>(smem + P.off_sidx);                // [WPE][2 or 3][NW][AG] partial pair masks (aliases sidx, earlier phase)
+    pc_t *part_c = reinterpret_cast<pc_t *>(smem + LO(partc));         // [WPE][AG] per-split nearest-cell candidates (cell index < 2^15)
+    u64 *pm = reinterpret_cast<u64 *>(smem + LO(sidx));                // [WPE][2 or 3][NW][AG] partial pair masks (aliases sidx, earlier phase)
     unsigned *owords = reinterpret_cast<unsigned *>(smem + P.off_cmask); // [word][AG] occupied bits (NW == 1; aliases cmask)
-    short *snei = reinterpret_cast<short *>(smem + P.off_snei);          // [AG][kTopoMax]
-    int *sncf = reinterpret_cast<int *>(smem + P.off_sncf);              // [AG]: nearest cell | in_flag<<30
-    u64 *snear = reinterpret_cast<u64 *>(smem + P.off_snear);            // [NW][AG] nearby-agent masks
-    u64 *lrm = reinterpret_cast<u64 *>(smem + P.off_lat);                // [EPB][64] lattice row masks
-    short *lrs = reinterpret_cast<short *>(smem + P.off_lat + (size_t)EPB * 64 * 8);   // [EPB][64] row starts
-    unsigned *cov = reinterpret_cast<unsigned *>(smem + P.off_cov);      // [EPB][ngw+1] cells within r_avoid/2 of ANY agent
-    int *sflag = reinterpret_cast<int *>(smem + P.off_flag);             // per-lane exception flags: generic launches [AG] ints; lattice launches one BYTE per agent thread (flag_* below)
+    short *snei = reinterpret_cast<short *>(smem + LO(snei));          // [AG][kTopoMax]
+    int *sncf = reinterpret_cast<int *>(smem + LO(sncf));              // [AG]: nearest cell | in_flag<<30
+    u64 *snear = reinterpret_cast<u64 *>(smem + LO(snear));            // [NW][AG] nearby-agent masks
+    u64 *lrm = reinterpret_cast<u64 *>(smem + LO(lat));                // [EPB][64] lattice row masks
+    short *lrs = reinterpret_cast<short *>(smem + LO(lat) + (size_t)EPB * 64 * 8);   // [EPB][64] row starts
+    unsigned *cov = reinterpret_cast<unsigned *>(smem + LO(cov));      // [EPB][ngw+1] cells within r_avoid/2 of ANY agent
+    int *sflag = reinterpret_cast<int *>(smem + LO(flag));             // per-lane exception flags: generic launches [AG] ints; lattice launches one BYTE per agent thread (flag_* below)
     unsigned char *pc = smem + P.off_pc;                                 // [word][AG] kept-bit counts
     // row-space representation of the lattice path (LAT): window row t of agent thread `at` = lattice row b0 + t, its
     // columns are stored relative to the agent's first column ca0 (<= 17 columns are ever in range: 32-bit words)
-    constexpr int NRC = 16;                                              // window rows stored per agent (lat_nrs <= 15)
-    float4 *hdr = reinterpret_cast<float4 *>(smem + P.off_hdr);          // [AG] {apr = a - ca0, bpr = b - b0, b0, ca0} (last two: ints)
-    unsigned *srow = reinterpret_cast<unsigned *>(smem + P.off_srow);    // [NRC][AG] sensed, then kept columns of window row t (17 bits) | cell index of the row's column ca0 << 17
-    unsigned char *pcr = smem + P.off_pcr;                               // [AG][NRC] kept cells per window row
-    u64 *covrow = reinterpret_cast<u64 *>(smem + P.off_cov);             // [EPB][64] columns within r_avoid/2 of ANY agent, per lattice row
-    unsigned char *perm = smem + P.off_perm;                             // [T/64][64] agent threads in ascending list length (per wave)
+    constexpr int NRC = LM::NRC;                                            // window rows stored per agent (lat_nrs <= 15)
+    float4 *hdr = reinterpret_cast<float4 *>(smem + LO(hdr));          // [AG] {apr = a - ca0, bpr = b - b0, b0, ca0} (last two: ints)
+    unsigned *srow = reinterpret_cast<unsigned *>(smem + LO(srow));    // [NRC][AG] sensed, then kept columns of window row t (17 bits) | cell index of the row's column ca0 << 17
+    unsigned char *pcr = smem + LO(pcr);                               // [AG][NRC] kept cells per window row
+    u64 *covrow = reinterpret_cast<u64 *>(smem + LO(cov));             // [EPB][64] columns within r_avoid/2 of ANY agent, per lattice row
+    unsigned char *perm = smem + LO(perm);                             // [T/64][64] agent threads in ascending list length (per wave)
     unsigned *orow = reinterpret_cast<unsigned *>(smem + P.off_orow);    // [NRC][AG] occupied columns (export launches only)
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1073,7 +1138,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
         }
     }
     part_c[sx * AG + at] = (pc_t)bc;
-    double *part_d = reinterpret_cast<double *>(smem + P.off_partd);     // [WPE - 1][AG] (lattice launches; the list phase's `perm` reuses it)
+    double *part_d = reinterpret_cast<double *>(smem + LO(partd));     // [WPE - 1][AG] (lattice launches; the list phase's `perm` reuses it)
     if constexpr (LAT) {
         // each walking split evaluates the exact distance of ITS candidate here, before the barrier (the gather overlaps the
         // other waves' walk); the merge behind the barrier then compares values that sit in LDS instead of every split
@@ -1987,6 +2052,8 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
 #endif
 }
 
+#undef LO
+
 // -------------------------------------------------------------------------------------------------
 // batched reset: AssemblySwarmEnv.reset(), ENV:156-219, for every environment at once.
 // Counter-based generator: draw k of environment g in episode ep under `seed` is
@@ -2592,26 +2659,16 @@ void layout_t(KP &k)
     k.off_sp = take((size_t)4 * AG * 8);
     k.cxq_stride = k.ngw * 64 + 4;             // floats: 2 per cell, +1 pair-of-pairs of padding
     if (k.lattice) {
-        // row-space lattice path: no per-cell bit sets at all
-        constexpr int NRC = 16;
-        k.off_hdr = take((size_t)AG * 16);
-        k.off_srow = take(max2((size_t)(NRC - 1) * AG * 4, (size_t)NW * 1536));   // window-row words (lat_nrs <= 15 rows) | scratch of the exact reward
-        k.off_pcr = take((size_t)AG * NRC);
-        k.off_sidx = take(max2((size_t)AG * k.g_stride * 2, pm_bytes));      // sidx | pm
-        k.off_partc = take((size_t)WPE * AG * 2);                             // nearest-cell candidates | partial ranks (16-bit)
-        k.off_partd = take((size_t)(WPE - 1) * AG * 8);                       // the walking splits' exact squared distances | perm
-        k.off_lat = take((size_t)EPB * 64 * (8 + 2));
-        k.off_cov = take((size_t)EPB * 64 * 8);
-        k.off_flag = take((size_t)AG);                                        // one byte per agent thread
-        k.off_snei = take((size_t)AG * kNeiStride * 2);
-        k.off_sncf = take((size_t)AG * 4);
-        k.off_snear = take(NW > 1 ? (size_t)NW * AG * 8 : 0);                 // (N <= 64: the nearby mask stays in a register)
-        k.off_perm = k.off_partd;                                             // T bytes, written two barriers after the distances were consumed
-        static_assert((size_t)T <= (size_t)(WPE - 1) * AG * 8, "perm must fit the distance array it reuses");
-        k.off_rres = 0;
-        k.smem_lat = (int)off;                           // lattice mode, no export
-        k.off_orow = take((size_t)NRC * AG * 4);         // only launches that export the index scratch use it
-        k.smem_lat_export = (int)off;
+        // row-space lattice path: no per-cell bit sets at all.  The map is LatMap's.  Geometries with G_::CT_MAP address every
+        // region through the same compile-time constants and read none of the run-time offsets but off_orow; the others read the
+        // offsets below, which are the same map's
+        typedef LatMap<NPAD, HALF> LM;
+        k.smem_lat = LM::total(k.g_stride);              // lattice mode, no export
+        k.off_orow = LM::orow_off(k.g_stride);           // only launches that export the index scratch use it
+        k.smem_lat_export = LM::total_export(k.g_stride);
+        k.off_sp = LM::sp; k.off_hdr = LM::hdr; k.off_srow = LM::srow; k.off_pcr = LM::pcr; k.off_sidx = LM::sidx;
+        k.off_partc = LM::partc; k.off_partd = LM::partd; k.off_lat = LM::lat; k.off_cov = LM::cov; k.off_flag = LM::flag;
+        k.off_snei = LM::snei; k.off_sncf = LM::sncf; k.off_snear = LM::snear; k.off_perm = LM::perm; k.off_rres = 0;
         k.off_cmask = k.off_sbits = k.off_obits = k.off_pc = k.off_cxyf = 0;     // generic scan only
         k.smem_generic = 0;
         return;
@@ -2634,16 +2691,23 @@ void layout_t(KP &k)
     k.off_hdr = k.off_srow = k.off_pcr = k.off_perm = k.off_rres = k.off_orow = k.off_partd = 0;
 }
 
-void layout(KP &k, int npad, bool half)
+// f(Geo<NPAD, HALF>{}) for the geometry of npad / half: the list of geometries, in one place
+template <typename F>
+void for_geometry(int npad, bool half, F &&f)
 {
     switch (npad) {
-    case 8: if (half) layout_t<8, true>(k); else layout_t<8, false>(k); break;
-    case 16: if (half) layout_t<16, true>(k); else layout_t<16, false>(k); break;
-    case 32: if (half) layout_t<32, true>(k); else layout_t<32, false>(k); break;
-    case 64: layout_t<64, false>(k); break;
-    case 128: layout_t<128, false>(k); break;
-    default: layout_t<256, false>(k); break;
+    case 8: if (half) f(Geo<8, true>{}); else f(Geo<8, false>{}); break;
+    case 16: if (half) f(Geo<16, true>{}); else f(Geo<16, false>{}); break;
+    case 32: if (half) f(Geo<32, true>{}); else f(Geo<32, false>{}); break;
+    case 64: f(Geo<64, false>{}); break;
+    case 128: f(Geo<128, false>{}); break;
+    default: f(Geo<256, false>{}); break;
     }
+}
+
+void layout(KP &k, int npad, bool half)
+{
+    for_geometry(npad, half, [&](auto g) { layout_t<decltype(g)::NPAD_, decltype(g)::HALF_>(k); });
 }
 
 // Decide the cell path of the next launches and lay out its LDS.  The row-space lattice path needs every env's cells to
@@ -3423,6 +3487,30 @@ int swarm_timer_stop(swarm_env_t *h, float *ms)
     return SWARM_OK;
 }
 
+// Diagnostic, host only (no device, no handle): the LDS map of the lattice launches of one instantiation, for the CPU test
+// that holds it in place.  out[0..1] = smem_lat / smem_lat_export as layout() hands them to the launches, out[2] = g_stride,
+// out[3] = off_orow, out[4..15] = the kernel's compile-time offsets of sp, hdr, srow, pcr, partc, partd, lat, cov, flag, snei,
+// sncf, sidx, out[16..27] = the same regions' run-time offsets in KP (read by the geometries without Geo::CT_MAP),
+// out[28] = Geo::CT_MAP.  Returns 0, or -1 for a geometry that has no instantiation.
+int swarm_debug_lds_map(int npad, int half, int g_max, int *out)
+{
+    if (!out || g_max < 1 || (half && npad >= 64)) return -1;
+    if (npad != 8 && npad != 16 && npad != 32 && npad != 64 && npad != 128 && npad != 256) return -1;
+    KP k;
+    std::memset(&k, 0, sizeof(k));
+    k.g_max = g_max; k.ng_max = 32; k.lattice = 1;
+    layout(k, npad, half != 0);
+    out[0] = k.smem_lat; out[1] = k.smem_lat_export; out[2] = k.g_stride; out[3] = k.off_orow;
+    for_geometry(npad, half != 0, [&](auto g) {
+        typedef LatMap<decltype(g)::NPAD_, decltype(g)::HALF_> LM;
+        const int o[12] = {LM::sp, LM::hdr, LM::srow, LM::pcr, LM::partc, LM::partd, LM::lat, LM::cov, LM::flag, LM::snei, LM::sncf, LM::sidx};
+        for (int q = 0; q < 12; ++q) out[4 + q] = o[q];
+        out[28] = decltype(g)::CT_MAP ? 1 : 0;
+    });
+    const int r[12] = {k.off_sp, k.off_hdr, k.off_srow, k.off_pcr, k.off_partc, k.off_partd, k.off_lat, k.off_cov, k.off_flag, k.off_snei, k.off_sncf, k.off_sidx};
+    for (int q = 0; q < 12; ++q) out[16 + q] = r[q];
+    return 0;
+}
 
 #ifdef SWARM_STAMPS
 // Diagnostic build only: run one step with per-wave phase clocks; out[grid][waves per workgroup][24] (host), returns grid size.
