@@ -229,7 +229,8 @@ int  swarm_timer_stop(swarm_env_t *h, float *elapsed_ms);   /* synchronizes on t
 /* Diagnostics: the library also exports two entry points that are deliberately NOT part of this interface and are declared
  * nowhere -- tools and tests bind them by name.  swarm_debug_lds_map(npad, half, g_max, out[32]) is host-only and reports the
  * LDS map of the lattice launches (tests/test_lds_map.py); swarm_debug_stamps(...) exists only in the -DSWARM_STAMPS build
- * (tools/phase_profile.py).  Their arguments are documented at their definitions in csrc/swarm_env.hip. */
+ * (tools/phase_profile.py).  Their arguments are documented at their definitions in csrc/swarm_env.hip,
+ * beside the step kernel whose tables they read; every other entry point is defined in csrc/env_api.hip. */
 
 /* ---- legacy symbols: exact reference signatures (AssemblyEnv.h:13-34,35-58,64-73,75-81,98-109) ---- */
 void _get_observation(double *p_input, double *dp_input, double *heading_input, double *obs_input,

@@ -1,7 +1,8 @@
 """Build libswarmenv.so (the HIP kernels + C ABI) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED: the kernels reproduce the
-reference's IEEE-double operation order (no FMA), see csrc/swarm_env.hip.
+reference's IEEE-double operation order (no FMA), see csrc/swarm_env.hip.  The env library is three sources: swarm_env.hip
+(the step kernel, by far the longest compile), env_kernels.hip (the side kernels) and env_api.hip (the handle and the C ABI).
 """
 import os
 import shutil
@@ -9,9 +10,8 @@ import subprocess
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
-SRCS = [os.path.join(PKG, "csrc", "swarm_env.hip"), os.path.join(PKG, "csrc", "legacy_shim.hip"),
-        os.path.join(PKG, "csrc", "policy_mlp.hip"), os.path.join(PKG, "csrc", "rollout.hip"),
-        os.path.join(PKG, "csrc", "rule_expert.hip")]
+SRCS = [os.path.join(PKG, "csrc", f) for f in ("swarm_env.hip", "env_kernels.hip", "env_api.hip", "legacy_shim.hip",
+                                               "policy_mlp.hip", "rollout.hip", "rule_expert.hip")]
 INC = os.path.join(ROOT, "include")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libswarmenv.so")
@@ -27,7 +27,7 @@ def hipcc_path():
 def needs_build():
     if not os.path.exists(LIB):
         return True
-    headers = [os.path.join(INC, h) for h in ("swarm_env.h", "swarm_policy.h", "swarm_rollout.h")] + [os.path.join(PKG, "csrc", "swarm_internal.h")]
+    headers = [os.path.join(INC, h) for h in ("swarm_env.h", "swarm_policy.h", "swarm_rollout.h")] + [os.path.join(PKG, "csrc", h) for h in ("swarm_internal.h", "env_types.h")]
     newest = max([os.path.getmtime(s) for s in SRCS + headers])
     return os.path.getmtime(LIB) < newest
 

@@ -1,0 +1,197 @@
+// Private to the three translation units of the env library -- swarm_env.hip (the step kernel and its launch),
+// env_kernels.hip (the side kernels) and env_api.hip (the handle and the C ABI): the kernel-argument types, the handle and
+// the functions through which the three call each other.  Not installed, not exported: the namespace has hidden visibility,
+// so the public ABI (swarm_env.h) does not change.  What the OTHER translation units of libswarmenv.so may ask of an env
+// handle is in swarm_internal.h.
+#ifndef SWARM_ENV_TYPES_H
+#define SWARM_ENV_TYPES_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "swarm_env.h"
+#include "swarm_internal.h"
+
+namespace swarm_internal __attribute__((visibility("hidden"))) {
+
+constexpr int kTopoMax = 6;
+constexpr int kNeiStride = 8;     // shorts per agent in the LDS neighbour list: 6 ids, [6] = collision flag
+constexpr double kSentinel = 1.0e200;     // coordinates of padding cells: d2 overflows to +inf
+
+// Per-environment description of the target cells as a subset of a (rotated) square lattice, when they are one
+// (the reference tiles a silhouette image into square cells and rotates / shifts them: assembly_cfg.py:56-99,
+// assembly.py:175-187).  Cell (column a, row b) sits at o + a*u + b*v and the cell index order is row-major.
+struct LatEnv {
+    double ox, oy;
+    double uxi, uyi, vxi, vyi;    // (p - o) . (uxi, uyi) = column coordinate, (p - o) . (vxi, vyi) = row coordinate
+    float R, Rc;                  // d_sen / l and (r_avoid / 2) / l in lattice steps
+    int nrows, ncols;
+    short rowstart[64];           // cell index of the first cell of each row
+    unsigned long long rowmask[64];   // occupied columns of each row
+};
+
+// The kernel argument of every env kernel.  Field order, types and size are part of the step kernel's device code (the
+// scalar loads address the fields by offset): append, never move.  off_cxy and off_rres are dead -- no kernel reads them.
+struct KP {
+    int n_env, n_a, ng_max, ngw, topo, g_max, occ_max, obs_dim;
+    int with_self, periodic, boundary, with_prior, export_idx;
+    int export_small;          // also write neighbor_index / nearest cell / in_flags to HBM (export launches only: the step itself keeps them in LDS)
+    int cxy_stride;            // double2 elements per env in LDS
+    int cxq_stride;            // floats per env in the fp32 pair layout
+    int g_stride;              // int16 elements per agent row in LDS
+    int off_cxy, off_sp, off_cmask, off_sbits, off_obits, off_sidx, off_snei, off_sncf, off_snear, off_pc;
+    int smem_lat, smem_lat_export, smem_generic;   // dynamic LDS bytes by launch kind
+    double c_sen, c_near, c_occ, c_avoid, c_ball;     // squared-distance cut-offs
+    double c_close, c_close2;  // (1.9 r_avoid)^2 and (3 r_avoid)^2 capped at c_sen: pre-selection radii of the neighbour insertion (any values are exact; the second is used for N > 128)
+    // fp32 pre-filter bands: d2_32 < *_lo  =>  exact test true;  d2_32 >= *_hi  =>  exact test false
+    float csen_lo, csen_hi, cocc_lo, cocc_hi;
+    float coord_lim;           // |coordinate| bound the bands were derived for
+    float min_tol_a, min_tol_b;   // nearest-cell ambiguity tolerance: a*sqrt(d2) + b*d2
+    float rew_ga, rew_gb;      // the reward is re-evaluated in fp64 when | |v| - 0.05 | <= rew_ga * n / den + rew_gb
+    int force_exact;           // debug: take every exact fallback path
+    int cap_int;               // G-1 odd: the cap's round(i*step) is an exact integer division by 2(G-1)
+    unsigned cap_magic; int cap_shift;
+    int cap_even;              // the expert's export pass: ties of round(i*step) go to even, as np.round sends them (assembly.py:564);
+                               // the observation itself rounds them away from zero (std::round, CPP:223).  Ties need G-1 even.
+    int dbg_phase, dbg_extra;  // diagnostics only (tools/ablate.py): run phase dbg_phase dbg_extra EXTRA times; the
+                               // phases are idempotent, so results are unchanged and the extra cost is the phase's cost
+    int off_cxyf, off_partc, off_lat, off_cov, off_flag;
+    // lattice (row-space) launches only: per-agent frame, per (window row, agent) column masks / first cell index, per-agent
+    // row counts, the agent permutation of the list phase, the fp32 reward verdicts, the occupied columns (export only)
+    int off_hdr, off_srow, off_pcr, off_perm, off_rres, off_orow, off_partd;
+    float rew_ga_lat, rew_gb_lat;   // guard band of the fp32 reward decision in lattice steps (see swarm_create)
+    float rew_thr_k;           // 0.05 / d_sen: the reward's |v| threshold in lattice steps is rew_thr_k * (d_sen / l)
+    int lattice;               // every env's cells are a lattice subset whose sensing window is <= 15 rows: row-space path
+    int lat_rw, lat_cw;        // row half-windows (lattice steps) for d_sen and r_avoid/2
+    int lat_nrs, lat_nrc;      // rows a radius can touch: floor(2 (rho_max + margin)) + 1, for d_sen and r_avoid/2
+    int lat_n32;               // every env's lattice has <= 32 columns: 32-bit row masks
+    double c_near_hi;          // c_near * (1 + 1e-9): pairs in [c_near, c_near_hi) flag the exact occupied-cell path
+    const LatEnv *lat;
+    double d_sen, r_avoid, size_a, size2, k_ball, k_wall, c_wall, vel_max, dt;
+    double bx0, by1, bx2, by3, w_half, h_half;
+    double *p, *dp;
+    int *nei, *near_cell, *in_flag;
+    double2 *sf_next;          // [E][N]: contact-spring force on agent i in the CURRENT state = the force term of the next step
+    const double *cells;       // [E][2][ng_max] (the ABI's layout)
+    const double2 *cells_xy;   // [E][ng_max] (x, y) interleaved copy: one 16-byte gather per cell
+    const int *n_g;
+    const double *c_in;
+    int *exp_sensed, *exp_occ;
+    void *prior_next;          // [E][N] pairs of the handle's obs dtype: the prior policy of the next step (written by every pass)
+    double pk_att, pk_rep, pk_ali;   // gains of the prior policy: attraction, repulsion, alignment (CPP:1128-1132: 2, 3, 2)
+    double pk_llm;             // repulsion gain of the Python twin that drives agent_strategy == 'llm' (ENV:895: 1.0)
+    int llm;                   // also evaluate that twin and leave it in act_next as the NEXT step's action (ENV:525-529)
+    double2 *act_next;         // [E][N]
+    long long *stamps;         // diagnostic build only (-DSWARM_STAMPS): per-block phase clocks
+};
+
+// The uploaded shape set, as the reset and shape-switch kernels read it
+struct ShapeSet {
+    int n_shapes;
+    const double *cells;      // [S][2][ng_max], shape frame (ENV: grid_center_origins[s].T)
+    const int *n_g;           // [S]
+    const double *l_cell;     // [S]
+    const double *c_in;       // [S] in-shape cut-off
+    const LatEnv *lat;        // [S] lattice of the un-rotated shape (nrows == 0: not a lattice)
+};
+
+// The host's record of one cell set (an env's, or a shape's of the uploaded set): is it a lattice subset, and if so its
+// LatEnv::R / Rc / ncols (read only where ok is set).
+struct LatInfo {
+    bool ok;
+    float R, Rc;
+    int ncols;
+};
+
+}  // namespace swarm_internal
+
+struct swarm_env {
+    swarm_config_t cfg;
+    swarm_internal::KP kp;
+    int device;
+    int npad;
+    hipStream_t stream;
+    hipEvent_t ev0, ev1;
+    bool have_cells, have_state, observed;
+    int attr_smem[24];
+    bool half;                     // the half-occupied geometry is in use (set_lattice_mode)
+    int n_cu;
+    std::vector<char> cells_set;
+    std::string err;
+    // device buffers
+    double *d_p, *d_dp, *d_cells, *d_cin;
+    double2 *d_cells_xy;
+    swarm_internal::LatEnv *d_lat;
+    // shape set for the device-side reset
+    int n_shapes;
+    double *d_shape_cells, *d_shape_l, *d_shape_cin;
+    int *d_shape_ng;
+    int *d_shape_idx;              // [E] shape index drawn by the last swarm_reset (-1 before / after swarm_set_cells)
+    swarm_internal::LatEnv *d_shape_lat;
+    std::vector<swarm_internal::LatInfo> shape_lat;    // per shape of the set
+    std::vector<swarm_internal::LatInfo> env_lat;      // per env; after swarm_reset: the shape set's maxima, valid for every env
+    bool lattice_disabled;
+    int *d_nei, *d_near, *d_inflag, *d_ng, *d_exp_sensed, *d_exp_occ;
+    double2 *d_sf;
+    void *d_prior;
+    double2 *d_act_next;           // [E][N] the 'llm' strategy's next action (cfg.llm_action)
+    double2 *d_act64;              // [E][N] fp64 action scratch of swarm_rollout_expert (first expert call)
+    // reference-shaped host I/O (swarm_step_host): library-owned step outputs on the device, the export block on the
+    // device, two pinned host copies of it (ping-pong: the previous step's arrays stay valid for one more step), a pinned
+    // staging buffer for the action
+    void *d_io_obs, *d_io_prior; float *d_io_rew; uint8_t *d_io_done;
+    double *d_io_block, *h_io_block[2];
+    void *h_io_action, *d_io_action;
+    size_t io_block_bytes;
+};
+
+namespace swarm_internal __attribute__((visibility("hidden"))) {
+
+// records msg as the handle's last error (h == NULL: the calling thread's swarm_create error) and returns code (env_api.hip)
+int fail(swarm_env *h, int code, const std::string &msg);
+
+#define HIP_TRY_AS(h, what, call)                                                             \
+    do {                                                                                       \
+        hipError_t e__ = (call);                                                               \
+        if (e__ != hipSuccess)                                                                 \
+            return swarm_internal::fail(h, SWARM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e__)); \
+    } while (0)
+#define HIP_TRY(h, call) HIP_TRY_AS(h, #call, call)
+// `call` is one of the launchers below, which return their launch's hipGetLastError(): the message names that
+#define HIP_LAUNCHED(h, call) HIP_TRY_AS(h, "hipGetLastError()", call)
+
+struct DeviceGuard {
+    int prev;
+    bool ok;
+    explicit DeviceGuard(int dev) : prev(-1), ok(false)
+    {
+        if (hipGetDevice(&prev) != hipSuccess) return;
+        ok = (prev == dev) || hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// ---- swarm_env.hip: the step kernel
+// lay out the dynamic LDS of the launches of geometry (npad, half) for k.lattice / k.ng_max / k.g_max: KP's strides, off_*, smem_*
+void env_layout(KP &k, int npad, bool half);
+// enqueue one step (do_step) or observation pass of the handle's current cell path on its stream
+int env_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior);
+
+// ---- env_kernels.hip: one launcher per side kernel; each enqueues on `st` and returns the launch's hipGetLastError()
+hipError_t launch_reset(hipStream_t st, const KP &kp, const ShapeSet &S, unsigned long long seed, unsigned long long episode,
+                        long long env_offset, double *cells, int *n_g, double *c_in, LatEnv *lat, int *shape_idx);
+hipError_t launch_select_shape(hipStream_t st, const ShapeSet &S, int s, int ng_max, int n_env, double *cells, double2 *cells_xy,
+                               int *n_g, double *c_in, LatEnv *lat, int *shape_idx);
+hipError_t launch_interleave(hipStream_t st, const double *cells, double2 *cells_xy, int ng_max, int e0, int count);
+hipError_t launch_metrics(hipStream_t st, const KP &kp, double *out);
+hipError_t launch_metrics_step(hipStream_t st, const KP &kp, int n_cu, double *out);
+// obs / prior hold the handle's obs_dtype (SWARM_F32 / SWARM_F64 / SWARM_BF16)
+hipError_t launch_export(hipStream_t st, int obs_dtype, const void *obs, const float *reward, const uint8_t *done,
+                         const void *prior, double *out, int D, long long EN, int with_prior);
+
+}  // namespace swarm_internal
+
+#endif

@@ -1,5 +1,5 @@
 // The rule-based expert controller (agent_strategy == 'rule', assembly.py:530-601) for the CURRENT state: the one kernel
-// behind swarm_rule_action (swarm_env.hip) and the rule source of swarm_rollout_expert (rollout.hip).  It consumes what the
+// behind swarm_rule_action (env_api.hip) and the rule source of swarm_rollout_expert (rollout.hip).  It consumes what the
 // index-export observation pass left in HBM (swarm_expert_view): nearest cell / in-shape flag and the capped sensed-cell list
 // (the same filter + np.round(i * step) selection as :544-572).
 #include <hip/hip_runtime.h>

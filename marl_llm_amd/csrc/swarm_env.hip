@@ -1,4 +1,7 @@
-// swarm_env.hip -- MI355X (gfx950 / CDNA4) batched AssemblySwarm environment step + its C ABI.
+// swarm_env.hip -- MI355X (gfx950 / CDNA4) batched AssemblySwarm environment step: the kernel, its LDS map and its launch.
+// Only what determines the step kernel's device code lives here (bench.py and tools/pmc_summary.py identify the kernel by
+// this file's hash): the side kernels are in env_kernels.hip, the handle and the C ABI in env_api.hip, the kernel-argument
+// struct KP and the handle's declaration in env_types.h.
 //
 // One fused kernel advances E independent environments by one AssemblySwarmEnv.step():
 //   contact / wall forces -> prior policy -> semi-implicit Euler -> neighbour search ->
@@ -30,91 +33,21 @@
 
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <new>
 #include <string>
 #include <type_traits>
 #include <utility>
-#include <vector>
 
 #include "swarm_env.h"
-#include "swarm_internal.h"
+#include "env_types.h"
+
+using namespace swarm_internal;
 
 namespace {
 
-constexpr int kTopoMax = 6;
-constexpr int kNeiStride = 8;     // shorts per agent in the LDS neighbour list: 6 ids, [6] = collision flag
 typedef unsigned long long u64;
-
-// Per-environment description of the target cells as a subset of a (rotated) square lattice, when they are one
-// (the reference tiles a silhouette image into square cells and rotates / shifts them: assembly_cfg.py:56-99,
-// assembly.py:175-187).  Cell (column a, row b) sits at o + a*u + b*v and the cell index order is row-major.
-struct LatEnv {
-    double ox, oy;
-    double uxi, uyi, vxi, vyi;    // (p - o) . (uxi, uyi) = column coordinate, (p - o) . (vxi, vyi) = row coordinate
-    float R, Rc;                  // d_sen / l and (r_avoid / 2) / l in lattice steps
-    int nrows, ncols;
-    short rowstart[64];           // cell index of the first cell of each row
-    unsigned long long rowmask[64];   // occupied columns of each row
-};
-
-struct KP {
-    int n_env, n_a, ng_max, ngw, topo, g_max, occ_max, obs_dim;
-    int with_self, periodic, boundary, with_prior, export_idx;
-    int export_small;          // also write neighbor_index / nearest cell / in_flags to HBM (export launches only: the step itself keeps them in LDS)
-    int cxy_stride;            // double2 elements per env in LDS
-    int cxq_stride;            // floats per env in the fp32 pair layout
-    int g_stride;              // int16 elements per agent row in LDS
-    int off_cxy, off_sp, off_cmask, off_sbits, off_obits, off_sidx, off_snei, off_sncf, off_snear, off_pc;
-    int smem_lat, smem_lat_export, smem_generic;   // dynamic LDS bytes by launch kind
-    double c_sen, c_near, c_occ, c_avoid, c_ball;     // squared-distance cut-offs
-    double c_close, c_close2;  // (1.9 r_avoid)^2 and (3 r_avoid)^2 capped at c_sen: pre-selection radii of the neighbour insertion (any values are exact; the second is used for N > 128)
-    // fp32 pre-filter bands: d2_32 < *_lo  =>  exact test true;  d2_32 >= *_hi  =>  exact test false
-    float csen_lo, csen_hi, cocc_lo, cocc_hi;
-    float coord_lim;           // |coordinate| bound the bands were derived for
-    float min_tol_a, min_tol_b;   // nearest-cell ambiguity tolerance: a*sqrt(d2) + b*d2
-    float rew_ga, rew_gb;      // the reward is re-evaluated in fp64 when | |v| - 0.05 | <= rew_ga * n / den + rew_gb
-    int force_exact;           // debug: take every exact fallback path
-    int cap_int;               // G-1 odd: the cap's round(i*step) is an exact integer division by 2(G-1)
-    unsigned cap_magic; int cap_shift;
-    int cap_even;              // the expert's export pass: ties of round(i*step) go to even, as np.round sends them (assembly.py:564);
-                               // the observation itself rounds them away from zero (std::round, CPP:223).  Ties need G-1 even.
-    int dbg_phase, dbg_extra;  // diagnostics only (tools/ablate.py): run phase dbg_phase dbg_extra EXTRA times; the
-                               // phases are idempotent, so results are unchanged and the extra cost is the phase's cost
-    int off_cxyf, off_partc, off_lat, off_cov, off_flag;
-    // lattice (row-space) launches only: per-agent frame, per (window row, agent) column masks / first cell index, per-agent
-    // row counts, the agent permutation of the list phase, the fp32 reward verdicts, the occupied columns (export only)
-    int off_hdr, off_srow, off_pcr, off_perm, off_rres, off_orow, off_partd;
-    float rew_ga_lat, rew_gb_lat;   // guard band of the fp32 reward decision in lattice steps (see swarm_create)
-    float rew_thr_k;           // 0.05 / d_sen: the reward's |v| threshold in lattice steps is rew_thr_k * (d_sen / l)
-    int lattice;               // every env's cells are a lattice subset whose sensing window is <= 15 rows: row-space path
-    int lat_rw, lat_cw;        // row half-windows (lattice steps) for d_sen and r_avoid/2
-    int lat_nrs, lat_nrc;      // rows a radius can touch: floor(2 (rho_max + margin)) + 1, for d_sen and r_avoid/2
-    int lat_n32;               // every env's lattice has <= 32 columns: 32-bit row masks
-    double c_near_hi;          // c_near * (1 + 1e-9): pairs in [c_near, c_near_hi) flag the exact occupied-cell path
-    const LatEnv *lat;
-    double d_sen, r_avoid, size_a, size2, k_ball, k_wall, c_wall, vel_max, dt;
-    double bx0, by1, bx2, by3, w_half, h_half;
-    double *p, *dp;
-    int *nei, *near_cell, *in_flag;
-    double2 *sf_next;          // [E][N]: contact-spring force on agent i in the CURRENT state = the force term of the next step
-    const double *cells;       // [E][2][ng_max] (the ABI's layout)
-    const double2 *cells_xy;   // [E][ng_max] (x, y) interleaved copy: one 16-byte gather per cell
-    const int *n_g;
-    const double *c_in;
-    int *exp_sensed, *exp_occ;
-    void *prior_next;          // [E][N] pairs of the handle's obs dtype: the prior policy of the next step (written by every pass)
-    double pk_att, pk_rep, pk_ali;   // gains of the prior policy: attraction, repulsion, alignment (CPP:1128-1132: 2, 3, 2)
-    double pk_llm;             // repulsion gain of the Python twin that drives agent_strategy == 'llm' (ENV:895: 1.0)
-    int llm;                   // also evaluate that twin and leave it in act_next as the NEXT step's action (ENV:525-529)
-    double2 *act_next;         // [E][N]
-    long long *stamps;         // diagnostic build only (-DSWARM_STAMPS): per-block phase clocks
-};
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 
@@ -341,7 +274,6 @@ template <int NPAD, bool HALF> struct LatMap {
     static_assert(pm_bytes <= sidx_bytes(0), "the pair masks must fit the list region they reuse");
 };
 
-constexpr double kSentinel = 1.0e200;     // coordinates of padding cells: d2 overflows to +inf
 
 // cos(pi * t) for t in [0, 1], absolute error ~2e-16 (Taylor in x = pi*min(t, 1-t) <= pi/2 up to x^22).
 // Only the reward's psi weights use it (CPP:1012-1020 calls libm cos(M_PI * z / r)); it is not bit-identical
@@ -2054,593 +1986,6 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
 
 #undef LO
 
-// -------------------------------------------------------------------------------------------------
-// batched reset: AssemblySwarmEnv.reset(), ENV:156-219, for every environment at once.
-// Counter-based generator: draw k of environment g in episode ep under `seed` is
-//     u = (mix64(mix64(mix64(seed + GOLD*(ep+1)) ^ g) + GOLD*(k+1)) >> 11) * 2^-53   in [0, 1)
-// (splitmix64 finaliser), so any env range can be generated on any rank without communication.  Draw slots mirror
-// the reference's order: 0 shape index (:160), 1 angle (:175), 2-3 the discarded offset (:182), 4-5 offset (:184-185),
-// 6 branch coin (:202), 7-8 cluster centre (:207-208), then per agent x, y (:203-208) and vx, vy (:215).
-// -------------------------------------------------------------------------------------------------
-struct ShapeSet {
-    int n_shapes;
-    const double *cells;      // [S][2][ng_max], shape frame (ENV: grid_center_origins[s].T)
-    const int *n_g;           // [S]
-    const double *l_cell;     // [S]
-    const double *c_in;       // [S] in-shape cut-off
-    const LatEnv *lat;        // [S] lattice of the un-rotated shape (nrows == 0: not a lattice)
-};
-
-__host__ __device__ inline unsigned long long mix64(unsigned long long z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__host__ __device__ inline double reset_u01(unsigned long long key, unsigned k)
-{
-    return (double)(mix64(key + 0x9E3779B97F4A7C15ull * (unsigned long long)(k + 1)) >> 11) * (1.0 / 9007199254740992.0);
-}
-
-__global__ void __launch_bounds__(256)
-k_reset(const KP P, const ShapeSet S, const unsigned long long seed, const unsigned long long episode,
-        const long long env_offset, double *cells_out, int *ng_out, double *cin_out, LatEnv *lat_out, int *shape_out)
-{
-    const int e = blockIdx.x, tid = threadIdx.x;
-    const unsigned long long key = mix64(mix64(seed + 0x9E3779B97F4A7C15ull * (episode + 1)) ^ (unsigned long long)(env_offset + e));
-    const double W = P.w_half, H = P.h_half;
-    int s = (int)(reset_u01(key, 0) * S.n_shapes);
-    s = s >= S.n_shapes ? S.n_shapes - 1 : s;
-    const double ang = M_PI * (2.0 * reset_u01(key, 1) - 1.0);
-    const double cs = cos(ang), sn = sin(ang);                       // rotate_matrix = [[c, s], [-s, c]], ENV:177
-    const double offx = (-W + 1) + reset_u01(key, 4) * (2 * W - 2);
-    const double offy = (-H + 1) + reset_u01(key, 5) * (2 * H - 2);
-    const int ng = S.n_g[s];
-    const double *sx_ = S.cells + (size_t)s * 2 * P.ng_max, *sy_ = sx_ + P.ng_max;
-    double *gx = cells_out + (size_t)e * 2 * P.ng_max, *gy = gx + P.ng_max;
-    for (int c = tid; c < P.ng_max; c += blockDim.x) {
-        double x = 0.0, y = 0.0;
-        if (c < ng) { x = cs * sx_[c] + sn * sy_[c] + offx; y = -sn * sx_[c] + cs * sy_[c] + offy; }   // ENV:178,187
-        gx[c] = x; gy[c] = y;
-    }
-    if (tid == 0) {
-        ng_out[e] = ng; cin_out[e] = S.c_in[s]; shape_out[e] = s;
-        LatEnv L = S.lat[s];
-        if (L.nrows > 0) {          // rotate / shift the shape's lattice: u' = R u, v' = R v, o' = R o + offset
-            // shape-frame basis from the stored inverse basis: u = uxi / |uxi|^2
-            const double iu = 1.0 / (L.uxi * L.uxi + L.uyi * L.uyi), iv = 1.0 / (L.vxi * L.vxi + L.vyi * L.vyi);
-            const double ux = L.uxi * iu, uy = L.uyi * iu, vx = L.vxi * iv, vy = L.vyi * iv;
-            const double rux = cs * ux + sn * uy, ruy = -sn * ux + cs * uy;
-            const double rvx = cs * vx + sn * vy, rvy = -sn * vx + cs * vy;
-            const double rox = cs * L.ox + sn * L.oy + offx, roy = -sn * L.ox + cs * L.oy + offy;
-            L.ox = rox; L.oy = roy;
-            L.uxi = rux / iu; L.uyi = ruy / iu; L.vxi = rvx / iv; L.vyi = rvy / iv;
-        }
-        lat_out[e] = L;
-    }
-    // agents (ENV:202-215)
-    const int N = P.n_a;
-    const bool spread = (2.0 * reset_u01(key, 6) - 1.0) > 0;
-    const double cx = (-W + 1) + reset_u01(key, 7) * (2 * W - 2), cy = (-H + 1) + reset_u01(key, 8) * (2 * H - 2);
-    for (int i = tid; i < N; i += blockDim.x) {
-        const double ux_ = reset_u01(key, 16 + i), uy_ = reset_u01(key, 16 + N + i);
-        double x, y;
-        if (spread) { x = -W + ux_ * (2 * W); y = -H + uy_ * (2 * H); }
-        else { x = (2.0 * ux_ - 1.0) + cx; y = (2.0 * uy_ - 1.0) + cy; }
-        P.p[(size_t)e * 2 * N + i] = x; P.p[(size_t)e * 2 * N + N + i] = y;
-        P.dp[(size_t)e * 2 * N + i] = -0.5 + reset_u01(key, 16 + 2 * N + i);
-        P.dp[(size_t)e * 2 * N + N + i] = -0.5 + reset_u01(key, 16 + 3 * N + i);
-    }
-}
-
-// -------------------------------------------------------------------------------------------------
-// evaluation metrics: AssemblySwarmWrapper.coverage_rate / distribution_uniformity /
-// voronoi_based_uniformity, /root/reference/cus_gym/gym/wrappers/customized_envs/assembly_wrapper.py:48-128, per env.
-// fp64 in numpy's operation order, including np.var's two-pass form and numpy's pairwise summation (blocks of 8
-// accumulators up to 128 elements, recursive halves above), so the values are bit-identical to the Python loops.
-// -------------------------------------------------------------------------------------------------
-__device__ double np_pairwise_sum(const double *a, int n)
-{
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    if (n <= 128) {
-        double r[8];
-        for (int k = 0; k < 8; ++k) r[k] = a[k];
-        int i;
-        for (i = 8; i < n - (n % 8); i += 8)
-            for (int k = 0; k < 8; ++k) r[k] += a[i + k];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += a[i];
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
-}
-
-// (np.var(v) - min(v)) / (max(v) - min(v)), assembly_wrapper.py:96-99,125-126; `tmp` holds n doubles of scratch
-__device__ double np_var_metric(const double *v, double *tmp, int n)
-{
-    const double mean = np_pairwise_sum(v, n) / n;
-    double mn = v[0], mx = v[0];
-    for (int i = 0; i < n; ++i) {
-        const double d = v[i] - mean;
-        tmp[i] = d * d;
-        mn = v[i] < mn ? v[i] : mn; mx = v[i] > mx ? v[i] : mx;
-    }
-    const double var = np_pairwise_sum(tmp, n) / n;
-    return (var - mn) / (mx - mn);
-}
-
-__global__ void __launch_bounds__(256)
-k_metrics(const KP P, double *__restrict__ out)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int N = P.n_a, e = blockIdx.x, tid = threadIdx.x;
-    double *px = reinterpret_cast<double *>(smem), *py = px + N;       // [N], [N]
-    double *val = py + N, *tmp = val + N;                              // [N] per-agent values, [N] scratch
-    int *cnt = reinterpret_cast<int *>(tmp + N);                       // [N] Voronoi counts, then [1] coverage count
-    const int ng = P.n_g[e];
-    const double *gx = P.cells + (size_t)e * 2 * P.ng_max, *gy = gx + P.ng_max;
-    for (int i = tid; i < N; i += blockDim.x) {
-        px[i] = P.p[(size_t)e * 2 * N + i]; py[i] = P.p[(size_t)e * 2 * N + N + i];
-        cnt[i] = 0;
-    }
-    if (tid == 0) cnt[N] = 0;
-    __syncthreads();
-    // coverage (assembly_wrapper.py:58-73) and Voronoi owner (:110-121) of every cell
-    const double half = P.r_avoid / 2;
-    for (int c = tid; c < ng; c += blockDim.x) {
-        bool covered = false;
-        double best = 0.0; int owner = 0;
-        for (int j = 0; j < N; ++j) {
-            const double dx = px[j] - gx[c], dy = py[j] - gy[c];
-            const double d = sqrt(dx * dx + dy * dy);                 // np.linalg.norm(axis=0)
-            covered = covered || (d < half);
-            if (j == 0 || d < best) { best = d; owner = j; }          // np.argmin: first minimum
-        }
-        if (covered) atomicAdd(&cnt[N], 1);
-        atomicAdd(&cnt[owner], 1);
-    }
-    // minimum non-zero distance of every agent (:85-93)
-    for (int i = tid; i < N; i += blockDim.x) {
-        double m = INFINITY;
-        for (int j = 0; j < N; ++j) {
-            const double dx = px[j] - px[i], dy = py[j] - py[i];
-            const double d = sqrt(dx * dx + dy * dy);
-            if (d != 0 && d < m) m = d;
-        }
-        val[i] = m;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        out[(size_t)e * 3 + 0] = (double)cnt[N] / ng;
-        out[(size_t)e * 3 + 1] = np_var_metric(val, tmp, N);
-    }
-    __syncthreads();
-    for (int i = tid; i < N; i += blockDim.x) val[i] = (double)cnt[i];
-    __syncthreads();
-    if (tid == 0) out[(size_t)e * 3 + 2] = np_var_metric(val, tmp, N);
-}
-
-// -------------------------------------------------------------------------------------------------
-// The per-step metrics kernel of the evaluation loop (swarm_rollout_eval): the same bits as k_metrics, which stays the
-// in-repo reference, at a fraction of its work.  WPE waves per env in a 256-thread workgroup: one (four envs per workgroup)
-// when the batch alone fills the chip, four (one env per workgroup, the cells and agents dealt over 256 lanes) for a small
-// batch, where one wave per env would leave most SIMDs idle and the launch would be latency-bound.
-//
-// Where k_metrics spends its time and why the cheaper form is exact.  With s = dx*dx + dy*dy (the same fp64 expression,
-// no contraction) every distance k_metrics uses is d = sqrt(s), and fp64 sqrt is correctly rounded, hence monotone:
-// s_a <= s_b implies d_a <= d_b.
-//   * coverage of a cell: any_j (d_j < r/2)  ==  (min_j d_j < r/2)  ==  (sqrt(min_j s_j) < r/2).  So only the minimum of
-//     the squared distances is needed, and with h2 = (r/2)^2 the verdict is read off it: s_min < h2 (1 - 2^-40) means
-//     sqrt(s_min) is more than 2^-42 relative (thousands of ulps) below r/2, s_min > h2 (1 + 2^-40) the same above; only
-//     inside that band is the exact sqrt compared.  This minimum skips NaN, as `d < r/2` does; the argmin's running
-//     minimum is seeded with agent 0 whatever it is, as np.argmin's loop in k_metrics is, so NaN states give the same bits.
-//   * Voronoi owner: np.argmin over the ROUNDED norms = the lowest index j with d_j == d_min.  The scan keeps the running
-//     minimum of s and the first index that reached it.  An earlier agent can share the rounded norm only if its s lies
-//     within a few 2^-52 of s_min; at the last update of the minimum the previous minimum (the smallest s of all earlier
-//     agents) is compared with s_new (1 + 2^-40): above it, every earlier sqrt is more than 2^-42 relative larger, so the
-//     index stands; otherwise (or for s below 1e-270, where the spacing of s is coarse) the cell is redone with k_metrics'
-//     own sqrt loop.  A later agent never wins a tie, in either form.
-//   * minimum non-zero distance of an agent: d != 0 iff s != 0, and the minimum commutes with sqrt: one sqrt per agent.
-//   * np.var: numpy's pairwise sum has eight independent accumulators per block of <= 128 elements; eight lanes run one
-//     each (the same additions in the same order), the ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) tree, the tail and the
-//     recursive halves above 128 elements are as in np_pairwise_sum.  Minimum and maximum do not depend on the order.
-// Per (cell, agent) pair that leaves two subtractions, two multiplications, one addition and a compare in fp64; the agents'
-// (x, y) are read as one 16-byte LDS broadcast.
-// -------------------------------------------------------------------------------------------------
-constexpr int kMsEnvs = 4;                                   // envs (= waves) per workgroup
-
-__device__ inline double wave_get(double v, int lane) { return __shfl(v, lane); }
-
-// np_pairwise_sum(a, n) by one whole wave (every lane calls with the same arguments and gets the same value); a in LDS
-__device__ double wave_pairwise_sum(const double *a, int n, int lane)
-{
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    if (n <= 128) {
-        const int n8 = n - (n % 8);
-        double r = 0.0;
-        if (lane < 8) {
-            r = a[lane];
-            for (int i = 8 + lane; i < n8; i += 8) r += a[i];
-        }
-        const double r0 = wave_get(r, 0), r1 = wave_get(r, 1), r2 = wave_get(r, 2), r3 = wave_get(r, 3);
-        const double r4 = wave_get(r, 4), r5 = wave_get(r, 5), r6 = wave_get(r, 6), r7 = wave_get(r, 7);
-        double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-        for (int i = n8; i < n; ++i) res += a[i];
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    const double lo = wave_pairwise_sum(a, n2, lane);
-    return lo + wave_pairwise_sum(a + n2, n - n2, lane);
-}
-
-template <int WPE>
-__global__ void __launch_bounds__(64 * kMsEnvs)
-k_metrics_step(const KP P, double *__restrict__ out, const int stride)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int T = 64 * WPE, EPBK = kMsEnvs / WPE;         // lanes per env, envs per workgroup
-    const int N = P.n_a, lane = threadIdx.x & 63, w = threadIdx.x / T, t = threadIdx.x % T;
-    const bool first = (threadIdx.x >> 6) % WPE == 0;         // the env's first wave runs the np.var tails
-    const int e_raw = blockIdx.x * EPBK + w;
-    const bool active = e_raw < P.n_env;                     // a surplus wave does no work but meets every barrier
-    const int e = active ? e_raw : P.n_env - 1;
-    unsigned char *base = smem + (size_t)w * stride;
-    double2 *xy = reinterpret_cast<double2 *>(base);                    // [N]
-    double *val = reinterpret_cast<double *>(base + (size_t)16 * N);   // [N] per-agent values
-    double *tmp = val + N;                                              // [N] scratch
-    int *cnt = reinterpret_cast<int *>(tmp + N);                        // [N] Voronoi counts, then [1] coverage count
-    const int ng = P.n_g[e];
-    const double *gx = P.cells + (size_t)e * 2 * P.ng_max, *gy = gx + P.ng_max;
-    for (int i = t; i < N; i += T) {
-        double2 q; q.x = P.p[(size_t)e * 2 * N + i]; q.y = P.p[(size_t)e * 2 * N + N + i];
-        xy[i] = q; cnt[i] = 0;
-    }
-    if (t == 0) cnt[N] = 0;
-    __syncthreads();
-    const double half = P.r_avoid / 2, h2 = half * half;
-    const double band = 1.0 + 0x1p-40, h2_lo = h2 * (1.0 - 0x1p-40), h2_hi = h2 * band;
-    int covered = 0;
-    for (int c = t; c < ng; c += T) {
-        const double cx = gx[c], cy = gy[c];
-        double best = 0.0, cmin = INFINITY; int owner = 0; bool amb = false;
-        for (int j = 0; j < N; ++j) {
-            const double2 q = xy[j];
-            const double dx = q.x - cx, dy = q.y - cy;
-            const double s2 = dx * dx + dy * dy;
-            cmin = s2 < cmin ? s2 : cmin;                     // a NaN never covers (d < r/2 is false), but it does seed argmin
-            if (j == 0) { best = s2; amb = s2 < 1e-270; }
-            else if (s2 < best) { amb = (best <= s2 * band) || (s2 < 1e-270); best = s2; owner = j; }
-        }
-        if (amb) {                                            // a tie after rounding is possible: k_metrics' own loop
-            double bd = 0.0; owner = 0;
-            for (int j = 0; j < N; ++j) {
-                const double2 q = xy[j];
-                const double dx = q.x - cx, dy = q.y - cy;
-                const double d = sqrt(dx * dx + dy * dy);
-                if (j == 0 || d < bd) { bd = d; owner = j; }
-            }
-        }
-        const bool cov = cmin < h2_lo ? true : (cmin > h2_hi ? false : sqrt(cmin) < half);
-        covered += cov ? 1 : 0;
-        atomicAdd(&cnt[owner], 1);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) covered += __shfl_xor(covered, o);
-    if (lane == 0) atomicAdd(&cnt[N], covered);                // an integer sum: the order does not matter
-    for (int i = t; i < N; i += T) {                           // minimum non-zero distance of every agent
-        const double2 a = xy[i];
-        double m = INFINITY;
-        for (int j = 0; j < N; ++j) {
-            const double2 q = xy[j];
-            const double dx = q.x - a.x, dy = q.y - a.y;
-            const double s2 = dx * dx + dy * dy;
-            if (s2 != 0 && s2 < m) m = s2;
-        }
-        val[i] = sqrt(m);
-    }
-    __syncthreads();
-    double res[2] = {0.0, 0.0};
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {                     // np_var_metric of val, by the env's first wave
-        double mean = 0.0, mn = 0.0, mx = 0.0;
-        if (first) {
-            mean = wave_pairwise_sum(val, N, lane) / N;
-            mn = val[0]; mx = val[0];
-            for (int i = lane; i < N; i += 64) {
-                const double v = val[i], d = v - mean;
-                tmp[i] = d * d;
-                mn = v < mn ? v : mn; mx = v > mx ? v : mx;
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
-                mn = a < mn ? a : mn; mx = b > mx ? b : mx;
-            }
-        }
-        __syncthreads();
-        if (first) {
-            const double var = wave_pairwise_sum(tmp, N, lane) / N;
-            res[pass] = (var - mn) / (mx - mn);
-        }
-        __syncthreads();
-        if (pass == 0) {
-            for (int i = t; i < N; i += T) val[i] = (double)cnt[i];
-            __syncthreads();
-        }
-    }
-    if (active && first && lane == 0) {
-        out[(size_t)e * 3 + 0] = (double)cnt[N] / ng;
-        out[(size_t)e * 3 + 1] = res[0];
-        out[(size_t)e * 3 + 2] = res[1];
-    }
-}
-
-
-// (x, y)-interleaved copy of the target cells of envs [e0, e0 + count): the step kernel gathers cells per lane, and one
-// 16-byte load per cell costs half the address-unit work of two 8-byte loads from the ABI's [2][ng_max] layout.
-__global__ void __launch_bounds__(256)
-k_interleave(const double *__restrict__ cells, double2 *__restrict__ out, int ng_max, int e0, int count)
-{
-    const size_t n = (size_t)count * ng_max;
-    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) {
-        const size_t e = e0 + q / ng_max, c = q % ng_max;
-        double2 g; g.x = cells[e * 2 * ng_max + c]; g.y = cells[e * 2 * ng_max + ng_max + c];
-        out[e * ng_max + c] = g;
-    }
-}
-
-// The device-side shape switch (swarm_select_shape; eval_assembly.py:34-57 process_shape with its rotation 0 and offset 0):
-// every env takes shape `s` of the uploaded set as it stands -- the whole cell row (the same doubles, padding included) into
-// both cell layouts, and the per-env scalars k_reset writes.  p / dp are not touched.
-__global__ void __launch_bounds__(256)
-k_select_shape(const ShapeSet S, const int s, const int ng_max, double *__restrict__ cells_out, double2 *__restrict__ cells_xy,
-               int *__restrict__ ng_out, double *__restrict__ cin_out, LatEnv *__restrict__ lat_out, int *__restrict__ shape_out)
-{
-    const int e = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;         // grid (ceil(ng_max / 256), n_env)
-    if (c < ng_max) {
-        double2 g; g.x = S.cells[(size_t)s * 2 * ng_max + c]; g.y = S.cells[(size_t)s * 2 * ng_max + ng_max + c];
-        cells_out[(size_t)e * 2 * ng_max + c] = g.x; cells_out[(size_t)e * 2 * ng_max + ng_max + c] = g.y;
-        cells_xy[(size_t)e * ng_max + c] = g;
-    }
-    if (c == 0) { ng_out[e] = S.n_g[s]; cin_out[e] = S.c_in[s]; shape_out[e] = s; lat_out[e] = S.lat[s]; }
-}
-
-// -------------------------------------------------------------------------------------------------
-// The reference-shaped host outputs ("a single host-side gather of obs / reward"): the step
-// leaves obs [E][N][D], reward [E][N], done [E][N], a_prior [E][N][2] on the device; the numpy API of
-// AssemblySwarmEnv.step returns obs (D, n_a) / reward (1, n_a) / a_prior (2, n_a) as float64 and done (1, n_a) as bool with
-// the environments side by side on the agent axis (assembly.py:487-666, 227-231, 353, 480-482).  k_export writes exactly
-// that block -- widened to double, transposed -- into ONE contiguous device buffer that a single hipMemcpyAsync moves
-// into pinned host memory: no per-step allocation, no host-side pass over the data.
-// Block layout (doubles): obs D*EN | a_prior 2*EN | reward EN | done EN bytes.
-// -------------------------------------------------------------------------------------------------
-template <typename OT> __device__ __forceinline__ double wide(OT v) { return (double)v; }
-template <> __device__ __forceinline__ double wide<__bf16>(__bf16 v) { return (double)(float)v; }
-
-template <typename OT>
-__global__ void __launch_bounds__(256)
-k_export(const OT *__restrict__ obs, const float *__restrict__ reward, const uint8_t *__restrict__ done,
-         const OT *__restrict__ prior, double *__restrict__ out, const int D, const long long EN, const int with_prior)
-{
-    // tile: 64 agent rows x 32 features through LDS: reads run along a row (features contiguous), writes along the agent axis
-    __shared__ double tile[32][65];
-    const int tid = threadIdx.x;
-    const long long r0 = (long long)blockIdx.x * 64;
-    for (int f0 = 0; f0 < D; f0 += 32) {
-        const int fw = D - f0 < 32 ? D - f0 : 32;
-        {
-            const int f = tid & 31;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int r = (tid >> 5) + 8 * k;
-                if (f < fw && r0 + r < EN) tile[f][r] = wide<OT>(obs[(size_t)(r0 + r) * D + f0 + f]);
-            }
-        }
-        __syncthreads();
-        {
-            const int r = tid & 63;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int f = (tid >> 6) + 4 * k;
-                if (f < fw && r0 + r < EN) __builtin_nontemporal_store(tile[f][r], &out[(size_t)(f0 + f) * EN + r0 + r]);
-            }
-        }
-        __syncthreads();
-    }
-    if (tid < 64 && r0 + tid < EN) {
-        const long long a = r0 + tid;
-        double *pri = out + (size_t)D * EN, *rew = pri + 2 * EN;
-        uint8_t *dn = reinterpret_cast<uint8_t *>(rew + EN);
-        if (with_prior) { pri[a] = wide<OT>(prior[2 * a]); pri[EN + a] = wide<OT>(prior[2 * a + 1]); }
-        if (reward != nullptr) rew[a] = (double)reward[a];
-        if (done != nullptr) dn[a] = done[a];
-    }
-}
-
-// -------------------------------------------------------------------------------------------------
-// host side
-// -------------------------------------------------------------------------------------------------
-
-thread_local std::string g_create_error;
-
-// smallest double x with sqrt(x) >= t (IEEE sqrt is correctly rounded and monotonic), so that
-// sqrt(d2) < t  <=>  d2 < x  for every d2 >= 0.
-double cut_lt(double t)
-{
-    if (!(t > 0)) return 0.0;
-    double x = t * t;
-    while (x > 0 && std::sqrt(x) >= t) x = std::nextafter(x, 0.0);
-    while (std::sqrt(x) < t) x = std::nextafter(x, INFINITY);
-    return x;
-}
-// sqrt(d2) <= t  <=>  d2 < cut_le(t)
-double cut_le(double t) { return cut_lt(std::nextafter(t, INFINITY)); }
-
-int npad_for(int n)
-{
-    int v = 8;
-    while (v < n) v <<= 1;
-    return v;
-}
-
-}  // namespace
-
-struct swarm_env {
-    swarm_config_t cfg;
-    KP kp;
-    int device;
-    int npad;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
-    bool have_cells, have_state, observed;
-    int attr_smem[24];
-    bool half;                     // the half-occupied geometry is in use (set_lattice_mode)
-    int n_cu;
-    std::vector<char> cells_set;
-    std::string err;
-    // device buffers
-    double *d_p, *d_dp, *d_cells, *d_cin;
-    double2 *d_cells_xy;
-    LatEnv *d_lat;
-    // shape set for the device-side reset
-    int n_shapes;
-    double *d_shape_cells, *d_shape_l, *d_shape_cin;
-    int *d_shape_ng;
-    int *d_shape_idx;              // [E] shape index drawn by the last swarm_reset (-1 before / after swarm_set_cells)
-    LatEnv *d_shape_lat;
-    bool shapes_lattice; float shapes_rmax, shapes_cmax; int shapes_ncols;
-    std::vector<char> shape_lat_ok;            // per shape of the set: a lattice subset (swarm_select_shape)
-    std::vector<float> shape_R, shape_Rc;
-    std::vector<int> shape_ncols;
-    std::vector<char> lat_ok;      // per env: cells are a lattice subset
-    std::vector<float> lat_R, lat_Rc;
-    std::vector<int> lat_ncols;
-    bool lattice_disabled;
-    int *d_nei, *d_near, *d_inflag, *d_ng, *d_exp_sensed, *d_exp_occ;
-    double2 *d_sf;
-    void *d_prior;
-    double2 *d_act_next;           // [E][N] the 'llm' strategy's next action (cfg.llm_action)
-    double2 *d_act64;              // [E][N] fp64 action scratch of swarm_rollout_expert (first expert call)
-    // reference-shaped host I/O (swarm_step_host): library-owned step outputs on the device, the export block on the
-    // device, two pinned host copies of it (ping-pong: the previous step's arrays stay valid for one more step), a pinned
-    // staging buffer for the action
-    void *d_io_obs, *d_io_prior; float *d_io_rew; uint8_t *d_io_done;
-    double *d_io_block, *h_io_block[2];
-    void *h_io_action, *d_io_action;
-    size_t io_block_bytes;
-};
-
-namespace {
-
-int fail(swarm_env *h, int code, const std::string &msg)
-{
-    if (h) h->err = msg; else g_create_error = msg;
-    return code;
-}
-
-#define HIP_TRY(h, call)                                                                       \
-    do {                                                                                       \
-        hipError_t e__ = (call);                                                               \
-        if (e__ != hipSuccess)                                                                 \
-            return fail(h, SWARM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
-struct DeviceGuard {
-    int prev;
-    bool ok;
-    explicit DeviceGuard(int dev) : prev(-1), ok(false)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) return;
-        ok = (prev == dev) || hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// Is this cell list a row-major subset of a square lattice (<= 64 x 64)?  Fills `L` (geometry only) if so.
-bool detect_lattice(const double *gx, const double *gy, int n, LatEnv &L)
-{
-    if (n < 2) return false;
-    // lattice step: the closest pair among consecutive cells (cells of one row are consecutive and one step apart)
-    double l2 = INFINITY; int k0 = -1;
-    for (int c = 0; c + 1 < n; ++c) {
-        const double dx = gx[c + 1] - gx[c], dy = gy[c + 1] - gy[c], d2 = dx * dx + dy * dy;
-        if (d2 < l2) { l2 = d2; k0 = c; }
-    }
-    if (!(l2 > 0) || k0 < 0) return false;
-    // the row direction u is one of the (at most four) distinct unit-step directions between consecutive cells
-    // (single-cell rows make consecutive cells vertical neighbours): try each until the order is row-major
-    double cand[4][2]; int ncand = 0;
-    for (int c = 0; c + 1 < n && ncand < 4; ++c) {
-        const double dx = gx[c + 1] - gx[c], dy = gy[c + 1] - gy[c], d2 = dx * dx + dy * dy;
-        if (d2 > l2 * (1.0 + 1e-6)) continue;
-        bool seen = false;
-        for (int q = 0; q < ncand; ++q)
-            if (std::fabs(cand[q][0] - dx) + std::fabs(cand[q][1] - dy) < 1e-6 * std::sqrt(l2)) seen = true;
-        if (!seen) { cand[ncand][0] = dx; cand[ncand][1] = dy; ++ncand; }
-    }
-    std::vector<int> ai((size_t)n), bi((size_t)n);
-    double ux = 0, uy = 0, vx = 0, vy = 0;
-    bool found = false;
-    for (int q = 0; q < ncand && !found; ++q) {
-        ux = cand[q][0]; uy = cand[q][1]; vx = -uy; vy = ux;
-        for (int pass = 0; pass < 2 && !found; ++pass) {
-            bool ok = true;
-            for (int c = 0; c < n && ok; ++c) {
-                const double rx = gx[c] - gx[0], ry = gy[c] - gy[0];
-                const double a = (rx * ux + ry * uy) / l2, b = (rx * vx + ry * vy) / l2;
-                const double ar = std::nearbyint(a), br = std::nearbyint(b);
-                if (std::fabs(a - ar) > 1e-6 || std::fabs(b - br) > 1e-6 || std::fabs(ar) > 4096 || std::fabs(br) > 4096) ok = false;
-                ai[(size_t)c] = (int)ar; bi[(size_t)c] = (int)br;
-            }
-            if (!ok) break;
-            // row-major order: within a row the column increases, rows increase
-            bool order = true, flip = false;
-            for (int c = 0; c + 1 < n; ++c) {
-                if (bi[(size_t)c + 1] == bi[(size_t)c]) { if (ai[(size_t)c + 1] <= ai[(size_t)c]) order = false; }
-                else if (bi[(size_t)c + 1] < bi[(size_t)c]) { flip = true; order = false; }
-            }
-            if (order) { found = true; break; }
-            if (pass == 0 && flip) { vx = -vx; vy = -vy; continue; }      // rows run the other way: mirror v
-            break;
-        }
-    }
-    if (!found) return false;
-    int amin = ai[0], amax = ai[0], bmin = bi[0], bmax = bi[0];
-    for (int c = 0; c < n; ++c) {
-        amin = std::min(amin, ai[(size_t)c]); amax = std::max(amax, ai[(size_t)c]);
-        bmin = std::min(bmin, bi[(size_t)c]); bmax = std::max(bmax, bi[(size_t)c]);
-    }
-    if (amax - amin + 1 > 64 || bmax - bmin + 1 > 64) return false;
-    std::memset(&L, 0, sizeof(L));
-    L.ncols = amax - amin + 1; L.nrows = bmax - bmin + 1;
-    for (int b = 0; b < 64; ++b) L.rowstart[b] = 0;
-    int prev_b = -1;
-    for (int c = 0; c < n; ++c) {
-        const int a = ai[(size_t)c] - amin, b = bi[(size_t)c] - bmin;
-        if (b != prev_b) { if (b < prev_b) return false; L.rowstart[b] = (short)c; prev_b = b; }
-        if (L.rowmask[b] & (1ull << a)) return false;
-        L.rowmask[b] |= 1ull << a;
-    }
-    L.ox = gx[0] - (ai[0] - amin) * ux - (bi[0] - bmin) * vx;
-    L.oy = gy[0] - (ai[0] - amin) * uy - (bi[0] - bmin) * vy;
-    L.uxi = ux / l2; L.uyi = uy / l2; L.vxi = vx / l2; L.vyi = vy / l2;
-    const double l = std::sqrt(l2);
-    L.R = (float)l;                 // caller turns the step length into radii
-    return true;
-}
-
 template <int NPAD, bool HALF>
 void layout_t(KP &k)
 {
@@ -2705,44 +2050,6 @@ void for_geometry(int npad, bool half, F &&f)
     }
 }
 
-void layout(KP &k, int npad, bool half)
-{
-    for_geometry(npad, half, [&](auto g) { layout_t<decltype(g)::NPAD_, decltype(g)::HALF_>(k); });
-}
-
-// Decide the cell path of the next launches and lay out its LDS.  The row-space lattice path needs every env's cells to
-// be a lattice subset AND a sensing window of at most 15 lattice rows (d_sen < ~7.5 cells: a window row then has at
-// most 17 columns -- one 32-bit word -- and a list at most 240 cells -- one byte per row count); anything else takes the
-// generic scan, which handles arbitrary cell sets.
-void set_lattice_mode(swarm_env *h, bool all_lattice, float rmax, float cmax, int ncols_max)
-{
-    KP &k = h->kp;
-    k.lat_n32 = ncols_max <= 32 ? 1 : 0;
-    k.lat_rw = (int)std::ceil(rmax + 0.02f);
-    k.lat_cw = (int)std::ceil(cmax + 0.02f);
-    k.lat_nrs = (int)std::floor(2.0f * (rmax + 0.01f)) + 1; k.lat_nrc = (int)std::floor(2.0f * (cmax + 0.01f)) + 1;
-    k.lattice = (all_lattice && !h->lattice_disabled && k.lat_nrs <= 15) ? 1 : 0;
-    {   // guard band of the fp32 reward decision of the lattice path, in lattice steps (R = d_sen / l <= rmax).  Per cell the
-        // model coordinate relative to the agent is off by dx: lattice fit tolerance 1.5e-6 steps, fp32 cast of the relative
-        // coordinate (|.| <= 17 steps) 2.1e-6, the walk's scaled form c / R - a / R (two products of magnitude <= 17 / R with
-        // a 1-ulp reciprocal, cancelling) 5e-6, margin: 1.2e-5.  As in swarm_create: psi is off by
-        // dpsi <= (pi^2 / 4) (2 sqrt(2) dx / R) + 1.2e-6, |v| by n (dpsi R + dx + thr dpsi) / den, thr = 0.05 R / d_sen;
-        // fp32 accumulation / division / sqrt: 4e-6 relative to d_sen, i.e. 4e-6 R / d_sen steps.  1.3x margin.
-        const double dx = 1.2e-5, R = std::fmax(1.0, (double)rmax), thr = 0.05 * R / k.d_sen;
-        const double dpsi_R = 2.4675 * 2.0 * std::sqrt(2.0) * dx + 1.2e-6 * R;      // dpsi * R (1.2e-6: degree-5 polynomial 6.5e-7 + the 1-ulp reciprocal scaling)
-        k.rew_ga_lat = (float)(1.3 * (dpsi_R + dx + thr * dpsi_R / R));
-        k.rew_gb_lat = (float)(4e-6 * R / k.d_sen);
-    }
-    // a small batch of small environments (N < 64) that leaves at least half of the chip's workgroup slots empty: the
-    // half-occupied geometry (Geo<NPAD, true>) -- twice the workgroups, eight lanes per agent in the list phase
-    {
-        const int epb_full = h->npad < 64 ? 64 / h->npad : 1;
-        const long long grid_full = ((long long)h->cfg.n_env + epb_full - 1) / epb_full;
-        h->half = k.lattice && h->npad < 64 && epb_full >= 2 && !(h->cfg.debug_flags & 4) && 2 * grid_full <= (long long)h->n_cu * 6;
-    }
-    layout(k, h->npad, h->half);
-}
-
 template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF>
 int launch_t(swarm_env *h, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior)
 {
@@ -2789,8 +2096,17 @@ int launch_n(swarm_env *h, bool do_step, const void *action, int act_f64, void *
                             : launch_l<NPAD, float, false>(h, action, act_f64, obs, reward, done, a_prior);
 }
 
-int launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done,
-           void *a_prior)
+}  // namespace
+
+namespace swarm_internal {
+
+void env_layout(KP &k, int npad, bool half)
+{
+    for_geometry(npad, half, [&](auto g) { layout_t<decltype(g)::NPAD_, decltype(g)::HALF_>(k); });
+}
+
+int env_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done,
+               void *a_prior)
 {
     // (SWARM_ONLY_NPAD: development builds with a single instantiation -- quick register / code-size checks and A/B runs)
 #ifndef SWARM_ONLY_NPAD
@@ -2804,691 +2120,12 @@ int launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *ob
     return fail(h, SWARM_ERR_INVALID, "unsupported agent count");
 }
 
-// Re-run the observation pass on the current state with the export switched on (the step keeps the index scratch in LDS and
-// writes none of it to HBM); it recomputes the same caches from the same state, so it is idempotent.  Always leaves nearest
-// cell / in-shape flag / neighbours in HBM; lists: also the sensed / occupied cell lists (allocated on first use); cap_even:
-// the expert's rounding of the sensed-list subsample (KP::cap_even).  Enqueued on the handle's stream, no synchronisation.
-int export_pass(swarm_env *h, bool lists, bool cap_even)
-{
-    if (lists && !h->d_exp_sensed) {
-        const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
-        HIP_TRY(h, hipMalloc((void **)&h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4));
-        HIP_TRY(h, hipMalloc((void **)&h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4));
-    }
-    h->kp.export_small = 1; h->kp.cap_even = cap_even;
-    if (lists) { h->kp.export_idx = 1; h->kp.exp_sensed = h->d_exp_sensed; h->kp.exp_occ = h->d_exp_occ; }
-    const int rc = launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-    h->kp.export_idx = 0; h->kp.export_small = 0; h->kp.cap_even = 0;
-    return rc;
-}
-
-}  // namespace
-
-int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out)
-{
-    if (!h || !out) return SWARM_ERR_INVALID;
-    out->device = h->device; out->n_env = h->cfg.n_env; out->n_agents = h->cfg.n_agents; out->obs_dim = h->kp.obs_dim;
-    out->obs_dtype = h->cfg.obs_dtype; out->with_prior = h->cfg.with_prior != 0; out->observed = h->observed;
-    out->g_max = h->kp.g_max; out->llm_action = h->cfg.llm_action != 0; out->n_shapes = h->n_shapes;
-    return SWARM_OK;
-}
-
-int swarm_internal_metrics_step(swarm_env_t *h, double *out)
-{
-    if (!h || !out) return SWARM_ERR_INVALID;
-    if (!h->have_cells || !h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_rollout_eval: cells / state not set");
-    DeviceGuard g(h->device);
-    const int stride = (36 * h->cfg.n_agents + 4 + 15) & ~15;             // per env: xy[N], val[N], tmp[N], cnt[N + 1]
-    // one wave per env needs about two waves per SIMD (4 SIMDs per CU) to hide its latencies; below that, four waves per env
-    if ((long long)h->cfg.n_env >= 8LL * h->n_cu)
-        hipLaunchKernelGGL(k_metrics_step<1>, dim3((unsigned)((h->cfg.n_env + kMsEnvs - 1) / kMsEnvs)), dim3(64 * kMsEnvs),
-                           (size_t)stride * kMsEnvs, h->stream, h->kp, out, stride);
-    else
-        hipLaunchKernelGGL(k_metrics_step<kMsEnvs>, dim3((unsigned)h->cfg.n_env), dim3(64 * kMsEnvs), (size_t)stride, h->stream,
-                           h->kp, out, stride);
-    HIP_TRY(h, hipGetLastError());
-    return SWARM_OK;
-}
-
-int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_expert_view *out)
-{
-    if (!h || !out) return SWARM_ERR_INVALID;
-    if (lists) {
-        if (!h->d_act64) HIP_TRY(h, hipMalloc((void **)&h->d_act64, (size_t)h->cfg.n_env * h->cfg.n_agents * sizeof(double2)));
-        const int rc = export_pass(h, true, true);
-        if (rc != SWARM_OK) return rc;
-    }
-    out->p = h->d_p; out->dp = h->d_dp; out->cells = h->d_cells;
-    out->near_cell = h->d_near; out->in_flag = h->d_inflag; out->exp_sensed = h->d_exp_sensed;
-    out->act_next = h->d_act_next; out->act64 = h->d_act64;
-    out->d_sen = h->kp.d_sen; out->r_avoid = h->kp.r_avoid;
-    out->n_env = h->cfg.n_env; out->n_agents = h->cfg.n_agents; out->g_max = h->kp.g_max; out->ng_max = h->kp.ng_max;
-    return SWARM_OK;
-}
+}  // namespace swarm_internal
 
 extern "C" {
 
-int swarm_abi_version(void) { return SWARM_ABI_VERSION; }
-
-void swarm_default_config(swarm_config_t *c)
-{
-    if (!c) return;
-    std::memset(c, 0, sizeof(*c));
-    c->n_env = 1; c->n_agents = 30; c->n_cells_max = 576;
-    c->topo_nei_max = 6; c->num_obs_grid_max = 80; c->num_occupied_grid_max = 200;
-    c->is_boundary = 1; c->with_self_state = 1; c->with_prior = 1;
-    c->obs_dtype = SWARM_F32; c->device = -1;
-    c->d_sen = 0.4; c->r_avoid = 0.15; c->size_a = 0.035;
-    c->k_ball = 30; c->k_wall = 100; c->c_wall = 5; c->vel_max = 0.8; c->dt = 0.1;
-    c->boundary[0] = -2.4; c->boundary[1] = 2.4; c->boundary[2] = 2.4; c->boundary[3] = -2.4;
-    c->prior_gain[0] = 2.0; c->prior_gain[1] = 3.0; c->prior_gain[2] = 2.0;      // AssemblyEnv.cpp:1128-1132
-    c->llm_repulsion = 1.0; c->llm_action = 0;                                   // assembly.py:895
-}
-
-const char *swarm_last_error(const swarm_env_t *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
-
-int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
-{
-    if (!cfg || !out) return fail(nullptr, SWARM_ERR_INVALID, "swarm_create: null argument");
-    *out = nullptr;
-    if (cfg->n_env < 1) return fail(nullptr, SWARM_ERR_INVALID, "n_env must be >= 1");
-    if (cfg->n_agents < 1 || cfg->n_agents > 256) return fail(nullptr, SWARM_ERR_INVALID, "n_agents must be in [1, 256]");
-    if (cfg->n_cells_max < 1 || cfg->n_cells_max > 32767) return fail(nullptr, SWARM_ERR_INVALID, "n_cells_max must be in [1, 32767]");
-    if (cfg->topo_nei_max < 1 || cfg->topo_nei_max > kTopoMax) return fail(nullptr, SWARM_ERR_INVALID, "topo_nei_max must be in [1, 6]");
-    if (cfg->num_obs_grid_max < 2 || cfg->num_obs_grid_max > 4096) return fail(nullptr, SWARM_ERR_INVALID, "num_obs_grid_max must be in [2, 4096]");
-    if (cfg->num_occupied_grid_max < 2) return fail(nullptr, SWARM_ERR_INVALID, "num_occupied_grid_max must be >= 2");
-    if (cfg->obs_dtype != SWARM_F32 && cfg->obs_dtype != SWARM_F64 && cfg->obs_dtype != SWARM_BF16) return fail(nullptr, SWARM_ERR_INVALID, "obs_dtype must be SWARM_F32, SWARM_F64 or SWARM_BF16");
-    if (!(cfg->d_sen > 0) || !(cfg->r_avoid > 0) || !(cfg->dt > 0)) return fail(nullptr, SWARM_ERR_INVALID, "d_sen, r_avoid, dt must be positive");
-
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail(nullptr, SWARM_ERR_HIP, std::string("no HIP device available (") + hipGetErrorString(e) + "); this library has no CPU path");
-    int dev = cfg->device;
-    if (dev < 0) { if (hipGetDevice(&dev) != hipSuccess) dev = 0; }
-    if (dev >= ndev) return fail(nullptr, SWARM_ERR_INVALID, "device ordinal out of range");
-
-    swarm_env *h = new (std::nothrow) swarm_env();
-    if (!h) return fail(nullptr, SWARM_ERR_INVALID, "out of host memory");
-    h->cfg = *cfg; h->device = dev; h->stream = nullptr; h->ev0 = h->ev1 = nullptr;
-    h->have_cells = h->have_state = h->observed = false;
-    for (int &a : h->attr_smem) a = -1;
-    h->half = false; h->n_cu = 256;
-    h->d_p = h->d_dp = h->d_cells = h->d_cin = nullptr; h->d_cells_xy = nullptr;
-    h->d_lat = nullptr;
-    h->n_shapes = 0; h->d_shape_cells = h->d_shape_l = h->d_shape_cin = nullptr; h->d_shape_ng = nullptr; h->d_shape_lat = nullptr; h->d_shape_idx = nullptr;
-    h->shapes_lattice = false; h->shapes_rmax = h->shapes_cmax = 0.0f; h->shapes_ncols = 0;
-    h->lat_ok.assign((size_t)cfg->n_env, 0);
-    h->lat_R.assign((size_t)cfg->n_env, 0.0f); h->lat_Rc.assign((size_t)cfg->n_env, 0.0f);
-    h->lat_ncols.assign((size_t)cfg->n_env, 0);
-    h->lattice_disabled = (cfg->debug_flags & 2) != 0;
-    h->d_nei = h->d_near = h->d_inflag = h->d_ng = h->d_exp_sensed = h->d_exp_occ = nullptr; h->d_sf = nullptr; h->d_prior = nullptr;
-    h->d_act_next = nullptr; h->d_act64 = nullptr;
-    h->d_io_obs = h->d_io_prior = nullptr; h->d_io_rew = nullptr; h->d_io_done = nullptr;
-    h->d_io_block = nullptr; h->h_io_block[0] = h->h_io_block[1] = nullptr; h->h_io_action = h->d_io_action = nullptr; h->io_block_bytes = 0;
-    h->cells_set.assign((size_t)cfg->n_env, 0);
-    h->npad = npad_for(cfg->n_agents);
-
-    KP &k = h->kp;
-    std::memset(&k, 0, sizeof(k));
-    k.n_env = cfg->n_env; k.n_a = cfg->n_agents; k.ng_max = cfg->n_cells_max;
-    k.topo = cfg->topo_nei_max; k.g_max = cfg->num_obs_grid_max; k.occ_max = cfg->num_occupied_grid_max;
-    k.with_self = cfg->with_self_state ? 1 : 0;
-    k.obs_dim = 2 * 2 * (k.topo + 1 + k.with_self) + 2 * k.g_max;               // ENV:801
-    k.boundary = cfg->is_boundary ? 1 : 0; k.periodic = cfg->is_boundary ? 0 : 1;  // ENV:99-103
-    k.with_prior = cfg->with_prior ? 1 : 0;
-    k.pk_att = cfg->prior_gain[0]; k.pk_rep = cfg->prior_gain[1]; k.pk_ali = cfg->prior_gain[2];
-    k.pk_llm = cfg->llm_repulsion; k.llm = cfg->llm_action ? 1 : 0;
-    k.d_sen = cfg->d_sen; k.r_avoid = cfg->r_avoid; k.size_a = cfg->size_a;
-    k.size2 = cfg->size_a + cfg->size_a;                                         // ENV:785-786
-    k.k_ball = cfg->k_ball; k.k_wall = cfg->k_wall; k.c_wall = cfg->c_wall; k.vel_max = cfg->vel_max; k.dt = cfg->dt;
-    k.bx0 = cfg->boundary[0]; k.by1 = cfg->boundary[1]; k.bx2 = cfg->boundary[2]; k.by3 = cfg->boundary[3];
-    k.w_half = (k.bx2 - k.bx0) / 2.0; k.h_half = (k.by1 - k.by3) / 2.0;         // CPP:70-71
-    k.c_sen = cut_lt(k.d_sen);                            // norm < d_sen              CPP:658,902
-    k.c_near = cut_lt(k.d_sen + k.r_avoid / 2.0);         // norm < d_sen + r_avoid/2  CPP:161
-    k.c_occ = cut_le(k.r_avoid / 2.0);                    // !(norm > r_avoid/2)       CPP:185
-    k.c_avoid = cut_lt(k.r_avoid);                        // r_avoid > norm            CPP:482
-    k.c_ball = cut_lt(k.size2);                           // d_center - sizes < 0      ENV:450-451
-    k.c_close2 = std::fmin(k.c_sen, (3.0 * k.r_avoid) * (3.0 * k.r_avoid));
-    k.c_close = std::fmin(k.c_sen, (1.9 * k.r_avoid) * (1.9 * k.r_avoid));   // 1.9: fewest insertion trips on the 64-agent workload (measured)
-    {   // fp32 pre-filter bands.  With |coordinates| <= S, a float-converted coordinate is off by <= 2^-24 S and
-        // their float difference by another 2^-24 S at most: dr = 4 * 2^-24 * S bounds each component of the fp32
-        // relative position (1.33x margin).  Then |d2_32 - d2_64| <= 2 sqrt(2) |r| dr + O(2^-23 d2) <= 3 sqrt(d2) dr + 2^-21 d2.
-        double S = 0.0;
-        for (int q = 0; q < 4; ++q) S = std::fmax(S, std::fabs(cfg->boundary[q]));
-        S = 1.5 * S + 1.0;
-        const double dr = 4.0 * std::ldexp(1.0, -24) * S;
-        auto band = [&](double c) { return 3.0 * std::sqrt(c) * dr + std::ldexp(1.0, -21) * c + 1e-12; };
-        auto f_below = [](double v) { float f = (float)v; while ((double)f > v) f = std::nextafterf(f, -INFINITY); return f; };
-        auto f_above = [](double v) { float f = (float)v; while ((double)f < v) f = std::nextafterf(f, INFINITY); return f; };
-        k.csen_lo = f_below(k.c_sen - band(k.c_sen)); k.csen_hi = f_above(k.c_sen + band(k.c_sen));
-        k.cocc_lo = f_below(k.c_occ - band(k.c_occ)); k.cocc_hi = f_above(k.c_occ + band(k.c_occ));
-        k.coord_lim = (float)S;
-        k.min_tol_a = (float)(2.0 * 3.0 * dr); k.min_tol_b = (float)(2.0 * std::ldexp(1.0, -21));
-        {   // error bound of the fp32 reward sums near the 0.05 threshold, v = |sum psi r| / sum psi over n list entries:
-            // each fp32 component of r is off by dx (two float conversions + the subtraction), u = |r|^2 / d_sen^2 by
-            // du <= 2 sqrt(2) dx / d_sen, psi by |dpsi/du| du + the polynomial's 4e-7 with |dpsi/du| <= pi^2 / 4; hence
-            // |dv| <= n (dpsi d_sen + dx + 0.05 dpsi) / den + (fp32 accumulation, division, sqrt: < 3e-6).  1.3x margin.
-            const double dx = 2.1 * std::ldexp(1.0, -24) * S;
-            const double dpsi = 2.4675 * (2.0 * std::sqrt(2.0) * dx / k.d_sen) + 4e-7;
-            k.rew_ga = (float)(1.3 * (dpsi * k.d_sen + dx + 0.0505 * dpsi));
-            k.rew_gb = 4e-6f;
-        }
-        k.rew_thr_k = (float)(0.05 / k.d_sen);
-        k.rew_ga_lat = k.rew_gb_lat = 0.0f;
-        k.force_exact = (cfg->debug_flags & 1) ? 1 : 0;
-        {   // unsigned division by D = 2 (G-1) (Granlund-Montgomery round-up method, exact for every 32-bit x)
-            const unsigned D = 2u * (unsigned)(k.g_max - 1);
-            int l = 0;
-            while ((1ull << l) < D) ++l;
-            k.cap_magic = (unsigned)((((1ull << l) - D) << 32) / D + 1);
-            k.cap_shift = l - 1;
-            // numerators stay below 2^32: 2 (G-1) (n_cells_max-1) + (G-1)
-            const unsigned long long xmax = 2ull * (k.g_max - 1) * (unsigned long long)k.ng_max + k.g_max;
-            k.cap_int = (((k.g_max - 1) & 1) == 1 && xmax < (1ull << 32) && l >= 1) ? 1 : 0;
-        }
-        k.dbg_phase = (cfg->debug_flags >> 8) & 0xF;
-        k.dbg_extra = (cfg->debug_flags >> 12) & 0xF;
-    }
-    layout(k, h->npad, false);
-
-    DeviceGuard g(dev);
-    if (!g.ok) { delete h; return fail(nullptr, SWARM_ERR_HIP, "hipSetDevice failed"); }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { delete h; return fail(nullptr, SWARM_ERR_HIP, "hipGetDeviceProperties failed"); }
-    h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if ((size_t)k.smem_generic > 160 * 1024) {
-        delete h;
-        return fail(nullptr, SWARM_ERR_INVALID, "configuration needs more LDS per workgroup than the device has (reduce n_cells_max / num_obs_grid_max)");
-    }
-    const size_t E = (size_t)cfg->n_env, N = (size_t)cfg->n_agents;
-    hipError_t a = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (a == hipSuccess) a = hipMalloc(p, bytes); };
-    alloc((void **)&h->d_p, E * 2 * N * 8); alloc((void **)&h->d_dp, E * 2 * N * 8);
-    alloc((void **)&h->d_cells, E * 2 * (size_t)k.ng_max * 8); alloc((void **)&h->d_cin, E * 8);
-    alloc((void **)&h->d_cells_xy, E * (size_t)k.ng_max * 16);
-    alloc((void **)&h->d_ng, E * 4); alloc((void **)&h->d_shape_idx, E * 4);
-    alloc((void **)&h->d_prior, E * N * 16);
-    if (cfg->llm_action) alloc((void **)&h->d_act_next, E * N * 16);
-    alloc((void **)&h->d_lat, E * sizeof(LatEnv));
-    alloc((void **)&h->d_nei, E * N * (size_t)k.topo * 4); alloc((void **)&h->d_near, E * N * 4);
-    alloc((void **)&h->d_inflag, E * N * 4); alloc((void **)&h->d_sf, E * N * 16);
-    if (a == hipSuccess) a = hipMemset(h->d_ng, 0, E * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_prior, 0, E * N * 16);
-    if (a == hipSuccess && h->d_act_next) a = hipMemset(h->d_act_next, 0, E * N * 16);
-    if (a == hipSuccess) a = hipMemset(h->d_shape_idx, 0xFF, E * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_nei, 0xFF, E * N * (size_t)k.topo * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_near, 0, E * N * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_inflag, 0, E * N * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_sf, 0, E * N * 16);
-    if (a == hipSuccess) a = hipMemset(h->d_cells, 0, E * 2 * (size_t)k.ng_max * 8);
-    if (a == hipSuccess) a = hipMemset(h->d_cells_xy, 0, E * (size_t)k.ng_max * 16);
-    if (a == hipSuccess) a = hipEventCreate(&h->ev0);
-    if (a == hipSuccess) a = hipEventCreate(&h->ev1);
-    if (a != hipSuccess) {
-        std::string m = std::string("device allocation failed: ") + hipGetErrorString(a);
-        swarm_destroy(h);
-        return fail(nullptr, SWARM_ERR_HIP, m);
-    }
-    k.p = h->d_p; k.dp = h->d_dp; k.nei = h->d_nei; k.near_cell = h->d_near; k.in_flag = h->d_inflag; k.sf_next = h->d_sf;
-    k.prior_next = h->d_prior; k.act_next = h->d_act_next;
-    k.cells = h->d_cells; k.cells_xy = h->d_cells_xy; k.n_g = h->d_ng; k.c_in = h->d_cin;
-    k.lat = h->d_lat; k.lattice = 0; k.lat_rw = k.lat_cw = 0; k.lat_nrs = k.lat_nrc = 0; k.lat_n32 = 0;
-    k.c_near_hi = k.c_near * (1.0 + 1e-9);
-    *out = h;
-    return SWARM_OK;
-}
-
-int swarm_destroy(swarm_env_t *h)
-{
-    if (!h) return SWARM_OK;
-    {
-        DeviceGuard g(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(h->d_p); (void)hipFree(h->d_dp); (void)hipFree(h->d_cells); (void)hipFree(h->d_cin); (void)hipFree(h->d_cells_xy);
-        (void)hipFree(h->d_ng); (void)hipFree(h->d_nei); (void)hipFree(h->d_near); (void)hipFree(h->d_inflag); (void)hipFree(h->d_sf);
-        (void)hipFree(h->d_exp_sensed); (void)hipFree(h->d_exp_occ); (void)hipFree(h->d_lat); (void)hipFree(h->d_shape_idx); (void)hipFree(h->d_prior);
-        (void)hipFree(h->d_shape_cells); (void)hipFree(h->d_shape_l); (void)hipFree(h->d_shape_cin); (void)hipFree(h->d_shape_ng); (void)hipFree(h->d_shape_lat);
-        (void)hipFree(h->d_act_next); (void)hipFree(h->d_act64); (void)hipFree(h->d_io_obs); (void)hipFree(h->d_io_prior); (void)hipFree(h->d_io_rew); (void)hipFree(h->d_io_done);
-        (void)hipFree(h->d_io_block); (void)hipFree(h->d_io_action);
-        if (h->h_io_block[0]) (void)hipHostFree(h->h_io_block[0]);
-        if (h->h_io_block[1]) (void)hipHostFree(h->h_io_block[1]);
-        if (h->h_io_action) (void)hipHostFree(h->h_io_action);
-        if (h->ev0) (void)hipEventDestroy(h->ev0);
-        if (h->ev1) (void)hipEventDestroy(h->ev1);
-    }
-    delete h;
-    return SWARM_OK;
-}
-
-int swarm_set_stream(swarm_env_t *h, void *s)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    h->stream = static_cast<hipStream_t>(s);
-    return SWARM_OK;
-}
-
-int swarm_synchronize(swarm_env_t *h)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    DeviceGuard g(h->device);
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SWARM_OK;
-}
-
-int swarm_obs_dim(const swarm_env_t *h) { return h ? h->kp.obs_dim : -1; }
-
-int swarm_set_cells(swarm_env_t *h, int env_begin, int count, const double *cells, const int32_t *n_g, const double *l_cell)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    if (!cells || !n_g || !l_cell) return fail(h, SWARM_ERR_INVALID, "swarm_set_cells: null argument");
-    if (env_begin < 0 || count < 1 || env_begin + count > h->cfg.n_env) return fail(h, SWARM_ERR_INVALID, "swarm_set_cells: env range out of bounds");
-    std::vector<double> cin((size_t)count);
-    for (int k = 0; k < count; ++k) {
-        if (n_g[k] < 1 || n_g[k] > h->cfg.n_cells_max) return fail(h, SWARM_ERR_INVALID, "swarm_set_cells: n_g must be in [1, n_cells_max]");
-        if (!(l_cell[k] > 0)) return fail(h, SWARM_ERR_INVALID, "swarm_set_cells: l_cell must be positive");
-        cin[(size_t)k] = cut_lt(std::sqrt(2) * l_cell[k] / 2);            // CPP:889
-    }
-    DeviceGuard g(h->device);
-    const size_t row = (size_t)2 * h->kp.ng_max;
-    HIP_TRY(h, hipMemcpyAsync(h->d_cells + (size_t)env_begin * row, cells, (size_t)count * row * 8, hipMemcpyDefault, h->stream));
-    {
-        const size_t n = (size_t)count * h->kp.ng_max;
-        hipLaunchKernelGGL(k_interleave, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream,
-                           h->d_cells, h->d_cells_xy, h->kp.ng_max, env_begin, count);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_ng + env_begin, n_g, (size_t)count * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_shape_idx + env_begin, 0xFF, (size_t)count * 4, h->stream));   // no longer a shape of the set
-    HIP_TRY(h, hipMemcpyAsync(h->d_cin + env_begin, cin.data(), (size_t)count * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));           // cin is a host temporary
-    {   // lattice detection on a host copy of what was uploaded (`cells` may be a device pointer)
-        std::vector<double> hc((size_t)count * row);
-        HIP_TRY(h, hipMemcpy(hc.data(), h->d_cells + (size_t)env_begin * row, (size_t)count * row * 8, hipMemcpyDeviceToHost));
-        std::vector<LatEnv> lat((size_t)count);
-        for (int k = 0; k < count; ++k) {
-            const double *gx = hc.data() + (size_t)k * row, *gy = gx + h->kp.ng_max;
-            LatEnv &L = lat[(size_t)k];
-            std::memset(&L, 0, sizeof(L));
-            const bool ok = !h->lattice_disabled && detect_lattice(gx, gy, n_g[k], L);
-            h->lat_ok[(size_t)(env_begin + k)] = ok ? 1 : 0;
-            if (ok) {
-                const double l = L.R;
-                L.R = (float)(h->kp.d_sen / l); L.Rc = (float)((h->kp.r_avoid / 2.0) / l);
-                h->lat_R[(size_t)(env_begin + k)] = L.R; h->lat_Rc[(size_t)(env_begin + k)] = L.Rc;
-                h->lat_ncols[(size_t)(env_begin + k)] = L.ncols;
-            }
-        }
-        HIP_TRY(h, hipMemcpy(h->d_lat + env_begin, lat.data(), (size_t)count * sizeof(LatEnv), hipMemcpyHostToDevice));
-        bool all = true; float rmax = 0.0f, cmax = 0.0f; int ncmax = 0;
-        for (int e2 = 0; e2 < h->cfg.n_env; ++e2) {
-            if (!h->lat_ok[(size_t)e2]) { all = false; break; }
-            rmax = std::max(rmax, h->lat_R[(size_t)e2]); cmax = std::max(cmax, h->lat_Rc[(size_t)e2]);
-            ncmax = std::max(ncmax, h->lat_ncols[(size_t)e2]);
-        }
-        set_lattice_mode(h, all, rmax, cmax, ncmax);
-    }
-    for (int k = 0; k < count; ++k) h->cells_set[(size_t)(env_begin + k)] = 1;
-    h->have_cells = true;
-    for (char c : h->cells_set) if (!c) { h->have_cells = false; break; }
-    h->observed = false;
-    return SWARM_OK;
-}
-
-int swarm_set_shapes(swarm_env_t *h, int n_shapes, const double *shape_cells, const int32_t *n_g, const double *l_cell)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    if (n_shapes < 1 || !shape_cells || !n_g || !l_cell) return fail(h, SWARM_ERR_INVALID, "swarm_set_shapes: bad argument");
-    const size_t row = (size_t)2 * h->kp.ng_max;
-    std::vector<double> cin((size_t)n_shapes);
-    std::vector<LatEnv> lat((size_t)n_shapes);
-    std::vector<char> s_ok((size_t)n_shapes, 0);
-    std::vector<float> s_R((size_t)n_shapes, 0.0f), s_Rc((size_t)n_shapes, 0.0f);
-    std::vector<int> s_nc((size_t)n_shapes, 0);
-    bool all = true; float rmax = 0.0f, cmax = 0.0f; int ncmax = 0;
-    for (int k = 0; k < n_shapes; ++k) {
-        if (n_g[k] < 1 || n_g[k] > h->cfg.n_cells_max) return fail(h, SWARM_ERR_INVALID, "swarm_set_shapes: n_g must be in [1, n_cells_max]");
-        if (!(l_cell[k] > 0)) return fail(h, SWARM_ERR_INVALID, "swarm_set_shapes: l_cell must be positive");
-        cin[(size_t)k] = cut_lt(std::sqrt(2) * l_cell[k] / 2);
-        LatEnv &L = lat[(size_t)k];
-        std::memset(&L, 0, sizeof(L));
-        const double *gx = shape_cells + (size_t)k * row, *gy = gx + h->kp.ng_max;
-        if (!h->lattice_disabled && detect_lattice(gx, gy, n_g[k], L)) {
-            const double l = L.R;
-            L.R = (float)(h->kp.d_sen / l); L.Rc = (float)((h->kp.r_avoid / 2.0) / l);
-            rmax = std::max(rmax, L.R); cmax = std::max(cmax, L.Rc); ncmax = std::max(ncmax, L.ncols);
-            s_ok[(size_t)k] = 1; s_R[(size_t)k] = L.R; s_Rc[(size_t)k] = L.Rc; s_nc[(size_t)k] = L.ncols;
-        } else { std::memset(&L, 0, sizeof(L)); all = false; }
-    }
-    DeviceGuard g(h->device);
-    (void)hipFree(h->d_shape_cells); (void)hipFree(h->d_shape_l); (void)hipFree(h->d_shape_cin); (void)hipFree(h->d_shape_ng); (void)hipFree(h->d_shape_lat);
-    h->d_shape_cells = h->d_shape_l = h->d_shape_cin = nullptr; h->d_shape_ng = nullptr; h->d_shape_lat = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_cells, (size_t)n_shapes * row * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_l, (size_t)n_shapes * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_cin, (size_t)n_shapes * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_ng, (size_t)n_shapes * 4));
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_lat, (size_t)n_shapes * sizeof(LatEnv)));
-    HIP_TRY(h, hipMemcpy(h->d_shape_cells, shape_cells, (size_t)n_shapes * row * 8, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_shape_l, l_cell, (size_t)n_shapes * 8, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_shape_cin, cin.data(), (size_t)n_shapes * 8, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_shape_ng, n_g, (size_t)n_shapes * 4, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_shape_lat, lat.data(), (size_t)n_shapes * sizeof(LatEnv), hipMemcpyHostToDevice));
-    h->n_shapes = n_shapes; h->shapes_lattice = all; h->shapes_rmax = rmax; h->shapes_cmax = cmax; h->shapes_ncols = ncmax;
-    h->shape_lat_ok = s_ok; h->shape_R = s_R; h->shape_Rc = s_Rc; h->shape_ncols = s_nc;
-    return SWARM_OK;
-}
-
-int swarm_reset(swarm_env_t *h, uint64_t seed, uint64_t episode, int64_t env_offset, void *obs)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    if (h->n_shapes < 1) return fail(h, SWARM_ERR_STATE, "swarm_reset: no shape set (swarm_set_shapes)");
-    DeviceGuard g(h->device);
-    ShapeSet S;
-    S.n_shapes = h->n_shapes; S.cells = h->d_shape_cells; S.n_g = h->d_shape_ng; S.l_cell = h->d_shape_l;
-    S.c_in = h->d_shape_cin; S.lat = h->d_shape_lat;
-    hipLaunchKernelGGL(k_reset, dim3(h->cfg.n_env), dim3(256), 0, h->stream, h->kp, S, (unsigned long long)seed,
-                       (unsigned long long)episode, (long long)env_offset, h->d_cells, h->d_ng, h->d_cin, h->d_lat, h->d_shape_idx);
-    HIP_TRY(h, hipGetLastError());
-    {
-        const size_t n = (size_t)h->cfg.n_env * h->kp.ng_max;
-        hipLaunchKernelGGL(k_interleave, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream,
-                           h->d_cells, h->d_cells_xy, h->kp.ng_max, 0, h->cfg.n_env);
-        HIP_TRY(h, hipGetLastError());
-    }
-    std::fill(h->cells_set.begin(), h->cells_set.end(), 1);
-    std::fill(h->lat_ok.begin(), h->lat_ok.end(), h->shapes_lattice ? 1 : 0);
-    // per-env bounds for a later partial swarm_set_cells: the shape set's maxima are valid for every env
-    std::fill(h->lat_R.begin(), h->lat_R.end(), h->shapes_rmax); std::fill(h->lat_Rc.begin(), h->lat_Rc.end(), h->shapes_cmax);
-    std::fill(h->lat_ncols.begin(), h->lat_ncols.end(), h->shapes_ncols);
-    h->have_cells = h->have_state = true;
-    set_lattice_mode(h, h->shapes_lattice, h->shapes_rmax, h->shapes_cmax, h->shapes_ncols);
-    h->observed = false;
-    return swarm_observe(h, obs);
-}
-
-int swarm_select_shape(swarm_env_t *h, int32_t shape_index, void *obs)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    if (h->n_shapes < 1) return fail(h, SWARM_ERR_STATE, "swarm_select_shape: no shape set (swarm_set_shapes)");
-    if (shape_index < 0 || shape_index >= h->n_shapes) return fail(h, SWARM_ERR_INVALID, "swarm_select_shape: shape_index outside [0, n_shapes)");
-    if (!h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_select_shape: state not set (swarm_set_state / swarm_reset)");
-    DeviceGuard g(h->device);
-    ShapeSet S;
-    S.n_shapes = h->n_shapes; S.cells = h->d_shape_cells; S.n_g = h->d_shape_ng; S.l_cell = h->d_shape_l;
-    S.c_in = h->d_shape_cin; S.lat = h->d_shape_lat;
-    hipLaunchKernelGGL(k_select_shape, dim3((unsigned)((h->kp.ng_max + 255) / 256), (unsigned)h->cfg.n_env), dim3(256), 0, h->stream, S,
-                       (int)shape_index, h->kp.ng_max, h->d_cells, h->d_cells_xy, h->d_ng, h->d_cin, h->d_lat, h->d_shape_idx);
-    HIP_TRY(h, hipGetLastError());
-    // the host bookkeeping swarm_set_cells would leave for E copies of this shape
-    const size_t s = (size_t)shape_index;
-    const bool ok = h->shape_lat_ok[s] != 0;
-    std::fill(h->cells_set.begin(), h->cells_set.end(), 1);
-    std::fill(h->lat_ok.begin(), h->lat_ok.end(), ok ? 1 : 0);
-    if (ok) {
-        std::fill(h->lat_R.begin(), h->lat_R.end(), h->shape_R[s]); std::fill(h->lat_Rc.begin(), h->lat_Rc.end(), h->shape_Rc[s]);
-        std::fill(h->lat_ncols.begin(), h->lat_ncols.end(), h->shape_ncols[s]);
-    }
-    h->have_cells = true;
-    set_lattice_mode(h, ok, ok ? h->shape_R[s] : 0.0f, ok ? h->shape_Rc[s] : 0.0f, ok ? h->shape_ncols[s] : 0);
-    h->observed = false;
-    return swarm_observe(h, obs);
-}
-
-int swarm_set_state(swarm_env_t *h, const double *p, const double *dp)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    if (!p || !dp) return fail(h, SWARM_ERR_INVALID, "swarm_set_state: null argument");
-    DeviceGuard g(h->device);
-    const size_t bytes = (size_t)h->cfg.n_env * 2 * h->cfg.n_agents * 8;
-    HIP_TRY(h, hipMemcpyAsync(h->d_p, p, bytes, hipMemcpyDefault, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_dp, dp, bytes, hipMemcpyDefault, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->have_state = true;
-    h->observed = false;
-    return SWARM_OK;
-}
-
-int swarm_metrics(swarm_env_t *h, double *out)
-{
-    if (!h || !out) return SWARM_ERR_INVALID;
-    if (!h->have_cells || !h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_metrics: cells / state not set");
-    DeviceGuard g(h->device);
-    const size_t smem = (size_t)h->cfg.n_agents * (4 * 8 + 4) + 16;
-    hipLaunchKernelGGL(k_metrics, dim3(h->cfg.n_env), dim3(256), smem, h->stream, h->kp, out);
-    HIP_TRY(h, hipGetLastError());
-    return SWARM_OK;
-}
-
-int swarm_get_cells(swarm_env_t *h, double *cells, int32_t *n_g)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    DeviceGuard g(h->device);
-    if (cells) HIP_TRY(h, hipMemcpyAsync(cells, h->d_cells, (size_t)h->cfg.n_env * 2 * h->kp.ng_max * 8, hipMemcpyDefault, h->stream));
-    if (n_g) HIP_TRY(h, hipMemcpyAsync(n_g, h->d_ng, (size_t)h->cfg.n_env * 4, hipMemcpyDefault, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SWARM_OK;
-}
-
-int swarm_get_shape_index(swarm_env_t *h, int32_t *shape_index)
-{
-    if (!h || !shape_index) return SWARM_ERR_INVALID;
-    DeviceGuard g(h->device);
-    HIP_TRY(h, hipMemcpyAsync(shape_index, h->d_shape_idx, (size_t)h->cfg.n_env * 4, hipMemcpyDefault, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SWARM_OK;
-}
-
-int swarm_get_state(swarm_env_t *h, double *p, double *dp)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    DeviceGuard g(h->device);
-    const size_t bytes = (size_t)h->cfg.n_env * 2 * h->cfg.n_agents * 8;
-    if (p) HIP_TRY(h, hipMemcpyAsync(p, h->d_p, bytes, hipMemcpyDefault, h->stream));
-    if (dp) HIP_TRY(h, hipMemcpyAsync(dp, h->d_dp, bytes, hipMemcpyDefault, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SWARM_OK;
-}
-
-int swarm_observe(swarm_env_t *h, void *obs)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    if (!h->have_cells) return fail(h, SWARM_ERR_STATE, "swarm_observe: target cells not set for every env (swarm_set_cells)");
-    if (!h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_observe: state not set (swarm_set_state)");
-    DeviceGuard g(h->device);
-    int rc = launch(h, false, nullptr, 0, obs, nullptr, nullptr, nullptr);
-    if (rc == SWARM_OK) h->observed = true;
-    return rc;
-}
-
-int swarm_step(swarm_env_t *h, const void *action, int action_dtype, void *obs, float *reward, uint8_t *done, void *a_prior)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    if (!action) {
-        // agent_strategy == 'llm' (assembly.py:525-529): the action is the Python twin of the prior policy, which the
-        // previous pass evaluated on this very state
-        if (!h->cfg.llm_action) return fail(h, SWARM_ERR_INVALID, "swarm_step: null action (only a handle created with llm_action may pass NULL)");
-        action = h->d_act_next; action_dtype = SWARM_F64;
-    }
-    if (action_dtype != SWARM_F32 && action_dtype != SWARM_F64) return fail(h, SWARM_ERR_INVALID, "swarm_step: bad action_dtype");
-    if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_step: call swarm_observe after setting cells/state (the reference's reset() ends with _get_obs())");
-    DeviceGuard g(h->device);
-    return launch(h, true, action, action_dtype == SWARM_F64, obs, reward, done, a_prior);
-}
-
-namespace {
-int io_alloc(swarm_env *h)
-{
-    if (h->d_io_block) return SWARM_OK;
-    const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents, D = (size_t)h->kp.obs_dim;
-    const size_t so = h->cfg.obs_dtype == SWARM_F64 ? 8 : h->cfg.obs_dtype == SWARM_BF16 ? 2 : 4;
-    h->io_block_bytes = (D * EN + 2 * EN + EN) * 8 + ((EN + 15) & ~size_t(15));
-    HIP_TRY(h, hipMalloc(&h->d_io_obs, EN * D * so));
-    HIP_TRY(h, hipMalloc(&h->d_io_prior, EN * 2 * so));
-    HIP_TRY(h, hipMalloc((void **)&h->d_io_rew, EN * 4));
-    HIP_TRY(h, hipMalloc((void **)&h->d_io_done, EN));
-    HIP_TRY(h, hipMalloc((void **)&h->d_io_block, h->io_block_bytes));
-    HIP_TRY(h, hipMalloc(&h->d_io_action, EN * 16));
-    HIP_TRY(h, hipHostMalloc((void **)&h->h_io_block[0], h->io_block_bytes, hipHostMallocDefault));
-    HIP_TRY(h, hipHostMalloc((void **)&h->h_io_block[1], h->io_block_bytes, hipHostMallocDefault));
-    HIP_TRY(h, hipHostMalloc(&h->h_io_action, EN * 16, hipHostMallocDefault));
-    HIP_TRY(h, hipMemset(h->d_io_block, 0, h->io_block_bytes));
-    std::memset(h->h_io_block[0], 0, h->io_block_bytes); std::memset(h->h_io_block[1], 0, h->io_block_bytes);
-    return SWARM_OK;
-}
-
-int io_export(swarm_env *h, int slot, bool stepped)
-{
-    const long long EN = (long long)h->cfg.n_env * h->cfg.n_agents;
-    const int D = h->kp.obs_dim, wp = (stepped && h->kp.with_prior) ? 1 : 0;
-    const unsigned grid = (unsigned)((EN + 63) / 64);
-    const float *rew = stepped ? h->d_io_rew : nullptr;
-    const uint8_t *dn = stepped ? h->d_io_done : nullptr;
-    if (h->cfg.obs_dtype == SWARM_F64)
-        hipLaunchKernelGGL(k_export<double>, dim3(grid), dim3(256), 0, h->stream, (const double *)h->d_io_obs, rew, dn, (const double *)h->d_io_prior, h->d_io_block, D, EN, wp);
-    else if (h->cfg.obs_dtype == SWARM_BF16)
-        hipLaunchKernelGGL(k_export<__bf16>, dim3(grid), dim3(256), 0, h->stream, (const __bf16 *)h->d_io_obs, rew, dn, (const __bf16 *)h->d_io_prior, h->d_io_block, D, EN, wp);
-    else
-        hipLaunchKernelGGL(k_export<float>, dim3(grid), dim3(256), 0, h->stream, (const float *)h->d_io_obs, rew, dn, (const float *)h->d_io_prior, h->d_io_block, D, EN, wp);
-    HIP_TRY(h, hipGetLastError());
-    // obs only (reset / observe) moves the obs part; a step moves the whole block
-    const size_t bytes = stepped ? h->io_block_bytes : (size_t)D * EN * 8;
-    HIP_TRY(h, hipMemcpyAsync(h->h_io_block[slot], h->d_io_block, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SWARM_OK;
-}
-}  // namespace
-
-int swarm_get_llm_action(swarm_env_t *h, double *action)
-{
-    if (!h || !action) return SWARM_ERR_INVALID;
-    if (!h->d_act_next) return fail(h, SWARM_ERR_STATE, "swarm_get_llm_action: handle was not created with llm_action");
-    if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_get_llm_action: nothing observed yet");
-    DeviceGuard g(h->device);
-    HIP_TRY(h, hipMemcpyAsync(action, h->d_act_next, (size_t)h->cfg.n_env * h->cfg.n_agents * 16, hipMemcpyDefault, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SWARM_OK;
-}
-
-int swarm_host_outputs(swarm_env_t *h, int slot, swarm_host_out_t *out)
-{
-    if (!h || !out || slot < 0 || slot > 1) return SWARM_ERR_INVALID;
-    DeviceGuard g(h->device);
-    int rc = io_alloc(h);
-    if (rc != SWARM_OK) return rc;
-    const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents, D = (size_t)h->kp.obs_dim;
-    double *b = h->h_io_block[slot];
-    out->obs = b; out->a_prior = b + D * EN; out->reward = b + D * EN + 2 * EN;
-    out->done = reinterpret_cast<uint8_t *>(b + D * EN + 3 * EN);
-    return SWARM_OK;
-}
-
-int swarm_observe_host(swarm_env_t *h, int slot)
-{
-    if (!h || slot < 0 || slot > 1) return SWARM_ERR_INVALID;
-    DeviceGuard g(h->device);
-    int rc = io_alloc(h);
-    if (rc != SWARM_OK) return rc;
-    rc = swarm_observe(h, h->d_io_obs);
-    if (rc != SWARM_OK) return rc;
-    return io_export(h, slot, false);
-}
-
-int swarm_step_host(swarm_env_t *h, const void *action, int action_dtype, int action_on_device, int slot)
-{
-    if (!h || slot < 0 || slot > 1) return SWARM_ERR_INVALID;
-    if (action && action_dtype != SWARM_F32 && action_dtype != SWARM_F64) return fail(h, SWARM_ERR_INVALID, "swarm_step_host: bad action_dtype");
-    if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_step_host: call swarm_observe(_host) after setting cells/state");
-    DeviceGuard g(h->device);
-    int rc = io_alloc(h);
-    if (rc != SWARM_OK) return rc;
-    const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
-    const void *act = action; int mode = 0;
-    if (!action) {
-        if (!h->cfg.llm_action) return fail(h, SWARM_ERR_INVALID, "swarm_step_host: null action");
-        act = h->d_act_next; mode = 1;                                   // agent-major doubles
-    } else if (action_on_device) {
-        mode = action_dtype == SWARM_F64 ? 1 : 0;                        // [E][N][2] device tensor, as swarm_step
-    } else {
-        // the reference's (2, n_a) host array: through the pinned staging buffer, read component-major by the kernel
-        const size_t bytes = EN * 2 * (action_dtype == SWARM_F64 ? 8 : 4);
-        std::memcpy(h->h_io_action, action, bytes);
-        HIP_TRY(h, hipMemcpyAsync(h->d_io_action, h->h_io_action, bytes, hipMemcpyHostToDevice, h->stream));
-        act = h->d_io_action; mode = 2 | (action_dtype == SWARM_F64 ? 1 : 0);
-    }
-    rc = launch(h, true, act, mode, h->d_io_obs, h->d_io_rew, h->d_io_done, h->kp.with_prior ? h->d_io_prior : nullptr);
-    if (rc != SWARM_OK) return rc;
-    return io_export(h, slot, true);
-}
-
-int swarm_get_indices(swarm_env_t *h, int32_t *neighbor_index, int32_t *in_flags, int32_t *sensed_index, int32_t *occupied_index)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_get_indices: nothing observed yet");
-    DeviceGuard g(h->device);
-    const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
-    const int rc = export_pass(h, sensed_index || occupied_index, false);
-    if (rc != SWARM_OK) return rc;
-    if (sensed_index) HIP_TRY(h, hipMemcpyAsync(sensed_index, h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4, hipMemcpyDefault, h->stream));
-    if (occupied_index) HIP_TRY(h, hipMemcpyAsync(occupied_index, h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4, hipMemcpyDefault, h->stream));
-    if (neighbor_index) HIP_TRY(h, hipMemcpyAsync(neighbor_index, h->d_nei, EN * (size_t)h->kp.topo * 4, hipMemcpyDefault, h->stream));
-    if (in_flags) HIP_TRY(h, hipMemcpyAsync(in_flags, h->d_inflag, EN * 4, hipMemcpyDefault, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SWARM_OK;
-}
-
-int swarm_rule_action(swarm_env_t *h, double *action)
-{
-    if (!h || !action) return SWARM_ERR_INVALID;
-    if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_rule_action: nothing observed yet");
-    if (h->kp.g_max > 128) return fail(h, SWARM_ERR_INVALID, "swarm_rule_action: num_obs_grid_max > 128 not supported");
-    DeviceGuard g(h->device);
-    int rc = export_pass(h, true, true);
-    if (rc != SWARM_OK) return rc;
-    swarm_expert_view v;
-    rc = swarm_internal_expert_view(h, false, &v);
-    if (rc != SWARM_OK) return rc;
-    HIP_TRY(h, swarm_internal_launch_rule(v, action, nullptr, h->stream));       // k_rule (rule_expert.hip)
-    return SWARM_OK;
-}
-
-int swarm_lattice_envs(const swarm_env_t *h)
-{
-    if (!h) return -1;
-    int n = 0;
-    for (char c : h->lat_ok) n += c ? 1 : 0;
-    return n;
-}
-
-double swarm_step_algorithmic_bytes(const swarm_env_t *h)
-{
-    if (!h) return 0.0;
-    // Per agent-step: action 2*4 r, state p/dp 4*8 r + 4*8 w (fp64 here), obs D*sizeof w, reward 4 + done 1 +
-    // prior 2*sizeof w; per env: target cells 2*n_g_max*8 r.  (with this build's dtypes.)
-    const double so = h->cfg.obs_dtype == SWARM_F64 ? 8.0 : h->cfg.obs_dtype == SWARM_BF16 ? 2.0 : 4.0;
-    const double per_agent = 8.0 + 64.0 + h->kp.obs_dim * so + 5.0 + 2.0 * so;
-    return (double)h->cfg.n_env * (h->cfg.n_agents * per_agent + 2.0 * h->kp.ng_max * 8.0);
-}
-
-int swarm_timer_start(swarm_env_t *h)
-{
-    if (!h) return SWARM_ERR_INVALID;
-    DeviceGuard g(h->device);
-    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-    return SWARM_OK;
-}
-
-int swarm_timer_stop(swarm_env_t *h, float *ms)
-{
-    if (!h || !ms) return SWARM_ERR_INVALID;
-    DeviceGuard g(h->device);
-    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-    HIP_TRY(h, hipEventSynchronize(h->ev1));
-    HIP_TRY(h, hipEventElapsedTime(ms, h->ev0, h->ev1));
-    return SWARM_OK;
-}
-
 // Diagnostic, host only (no device, no handle): the LDS map of the lattice launches of one instantiation, for the CPU test
-// that holds it in place.  out[0..1] = smem_lat / smem_lat_export as layout() hands them to the launches, out[2] = g_stride,
+// that holds it in place.  out[0..1] = smem_lat / smem_lat_export as env_layout() hands them to the launches, out[2] = g_stride,
 // out[3] = off_orow, out[4..15] = the kernel's compile-time offsets of sp, hdr, srow, pcr, partc, partd, lat, cov, flag, snei,
 // sncf, sidx, out[16..27] = the same regions' run-time offsets in KP (read by the geometries without Geo::CT_MAP),
 // out[28] = Geo::CT_MAP.  Returns 0, or -1 for a geometry that has no instantiation.
@@ -3499,7 +2136,7 @@ int swarm_debug_lds_map(int npad, int half, int g_max, int *out)
     KP k;
     std::memset(&k, 0, sizeof(k));
     k.g_max = g_max; k.ng_max = 32; k.lattice = 1;
-    layout(k, npad, half != 0);
+    env_layout(k, npad, half != 0);
     out[0] = k.smem_lat; out[1] = k.smem_lat_export; out[2] = k.g_stride; out[3] = k.off_orow;
     for_geometry(npad, half != 0, [&](auto g) {
         typedef LatMap<decltype(g)::NPAD_, decltype(g)::HALF_> LM;
@@ -3527,7 +2164,7 @@ int swarm_debug_stamps(swarm_env_t *h, const void *action, int action_dtype, voi
     if (hipMalloc((void **)&d, (size_t)grid * wpb * 24 * sizeof(long long)) != hipSuccess) return -1;
     (void)hipMemset(d, 0, (size_t)grid * wpb * 24 * sizeof(long long));
     h->kp.stamps = d;
-    int rc = launch(h, true, action, action_dtype == SWARM_F64, obs, reward, done, a_prior);
+    int rc = env_launch(h, true, action, action_dtype == SWARM_F64, obs, reward, done, a_prior);
     h->kp.stamps = nullptr;
     if (rc == SWARM_OK && hipMemcpy(out, d, (size_t)grid * wpb * 24 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
     (void)hipFree(d);

@@ -1,5 +1,5 @@
 // Internal interface between the translation units of libswarmenv.so: what the device rollout loop (rollout.hip) needs to
-// know about the two opaque handles, the rule-expert kernel's launcher (rule_expert.hip; called by swarm_env.hip and
+// know about the two opaque handles, the rule-expert kernel's launcher (rule_expert.hip; called by env_api.hip and
 // rollout.hip) and the counter-based hash every in-kernel generator is built from.  Not installed, not exported: the
 // accessors have hidden visibility, so the public ABI (swarm_env.h, swarm_policy.h, swarm_rollout.h) does not change.
 #ifndef SWARM_INTERNAL_H
@@ -90,7 +90,7 @@ SWARM_HIDDEN int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_ex
 SWARM_HIDDEN hipError_t swarm_internal_launch_rule(const swarm_expert_view &v, double *act64, float *act32, hipStream_t st);
 
 // The evaluation loop's per-step metrics launch: out[E][3] (DEVICE), bit for bit what swarm_metrics writes (k_metrics_step in
-// swarm_env.hip).  Enqueued on the handle's stream; no host synchronisation.
+// env_kernels.hip).  Enqueued on the handle's stream; no host synchronisation.
 SWARM_HIDDEN int swarm_internal_metrics_step(swarm_env_t *h, double *out);
 
 struct swarm_policy_info {

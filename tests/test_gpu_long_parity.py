@@ -298,7 +298,7 @@ def test_whole_batch_at_bench_state(oracle, shapes, tag, n_a, n_env, env_offset,
 # Lattice mode switching mid-trajectory
 # ------------------------------------------------------------------------------------------------------------------------
 def _lat_nrs(cells, n_g, d_sen=D_SEN):
-    """set_lattice_mode's window-row count for a batch of lattice cell sets (swarm_env.hip: detect_lattice fits the step as
+    """set_lattice_mode's window-row count for a batch of lattice cell sets (env_api.hip: detect_lattice fits the step as
     the closest pair of consecutive cells, stored as float; swarm_set_cells takes R = d_sen / step; set_lattice_mode takes
     floor(2 (max R + 0.01)) + 1 in float).  The lattice kernel runs while this is <= 15."""
     rmax = np.float32(0)

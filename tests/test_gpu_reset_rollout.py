@@ -186,3 +186,43 @@ def test_eval_metrics_match_wrapper_restatement(shapes, n_a, n_env):
         assert np.array_equal(m[e], ref, equal_nan=True), (e, m[e], ref)
     assert (m[:, 0] > 0).any()
     sb.close()
+
+
+def test_partial_set_cells_after_device_reset():
+    """swarm_set_cells on ONE env after a device reset, where the other envs' lattice records are the shape set's maxima and
+    not their own: an off-lattice cell set demotes the batch to the generic scan, the original cells promote it back, and
+    either way one step equals, bit for bit, the step of a twin handle that never takes the lattice path (debug_flags=2)
+    and was given the same cells and state."""
+    from marl_llm_amd.batched import SwarmBatch
+    from marl_llm_amd.shapes import SHAPE_NAMES, r_avoid_for, synthetic_shape_set
+    two = synthetic_shape_set(SHAPE_NAMES[:2])
+    E, n_a, k = 4, 8, 2
+    ra = r_avoid_for(n_a, two)
+    ng_max = max(np.asarray(g).shape[0] for g in two["grid_coords"])
+    mk = lambda flags: SwarmBatch(n_env=E, n_agents=n_a, n_cells_max=ng_max, r_avoid=ra, obs_dtype=torch.float64, debug_flags=flags)
+    sb, twin = mk(0), mk(2)
+    try:
+        sb.set_shapes(two)
+        sb.reset(seed=31)
+        assert sb.lattice_envs() == E
+        cells, n_g = sb.get_cells()
+        l_cell = np.asarray(two["l_cell"], np.float64)[sb.get_shape_index()]
+        twin.set_cells(cells, n_g, l_cell)
+        twin.set_state(*sb.get_state())
+        assert twin.lattice_envs() == 0
+        jit = cells[k:k + 1].copy()
+        jit[0, :, : n_g[k]] += np.random.default_rng(5).normal(0, 0.004, (2, n_g[k]))
+        gen = torch.Generator(device=sb.device).manual_seed(7)
+        for one, n_lat in ((jit, E - 1), (cells[k:k + 1], E)):
+            for b in (sb, twin):
+                b.set_cells(one, n_g[k:k + 1], l_cell[k:k + 1], env_begin=k)
+                b.observe()
+            assert sb.lattice_envs() == n_lat and twin.lattice_envs() == 0
+            act = torch.rand((E, n_a, 2), device=sb.device, generator=gen) * 2 - 1
+            got, ref = sb.step(act), twin.step(act)
+            for name, a, b in zip(("obs", "reward", "done", "a_prior"), got, ref):
+                assert torch.equal(a, b), (n_lat, name)
+            for name, a, b in zip(("p", "dp"), sb.get_state(), twin.get_state()):
+                assert torch.equal(a, b), (n_lat, name)
+    finally:
+        sb.close(); twin.close()
