@@ -673,9 +673,16 @@ int io_export(swarm_env *h, int slot, bool stepped)
     const float *rew = stepped ? h->d_io_rew : nullptr;
     const uint8_t *dn = stepped ? h->d_io_done : nullptr;
     HIP_LAUNCHED(h, launch_export(h->stream, h->cfg.obs_dtype, h->d_io_obs, rew, dn, h->d_io_prior, h->d_io_block, D, EN, wp));
-    // obs only (reset / observe) moves the obs part; a step moves the whole block
-    const size_t bytes = stepped ? h->io_block_bytes : (size_t)D * EN * 8;
+    // obs only (reset / observe) moves the obs part; a step moves the whole block -- without with_prior in two pieces around
+    // the a_prior part, which k_export did not write: the slot's a_prior array then stays as the caller left it
+    const size_t obs_bytes = (size_t)D * EN * 8, pri_bytes = (size_t)2 * EN * 8;
+    const size_t bytes = !stepped ? obs_bytes : wp ? h->io_block_bytes : obs_bytes;
     HIP_TRY(h, hipMemcpyAsync(h->h_io_block[slot], h->d_io_block, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (stepped && !wp) {
+        const size_t off = obs_bytes + pri_bytes;
+        HIP_TRY(h, hipMemcpyAsync((char *)h->h_io_block[slot] + off, (const char *)h->d_io_block + off, h->io_block_bytes - off,
+                                  hipMemcpyDeviceToHost, h->stream));
+    }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SWARM_OK;
 }

@@ -367,10 +367,11 @@ def numpy_dist_b2b(p, is_periodic=False, w_half=2.4, h_half=2.4, size_a=SIZE_A):
 
 def ref_step(ref, p, dp, a, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN, boundary=BOUNDARY,
              is_boundary=True, with_self=True, *, size_a=SIZE_A, k_ball=K_BALL, k_wall=K_WALL, c_wall=C_WALL,
-             vel_max=VEL_MAX, dt=DT):
+             vel_max=VEL_MAX, dt=DT, topo=TOPO, g_max=G_MAX, occ_max=OCC_MAX):
     """AssemblySwarmEnv.step (assembly.py:487-666; 'input' strategy, 'llm_rl' method) restated with the
     five native calls going to the REAL reference library `ref` (a RefLib).  Inputs are not modified.  The keyword-only
-    constants are the env's attributes of the same names (assembly.py:44-79), defaulting to the reference's values."""
+    constants are the env's attributes of the same names (assembly.py:44-79), defaulting to the reference's values; topo,
+    g_max, occ_max are topo_nei_max, num_obs_grid_max, num_occupied_grid_max (assembly.py:34,128,130)."""
     p = np.array(p, np.float64, order="C"); dp = np.array(dp, np.float64, order="C")
     is_periodic = not is_boundary
     w_half = (boundary[2] - boundary[0]) / 2; h_half = (boundary[1] - boundary[3]) / 2
@@ -391,7 +392,7 @@ def ref_step(ref, p, dp, a, grid, neighbor_index, l_cell, r_avoid, d_sen=D_SEN, 
         p[0, p[0, :] > boundary[2]] -= 2 * w_half
         p[1, p[1, :] < boundary[3]] += 2 * h_half
         p[1, p[1, :] > boundary[1]] -= 2 * h_half
-    o = ref.get_observation(p, dp, grid, l_cell, r_avoid, d_sen, boundary, is_periodic, with_self)
+    o = ref.get_observation(p, dp, grid, l_cell, r_avoid, d_sen, boundary, is_periodic, with_self, topo, g_max, occ_max)
     rew = ref.get_reward(p, grid, o["neighbor_index"], o["in_flags"], o["sensed_index"], r_avoid, d_sen,
                          boundary, is_periodic, o["occupied_index"])
     o.update(p=p, dp=dp, reward=rew, a_prior=a_prior, done=np.zeros((1, p.shape[1]), bool))

@@ -150,22 +150,31 @@ def pad_cells(grids, ng_max):
     return cells, n_g
 
 
-def oracle_run(oracle, cases, acts, r_avoid, d_sen=0.4, boundary=DEFAULT_BOX, periodic=False, prior_gain=(2.0, 3.0, 2.0), **phys):
+def oracle_run(oracle, cases, acts, r_avoid, d_sen=0.4, boundary=DEFAULT_BOX, periodic=False, prior_gain=(2.0, 3.0, 2.0), *,
+               topo=None, g_max=None, occ_max=None, with_self=True, feedback=None, **phys):
     """The oracle's trajectory of every case (p, dp, grid, l_cell) of `cases`: get_observation, then one step per entry of
     `acts` ([E, N, 2] float32 actions; None = the previous step's prior rounded to float32, as a float32 policy would feed it
     back).  Returns (first [E] observation dicts, steps [T][E] oracle.step dicts each with the float32 action it took under
     "act" ([N, 2]), counts) where counts holds what the trajectory reached, from the oracle's own functions: agent-agent
     contacts, contacts with each wall [left, top, right, bottom], velocity components clipped at +-vel_max, absolute wraps
-    at each edge [left, top, right, bottom] and neighbour-list entries that exist only through the periodic wrap."""
+    at each edge [left, top, right, bottom] and neighbour-list entries that exist only through the periodic wrap.
+    topo, g_max, occ_max: the list caps (default: the oracle's constants); with_self: the own-state block.  feedback: what a
+    None entry of `acts` feeds back, a function of the previous step's a_prior (2, N) float64 returning the [N, 2] float32
+    action (default: the prior rounded once to float32; obs_feedback gives a float32 / bfloat16 handle's)."""
+    from oracle.oracle_py import G_MAX, OCC_MAX, TOPO
     ph = physics(**phys)
+    cap = dict(topo=TOPO if topo is None else topo, g_max=G_MAX if g_max is None else g_max, occ_max=OCC_MAX if occ_max is None else occ_max)
+    if feedback is None:
+        feedback = lambda prior: prior.T.astype(np.float32)
     b = np.array(boundary, np.float64)
     w_half, h_half = (b[2] - b[0]) / 2, (b[1] - b[3]) / 2
-    first = [oracle.get_observation(p, dp, g, l, r_avoid, d_sen=d_sen, boundary=b, is_periodic=periodic) for p, dp, g, l in cases]
+    first = [oracle.get_observation(p, dp, g, l, r_avoid, d_sen=d_sen, boundary=b, is_periodic=periodic, with_self=with_self, **cap)
+             for p, dp, g, l in cases]
     state = [(c[0], c[1], o["neighbor_index"]) for c, o in zip(cases, first)]
     counts = dict(contact=0, wall=np.zeros(4, int), clip=0, wrap=np.zeros(4, int), wrap_only=0)
 
     def wrap_only(p, dp, g, l, nei):
-        plain = oracle.get_observation(p, dp, g, l, r_avoid, d_sen=d_sen, boundary=b, is_periodic=False)["neighbor_index"]
+        plain = oracle.get_observation(p, dp, g, l, r_avoid, d_sen=d_sen, boundary=b, is_periodic=False, **cap)["neighbor_index"]
         return sum(len(set(a[a >= 0]) - set(q[q >= 0])) for a, q in zip(nei, plain))
 
     if periodic:
@@ -174,13 +183,13 @@ def oracle_run(oracle, cases, acts, r_avoid, d_sen=0.4, boundary=DEFAULT_BOX, pe
     for t, act in enumerate(acts):
         row = []
         for e, (p, dp, nei) in enumerate(state):
-            a = np.ascontiguousarray(act[e] if act is not None else steps[-1][e]["a_prior"].T.astype(np.float32))
+            a = np.ascontiguousarray(act[e] if act is not None else feedback(steps[-1][e]["a_prior"]))
             g, l = cases[e][2], cases[e][3]
             counts["contact"] += int(oracle.dist_b2b(p, b, periodic, ph["size_a"])[2].sum())
             if not periodic:
                 counts["wall"] += oracle.dist_b2w(p, b, ph["size_a"])[1].sum(axis=1)
             s = oracle.step(p, dp, np.ascontiguousarray(a.T), g, nei, l, r_avoid, d_sen=d_sen, boundary=b, is_boundary=not periodic,
-                            prior_gain=prior_gain, **ph)
+                            with_self=with_self, prior_gain=prior_gain, **cap, **ph)
             counts["clip"] += int((np.abs(s["dp"]) == ph["vel_max"]).sum())
             if periodic:
                 d = s["p"] - p
@@ -278,6 +287,126 @@ class ThreadedOracle:
                                                      self.r_avoid, is_periodic=not self.is_boundary, with_self=self.with_self)
         self._map(work, len(envs))
         return {k: np.stack([r[k] for r in res]) for k in res[0]}
+
+
+# ---- list caps and observation dtypes of the env step (test_gpu_caps_parity.py, test_oracle_vs_reference.py) ----
+# id -> (topo, g_max, occ_max)
+CAPS_ROWS = {
+    "default": (6, 80, 200),        # the two-slots-per-lane sensed writer; used by the dtype matrix only
+    "t1_g5": (1, 5, 200),           # G - 1 even: the reference's fp64 round(); almost every list capped; D = 18 / 22 < one export tile
+    "t3_g10_o7": (3, 10, 7),        # G - 1 odd: the integer cap arithmetic; binding occupied cap
+    "t2_g16_o20": (2, 16, 20),
+    "t6_g33_o33": (6, 33, 33),      # odd pairs per row; lists capped for some agents and not for others
+    "t6_g79_o64": (6, 79, 64),      # odd pairs per row, one below the two-slot form, slot loop past lane 63
+    "t5_g81": (5, 81, 200),         # one above it
+    "t4_g128_o11": (4, 128, 11),    # the longest list the rule expert accepts; the sensed cap never binds
+    "t6_g80_o20": (6, 80, 20),      # two-slot writer with a binding occupied cap
+}
+CAPS_NS = (5, 8, 16, 17, 30, 32, 64, 65, 128, 200, 256)          # the caps matrix (float64)
+CAPS_DTYPE_NS = (5, 8, 30, 32, 64, 100, 200, 256)                # the dtype matrix (float32, bfloat16)
+CAPS_DTYPE_ROWS = ("default", "t6_g80_o20", "t6_g33_o33", "t5_g81", "t1_g5")
+CAPS_STEPS = 4
+
+
+def caps_envs(n_a):
+    """Env count of a caps case: small, and no multiple of the envs per workgroup."""
+    return 11 if n_a <= 16 else 5 if n_a <= 64 else 3
+
+
+def as_obs_dtype(x, dtype):
+    """What a handle of obs dtype `dtype` ("f64", "f32", "bf16") has to return for the oracle's float64 array x, widened back
+    exactly to a numpy array (float64 for "f64", else float32) so that == compares values of the narrow format.
+      f64   x itself
+      f32   x rounded once to float32
+      bf16  x rounded to float32 and THEN to bfloat16, both to nearest-even (include/swarm_env.h: "the f32 value rounded to
+            nearest-even"; the kernel's to_out<__bf16> is (__bf16)(float)v).
+    Rounding the double to bfloat16 directly (bf16_direct) is NOT the contract, even where the two agree: they differ where
+    the float32 rounding lands exactly on the midpoint of two bfloat16 values the double was not on -- about one value in
+    2^17 -- and there the contract is the twice-rounded one, the value a float32 handle's output gives when cast."""
+    import torch
+    if dtype == "f64":
+        return np.asarray(x, np.float64)
+    t = torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(torch.float32)
+    if dtype == "bf16":
+        t = t.to(torch.bfloat16).to(torch.float32)
+    elif dtype != "f32":
+        raise ValueError(dtype)
+    return t.numpy()
+
+
+def bf16_direct(x):
+    """float64 -> bfloat16 in ONE nearest-even rounding (8 significant bits), widened back; normal range only.  Not the
+    contract (as_obs_dtype): the tests use it to count the values on which a kernel rounding this way would be caught."""
+    m, e = np.frexp(np.asarray(x, np.float64))
+    return np.ldexp(np.rint(m * 256.0) / 256.0, e).astype(np.float32)
+
+
+def obs_feedback(dtype):
+    """oracle_run's `feedback` for a handle of obs dtype `dtype`: the prior as that handle returns it, widened to float32."""
+    return lambda prior: np.ascontiguousarray(as_obs_dtype(prior.T, dtype).astype(np.float32))
+
+
+def caps_trajectory(oracle, shapes, row, n_a, dtype="f64", periodic=False, with_self=True):
+    """The inputs of one caps case and the oracle's trajectory of them: caps_envs(n_a) envs -- two thirds make_case envs
+    clustered on the shape, every third an adversarial_case (thresholds meeting the capped lists) -- observe, then
+    CAPS_STEPS steps alternating random float32 actions with the fed-back prior as a handle of `dtype` returns it.
+    Deterministic in its arguments.  Returns (cases, oracle_run's result, r_avoid)."""
+    from marl_llm_amd.shapes import r_avoid_for
+    topo, g_max, occ_max = CAPS_ROWS[row]
+    rng = np.random.default_rng([list(CAPS_ROWS).index(row), n_a, int(periodic), int(with_self), 41])
+    ra = r_avoid_for(n_a, shapes)
+    n_env = caps_envs(n_a)
+    cases = []
+    for e in range(n_env):
+        if e % 3 != 2:
+            cases.append(make_case(rng, shapes, n_a, 1))
+            continue
+        p, dp, g, l_cell = adversarial_case(rng, shapes, n_a, ra)
+        for j in range(1, n_a):             # coincident agents: the reference's choice of "self" among them is its sort's
+            while (p[:, :j] == p[:, [j]]).all(axis=0).any():
+                p[0, j] += 1e-9
+        cases.append((p, dp, g, l_cell))
+    ref = oracle_run(oracle, cases, random_actions(rng, CAPS_STEPS, n_env, n_a), ra, periodic=periodic, topo=topo, g_max=g_max,
+                     occ_max=occ_max, with_self=with_self, feedback=obs_feedback(dtype))
+    return cases, ref, ra
+
+
+def cap_round_parts_ways(g_max, n):
+    """Does a sensed list of uncapped length n > g_max have a slot q whose rank round(q * ((n - 1) / (g_max - 1))) in the
+    reference's fp64 (std::round: half away from zero, of the rounded product of the rounded quotient) differs from the
+    exact quotient rounded half up, floor((2 q (n - 1) + g_max - 1) / (2 (g_max - 1)))?  Only exact ties can, so only even
+    g_max - 1, and only where the fp64 product lands below the tie (never for g_max - 1 a power of two).  These are the
+    lengths at which a kernel taking the integer form at the wrong parity of g_max - 1 selects another cell."""
+    q = np.arange(g_max)
+    v = q * ((n - 1) / (g_max - 1))
+    fp = np.floor(v) + (v - np.floor(v) >= 0.5)
+    return bool((fp != (2 * q * (n - 1) + g_max - 1) // (2 * (g_max - 1))).any())
+
+
+def caps_reach(oracle, cases, row, ref, r_avoid, periodic=False):
+    """What a caps trajectory reached, from the oracle alone, over every observation of it (the first and each step's), in
+    agent-steps: sensed_over / sensed_under -- the UNCAPPED filtered sensed list (the oracle's observation with g_max =
+    occ_max = n_g) longer / shorter than g_max; occ_over -- the uncapped occupied list longer than occ_max; nei_full /
+    nei_part -- neighbour lists with all topo entries / fewer; rew1 / rew0 -- rewards of 1 / 0; tie_below -- capped sensed lists
+    of a length at which cap_round_parts_ways."""
+    topo, g_max, occ_max = CAPS_ROWS[row]
+    first, steps, _ = ref
+    c = dict(sensed_over=0, sensed_under=0, occ_over=0, nei_full=0, nei_part=0, rew1=0, rew0=0, tie_below=0, agent_steps=0)
+    for e, (p0, dp0, g, l) in enumerate(cases):
+        n_g = g.shape[1]
+        states = [(p0, dp0, first[e]["neighbor_index"])] + [(row_[e]["p"], row_[e]["dp"], row_[e]["neighbor_index"]) for row_ in steps]
+        for p, dp, nei in states:
+            o = oracle.get_observation(p, dp, g, l, r_avoid, is_periodic=periodic, topo=topo, g_max=n_g, occ_max=n_g)
+            n_s, n_o = (o["sensed_index"] >= 0).sum(axis=1), (o["occupied_index"] >= 0).sum(axis=1)
+            c["sensed_over"] += int((n_s > g_max).sum()); c["sensed_under"] += int((n_s < g_max).sum())
+            c["occ_over"] += int((n_o > occ_max).sum())
+            c["tie_below"] += sum(cap_round_parts_ways(g_max, int(n)) for n in n_s[n_s > g_max])
+            full = (nei >= 0).all(axis=1)
+            c["nei_full"] += int(full.sum()); c["nei_part"] += int((~full).sum())
+            c["agent_steps"] += p.shape[1]
+        for row_ in steps:
+            c["rew1"] += int((row_[e]["reward"] == 1).sum()); c["rew0"] += int((row_[e]["reward"] == 0).sum())
+    return c
 
 
 # ---- counter-based generators of the policy and rollout kernels (include/swarm_policy.h, include/swarm_rollout.h) ----
