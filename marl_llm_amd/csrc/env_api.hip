@@ -11,6 +11,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "swarm_env.h"
@@ -154,13 +155,15 @@ void set_lattice_mode(swarm_env *h, bool all_lattice, float rmax, float cmax, in
 // the expert's rounding of the sensed-list subsample (KP::cap_even).  Enqueued on the handle's stream, no synchronisation.
 int export_pass(swarm_env *h, bool lists, bool cap_even)
 {
-    if (lists && !h->d_exp_sensed) {
+    if (lists && !h->d_exp_occ) {
         const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
-        HIP_TRY(h, hipMalloc((void **)&h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4));
-        HIP_TRY(h, hipMalloc((void **)&h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4));
+        DevBuf<int> sensed, occ;
+        HIP_ALLOC(h, sensed, EN * (size_t)h->kp.g_max);
+        HIP_ALLOC(h, occ, EN * (size_t)h->kp.occ_max);
+        h->d_exp_sensed = std::move(sensed); h->d_exp_occ = std::move(occ);
     }
     h->kp.export_small = 1; h->kp.cap_even = cap_even;
-    if (lists) { h->kp.export_idx = 1; h->kp.exp_sensed = h->d_exp_sensed; h->kp.exp_occ = h->d_exp_occ; }
+    if (lists) { h->kp.export_idx = 1; h->kp.exp_sensed = h->d_exp_sensed.get(); h->kp.exp_occ = h->d_exp_occ.get(); }
     const int rc = env_launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
     h->kp.export_idx = 0; h->kp.export_small = 0; h->kp.cap_even = 0;
     return rc;
@@ -198,15 +201,15 @@ LatInfo lattice_mode_of(swarm_env *h, const LatInfo *first, const LatInfo *last,
 ShapeSet shape_set(const swarm_env *h)
 {
     ShapeSet S;
-    S.n_shapes = h->n_shapes; S.cells = h->d_shape_cells; S.n_g = h->d_shape_ng; S.l_cell = h->d_shape_l;
-    S.c_in = h->d_shape_cin; S.lat = h->d_shape_lat;
+    S.n_shapes = h->n_shapes; S.cells = h->d_shape_cells.get(); S.n_g = h->d_shape_ng.get(); S.l_cell = h->d_shape_l.get();
+    S.c_in = h->d_shape_cin.get(); S.lat = h->d_shape_lat.get();
     return S;
 }
 
 // refresh the (x, y)-interleaved copy of the cells of envs [e0, e0 + count)
 int interleave(swarm_env *h, int e0, int count)
 {
-    HIP_LAUNCHED(h, launch_interleave(h->stream, h->d_cells, h->d_cells_xy, h->kp.ng_max, e0, count));
+    HIP_LAUNCHED(h, launch_interleave(h->stream, h->d_cells.get(), h->d_cells_xy.get(), h->kp.ng_max, e0, count));
     return SWARM_OK;
 }
 
@@ -240,13 +243,13 @@ int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_expert_view *ou
 {
     if (!h || !out) return SWARM_ERR_INVALID;
     if (lists) {
-        if (!h->d_act64) HIP_TRY(h, hipMalloc((void **)&h->d_act64, (size_t)h->cfg.n_env * h->cfg.n_agents * sizeof(double2)));
+        if (!h->d_act64) HIP_ALLOC(h, h->d_act64, (size_t)h->cfg.n_env * h->cfg.n_agents);
         const int rc = export_pass(h, true, true);
         if (rc != SWARM_OK) return rc;
     }
-    out->p = h->d_p; out->dp = h->d_dp; out->cells = h->d_cells;
-    out->near_cell = h->d_near; out->in_flag = h->d_inflag; out->exp_sensed = h->d_exp_sensed;
-    out->act_next = h->d_act_next; out->act64 = h->d_act64;
+    out->p = h->d_p.get(); out->dp = h->d_dp.get(); out->cells = h->d_cells.get();
+    out->near_cell = h->d_near.get(); out->in_flag = h->d_inflag.get(); out->exp_sensed = h->d_exp_sensed.get();
+    out->act_next = h->d_act_next.get(); out->act64 = h->d_act64.get();
     out->d_sen = h->kp.d_sen; out->r_avoid = h->kp.r_avoid;
     out->n_env = h->cfg.n_env; out->n_agents = h->cfg.n_agents; out->g_max = h->kp.g_max; out->ng_max = h->kp.ng_max;
     return SWARM_OK;
@@ -296,24 +299,14 @@ int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
 
     swarm_env *h = new (std::nothrow) swarm_env();
     if (!h) return fail(nullptr, SWARM_ERR_INVALID, "out of host memory");
-    h->cfg = *cfg; h->device = dev; h->stream = nullptr; h->ev0 = h->ev1 = nullptr;
-    h->have_cells = h->have_state = h->observed = false;
+    h->cfg = *cfg; h->device = dev;
     for (int &a : h->attr_smem) a = -1;
-    h->half = false; h->n_cu = 256;
-    h->d_p = h->d_dp = h->d_cells = h->d_cin = nullptr; h->d_cells_xy = nullptr;
-    h->d_lat = nullptr;
-    h->n_shapes = 0; h->d_shape_cells = h->d_shape_l = h->d_shape_cin = nullptr; h->d_shape_ng = nullptr; h->d_shape_lat = nullptr; h->d_shape_idx = nullptr;
     h->env_lat.assign((size_t)cfg->n_env, LatInfo{false, 0.0f, 0.0f, 0});
     h->lattice_disabled = (cfg->debug_flags & 2) != 0;
-    h->d_nei = h->d_near = h->d_inflag = h->d_ng = h->d_exp_sensed = h->d_exp_occ = nullptr; h->d_sf = nullptr; h->d_prior = nullptr;
-    h->d_act_next = nullptr; h->d_act64 = nullptr;
-    h->d_io_obs = h->d_io_prior = nullptr; h->d_io_rew = nullptr; h->d_io_done = nullptr;
-    h->d_io_block = nullptr; h->h_io_block[0] = h->h_io_block[1] = nullptr; h->h_io_action = h->d_io_action = nullptr; h->io_block_bytes = 0;
     h->cells_set.assign((size_t)cfg->n_env, 0);
     h->npad = npad_for(cfg->n_agents);
 
     KP &k = h->kp;
-    std::memset(&k, 0, sizeof(k));
     k.n_env = cfg->n_env; k.n_a = cfg->n_agents; k.ng_max = cfg->n_cells_max;
     k.topo = cfg->topo_nei_max; k.g_max = cfg->num_obs_grid_max; k.occ_max = cfg->num_occupied_grid_max;
     k.with_self = cfg->with_self_state ? 1 : 0;
@@ -386,26 +379,20 @@ int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
     }
     const size_t E = (size_t)cfg->n_env, N = (size_t)cfg->n_agents;
     hipError_t a = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (a == hipSuccess) a = hipMalloc(p, bytes); };
-    alloc((void **)&h->d_p, E * 2 * N * 8); alloc((void **)&h->d_dp, E * 2 * N * 8);
-    alloc((void **)&h->d_cells, E * 2 * (size_t)k.ng_max * 8); alloc((void **)&h->d_cin, E * 8);
-    alloc((void **)&h->d_cells_xy, E * (size_t)k.ng_max * 16);
-    alloc((void **)&h->d_ng, E * 4); alloc((void **)&h->d_shape_idx, E * 4);
-    alloc((void **)&h->d_prior, E * N * 16);
-    if (cfg->llm_action) alloc((void **)&h->d_act_next, E * N * 16);
-    alloc((void **)&h->d_lat, E * sizeof(LatEnv));
-    alloc((void **)&h->d_nei, E * N * (size_t)k.topo * 4); alloc((void **)&h->d_near, E * N * 4);
-    alloc((void **)&h->d_inflag, E * N * 4); alloc((void **)&h->d_sf, E * N * 16);
-    if (a == hipSuccess) a = hipMemset(h->d_ng, 0, E * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_prior, 0, E * N * 16);
-    if (a == hipSuccess && h->d_act_next) a = hipMemset(h->d_act_next, 0, E * N * 16);
-    if (a == hipSuccess) a = hipMemset(h->d_shape_idx, 0xFF, E * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_nei, 0xFF, E * N * (size_t)k.topo * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_near, 0, E * N * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_inflag, 0, E * N * 4);
-    if (a == hipSuccess) a = hipMemset(h->d_sf, 0, E * N * 16);
-    if (a == hipSuccess) a = hipMemset(h->d_cells, 0, E * 2 * (size_t)k.ng_max * 8);
-    if (a == hipSuccess) a = hipMemset(h->d_cells_xy, 0, E * (size_t)k.ng_max * 16);
+    // count: elements of the buffer's type; fill >= 0: the byte every element of the new buffer is set to
+    auto alloc = [&](auto &buf, size_t count, int fill = -1) {
+        if (a == hipSuccess) a = buf.alloc(count);
+        if (a == hipSuccess && fill >= 0) a = hipMemset(buf.get(), fill, count * sizeof(*buf.get()));
+    };
+    alloc(h->d_p, E * 2 * N); alloc(h->d_dp, E * 2 * N);
+    alloc(h->d_cells, E * 2 * (size_t)k.ng_max, 0); alloc(h->d_cin, E);
+    alloc(h->d_cells_xy, E * (size_t)k.ng_max, 0);
+    alloc(h->d_ng, E, 0); alloc(h->d_shape_idx, E, 0xFF);
+    alloc(h->d_prior, E * N * 16, 0);
+    if (cfg->llm_action) alloc(h->d_act_next, E * N, 0);
+    alloc(h->d_lat, E);
+    alloc(h->d_nei, E * N * (size_t)k.topo, 0xFF); alloc(h->d_near, E * N, 0);
+    alloc(h->d_inflag, E * N, 0); alloc(h->d_sf, E * N, 0);
     if (a == hipSuccess) a = hipEventCreate(&h->ev0);
     if (a == hipSuccess) a = hipEventCreate(&h->ev1);
     if (a != hipSuccess) {
@@ -413,10 +400,10 @@ int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
         swarm_destroy(h);
         return fail(nullptr, SWARM_ERR_HIP, m);
     }
-    k.p = h->d_p; k.dp = h->d_dp; k.nei = h->d_nei; k.near_cell = h->d_near; k.in_flag = h->d_inflag; k.sf_next = h->d_sf;
-    k.prior_next = h->d_prior; k.act_next = h->d_act_next;
-    k.cells = h->d_cells; k.cells_xy = h->d_cells_xy; k.n_g = h->d_ng; k.c_in = h->d_cin;
-    k.lat = h->d_lat; k.lattice = 0; k.lat_rw = k.lat_cw = 0; k.lat_nrs = k.lat_nrc = 0; k.lat_n32 = 0;
+    k.p = h->d_p.get(); k.dp = h->d_dp.get(); k.nei = h->d_nei.get(); k.near_cell = h->d_near.get(); k.in_flag = h->d_inflag.get(); k.sf_next = h->d_sf.get();
+    k.prior_next = h->d_prior.get(); k.act_next = h->d_act_next.get();
+    k.cells = h->d_cells.get(); k.cells_xy = h->d_cells_xy.get(); k.n_g = h->d_ng.get(); k.c_in = h->d_cin.get();
+    k.lat = h->d_lat.get(); k.lattice = 0; k.lat_rw = k.lat_cw = 0; k.lat_nrs = k.lat_nrc = 0; k.lat_n32 = 0;
     k.c_near_hi = k.c_near * (1.0 + 1e-9);
     *out = h;
     return SWARM_OK;
@@ -425,21 +412,10 @@ int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
 int swarm_destroy(swarm_env_t *h)
 {
     if (!h) return SWARM_OK;
-    {
-        DeviceGuard g(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(h->d_p); (void)hipFree(h->d_dp); (void)hipFree(h->d_cells); (void)hipFree(h->d_cin); (void)hipFree(h->d_cells_xy);
-        (void)hipFree(h->d_ng); (void)hipFree(h->d_nei); (void)hipFree(h->d_near); (void)hipFree(h->d_inflag); (void)hipFree(h->d_sf);
-        (void)hipFree(h->d_exp_sensed); (void)hipFree(h->d_exp_occ); (void)hipFree(h->d_lat); (void)hipFree(h->d_shape_idx); (void)hipFree(h->d_prior);
-        (void)hipFree(h->d_shape_cells); (void)hipFree(h->d_shape_l); (void)hipFree(h->d_shape_cin); (void)hipFree(h->d_shape_ng); (void)hipFree(h->d_shape_lat);
-        (void)hipFree(h->d_act_next); (void)hipFree(h->d_act64); (void)hipFree(h->d_io_obs); (void)hipFree(h->d_io_prior); (void)hipFree(h->d_io_rew); (void)hipFree(h->d_io_done);
-        (void)hipFree(h->d_io_block); (void)hipFree(h->d_io_action);
-        if (h->h_io_block[0]) (void)hipHostFree(h->h_io_block[0]);
-        if (h->h_io_block[1]) (void)hipHostFree(h->h_io_block[1]);
-        if (h->h_io_action) (void)hipHostFree(h->h_io_action);
-        if (h->ev0) (void)hipEventDestroy(h->ev0);
-        if (h->ev1) (void)hipEventDestroy(h->ev1);
-    }
+    DeviceGuard g(h->device);          // the handle's buffers are freed with its device current
+    (void)hipStreamSynchronize(h->stream);
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
     delete h;
     return SWARM_OK;
 }
@@ -474,21 +450,21 @@ int swarm_set_cells(swarm_env_t *h, int env_begin, int count, const double *cell
     }
     DeviceGuard g(h->device);
     const size_t row = (size_t)2 * h->kp.ng_max;
-    HIP_TRY(h, hipMemcpyAsync(h->d_cells + (size_t)env_begin * row, cells, (size_t)count * row * 8, hipMemcpyDefault, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_cells.get() + (size_t)env_begin * row, cells, (size_t)count * row * 8, hipMemcpyDefault, h->stream));
     if (int rc = interleave(h, env_begin, count)) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_ng + env_begin, n_g, (size_t)count * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_shape_idx + env_begin, 0xFF, (size_t)count * 4, h->stream));   // no longer a shape of the set
-    HIP_TRY(h, hipMemcpyAsync(h->d_cin + env_begin, cin.data(), (size_t)count * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_ng.get() + env_begin, n_g, (size_t)count * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_shape_idx.get() + env_begin, 0xFF, (size_t)count * 4, h->stream));   // no longer a shape of the set
+    HIP_TRY(h, hipMemcpyAsync(h->d_cin.get() + env_begin, cin.data(), (size_t)count * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));           // cin is a host temporary
     {   // lattice detection on a host copy of what was uploaded (`cells` may be a device pointer)
         std::vector<double> hc((size_t)count * row);
-        HIP_TRY(h, hipMemcpy(hc.data(), h->d_cells + (size_t)env_begin * row, (size_t)count * row * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(hc.data(), h->d_cells.get() + (size_t)env_begin * row, (size_t)count * row * 8, hipMemcpyDeviceToHost));
         std::vector<LatEnv> lat((size_t)count);
         for (int k = 0; k < count; ++k) {
             const double *gx = hc.data() + (size_t)k * row, *gy = gx + h->kp.ng_max;
             h->env_lat[(size_t)(env_begin + k)] = classify_cells(h, gx, gy, n_g[k], lat[(size_t)k]);
         }
-        HIP_TRY(h, hipMemcpy(h->d_lat + env_begin, lat.data(), (size_t)count * sizeof(LatEnv), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_lat.get() + env_begin, lat.data(), (size_t)count * sizeof(LatEnv), hipMemcpyHostToDevice));
         lattice_mode_of(h, h->env_lat.data(), h->env_lat.data() + h->env_lat.size(), true);
     }
     for (int k = 0; k < count; ++k) h->cells_set[(size_t)(env_begin + k)] = 1;
@@ -514,19 +490,18 @@ int swarm_set_shapes(swarm_env_t *h, int n_shapes, const double *shape_cells, co
         info[(size_t)k] = classify_cells(h, gx, gy, n_g[k], lat[(size_t)k]);
     }
     DeviceGuard g(h->device);
-    (void)hipFree(h->d_shape_cells); (void)hipFree(h->d_shape_l); (void)hipFree(h->d_shape_cin); (void)hipFree(h->d_shape_ng); (void)hipFree(h->d_shape_lat);
-    h->d_shape_cells = h->d_shape_l = h->d_shape_cin = nullptr; h->d_shape_ng = nullptr; h->d_shape_lat = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_cells, (size_t)n_shapes * row * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_l, (size_t)n_shapes * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_cin, (size_t)n_shapes * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_ng, (size_t)n_shapes * 4));
-    HIP_TRY(h, hipMalloc((void **)&h->d_shape_lat, (size_t)n_shapes * sizeof(LatEnv)));
-    HIP_TRY(h, hipMemcpy(h->d_shape_cells, shape_cells, (size_t)n_shapes * row * 8, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_shape_l, l_cell, (size_t)n_shapes * 8, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_shape_cin, cin.data(), (size_t)n_shapes * 8, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_shape_ng, n_g, (size_t)n_shapes * 4, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_shape_lat, lat.data(), (size_t)n_shapes * sizeof(LatEnv), hipMemcpyHostToDevice));
-    h->n_shapes = n_shapes; h->shape_lat = info;
+    // the new set is built aside and replaces the old one only when it is complete: a failure leaves the old set in force
+    const size_t S = (size_t)n_shapes;
+    DevBuf<double> d_cells, d_l, d_cin; DevBuf<int> d_ng; DevBuf<LatEnv> d_lat;
+    HIP_ALLOC(h, d_cells, S * row); HIP_ALLOC(h, d_l, S); HIP_ALLOC(h, d_cin, S); HIP_ALLOC(h, d_ng, S); HIP_ALLOC(h, d_lat, S);
+    HIP_TRY(h, hipMemcpy(d_cells.get(), shape_cells, S * row * 8, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d_l.get(), l_cell, S * 8, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d_cin.get(), cin.data(), S * 8, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d_ng.get(), n_g, S * 4, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d_lat.get(), lat.data(), S * sizeof(LatEnv), hipMemcpyHostToDevice));
+    h->d_shape_cells = std::move(d_cells); h->d_shape_l = std::move(d_l); h->d_shape_cin = std::move(d_cin);
+    h->d_shape_ng = std::move(d_ng); h->d_shape_lat = std::move(d_lat);
+    h->n_shapes = n_shapes; h->shape_lat = std::move(info);
     return SWARM_OK;
 }
 
@@ -535,7 +510,7 @@ int swarm_reset(swarm_env_t *h, uint64_t seed, uint64_t episode, int64_t env_off
     if (!h) return SWARM_ERR_INVALID;
     if (h->n_shapes < 1) return fail(h, SWARM_ERR_STATE, "swarm_reset: no shape set (swarm_set_shapes)");
     DeviceGuard g(h->device);
-    HIP_LAUNCHED(h, launch_reset(h->stream, h->kp, shape_set(h), seed, episode, env_offset, h->d_cells, h->d_ng, h->d_cin, h->d_lat, h->d_shape_idx));
+    HIP_LAUNCHED(h, launch_reset(h->stream, h->kp, shape_set(h), seed, episode, env_offset, h->d_cells.get(), h->d_ng.get(), h->d_cin.get(), h->d_lat.get(), h->d_shape_idx.get()));
     if (int rc = interleave(h, 0, h->cfg.n_env)) return rc;
     std::fill(h->cells_set.begin(), h->cells_set.end(), 1);
     h->have_cells = h->have_state = true;
@@ -553,8 +528,8 @@ int swarm_select_shape(swarm_env_t *h, int32_t shape_index, void *obs)
     if (shape_index < 0 || shape_index >= h->n_shapes) return fail(h, SWARM_ERR_INVALID, "swarm_select_shape: shape_index outside [0, n_shapes)");
     if (!h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_select_shape: state not set (swarm_set_state / swarm_reset)");
     DeviceGuard g(h->device);
-    HIP_LAUNCHED(h, launch_select_shape(h->stream, shape_set(h), (int)shape_index, h->kp.ng_max, h->cfg.n_env, h->d_cells, h->d_cells_xy,
-                                        h->d_ng, h->d_cin, h->d_lat, h->d_shape_idx));
+    HIP_LAUNCHED(h, launch_select_shape(h->stream, shape_set(h), (int)shape_index, h->kp.ng_max, h->cfg.n_env, h->d_cells.get(), h->d_cells_xy.get(),
+                                        h->d_ng.get(), h->d_cin.get(), h->d_lat.get(), h->d_shape_idx.get()));
     // the host bookkeeping swarm_set_cells would leave for E copies of this shape
     const LatInfo *one = h->shape_lat.data() + shape_index;
     std::fill(h->cells_set.begin(), h->cells_set.end(), 1);
@@ -571,8 +546,8 @@ int swarm_set_state(swarm_env_t *h, const double *p, const double *dp)
     if (!p || !dp) return fail(h, SWARM_ERR_INVALID, "swarm_set_state: null argument");
     DeviceGuard g(h->device);
     const size_t bytes = (size_t)h->cfg.n_env * 2 * h->cfg.n_agents * 8;
-    HIP_TRY(h, hipMemcpyAsync(h->d_p, p, bytes, hipMemcpyDefault, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_dp, dp, bytes, hipMemcpyDefault, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_p.get(), p, bytes, hipMemcpyDefault, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_dp.get(), dp, bytes, hipMemcpyDefault, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->have_state = true;
     h->observed = false;
@@ -592,8 +567,8 @@ int swarm_get_cells(swarm_env_t *h, double *cells, int32_t *n_g)
 {
     if (!h) return SWARM_ERR_INVALID;
     DeviceGuard g(h->device);
-    if (cells) HIP_TRY(h, hipMemcpyAsync(cells, h->d_cells, (size_t)h->cfg.n_env * 2 * h->kp.ng_max * 8, hipMemcpyDefault, h->stream));
-    if (n_g) HIP_TRY(h, hipMemcpyAsync(n_g, h->d_ng, (size_t)h->cfg.n_env * 4, hipMemcpyDefault, h->stream));
+    if (cells) HIP_TRY(h, hipMemcpyAsync(cells, h->d_cells.get(), (size_t)h->cfg.n_env * 2 * h->kp.ng_max * 8, hipMemcpyDefault, h->stream));
+    if (n_g) HIP_TRY(h, hipMemcpyAsync(n_g, h->d_ng.get(), (size_t)h->cfg.n_env * 4, hipMemcpyDefault, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SWARM_OK;
 }
@@ -602,7 +577,7 @@ int swarm_get_shape_index(swarm_env_t *h, int32_t *shape_index)
 {
     if (!h || !shape_index) return SWARM_ERR_INVALID;
     DeviceGuard g(h->device);
-    HIP_TRY(h, hipMemcpyAsync(shape_index, h->d_shape_idx, (size_t)h->cfg.n_env * 4, hipMemcpyDefault, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(shape_index, h->d_shape_idx.get(), (size_t)h->cfg.n_env * 4, hipMemcpyDefault, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SWARM_OK;
 }
@@ -612,8 +587,8 @@ int swarm_get_state(swarm_env_t *h, double *p, double *dp)
     if (!h) return SWARM_ERR_INVALID;
     DeviceGuard g(h->device);
     const size_t bytes = (size_t)h->cfg.n_env * 2 * h->cfg.n_agents * 8;
-    if (p) HIP_TRY(h, hipMemcpyAsync(p, h->d_p, bytes, hipMemcpyDefault, h->stream));
-    if (dp) HIP_TRY(h, hipMemcpyAsync(dp, h->d_dp, bytes, hipMemcpyDefault, h->stream));
+    if (p) HIP_TRY(h, hipMemcpyAsync(p, h->d_p.get(), bytes, hipMemcpyDefault, h->stream));
+    if (dp) HIP_TRY(h, hipMemcpyAsync(dp, h->d_dp.get(), bytes, hipMemcpyDefault, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SWARM_OK;
 }
@@ -636,7 +611,7 @@ int swarm_step(swarm_env_t *h, const void *action, int action_dtype, void *obs, 
         // agent_strategy == 'llm' (assembly.py:525-529): the action is the Python twin of the prior policy, which the
         // previous pass evaluated on this very state
         if (!h->cfg.llm_action) return fail(h, SWARM_ERR_INVALID, "swarm_step: null action (only a handle created with llm_action may pass NULL)");
-        action = h->d_act_next; action_dtype = SWARM_F64;
+        action = h->d_act_next.get(); action_dtype = SWARM_F64;
     }
     if (action_dtype != SWARM_F32 && action_dtype != SWARM_F64) return fail(h, SWARM_ERR_INVALID, "swarm_step: bad action_dtype");
     if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_step: call swarm_observe after setting cells/state (the reference's reset() ends with _get_obs())");
@@ -648,21 +623,22 @@ int swarm_step(swarm_env_t *h, const void *action, int action_dtype, void *obs, 
 // the set of exported symbols, so they stay where a dlsym finds them)
 int io_alloc(swarm_env *h)
 {
-    if (h->d_io_block) return SWARM_OK;
+    if (h->h_io_action) return SWARM_OK;
     const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents, D = (size_t)h->kp.obs_dim;
     const size_t so = h->cfg.obs_dtype == SWARM_F64 ? 8 : h->cfg.obs_dtype == SWARM_BF16 ? 2 : 4;
-    h->io_block_bytes = (D * EN + 2 * EN + EN) * 8 + ((EN + 15) & ~size_t(15));
-    HIP_TRY(h, hipMalloc(&h->d_io_obs, EN * D * so));
-    HIP_TRY(h, hipMalloc(&h->d_io_prior, EN * 2 * so));
-    HIP_TRY(h, hipMalloc((void **)&h->d_io_rew, EN * 4));
-    HIP_TRY(h, hipMalloc((void **)&h->d_io_done, EN));
-    HIP_TRY(h, hipMalloc((void **)&h->d_io_block, h->io_block_bytes));
-    HIP_TRY(h, hipMalloc(&h->d_io_action, EN * 16));
-    HIP_TRY(h, hipHostMalloc((void **)&h->h_io_block[0], h->io_block_bytes, hipHostMallocDefault));
-    HIP_TRY(h, hipHostMalloc((void **)&h->h_io_block[1], h->io_block_bytes, hipHostMallocDefault));
-    HIP_TRY(h, hipHostMalloc(&h->h_io_action, EN * 16, hipHostMallocDefault));
-    HIP_TRY(h, hipMemset(h->d_io_block, 0, h->io_block_bytes));
-    std::memset(h->h_io_block[0], 0, h->io_block_bytes); std::memset(h->h_io_block[1], 0, h->io_block_bytes);
+    const size_t block_bytes = (D * EN + 2 * EN + EN) * 8 + ((EN + 15) & ~size_t(15));
+    // built aside and handed to the handle complete (h_io_action last, which the test above reads): a failure leaves nothing
+    DevBuf<char> obs, prior, action; DevBuf<float> rew; DevBuf<uint8_t> done; DevBuf<double> block;
+    DevBuf<double, true> hblock0, hblock1; DevBuf<char, true> haction;
+    HIP_ALLOC(h, obs, EN * D * so); HIP_ALLOC(h, prior, EN * 2 * so); HIP_ALLOC(h, rew, EN); HIP_ALLOC(h, done, EN);
+    HIP_ALLOC(h, block, block_bytes / 8); HIP_ALLOC(h, action, EN * 16);
+    HIP_ALLOC(h, hblock0, block_bytes / 8); HIP_ALLOC(h, hblock1, block_bytes / 8); HIP_ALLOC(h, haction, EN * 16);
+    HIP_TRY(h, hipMemset(block.get(), 0, block_bytes));
+    std::memset(hblock0.get(), 0, block_bytes); std::memset(hblock1.get(), 0, block_bytes);
+    h->io_block_bytes = block_bytes;
+    h->d_io_obs = std::move(obs); h->d_io_prior = std::move(prior); h->d_io_rew = std::move(rew); h->d_io_done = std::move(done);
+    h->d_io_block = std::move(block); h->d_io_action = std::move(action);
+    h->h_io_block[0] = std::move(hblock0); h->h_io_block[1] = std::move(hblock1); h->h_io_action = std::move(haction);
     return SWARM_OK;
 }
 
@@ -670,17 +646,17 @@ int io_export(swarm_env *h, int slot, bool stepped)
 {
     const long long EN = (long long)h->cfg.n_env * h->cfg.n_agents;
     const int D = h->kp.obs_dim, wp = (stepped && h->kp.with_prior) ? 1 : 0;
-    const float *rew = stepped ? h->d_io_rew : nullptr;
-    const uint8_t *dn = stepped ? h->d_io_done : nullptr;
-    HIP_LAUNCHED(h, launch_export(h->stream, h->cfg.obs_dtype, h->d_io_obs, rew, dn, h->d_io_prior, h->d_io_block, D, EN, wp));
+    const float *rew = stepped ? h->d_io_rew.get() : nullptr;
+    const uint8_t *dn = stepped ? h->d_io_done.get() : nullptr;
+    HIP_LAUNCHED(h, launch_export(h->stream, h->cfg.obs_dtype, h->d_io_obs.get(), rew, dn, h->d_io_prior.get(), h->d_io_block.get(), D, EN, wp));
     // obs only (reset / observe) moves the obs part; a step moves the whole block -- without with_prior in two pieces around
     // the a_prior part, which k_export did not write: the slot's a_prior array then stays as the caller left it
     const size_t obs_bytes = (size_t)D * EN * 8, pri_bytes = (size_t)2 * EN * 8;
     const size_t bytes = !stepped ? obs_bytes : wp ? h->io_block_bytes : obs_bytes;
-    HIP_TRY(h, hipMemcpyAsync(h->h_io_block[slot], h->d_io_block, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->h_io_block[slot].get(), h->d_io_block.get(), bytes, hipMemcpyDeviceToHost, h->stream));
     if (stepped && !wp) {
         const size_t off = obs_bytes + pri_bytes;
-        HIP_TRY(h, hipMemcpyAsync((char *)h->h_io_block[slot] + off, (const char *)h->d_io_block + off, h->io_block_bytes - off,
+        HIP_TRY(h, hipMemcpyAsync((char *)h->h_io_block[slot].get() + off, (const char *)h->d_io_block.get() + off, h->io_block_bytes - off,
                                   hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -693,7 +669,7 @@ int swarm_get_llm_action(swarm_env_t *h, double *action)
     if (!h->d_act_next) return fail(h, SWARM_ERR_STATE, "swarm_get_llm_action: handle was not created with llm_action");
     if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_get_llm_action: nothing observed yet");
     DeviceGuard g(h->device);
-    HIP_TRY(h, hipMemcpyAsync(action, h->d_act_next, (size_t)h->cfg.n_env * h->cfg.n_agents * 16, hipMemcpyDefault, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(action, h->d_act_next.get(), (size_t)h->cfg.n_env * h->cfg.n_agents * 16, hipMemcpyDefault, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SWARM_OK;
 }
@@ -705,7 +681,7 @@ int swarm_host_outputs(swarm_env_t *h, int slot, swarm_host_out_t *out)
     int rc = io_alloc(h);
     if (rc != SWARM_OK) return rc;
     const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents, D = (size_t)h->kp.obs_dim;
-    double *b = h->h_io_block[slot];
+    double *b = h->h_io_block[slot].get();
     out->obs = b; out->a_prior = b + D * EN; out->reward = b + D * EN + 2 * EN;
     out->done = reinterpret_cast<uint8_t *>(b + D * EN + 3 * EN);
     return SWARM_OK;
@@ -717,7 +693,7 @@ int swarm_observe_host(swarm_env_t *h, int slot)
     DeviceGuard g(h->device);
     int rc = io_alloc(h);
     if (rc != SWARM_OK) return rc;
-    rc = swarm_observe(h, h->d_io_obs);
+    rc = swarm_observe(h, h->d_io_obs.get());
     if (rc != SWARM_OK) return rc;
     return io_export(h, slot, false);
 }
@@ -734,17 +710,17 @@ int swarm_step_host(swarm_env_t *h, const void *action, int action_dtype, int ac
     const void *act = action; int mode = 0;
     if (!action) {
         if (!h->cfg.llm_action) return fail(h, SWARM_ERR_INVALID, "swarm_step_host: null action");
-        act = h->d_act_next; mode = 1;                                   // agent-major doubles
+        act = h->d_act_next.get(); mode = 1;                                   // agent-major doubles
     } else if (action_on_device) {
         mode = action_dtype == SWARM_F64 ? 1 : 0;                        // [E][N][2] device tensor, as swarm_step
     } else {
         // the reference's (2, n_a) host array: through the pinned staging buffer, read component-major by the kernel
         const size_t bytes = EN * 2 * (action_dtype == SWARM_F64 ? 8 : 4);
-        std::memcpy(h->h_io_action, action, bytes);
-        HIP_TRY(h, hipMemcpyAsync(h->d_io_action, h->h_io_action, bytes, hipMemcpyHostToDevice, h->stream));
-        act = h->d_io_action; mode = 2 | (action_dtype == SWARM_F64 ? 1 : 0);
+        std::memcpy(h->h_io_action.get(), action, bytes);
+        HIP_TRY(h, hipMemcpyAsync(h->d_io_action.get(), h->h_io_action.get(), bytes, hipMemcpyHostToDevice, h->stream));
+        act = h->d_io_action.get(); mode = 2 | (action_dtype == SWARM_F64 ? 1 : 0);
     }
-    rc = env_launch(h, true, act, mode, h->d_io_obs, h->d_io_rew, h->d_io_done, h->kp.with_prior ? h->d_io_prior : nullptr);
+    rc = env_launch(h, true, act, mode, h->d_io_obs.get(), h->d_io_rew.get(), h->d_io_done.get(), h->kp.with_prior ? h->d_io_prior.get() : nullptr);
     if (rc != SWARM_OK) return rc;
     return io_export(h, slot, true);
 }
@@ -757,10 +733,10 @@ int swarm_get_indices(swarm_env_t *h, int32_t *neighbor_index, int32_t *in_flags
     const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents;
     const int rc = export_pass(h, sensed_index || occupied_index, false);
     if (rc != SWARM_OK) return rc;
-    if (sensed_index) HIP_TRY(h, hipMemcpyAsync(sensed_index, h->d_exp_sensed, EN * (size_t)h->kp.g_max * 4, hipMemcpyDefault, h->stream));
-    if (occupied_index) HIP_TRY(h, hipMemcpyAsync(occupied_index, h->d_exp_occ, EN * (size_t)h->kp.occ_max * 4, hipMemcpyDefault, h->stream));
-    if (neighbor_index) HIP_TRY(h, hipMemcpyAsync(neighbor_index, h->d_nei, EN * (size_t)h->kp.topo * 4, hipMemcpyDefault, h->stream));
-    if (in_flags) HIP_TRY(h, hipMemcpyAsync(in_flags, h->d_inflag, EN * 4, hipMemcpyDefault, h->stream));
+    if (sensed_index) HIP_TRY(h, hipMemcpyAsync(sensed_index, h->d_exp_sensed.get(), EN * (size_t)h->kp.g_max * 4, hipMemcpyDefault, h->stream));
+    if (occupied_index) HIP_TRY(h, hipMemcpyAsync(occupied_index, h->d_exp_occ.get(), EN * (size_t)h->kp.occ_max * 4, hipMemcpyDefault, h->stream));
+    if (neighbor_index) HIP_TRY(h, hipMemcpyAsync(neighbor_index, h->d_nei.get(), EN * (size_t)h->kp.topo * 4, hipMemcpyDefault, h->stream));
+    if (in_flags) HIP_TRY(h, hipMemcpyAsync(in_flags, h->d_inflag.get(), EN * 4, hipMemcpyDefault, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SWARM_OK;
 }

@@ -109,43 +109,42 @@ struct LatInfo {
 }  // namespace swarm_internal
 
 struct swarm_env {
-    swarm_config_t cfg;
-    swarm_internal::KP kp;
-    int device;
-    int npad;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
-    bool have_cells, have_state, observed;
+    template <class T, bool PINNED = false> using Buf = swarm_internal::DevBuf<T, PINNED>;
+    swarm_config_t cfg = {};
+    swarm_internal::KP kp = {};
+    int device = 0, npad = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool have_cells = false, have_state = false, observed = false;
     int attr_smem[24];
-    bool half;                     // the half-occupied geometry is in use (set_lattice_mode)
-    int n_cu;
+    bool half = false;             // the half-occupied geometry is in use (set_lattice_mode)
+    int n_cu = 256;
     std::vector<char> cells_set;
     std::string err;
-    // device buffers
-    double *d_p, *d_dp, *d_cells, *d_cin;
-    double2 *d_cells_xy;
-    swarm_internal::LatEnv *d_lat;
-    // shape set for the device-side reset
-    int n_shapes;
-    double *d_shape_cells, *d_shape_l, *d_shape_cin;
-    int *d_shape_ng;
-    int *d_shape_idx;              // [E] shape index drawn by the last swarm_reset (-1 before / after swarm_set_cells)
-    swarm_internal::LatEnv *d_shape_lat;
+    // device buffers: owned by the handle, freed when swarm_destroy deletes it (with the handle's device current)
+    Buf<double> d_p, d_dp, d_cells, d_cin;
+    Buf<double2> d_cells_xy;
+    Buf<swarm_internal::LatEnv> d_lat;
+    // shape set for the device-side reset: replaced as a whole by a swarm_set_shapes that succeeded
+    int n_shapes = 0;
+    Buf<double> d_shape_cells, d_shape_l, d_shape_cin;
+    Buf<int> d_shape_ng, d_shape_idx;   // d_shape_idx: [E] shape index drawn by the last swarm_reset (-1 before / after swarm_set_cells)
+    Buf<swarm_internal::LatEnv> d_shape_lat;
     std::vector<swarm_internal::LatInfo> shape_lat;    // per shape of the set
     std::vector<swarm_internal::LatInfo> env_lat;      // per env; after swarm_reset: the shape set's maxima, valid for every env
-    bool lattice_disabled;
-    int *d_nei, *d_near, *d_inflag, *d_ng, *d_exp_sensed, *d_exp_occ;
-    double2 *d_sf;
-    void *d_prior;
-    double2 *d_act_next;           // [E][N] the 'llm' strategy's next action (cfg.llm_action)
-    double2 *d_act64;              // [E][N] fp64 action scratch of swarm_rollout_expert (first expert call)
+    bool lattice_disabled = false;
+    Buf<int> d_nei, d_near, d_inflag, d_ng;
+    Buf<int> d_exp_sensed, d_exp_occ;   // the export lists (first call that asks for them): both set, or neither
+    Buf<double2> d_sf;
+    Buf<char> d_prior;
+    Buf<double2> d_act_next;       // [E][N] the 'llm' strategy's next action (cfg.llm_action)
+    Buf<double2> d_act64;          // [E][N] fp64 action scratch of swarm_rollout_expert (first expert call)
     // reference-shaped host I/O (swarm_step_host): library-owned step outputs on the device, the export block on the
     // device, two pinned host copies of it (ping-pong: the previous step's arrays stay valid for one more step), a pinned
-    // staging buffer for the action
-    void *d_io_obs, *d_io_prior; float *d_io_rew; uint8_t *d_io_done;
-    double *d_io_block, *h_io_block[2];
-    void *h_io_action, *d_io_action;
-    size_t io_block_bytes;
+    // staging buffer for the action.  Allocated by the first call that needs them (io_alloc): all set, or none.
+    Buf<char> d_io_obs, d_io_prior, d_io_action; Buf<float> d_io_rew; Buf<uint8_t> d_io_done; Buf<double> d_io_block;
+    Buf<double, true> h_io_block[2]; Buf<char, true> h_io_action;
+    size_t io_block_bytes = 0;
 };
 
 namespace swarm_internal __attribute__((visibility("hidden"))) {
@@ -162,17 +161,8 @@ int fail(swarm_env *h, int code, const std::string &msg);
 #define HIP_TRY(h, call) HIP_TRY_AS(h, #call, call)
 // `call` is one of the launchers below, which return their launch's hipGetLastError(): the message names that
 #define HIP_LAUNCHED(h, call) HIP_TRY_AS(h, "hipGetLastError()", call)
-
-struct DeviceGuard {
-    int prev;
-    bool ok;
-    explicit DeviceGuard(int dev) : prev(-1), ok(false)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) return;
-        ok = (prev == dev) || hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
+// allocate `count` elements into the DevBuf `buf`: the message names hipMalloc / hipHostMalloc and the buffer
+#define HIP_ALLOC(h, buf, count) HIP_TRY_AS(h, std::string((buf).kCall) + "(" #buf ")", (buf).alloc(count))
 
 // ---- swarm_env.hip: the step kernel
 // lay out the dynamic LDS of the launches of geometry (npad, half) for k.lattice / k.ng_max / k.g_max: KP's strides, off_*, smem_*

@@ -22,8 +22,11 @@
 #include <vector>
 
 #include "swarm_env.h"
+#include "swarm_internal.h"
 
 namespace {
+
+using swarm_internal::DevBuf;
 
 std::mutex g_mu;
 
@@ -39,26 +42,29 @@ void legacy_fail(const char *fn, const char *why)
     std::fprintf(stderr, "libswarmenv: %s: %s\n", fn, why);
 }
 
+// (The two process-wide owners below are never destroyed: their device memory lives until the process ends, as it always
+// has -- a static destructor would call hipFree after the HIP runtime may already have shut down.)
 struct Arena {          // grow-only device scratch, reset per call
-    char *base = nullptr;
+    DevBuf<char> base;
     size_t cap = 0, used = 0;
     bool reserve(size_t bytes)
     {
-        if (bytes <= cap) { used = 0; return true; }
-        if (base) (void)hipFree(base);
-        base = nullptr; cap = 0; used = 0;
-        if (hipMalloc((void **)&base, bytes) != hipSuccess) return false;
+        used = 0;
+        if (bytes <= cap) return true;
+        cap = 0;
+        if (base.alloc(bytes) != hipSuccess) return false;      // frees the smaller block first
         cap = bytes;
         return true;
     }
     template <typename T> T *take(size_t n)
     {
         used = (used + 255) & ~size_t(255);
-        T *p = reinterpret_cast<T *>(base + used);
+        T *p = reinterpret_cast<T *>(base.get() + used);
         used += n * sizeof(T);
         return p;
     }
-} g_arena;
+};
+Arena &g_arena = *new Arena;
 
 bool device_ok(const char *fn)
 {
@@ -212,16 +218,15 @@ __global__ void k_legacy_prior(const double *p, const double *dp, double *a_prio
 struct ObsCtx {
     swarm_env_t *h = nullptr;
     swarm_config_t cfg;
-    double *d_obs = nullptr;
-    int32_t *d_nei = nullptr, *d_inf = nullptr, *d_sen = nullptr, *d_occ = nullptr;
+    DevBuf<double> d_obs;
+    DevBuf<int32_t> d_nei, d_inf, d_sen, d_occ;
     void drop()
     {
         if (h) swarm_destroy(h);
-        h = nullptr;
-        (void)hipFree(d_obs); (void)hipFree(d_nei); (void)hipFree(d_inf); (void)hipFree(d_sen); (void)hipFree(d_occ);
-        d_obs = nullptr; d_nei = d_inf = d_sen = d_occ = nullptr;
+        *this = ObsCtx();           // the move-assignment frees the five arrays
     }
-} g_obs;
+};
+ObsCtx &g_obs = *new ObsCtx;
 
 void fill_nan(double *a, size_t n) { for (size_t k = 0; k < n; ++k) a[k] = std::numeric_limits<double>::quiet_NaN(); }
 
@@ -260,25 +265,25 @@ void _get_observation(double *p_input, double *dp_input, double *heading_input, 
         g_obs.cfg = c;
         const int D = swarm_obs_dim(g_obs.h);
         if (D != obs_dim_agent) { g_obs.drop(); return bail("obs_dim_agent does not match 4*(topo+1+self)+2*num_obs_grid_max"); }
-        bool a = ok(hipMalloc((void **)&g_obs.d_obs, nobs * 8), fn, "hipMalloc") &&
-                 ok(hipMalloc((void **)&g_obs.d_nei, (size_t)n_a * topo_nei_max * 4), fn, "hipMalloc") &&
-                 ok(hipMalloc((void **)&g_obs.d_inf, (size_t)n_a * 4), fn, "hipMalloc") &&
-                 ok(hipMalloc((void **)&g_obs.d_sen, (size_t)n_a * num_obs_grid_max * 4), fn, "hipMalloc") &&
-                 ok(hipMalloc((void **)&g_obs.d_occ, (size_t)n_a * num_occupied_grid_max * 4), fn, "hipMalloc");
+        bool a = ok(g_obs.d_obs.alloc(nobs), fn, "hipMalloc") &&
+                 ok(g_obs.d_nei.alloc((size_t)n_a * topo_nei_max), fn, "hipMalloc") &&
+                 ok(g_obs.d_inf.alloc((size_t)n_a), fn, "hipMalloc") &&
+                 ok(g_obs.d_sen.alloc((size_t)n_a * num_obs_grid_max), fn, "hipMalloc") &&
+                 ok(g_obs.d_occ.alloc((size_t)n_a * num_occupied_grid_max), fn, "hipMalloc");
         if (!a) { g_obs.drop(); return bail("device allocation failed"); }
     }
     swarm_env_t *h = g_obs.h;
     int32_t ng = n_g;
     if (swarm_set_cells(h, 0, 1, grid_center_input, &ng, &l_cell) != SWARM_OK) return bail(swarm_last_error(h));
     if (swarm_set_state(h, p_input, dp_input) != SWARM_OK) return bail(swarm_last_error(h));
-    if (swarm_observe(h, g_obs.d_obs) != SWARM_OK) return bail(swarm_last_error(h));
-    if (swarm_get_indices(h, g_obs.d_nei, g_obs.d_inf, g_obs.d_sen, g_obs.d_occ) != SWARM_OK) return bail(swarm_last_error(h));
+    if (swarm_observe(h, g_obs.d_obs.get()) != SWARM_OK) return bail(swarm_last_error(h));
+    if (swarm_get_indices(h, g_obs.d_nei.get(), g_obs.d_inf.get(), g_obs.d_sen.get(), g_obs.d_occ.get()) != SWARM_OK) return bail(swarm_last_error(h));
     std::vector<double> rows(nobs);
-    bool a = ok(hipMemcpy(rows.data(), g_obs.d_obs, nobs * 8, hipMemcpyDeviceToHost), fn, "hipMemcpy") &&
-             ok(hipMemcpy(neighbor_index_input, g_obs.d_nei, (size_t)n_a * topo_nei_max * 4, hipMemcpyDeviceToHost), fn, "hipMemcpy") &&
-             ok(hipMemcpy(in_flags_input, g_obs.d_inf, (size_t)n_a * 4, hipMemcpyDeviceToHost), fn, "hipMemcpy") &&
-             ok(hipMemcpy(sensed_index_input, g_obs.d_sen, (size_t)n_a * num_obs_grid_max * 4, hipMemcpyDeviceToHost), fn, "hipMemcpy") &&
-             ok(hipMemcpy(occupied_index_input, g_obs.d_occ, (size_t)n_a * num_occupied_grid_max * 4, hipMemcpyDeviceToHost), fn, "hipMemcpy");
+    bool a = ok(hipMemcpy(rows.data(), g_obs.d_obs.get(), nobs * 8, hipMemcpyDeviceToHost), fn, "hipMemcpy") &&
+             ok(hipMemcpy(neighbor_index_input, g_obs.d_nei.get(), (size_t)n_a * topo_nei_max * 4, hipMemcpyDeviceToHost), fn, "hipMemcpy") &&
+             ok(hipMemcpy(in_flags_input, g_obs.d_inf.get(), (size_t)n_a * 4, hipMemcpyDeviceToHost), fn, "hipMemcpy") &&
+             ok(hipMemcpy(sensed_index_input, g_obs.d_sen.get(), (size_t)n_a * num_obs_grid_max * 4, hipMemcpyDeviceToHost), fn, "hipMemcpy") &&
+             ok(hipMemcpy(occupied_index_input, g_obs.d_occ.get(), (size_t)n_a * num_occupied_grid_max * 4, hipMemcpyDeviceToHost), fn, "hipMemcpy");
     if (!a) return bail("copy back failed");
     for (int i = 0; i < n_a; ++i)                 // rows [N][D] -> the reference's (D, N), AssemblyEnv.cpp:324-328
         for (int r = 0; r < obs_dim_agent; ++r) obs_input[(size_t)r * n_a + i] = rows[(size_t)i * obs_dim_agent + r];

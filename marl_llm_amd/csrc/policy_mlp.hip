@@ -54,6 +54,7 @@ struct MlpParams {
     unsigned long long row_offset;     // global index of row 0 of this call (a rank's shard of the batch)
 };
 
+using swarm_internal::DeviceGuard;
 using swarm_internal::pmix64;
 using swarm_internal::swarm_noise_key;
 
@@ -296,12 +297,12 @@ void set_smem()
 
 }  // namespace
 
-struct swarm_policy {
+struct SWARM_HIDDEN swarm_policy {     // hidden: its implicit destructor must not become an exported weak symbol
     int device, in_dim, hidden, act_dim;
-    int precision;                 // 0 = bf16 (default), 1 = bf16x3
-    void *d_blob;
+    int precision = 0;             // 0 = bf16 (default), 1 = bf16x3
+    swarm_internal::DevBuf<unsigned char> d_blob;     // the packed weights and biases p points into
     MlpParams p;
-    bool smem_set;
+    bool smem_set = false;
 };
 
 int swarm_internal_policy_info(const swarm_policy_t *p, swarm_policy_info *out)
@@ -328,7 +329,8 @@ int swarm_policy_create(const float *w1, const float *b1, const float *w2, const
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_policy_error = "swarm_policy_create: no HIP device (there is no CPU path)"; return SWARM_POLICY_ERR_HIP; }
     if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    if (device >= ndev || hipSetDevice(device) != hipSuccess) { g_policy_error = "swarm_policy_create: bad device"; return SWARM_POLICY_ERR_HIP; }
+    const DeviceGuard guard(device < ndev ? device : -1);       // -1 is no device: !ok
+    if (!guard.ok) { g_policy_error = "swarm_policy_create: bad device"; return SWARM_POLICY_ERR_HIP; }
 
     // blob: [w1 | w2 | w3 | w4] fragments (8 bf16 per lane), then [b1 | b2 | b3 | b4] fp32
     const size_t frag = 64 * 8;                                   // bf16 elements per fragment
@@ -379,16 +381,14 @@ int swarm_policy_create(const float *w1, const float *b1, const float *w2, const
 
     swarm_policy *p = new (std::nothrow) swarm_policy;
     if (!p) return SWARM_POLICY_ERR_INVALID;
-    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim; p->d_blob = nullptr; p->smem_set = false;
-    p->precision = 0;
-    if (hipMalloc(&p->d_blob, bytes) != hipSuccess || hipMemcpy(p->d_blob, blob.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        if (p->d_blob) (void)hipFree(p->d_blob);
+    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim;
+    if (p->d_blob.alloc(bytes) != hipSuccess || hipMemcpy(p->d_blob.get(), blob.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
         delete p;
         g_policy_error = "swarm_policy_create: device allocation / upload failed";
         return SWARM_POLICY_ERR_HIP;
     }
-    const bf8 *wd = reinterpret_cast<const bf8 *>(p->d_blob);
-    const float *bd = reinterpret_cast<const float *>(static_cast<unsigned char *>(p->d_blob) + 2 * w_elems * 2);
+    const bf8 *wd = reinterpret_cast<const bf8 *>(p->d_blob.get());
+    const float *bd = reinterpret_cast<const float *>(p->d_blob.get() + 2 * w_elems * 2);
     p->p.w1 = wd; p->p.w2 = wd + n_hid / 8; p->p.w3 = wd + 2 * n_hid / 8; p->p.w4 = wd + 3 * n_hid / 8;
     const bf8 *ld = wd + w_elems / 8;
     p->p.l1 = ld; p->p.l2 = ld + n_hid / 8; p->p.l3 = ld + 2 * n_hid / 8; p->p.l4 = ld + 3 * n_hid / 8;
@@ -401,11 +401,7 @@ int swarm_policy_create(const float *w1, const float *b1, const float *w2, const
 void swarm_policy_destroy(swarm_policy_t *p)
 {
     if (!p) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(p->device);
-    (void)hipFree(p->d_blob);
-    (void)hipSetDevice(prev);
+    const DeviceGuard guard(p->device);
     delete p;
 }
 
@@ -417,9 +413,8 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
     if (!p || !obs || !act || rows < 0) { g_policy_error = "swarm_policy_forward: bad argument"; return SWARM_POLICY_ERR_INVALID; }
     if (in_bf16 && (p->in_dim & 7)) { g_policy_error = "swarm_policy_forward_bf16: in_dim must be a multiple of 8"; return SWARM_POLICY_ERR_INVALID; }
     if (rows == 0) return SWARM_POLICY_OK;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (hipSetDevice(p->device) != hipSuccess) { g_policy_error = "swarm_policy_forward: hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
+    const DeviceGuard guard(p->device);
+    if (!guard.ok) { g_policy_error = "swarm_policy_forward: hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
     MlpParams q = p->p;
     q.rows = rows;
     q.noise_scale = noise_scale > 0.0f ? noise_scale : 0.0f;
@@ -454,7 +449,6 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
         else launch_policy<false, 1, false>(g, b, st, q, obs, act, log_pi, logpi_c);
     }
     const hipError_t e = hipGetLastError();
-    (void)hipSetDevice(prev);
     if (e != hipSuccess) { g_policy_error = std::string("swarm_policy_forward: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
     return SWARM_POLICY_OK;
 }

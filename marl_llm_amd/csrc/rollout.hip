@@ -17,6 +17,7 @@
 
 namespace {
 
+using swarm_internal::DeviceGuard;
 using swarm_internal::np_sum_stream;
 using swarm_internal::np_clip1;
 using swarm_internal::pmix64;
@@ -137,17 +138,6 @@ __global__ void __launch_bounds__(kThreads) k_act_f32(const double2 *__restrict_
     dst[row] = make_float2((float)a.x, (float)a.y);
 }
 
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) { prev = -1; return; }
-        ok = prev == dev || hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 // ---- validation shared by the entry points: each returns SWARM_OK or fail()'s code, in the order the callers document
 
 // The handles' infos (pol, pi: NULL for an entry point without a policy), steps and the devices.
@@ -197,7 +187,7 @@ int hip_check(const char *who, hipError_t e, const char *what)
 struct Loop {
     const char *const who;
     swarm_env_t *const env;
-    DeviceScope dev;
+    DeviceGuard dev;
     void *const stream;                                                     // as the libraries' entry points take it
     const hipStream_t st;
     const long long rows;

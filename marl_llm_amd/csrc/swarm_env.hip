@@ -2160,14 +2160,13 @@ int swarm_debug_stamps(swarm_env_t *h, const void *action, int action_dtype, voi
     const int grid = (h->cfg.n_env + epb - 1) / epb;   // same for every Geo<NPAD>
     const int wpb = (h->npad < 64 ? 64 : h->npad) * 4 / 64;      // waves per workgroup
     if (grid > max_blocks) return -1;
-    long long *d = nullptr;
-    if (hipMalloc((void **)&d, (size_t)grid * wpb * 24 * sizeof(long long)) != hipSuccess) return -1;
-    (void)hipMemset(d, 0, (size_t)grid * wpb * 24 * sizeof(long long));
-    h->kp.stamps = d;
+    DevBuf<long long> d;
+    if (d.alloc((size_t)grid * wpb * 24) != hipSuccess) return -1;
+    (void)hipMemset(d.get(), 0, (size_t)grid * wpb * 24 * sizeof(long long));
+    h->kp.stamps = d.get();
     int rc = env_launch(h, true, action, action_dtype == SWARM_F64, obs, reward, done, a_prior);
     h->kp.stamps = nullptr;
-    if (rc == SWARM_OK && hipMemcpy(out, d, (size_t)grid * wpb * 24 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
-    (void)hipFree(d);
+    if (rc == SWARM_OK && hipMemcpy(out, d.get(), (size_t)grid * wpb * 24 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
     return rc == SWARM_OK ? grid : -1;
 }
 #endif

@@ -1,7 +1,8 @@
 // Internal interface between the translation units of libswarmenv.so: what the device rollout loop (rollout.hip) needs to
 // know about the two opaque handles, the rule-expert kernel's launcher (rule_expert.hip; called by env_api.hip and
-// rollout.hip) and the counter-based hash every in-kernel generator is built from.  Not installed, not exported: the
-// accessors have hidden visibility, so the public ABI (swarm_env.h, swarm_policy.h, swarm_rollout.h) does not change.
+// rollout.hip), the counter-based hash every in-kernel generator is built from, and the two resource owners of the host code:
+// DeviceGuard (the current device) and DevBuf (one device or pinned allocation).  Not installed, not exported: the accessors
+// and the owners have hidden visibility, so the public ABI (swarm_env.h, swarm_policy.h, swarm_rollout.h) does not change.
 #ifndef SWARM_INTERNAL_H
 #define SWARM_INTERNAL_H
 
@@ -57,6 +58,49 @@ __device__ inline double np_sum_stream(int n, F f)
 // np.clip(v, -1, 1): NaN compares false both ways and passes through (fmin / fmax would return the bound); every other
 // value, -0.0 included, is what fmin(fmax(v, -1.0), 1.0) gives.
 __device__ inline double np_clip1(double v) { return v < -1.0 ? -1.0 : (v > 1.0 ? 1.0 : v); }
+
+}  // namespace swarm_internal
+
+namespace swarm_internal __attribute__((visibility("hidden"))) {
+
+// Makes `dev` the calling thread's device and restores the previous one on exit; ok: `dev` is current.
+struct DeviceGuard {
+    int prev;
+    bool ok;
+    explicit DeviceGuard(int dev) : prev(-1), ok(false)
+    {
+        if (hipGetDevice(&prev) != hipSuccess) return;
+        ok = (prev == dev) || hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// Owner of one hipMalloc (PINNED: hipHostMalloc) allocation of T elements.  Empty until alloc() succeeds and again after a
+// failed alloc() or a move out of it; the allocation is freed by the destructor, by the next alloc() (before the new one is
+// made) and by a move-assignment into the buffer.  Frees go to the device that is current: owners destroy their buffers
+// under a DeviceGuard.
+template <class T, bool PINNED = false>
+class DevBuf {
+    T *p_ = nullptr;
+    void release() { if (p_) (void)(PINNED ? hipHostFree(p_) : hipFree(p_)); p_ = nullptr; }
+
+public:
+    static constexpr const char *kCall = PINNED ? "hipHostMalloc" : "hipMalloc";
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t count)
+    {
+        release();
+        const hipError_t e = PINNED ? hipHostMalloc((void **)&p_, count * sizeof(T), hipHostMallocDefault)
+                                    : hipMalloc((void **)&p_, count * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+    T *get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+};
 
 }  // namespace swarm_internal
 
