@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define SWARM_ABI_VERSION 4
+#define SWARM_ABI_VERSION 5
 
 enum { SWARM_F32 = 0, SWARM_F64 = 1, SWARM_BF16 = 2 };
 
@@ -88,8 +88,11 @@ typedef struct swarm_config {
                                      * policy kernel of swarm_policy.h directly) */
     int32_t device;                 /* HIP device ordinal, -1 = current */
     int32_t debug_flags;            /* bit 0: force every exact (fp64) fallback path of the fp32 pre-filters; bit 1: disable the lattice path;
-                                     * bit 2: a small batch keeps the full workgroup geometry (no half-occupied variant) -- results are
-                                     * identical with any of them; bits 8..15: diagnostics (tools/ablate.py) */
+                                     * bit 2: a small batch keeps the full workgroup geometry (no half-occupied variant); bit 3: a batch
+                                     * that holds both cell sets the lattice walk serves and cell sets it does not runs the generic scan
+                                     * for every env (one launch) instead of one launch of each kernel; bit 4: those two launches run
+                                     * one after the other on the handle's stream instead of side by side -- results are identical
+                                     * with any of them; bits 8..15: diagnostics (tools/ablate.py) */
     double d_sen;                   /* assembly.py:199  = 0.4 */
     double r_avoid;                 /* assembly.py:124 */
     double size_a;                  /* assembly.py:44   = 0.035 */
@@ -212,10 +215,24 @@ int  swarm_get_indices(swarm_env_t *h, int32_t *neighbor_index, int32_t *in_flag
                        int32_t *sensed_index, int32_t *occupied_index);
 
 /* How many environments currently have target cells that are a row-major subset of a square lattice (the reference's
- * tiled shapes always are, its seven fig PNGs included).  When ALL do (any n_agents up to 256; the sensing window must span at most 15
- * lattice rows), the sensed / occupied bit sets are built by a row walk over the lattice instead of the all-cells scan; results are
- * identical.  debug_flags bit 1 disables that path. */
+ * tiled shapes always are, its seven fig PNGs included).  For such an env (any n_agents up to 256) whose own sensing window spans
+ * at most 15 lattice rows, the sensed / occupied bit sets are built by a row walk over the lattice instead of the all-cells scan;
+ * results are identical.  The choice is made per workgroup, not per batch (swarm_path_envs): other envs of the batch keep the
+ * all-cells scan without taking the row walk from this one.  debug_flags bit 1 disables that path.  After swarm_reset the
+ * answer is n_env if every shape of the set is such a lattice, else 0. */
 int  swarm_lattice_envs(const swarm_env_t *h);
+
+/* How many environments the next launch steps with the row walk (*walk_envs) and with the all-cells scan (*scan_envs); the two
+ * add up to n_env.  The unit is the workgroup: with n_agents < 64 one workgroup holds 64 / npad envs (npad = n_agents rounded up
+ * to a power of two, at least 8), and one env that needs the scan takes its whole workgroup to it.  A batch with envs of both
+ * kinds is stepped by two launches, one of each kernel, each returning at once from the other's workgroups; a batch of one kind
+ * by one launch, as is any batch with debug_flags bit 3 (all scan).  Synchronises the handle's stream and reads the envs'
+ * device records: after swarm_reset only they know which env drew which shape.  SWARM_ERR_STATE before every env has cells.
+ * Cost: the two launches run side by side, which pays while one of them is small; where both are large (about half the
+ * workgroups each) the serial form (debug_flags bit 4) is faster, and a batch in which NO workgroup walks (N < 64 with an
+ * off-lattice env in every workgroup) still pays for a lattice launch that only exits -- bit 3 is the cheaper setting there
+ * ("Mixed batches"). */
+int  swarm_path_envs(swarm_env_t *h, int32_t *walk_envs, int32_t *scan_envs);
 
 /* Roofline helper: bytes one swarm_step moves by SURVEY.md section 8d's accounting IN THIS BUILD'S DTYPES (fp64 state and
  * cells); bench.py's `roofline` uses section 8d's own fp32 figure (821 B per agent-step + 8 B per cell) and reports this one

@@ -336,6 +336,14 @@ class SwarmBatch:
         """Number of envs whose target cells were recognised as a lattice subset (fast sensed/occupied path)."""
         return int(self.lib.swarm_lattice_envs(self.handle))
 
+    def path_envs(self):
+        """(walk, scan): how many envs the next launch steps with the lattice row walk and with the all-cells scan, counted
+        by workgroup (swarm_path_envs).  Synchronises the stream."""
+        walk, scan = ctypes.c_int32(), ctypes.c_int32()
+        self._sync_stream()
+        check(self.lib, self.handle, self.lib.swarm_path_envs(self.handle, ctypes.byref(walk), ctypes.byref(scan)))
+        return int(walk.value), int(scan.value)
+
     # -- measurement helpers --------------------------------------------------------------------------
     def algorithmic_bytes_per_step(self):
         return float(self.lib.swarm_step_algorithmic_bytes(self.handle))

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <new>
@@ -116,18 +117,27 @@ bool detect_lattice(const double *gx, const double *gy, int n, LatEnv &L)
     return true;
 }
 
-// Decide the cell path of the next launches and lay out its LDS.  The row-space lattice path needs every env's cells to
-// be a lattice subset AND a sensing window of at most 15 lattice rows (d_sen < ~7.5 cells: a window row then has at
-// most 17 columns -- one 32-bit word -- and a list at most 240 cells -- one byte per row count); anything else takes the
-// generic scan, which handles arbitrary cell sets.
-void set_lattice_mode(swarm_env *h, bool all_lattice, float rmax, float cmax, int ncols_max)
+// Window rows of the row walk for a cell set with d_sen = R lattice steps; the walk serves at most 15 (d_sen < ~7.5 cells: a
+// window row then has at most 17 columns -- one 32-bit word -- and a list at most 240 cells -- one byte per row count).
+int window_rows(float R) { return (int)std::floor(2.0f * (R + 0.01f)) + 1; }
+
+// Decide the cell path of the next launches and lay out its LDS.  A cell set WALKS (row-space lattice path) when it is a
+// lattice subset whose own sensing window is at most 15 lattice rows; any other set takes the generic scan, which handles
+// arbitrary cell sets.  any_walk / any_scan: some env of the batch may hold a walking / a scanning set; rmax, cmax,
+// ncols_max: the maxima over the walking sets.  All walk: one lattice launch; none walks: one generic launch; both kinds:
+// PATH_MIXED, two launches that share the envs out by workgroup (env_launch) -- or, with debug_flags bit 3, one generic
+// launch for the whole batch.
+void set_lattice_mode(swarm_env *h, bool any_walk, bool any_scan, float rmax, float cmax, int ncols_max)
 {
     KP &k = h->kp;
     k.lat_n32 = ncols_max <= 32 ? 1 : 0;
     k.lat_rw = (int)std::ceil(rmax + 0.02f);
     k.lat_cw = (int)std::ceil(cmax + 0.02f);
-    k.lat_nrs = (int)std::floor(2.0f * (rmax + 0.01f)) + 1; k.lat_nrc = (int)std::floor(2.0f * (cmax + 0.01f)) + 1;
-    k.lattice = (all_lattice && !h->lattice_disabled && k.lat_nrs <= 15) ? 1 : 0;
+    k.lat_nrs = window_rows(rmax); k.lat_nrc = window_rows(cmax);
+    const bool demote = (h->cfg.debug_flags & 8) != 0;
+    h->path_mode = (!any_walk || h->lattice_disabled || k.lat_nrs > 15 || (any_scan && demote)) ? PATH_SCAN : any_scan ? PATH_MIXED : PATH_WALK;
+    k.lattice = h->path_mode != PATH_SCAN ? 1 : 0;
+    k.path_filter = 0;                                     // (a mixed batch's launches set it in their own copies of KP)
     {   // guard band of the fp32 reward decision of the lattice path, in lattice steps (R = d_sen / l <= rmax).  Per cell the
         // model coordinate relative to the agent is off by dx: lattice fit tolerance 1.5e-6 steps, fp32 cast of the relative
         // coordinate (|.| <= 17 steps) 2.1e-6, the walk's scaled form c / R - a / R (two products of magnitude <= 17 / R with
@@ -140,11 +150,12 @@ void set_lattice_mode(swarm_env *h, bool all_lattice, float rmax, float cmax, in
         k.rew_gb_lat = (float)(4e-6 * R / k.d_sen);
     }
     // a small batch of small environments (N < 64) that leaves at least half of the chip's workgroup slots empty: the
-    // half-occupied geometry (Geo<NPAD, true>) -- twice the workgroups, eight lanes per agent in the list phase
+    // half-occupied geometry (Geo<NPAD, true>) -- twice the workgroups, eight lanes per agent in the list phase.  It exists
+    // for the lattice kernel only, and the two launches of a mixed batch must share one workgroup -> env map: all-walk only
     {
         const int epb_full = h->npad < 64 ? 64 / h->npad : 1;
         const long long grid_full = ((long long)h->cfg.n_env + epb_full - 1) / epb_full;
-        h->half = k.lattice && h->npad < 64 && epb_full >= 2 && !(h->cfg.debug_flags & 4) && 2 * grid_full <= (long long)h->n_cu * 6;
+        h->half = h->path_mode == PATH_WALK && h->npad < 64 && epb_full >= 2 && !(h->cfg.debug_flags & 4) && 2 * grid_full <= (long long)h->n_cu * 6;
     }
     env_layout(k, h->npad, h->half);
 }
@@ -169,32 +180,37 @@ int export_pass(swarm_env *h, bool lists, bool cap_even)
     return rc;
 }
 
-// Classify one cell set: is it a lattice subset (and is the lattice path allowed on this handle)?  If so L is its lattice with
-// the step length turned into the radii R / Rc; if not L is all zero.
+// Classify one cell set: is it a lattice subset (and is the lattice path allowed on this handle), and does it walk?  If it
+// walks L is its lattice with the step length turned into the radii R / Rc; if not L is all zero (nrows == 0), which is what
+// tells the kernels of a mixed batch that the generic launch steps this env.
 LatInfo classify_cells(const swarm_env *h, const double *gx, const double *gy, int n, LatEnv &L)
 {
     std::memset(&L, 0, sizeof(L));
     if (h->lattice_disabled || !detect_lattice(gx, gy, n, L)) {
         std::memset(&L, 0, sizeof(L));
-        return LatInfo{false, 0.0f, 0.0f, 0};
+        return LatInfo{false, false, true, 0.0f, 0.0f, 0};
     }
     const double l = L.R;
     L.R = (float)(h->kp.d_sen / l); L.Rc = (float)((h->kp.r_avoid / 2.0) / l);
-    return LatInfo{true, L.R, L.Rc, L.ncols};
+    const LatInfo info = {true, window_rows(L.R) <= 15, window_rows(L.R) > 15, L.R, L.Rc, L.ncols};
+    if (!info.walk) std::memset(&L, 0, sizeof(L));
+    return info;
 }
 
-// Choose the cell path for the cell sets [first, last): all lattices?, and the largest R / Rc / column count among them.  A
-// range of envs stops at the first env that is no lattice (stop_at_miss), a range of shapes passes over such shapes; the
-// path is the generic scan either way.  Returns what it handed to set_lattice_mode.
-LatInfo lattice_mode_of(swarm_env *h, const LatInfo *first, const LatInfo *last, bool stop_at_miss)
+// Choose the cell path for the cell sets [first, last) (envs, or the shapes of the set a reset draws from): are all
+// lattices, does any walk, does any scan, and the largest R / Rc / column count among those that walk.  Returns that
+// summary, which is what it handed to set_lattice_mode.
+LatInfo lattice_mode_of(swarm_env *h, const LatInfo *first, const LatInfo *last)
 {
-    LatInfo m = {true, 0.0f, 0.0f, 0};
+    LatInfo m = {true, false, false, 0.0f, 0.0f, 0};
     for (; first != last; ++first) {
-        if (!first->ok) { m.ok = false; if (stop_at_miss) break; continue; }
+        m.ok = m.ok && first->ok; m.scan = m.scan || first->scan;
+        if (!first->walk) continue;
+        m.walk = true;
         m.R = std::max(m.R, first->R); m.Rc = std::max(m.Rc, first->Rc);
         m.ncols = std::max(m.ncols, first->ncols);
     }
-    set_lattice_mode(h, m.ok, m.R, m.Rc, m.ncols);
+    set_lattice_mode(h, m.walk, m.scan, m.R, m.Rc, m.ncols);
     return m;
 }
 
@@ -301,7 +317,7 @@ int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
     if (!h) return fail(nullptr, SWARM_ERR_INVALID, "out of host memory");
     h->cfg = *cfg; h->device = dev;
     for (int &a : h->attr_smem) a = -1;
-    h->env_lat.assign((size_t)cfg->n_env, LatInfo{false, 0.0f, 0.0f, 0});
+    h->env_lat.assign((size_t)cfg->n_env, LatInfo{false, false, true, 0.0f, 0.0f, 0});
     h->lattice_disabled = (cfg->debug_flags & 2) != 0;
     h->cells_set.assign((size_t)cfg->n_env, 0);
     h->npad = npad_for(cfg->n_agents);
@@ -416,6 +432,9 @@ int swarm_destroy(swarm_env_t *h)
     (void)hipStreamSynchronize(h->stream);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
+    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     delete h;
     return SWARM_OK;
 }
@@ -465,7 +484,7 @@ int swarm_set_cells(swarm_env_t *h, int env_begin, int count, const double *cell
             h->env_lat[(size_t)(env_begin + k)] = classify_cells(h, gx, gy, n_g[k], lat[(size_t)k]);
         }
         HIP_TRY(h, hipMemcpy(h->d_lat.get() + env_begin, lat.data(), (size_t)count * sizeof(LatEnv), hipMemcpyHostToDevice));
-        lattice_mode_of(h, h->env_lat.data(), h->env_lat.data() + h->env_lat.size(), true);
+        lattice_mode_of(h, h->env_lat.data(), h->env_lat.data() + h->env_lat.size());
     }
     for (int k = 0; k < count; ++k) h->cells_set[(size_t)(env_begin + k)] = 1;
     h->have_cells = true;
@@ -514,8 +533,9 @@ int swarm_reset(swarm_env_t *h, uint64_t seed, uint64_t episode, int64_t env_off
     if (int rc = interleave(h, 0, h->cfg.n_env)) return rc;
     std::fill(h->cells_set.begin(), h->cells_set.end(), 1);
     h->have_cells = h->have_state = true;
-    // per-env bounds for a later partial swarm_set_cells: the shape set's maxima are valid for every env
-    const LatInfo all = lattice_mode_of(h, h->shape_lat.data(), h->shape_lat.data() + h->shape_lat.size(), false);
+    // per-env bounds for a later partial swarm_set_cells: the shape set's summary is valid for every env (which env drew a
+    // shape that walks only the device records know: a set with both kinds leaves the batch mixed)
+    const LatInfo all = lattice_mode_of(h, h->shape_lat.data(), h->shape_lat.data() + h->shape_lat.size());
     std::fill(h->env_lat.begin(), h->env_lat.end(), all);
     h->observed = false;
     return swarm_observe(h, obs);
@@ -535,7 +555,7 @@ int swarm_select_shape(swarm_env_t *h, int32_t shape_index, void *obs)
     std::fill(h->cells_set.begin(), h->cells_set.end(), 1);
     std::fill(h->env_lat.begin(), h->env_lat.end(), *one);
     h->have_cells = true;
-    lattice_mode_of(h, one, one + 1, true);
+    lattice_mode_of(h, one, one + 1);
     h->observed = false;
     return swarm_observe(h, obs);
 }
@@ -762,6 +782,31 @@ int swarm_lattice_envs(const swarm_env_t *h)
     int n = 0;
     for (const LatInfo &i : h->env_lat) n += i.ok ? 1 : 0;
     return n;
+}
+
+int swarm_path_envs(swarm_env_t *h, int32_t *walk_envs, int32_t *scan_envs)
+{
+    if (!h) return SWARM_ERR_INVALID;
+    if (!walk_envs || !scan_envs) return fail(h, SWARM_ERR_INVALID, "swarm_path_envs: null argument");
+    if (!h->have_cells) return fail(h, SWARM_ERR_STATE, "swarm_path_envs: target cells not set for every env (swarm_set_cells)");
+    DeviceGuard g(h->device);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const int E = h->cfg.n_env;
+    int walk = h->path_mode == PATH_WALK ? E : 0;
+    if (h->path_mode == PATH_MIXED) {
+        // what the two launches' filters read: nrows of every env's device record, by workgroup of the full geometry
+        std::vector<int> nrows((size_t)E);
+        HIP_TRY(h, hipMemcpy2D(nrows.data(), sizeof(int), reinterpret_cast<const char *>(h->d_lat.get()) + offsetof(LatEnv, nrows), sizeof(LatEnv),
+                               sizeof(int), (size_t)E, hipMemcpyDeviceToHost));
+        const int epb = h->npad < 64 ? 64 / h->npad : 1;
+        for (int e0 = 0; e0 < E; e0 += epb) {
+            bool any_zero = false;
+            for (int k = 0; k < epb; ++k) any_zero = any_zero || nrows[(size_t)std::min(e0 + k, E - 1)] == 0;
+            if (!any_zero) walk += std::min(epb, E - e0);
+        }
+    }
+    *walk_envs = walk; *scan_envs = E - walk;
+    return SWARM_OK;
 }
 
 double swarm_step_algorithmic_bytes(const swarm_env_t *h)

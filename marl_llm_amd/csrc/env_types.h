@@ -64,7 +64,8 @@ struct KP {
     int off_hdr, off_srow, off_pcr, off_perm, off_rres, off_orow, off_partd;
     float rew_ga_lat, rew_gb_lat;   // guard band of the fp32 reward decision in lattice steps (see swarm_create)
     float rew_thr_k;           // 0.05 / d_sen: the reward's |v| threshold in lattice steps is rew_thr_k * (d_sen / l)
-    int lattice;               // every env's cells are a lattice subset whose sensing window is <= 15 rows: row-space path
+    int lattice;               // this launch takes the row-space path: every env it steps has cells that are a lattice subset whose
+                               // sensing window is <= 15 rows (a mixed batch's other envs go to a second, generic launch: path_filter)
     int lat_rw, lat_cw;        // row half-windows (lattice steps) for d_sen and r_avoid/2
     int lat_nrs, lat_nrc;      // rows a radius can touch: floor(2 (rho_max + margin)) + 1, for d_sen and r_avoid/2
     int lat_n32;               // every env's lattice has <= 32 columns: 32-bit row masks
@@ -86,6 +87,11 @@ struct KP {
     int llm;                   // also evaluate that twin and leave it in act_next as the NEXT step's action (ENV:525-529)
     double2 *act_next;         // [E][N]
     long long *stamps;         // diagnostic build only (-DSWARM_STAMPS): per-block phase clocks
+    int path_filter;           // 0: every workgroup runs.  The two launches of a mixed batch (env_launch): 1 = the lattice launch, a
+                               // workgroup returns at once if ANY of its envs has lat[e].nrows == 0; 2 = the generic launch, a
+                               // workgroup returns at once if ALL of its envs have nrows > 0 -- each env is stepped by exactly one.
+                               // The host picks the filtered instantiation of the kernel by it (k_env's FILT); the kernel's own
+                               // test is compiled in, by the launch kind
 };
 
 // The uploaded shape set, as the reset and shape-switch kernels read it
@@ -98,13 +104,19 @@ struct ShapeSet {
     const LatEnv *lat;        // [S] lattice of the un-rotated shape (nrows == 0: not a lattice)
 };
 
-// The host's record of one cell set (an env's, or a shape's of the uploaded set): is it a lattice subset, and if so its
-// LatEnv::R / Rc / ncols (read only where ok is set).
+// The host's record of one cell set (an env's, or a shape's of the uploaded set): is it a lattice subset (ok), and does the
+// row walk serve it (walk: a lattice whose OWN sensing window is <= 15 rows, on a handle with the lattice path enabled; its
+// LatEnv::R / Rc / ncols are read only where walk is set)?  A set that does not walk is uploaded with an all-zero LatEnv.
+// scan = !walk for one cell set.  After swarm_reset the host does not know which env drew which shape: every env then holds
+// the shape set's summary, where walk / scan say that SOME shape walks / does not, and both may be set.
 struct LatInfo {
-    bool ok;
+    bool ok, walk, scan;
     float R, Rc;
     int ncols;
 };
+
+// The cell path of the next launches (set_lattice_mode): one lattice launch, one generic launch, or both with KP::path_filter
+enum PathMode { PATH_SCAN = 0, PATH_WALK = 1, PATH_MIXED = 2 };
 
 }  // namespace swarm_internal
 
@@ -116,8 +128,13 @@ struct swarm_env {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_cells = false, have_state = false, observed = false;
-    int attr_smem[24];
-    bool half = false;             // the half-occupied geometry is in use (set_lattice_mode)
+    int attr_smem[48];
+    bool half = false;             // the half-occupied geometry is in use (set_lattice_mode; all-walk batches only)
+    int path_mode = swarm_internal::PATH_SCAN;
+    // the generic launch of a mixed batch runs beside the lattice launch on this stream, forked from and joined to the
+    // handle's stream by the two events; created by the first mixed launch that overlaps, destroyed by swarm_destroy
+    hipStream_t aux_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int n_cu = 256;
     std::vector<char> cells_set;
     std::string err;

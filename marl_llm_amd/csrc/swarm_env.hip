@@ -329,7 +329,10 @@ __device__ __forceinline__ float psi5_u_f32(float u)
     return c;
 }
 
-template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF = false>
+// FILT: one of the two launches of a mixed batch (KP::path_filter).  A template parameter and not a run-time test: any early
+// exit, however cheap, changes how the generic kernel's scalar registers are spilled (+10 KB of lane reads at N = 64, past
+// the instruction cache), so the kernels of unmixed batches are compiled without it and stay what they were.
+template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF = false, bool FILT = false>
 __global__ void __launch_bounds__((Geo<NPAD, HALF>::T), (LAT ? Geo<NPAD, HALF>::WPS_LAT : Geo<NPAD, HALF>::WPS_GEN))
 k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__restrict__ obs,
       float *__restrict__ reward, uint8_t *__restrict__ done, OT *__restrict__ a_prior)
@@ -338,6 +341,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
     constexpr int AG = G_::AG, EPB = G_::EPB, NW = G_::NW, WPE = G_::WPE, T = G_::T;
     constexpr int ACTW = G_::ACTW, LPA = G_::LPA, AGW = G_::AGW;
     static_assert(!HALF || LAT, "the half-occupied geometry exists for the lattice path only");
+    static_assert(!HALF || !FILT, "the launches of a mixed batch use the full geometry");
     typedef typename Pair<OT>::type OT2;
 
     extern __shared__ __align__(16) unsigned char smem[];
@@ -374,6 +378,17 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
     unsigned char *perm = smem + LO(perm);                             // [T/64][64] agent threads in ascending list length (per wave)
     unsigned *orow = reinterpret_cast<unsigned *>(smem + P.off_orow);    // [NRC][AG] occupied columns (export launches only)
 
+    // a mixed batch (KP::path_filter != 0) is two launches over the same grid: this workgroup belongs to the lattice launch
+    // if every one of its envs has a lattice record (nrows > 0), else -- as a whole -- to the generic one.  Scalar loads and a
+    // workgroup-uniform exit, ahead of the first LDS write and the first barrier.
+    if constexpr (FILT) {
+        bool any_zero = false;
+        for (int k = 0; k < EPB; ++k) {
+            const int ek = blockIdx.x * EPB + k;
+            any_zero = any_zero || P.lat[ek < P.n_env ? ek : P.n_env - 1].nrows == 0;
+        }
+        if (any_zero == LAT) return;
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     STAMP(0);
     const int at = tid % AG;                 // agent thread
@@ -2050,50 +2065,80 @@ void for_geometry(int npad, bool half, F &&f)
     }
 }
 
-template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF>
-int launch_t(swarm_env *h, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior)
+// What one launch of the step kernel takes from its caller: the kernel argument (kp->lattice chooses the kernel), the stream,
+// and whether the lattice kernel runs in the half-occupied geometry
+struct Launch {
+    const KP *kp;
+    hipStream_t st;
+    bool half;
+};
+
+template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF, bool FILT = false>
+int launch_t(swarm_env *h, const Launch &l, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior)
 {
     constexpr int T = Geo<NPAD, HALF>::T, EPB = Geo<NPAD, HALF>::EPB;
-    auto kern = k_env<NPAD, OT, DO_STEP, LAT, HALF>;
-    int smem = !LAT ? h->kp.smem_generic : (h->kp.export_idx ? h->kp.smem_lat_export : h->kp.smem_lat);
+    auto kern = k_env<NPAD, OT, DO_STEP, LAT, HALF, FILT>;
+    const KP &kp = *l.kp;
+    int smem = !LAT ? kp.smem_generic : (kp.export_idx ? kp.smem_lat_export : kp.smem_lat);
 #ifdef SWARM_EXTRA_SMEM
     smem += SWARM_EXTRA_SMEM;                            // occupancy experiments only
 #endif
-    int &attr = h->attr_smem[(DO_STEP ? 1 : 0) + (sizeof(OT) == 8 ? 2 : sizeof(OT) == 2 ? 4 : 0) + (LAT ? 6 : 0) + (HALF ? 12 : 0)];   // raise the dynamic-LDS cap once per instantiation
+    int &attr = h->attr_smem[(DO_STEP ? 1 : 0) + (sizeof(OT) == 8 ? 2 : sizeof(OT) == 2 ? 4 : 0) + (LAT ? 6 : 0) + (HALF ? 12 : 0) + (FILT ? 24 : 0)];   // raise the dynamic-LDS cap once per instantiation
     if (attr < smem) {
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr = smem;
     }
     const int grid = (h->cfg.n_env + EPB - 1) / EPB;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T), smem, h->stream, h->kp, action, act_f64,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(T), smem, l.st, kp, action, act_f64,
                        static_cast<OT *>(obs), reward, done, static_cast<OT *>(a_prior));
     HIP_TRY(h, hipGetLastError());
     return SWARM_OK;
 }
 
 template <int NPAD, typename OT, bool DO_STEP>
-int launch_l(swarm_env *h, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior)
+int launch_l(swarm_env *h, const Launch &l, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior)
 {
     if constexpr (NPAD < 64) {
-        if (h->kp.lattice && h->half) return launch_t<NPAD, OT, DO_STEP, true, true>(h, action, act_f64, obs, reward, done, a_prior);
+        if (l.kp->lattice && l.half) return launch_t<NPAD, OT, DO_STEP, true, true>(h, l, action, act_f64, obs, reward, done, a_prior);
     }
-    return h->kp.lattice ? launch_t<NPAD, OT, DO_STEP, true, false>(h, action, act_f64, obs, reward, done, a_prior)
-                         : launch_t<NPAD, OT, DO_STEP, false, false>(h, action, act_f64, obs, reward, done, a_prior);
+    if (l.kp->path_filter != 0) {              // a launch of a mixed batch: 1 = its lattice launch, 2 = its generic launch
+        if (l.kp->path_filter != (l.kp->lattice ? 1 : 2) || l.half) return fail(h, SWARM_ERR_INVALID, "env_launch: path_filter does not match the launch");
+        return l.kp->lattice ? launch_t<NPAD, OT, DO_STEP, true, false, true>(h, l, action, act_f64, obs, reward, done, a_prior)
+                             : launch_t<NPAD, OT, DO_STEP, false, false, true>(h, l, action, act_f64, obs, reward, done, a_prior);
+    }
+    return l.kp->lattice ? launch_t<NPAD, OT, DO_STEP, true, false>(h, l, action, act_f64, obs, reward, done, a_prior)
+                         : launch_t<NPAD, OT, DO_STEP, false, false>(h, l, action, act_f64, obs, reward, done, a_prior);
 }
 
 template <int NPAD>
-int launch_n(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done,
+int launch_n(swarm_env *h, const Launch &l, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done,
              void *a_prior)
 {
     const int dt = h->cfg.obs_dtype;
     if (do_step) {
-        return dt == SWARM_F64 ? launch_l<NPAD, double, true>(h, action, act_f64, obs, reward, done, a_prior)
-             : dt == SWARM_BF16 ? launch_l<NPAD, __bf16, true>(h, action, act_f64, obs, reward, done, a_prior)
-                                : launch_l<NPAD, float, true>(h, action, act_f64, obs, reward, done, a_prior);
+        return dt == SWARM_F64 ? launch_l<NPAD, double, true>(h, l, action, act_f64, obs, reward, done, a_prior)
+             : dt == SWARM_BF16 ? launch_l<NPAD, __bf16, true>(h, l, action, act_f64, obs, reward, done, a_prior)
+                                : launch_l<NPAD, float, true>(h, l, action, act_f64, obs, reward, done, a_prior);
     }
-    return dt == SWARM_F64 ? launch_l<NPAD, double, false>(h, action, act_f64, obs, reward, done, a_prior)
-         : dt == SWARM_BF16 ? launch_l<NPAD, __bf16, false>(h, action, act_f64, obs, reward, done, a_prior)
-                            : launch_l<NPAD, float, false>(h, action, act_f64, obs, reward, done, a_prior);
+    return dt == SWARM_F64 ? launch_l<NPAD, double, false>(h, l, action, act_f64, obs, reward, done, a_prior)
+         : dt == SWARM_BF16 ? launch_l<NPAD, __bf16, false>(h, l, action, act_f64, obs, reward, done, a_prior)
+                            : launch_l<NPAD, float, false>(h, l, action, act_f64, obs, reward, done, a_prior);
+}
+
+// one launch of the step kernel: the instantiation of the handle's agent count and obs dtype that l asks for
+int launch_one(swarm_env *h, const Launch &l, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done,
+               void *a_prior)
+{
+    // (SWARM_ONLY_NPAD: development builds with a single instantiation -- quick register / code-size checks and A/B runs)
+#ifndef SWARM_ONLY_NPAD
+#define SWARM_ONLY_NPAD 0
+#endif
+#define SWARM_CASE(n) case n: if (SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) return launch_n<(SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) ? n : (SWARM_ONLY_NPAD)>(h, l, do_step, action, act_f64, obs, reward, done, a_prior); break
+    switch (h->npad) {
+    SWARM_CASE(8); SWARM_CASE(16); SWARM_CASE(32); SWARM_CASE(64); SWARM_CASE(128); SWARM_CASE(256);
+    }
+#undef SWARM_CASE
+    return fail(h, SWARM_ERR_INVALID, "unsupported agent count");
 }
 
 }  // namespace
@@ -2108,16 +2153,38 @@ void env_layout(KP &k, int npad, bool half)
 int env_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done,
                void *a_prior)
 {
-    // (SWARM_ONLY_NPAD: development builds with a single instantiation -- quick register / code-size checks and A/B runs)
-#ifndef SWARM_ONLY_NPAD
-#define SWARM_ONLY_NPAD 0
-#endif
-#define SWARM_CASE(n) case n: if (SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) return launch_n<(SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) ? n : (SWARM_ONLY_NPAD)>(h, do_step, action, act_f64, obs, reward, done, a_prior); break
-    switch (h->npad) {
-    SWARM_CASE(8); SWARM_CASE(16); SWARM_CASE(32); SWARM_CASE(64); SWARM_CASE(128); SWARM_CASE(256);
+    if (h->path_mode != PATH_MIXED)          // one kernel for the whole batch, as the handle's KP describes it
+        return launch_one(h, Launch{&h->kp, h->stream, h->half}, do_step, action, act_f64, obs, reward, done, a_prior);
+    // A mixed batch: the generic kernel steps the workgroups that hold an env without a lattice record, the lattice kernel the
+    // others; both over the full geometry, so that they agree on which envs a workgroup holds, and each returns at once from
+    // the other's workgroups (KP::path_filter).  The generic launch's KP is the handle's (export switches, pointers and all)
+    // with the generic LDS layout.  The launches touch disjoint envs, so the generic one runs beside the lattice one on the
+    // handle's auxiliary stream, forked from and joined to the handle's stream by events -- no host synchronisation;
+    // debug_flags bit 4: one after the other on the handle's stream.
+    KP gen = h->kp, lat = h->kp;
+    gen.lattice = 0; env_layout(gen, h->npad, false); gen.path_filter = 2;
+    lat.path_filter = 1;
+    if (h->cfg.debug_flags & 16) {
+        const int rc = launch_one(h, Launch{&gen, h->stream, false}, do_step, action, act_f64, obs, reward, done, a_prior);
+        if (rc != SWARM_OK) return rc;
+        return launch_one(h, Launch{&lat, h->stream, false}, do_step, action, act_f64, obs, reward, done, a_prior);
     }
-#undef SWARM_CASE
-    return fail(h, SWARM_ERR_INVALID, "unsupported agent count");
+    if (!h->aux_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
+    if (!h->ev_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    if (!h->ev_join) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+    HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
+    // from here the aux stream may hold work: nothing returns before the streams are joined again
+    const int rc_gen = launch_one(h, Launch{&gen, h->aux_stream, false}, do_step, action, act_f64, obs, reward, done, a_prior);
+    hipError_t e_join = hipEventRecord(h->ev_join, h->aux_stream);
+    const int rc_lat = launch_one(h, Launch{&lat, h->stream, false}, do_step, action, act_f64, obs, reward, done, a_prior);
+    if (e_join == hipSuccess) e_join = hipStreamWaitEvent(h->stream, h->ev_join, 0);
+    if (e_join != hipSuccess) {                  // no event to wait on: the host waits for the generic launch instead (under a
+                                                 // graph capture that wait fails too; the call is failing already and says so)
+        (void)hipStreamSynchronize(h->aux_stream);
+        if (rc_gen == SWARM_OK && rc_lat == SWARM_OK) HIP_TRY_AS(h, "joining the generic launch of a mixed batch", e_join);
+    }
+    return rc_gen != SWARM_OK ? rc_gen : rc_lat;
 }
 
 }  // namespace swarm_internal

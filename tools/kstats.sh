@@ -4,10 +4,16 @@
 # the code past the cache costs far more than it saves -- check after every kernel edit.
 R=$(cd $(dirname $0)/.. && pwd)
 T=$(mktemp -d)
-cd $T && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -I$R/include --save-temps -c $R/marl_llm_amd/csrc/swarm_env.hip -o $T/o.o 2>/dev/null
+# every k_env instantiation is listed, by its template arguments as the symbol spells them: I Li<NPAD>E <f|d|DF16b = OBS_T>
+# Lb<DO_STEP>E Lb<LAT>E Lb<HALF>E Lb<FILT>E.  USE_ASM=<file>: read a kept assembly (KEEP_ASM) instead of compiling the step kernel.
 S=$T/swarm_env-hip-amdgcn-amd-amdhsa-gfx950.s
-for K in "ILi64EfLb1ELb1ELb0E" "ILi64EfLb1ELb0ELb0E" "ILi64EfLb0ELb1ELb0E" "ILi32EfLb1ELb1ELb0E" "ILi32EfLb1ELb1ELb1E" "ILi8EfLb1ELb1ELb0E" "ILi128EfLb1ELb1ELb0E" "ILi256EfLb1ELb1ELb0E" "ILi256EfLb1ELb0ELb0E" "ILi64EdLb1ELb1ELb0E"; do
-  L=$(grep -n "^_ZN12_GLOBAL__N_15k_env${K}EEv[A-Za-z0-9_]*:" $S | cut -d: -f1)
+if [ -n "$USE_ASM" ]; then cp $USE_ASM $S; else
+cd $T && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -I$R/include --save-temps -c $R/marl_llm_amd/csrc/swarm_env.hip -o $T/o.o 2>/dev/null
+fi
+cd $T
+for SYM in $(grep -o "^_ZN12_GLOBAL__N_15k_envI[A-Za-z0-9_]*:" $S | tr -d : | sort); do
+  K=${SYM#_ZN12_GLOBAL__N_15k_env}; K=${K%%EEv*}
+  L=$(grep -n "^${SYM}:" $S | cut -d: -f1)
   E=$(awk -v L=$L 'NR>L && /\.end_amdhsa_kernel/{print NR; exit}' $S)
   echo "k_env<$K>" $(awk -v L=$L 'NR>L && /; (NumVgprs|ScratchSize|Occupancy|codeLenInByte)/{printf "%s ", $0; n++} n>=4{exit}' $S) "; spill instructions:" $(sed -n "${L},${E}p" $S | grep -c "Folded Spill\|Folded Reload")
 done

@@ -1,17 +1,23 @@
 #!/usr/bin/env python3
 """Consistency stress (GPU): free-running batches with noisy prior actions through the four code-path combinations --
 fast / every exact fallback forced (debug_flags bit 0) x lattice walk / generic scan (bit 1) -- must produce bit-identical
-observations, rewards, priors, state and index scratch.  Complements tests/test_gpu_parity.py (which checks against the
+observations, rewards, priors, state and index scratch; so must a mixed batch (every second env's cells jittered off the
+lattice: one launch of each kernel per step) and its generic-only twin (bit 1).  Complements tests/test_gpu_parity.py (which checks against the
 oracle at sizes the oracle finishes in seconds) at millions of agent-steps."""
 import sys, torch, numpy as np
-sys.path.insert(0, '/root/repo')
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from marl_llm_amd.batched import SwarmBatch
 from marl_llm_amd.shapes import r_avoid_for, synthetic_shape_set
 from marl_llm_amd.synth import synthetic_batch
 shapes = synthetic_shape_set()
-def run(n_a, E, flags, steps, seed, frac, g_max=80):
+def run(n_a, E, flags, steps, seed, frac, g_max=80, mixed=False):
     ra = r_avoid_for(n_a, shapes)
     sy = synthetic_batch(E, n_a, shapes, seed=seed, assembled_fraction=frac)
+    if mixed:                     # half the envs leave the lattice: their workgroups go to the generic launch
+        rng = np.random.default_rng(seed)
+        for e in range(0, E, 2):
+            sy["cells"][e, :, : sy["n_g"][e]] += rng.normal(0, 0.004, (2, sy["n_g"][e]))
     sb = SwarmBatch(n_env=E, n_agents=n_a, n_cells_max=sy["cells"].shape[2], r_avoid=ra, debug_flags=flags, g_max=g_max, device="cuda:0")
     sb.set_cells(sy["cells"], sy["n_g"], sy["l_cell"]); sb.set_state(sy["p"], sy["dp"]); sb.observe()
     gen = torch.Generator(device="cuda").manual_seed(seed)
@@ -39,4 +45,10 @@ for (n_a, E, steps, frac, g_max) in CASES:
         same = all(torch.equal(a, b) for a, b in zip(ref, got))
         ok &= same
         print(f"N={n_a} E={E} steps={steps} frac={frac} G={g_max} flags={flags}: {'identical' if same else 'MISMATCH'}  reward sum {ref[1].sum().item():.0f}", flush=True)
+for (n_a, E, steps, frac, g_max) in CASES:
+    ref = run(n_a, E, 0, steps, SEED, frac, g_max, mixed=True)
+    got = run(n_a, E, 2, steps, SEED, frac, g_max, mixed=True)
+    same = all(torch.equal(a, b) for a, b in zip(ref, got))
+    ok &= same
+    print(f"N={n_a} E={E} steps={steps} frac={frac} G={g_max} mixed, default vs flags=2: {'identical' if same else 'MISMATCH'}  reward sum {ref[1].sum().item():.0f}", flush=True)
 print("ALL IDENTICAL" if ok else "FAILURES")
