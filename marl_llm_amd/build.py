@@ -15,6 +15,8 @@ SRCS = [os.path.join(PKG, "csrc", f) for f in ("swarm_env.hip", "env_kernels.hip
 INC = os.path.join(ROOT, "include")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libswarmenv.so")
+# what every source is compiled with, here and in tools/isa_diff.py (the include directory and -DSWARM_STAMPS come on top)
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 
 
 def hipcc_path():
@@ -39,8 +41,7 @@ def build_lib(force=False, verbose=False, stamps=False):
     if not stamps and not force and not needs_build():
         return LIB
     os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-           "-I" + INC] + (["-DSWARM_STAMPS"] if stamps else []) + SRCS + ["-o", out]
+    cmd = [hipcc_path()] + HIPCC_FLAGS + ["-shared", "-I" + INC] + (["-DSWARM_STAMPS"] if stamps else []) + SRCS + ["-o", out]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

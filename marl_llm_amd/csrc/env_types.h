@@ -34,12 +34,13 @@ struct LatEnv {
 };
 
 // The kernel argument of every env kernel.  Field order, types and size are part of the step kernel's device code (the
-// scalar loads address the fields by offset): append, never move.  off_cxy and off_rres are dead -- no kernel reads them.
+// scalar loads address the fields by offset): append, never move.  cxy_stride, off_cxy and off_rres are dead -- no kernel
+// reads them and the host leaves them zero; they keep their places for the fields behind them.
 struct KP {
     int n_env, n_a, ng_max, ngw, topo, g_max, occ_max, obs_dim;
     int with_self, periodic, boundary, with_prior, export_idx;
     int export_small;          // also write neighbor_index / nearest cell / in_flags to HBM (export launches only: the step itself keeps them in LDS)
-    int cxy_stride;            // double2 elements per env in LDS
+    int cxy_stride;            // dead (was: double2 elements per env in LDS)
     int cxq_stride;            // floats per env in the fp32 pair layout
     int g_stride;              // int16 elements per agent row in LDS
     int off_cxy, off_sp, off_cmask, off_sbits, off_obits, off_sidx, off_snei, off_sncf, off_snear, off_pc;

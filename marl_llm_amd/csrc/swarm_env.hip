@@ -314,8 +314,6 @@ __device__ __forceinline__ float psi_u_f32(float u)
     return c;
 }
 
-// LAT: every env's target cells are a lattice subset (host-detected, KP::lattice) -- a compile-time switch, so that each
-// instantiation carries ONE cell path and stays inside the 64 KB instruction cache.
 // The same weight as a degree-5 polynomial (Chebyshev-node fit; |abs err| < 6.5e-7 in fp32 Horner form): one fused multiply-add
 // less per kept cell in the lattice path's list walk; the reward's guard band there allows 1.2e-6 for it (set_lattice_mode).
 __device__ __forceinline__ float psi5_u_f32(float u)
@@ -329,9 +327,31 @@ __device__ __forceinline__ float psi5_u_f32(float u)
     return c;
 }
 
+// LAT: every env's target cells are a lattice subset (host-detected, KP::lattice) -- a compile-time switch, so that each
+// instantiation carries ONE cell path and stays inside the 64 KB instruction cache: the row-space lattice walk, or the
+// generic scan of all cells.
 // FILT: one of the two launches of a mixed batch (KP::path_filter).  A template parameter and not a run-time test: any early
 // exit, however cheap, changes how the generic kernel's scalar registers are spilled (+10 KB of lane reads at N = 64, past
 // the instruction cache), so the kernels of unmixed batches are compiled without it and stay what they were.
+//
+// The kernel in order, and what ends each part ("barrier": __syncthreads; "lattice | generic" where the two paths differ):
+//   1 prologue      the step's global loads; lattice row tables | fp32 cell copy -> LDS; split A: forces, integration, new
+//                   state -> LDS and HBM.  Barrier: state, tables and cell copy are published.
+//   2 pair pass     the threshold masks of every agent pair, dealt over the splits.  Barrier: the masks are complete.  Then
+//                   split B alone: ordered neighbour insertion, contact spring of the next step -- beside the others' part 3.
+//   3 walk | scan   sensed rows, covered columns and the walking splits' nearest-cell candidates | sensed words, occupied
+//                   words (N <= 64) or per-cell ballots, every split's candidate.  Barrier: also publishes B's neighbour lists.
+//   4 merge         nearest cell and in-shape flag, in every split alike; split A stores them.  No barrier of its own: the
+//                   next one publishes them.
+//   5 lattice tail  (K) kept rows, their counts, list fill: barrier.  (S) rank by list length: barrier.  (E) list emission
+//                   and fp32 reward sums, each wave for its own sixteen agents: wave barrier.  (R) reward, inside the wave.
+//                   Then part 7, no barrier.
+//     generic tail  occupied-cell filter: barrier.  Clearing the rank-select bits: barrier.  Rank select: barrier (N > 64, or
+//                   an agent over the cap).  List emission: the same barrier.  fp32 reward sums: barrier.  Verdict and
+//                   reward on split A.
+//   6 export        export launches only, split A (lattice: behind a barrier, the other waves' lists must be complete).
+//   7 outputs       prior policy of the next step (split B), observation heads, sensed rows.  No barrier; the workgroup
+//                   ends with its slowest wave.  The lattice kernel runs them at the end of part 5, ahead of part 6.
 template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF = false, bool FILT = false>
 __global__ void __launch_bounds__((Geo<NPAD, HALF>::T), (LAT ? Geo<NPAD, HALF>::WPS_LAT : Geo<NPAD, HALF>::WPS_GEN))
 k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__restrict__ obs,
@@ -349,34 +369,39 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
     // (Geo::CT_MAP), else layout_t's run-time offsets -- on lattice launches the same map, handed over in KP
     typedef LatMap<NPAD, HALF> LM;
 #define LO(r) ((LAT && G_::CT_MAP) ? LM::r : P.off_##r)
-    float *cxq = reinterpret_cast<float *>(smem + P.off_cxyf);          // fp32 cells, per PAIR {xa, xb, ya, yb} (pre-filter)
-    double *sp = reinterpret_cast<double *>(smem + LO(sp));            // [4][AG]: px, py, vx, vy
-    u64 *cmask = reinterpret_cast<u64 *>(smem + P.off_cmask);            // [cell][NW]
-    float *rsum = reinterpret_cast<float *>(smem + P.off_cmask);         // [WPE][3][AG]  (aliases cmask, later phase)
-    unsigned *sbits = reinterpret_cast<unsigned *>(smem + P.off_sbits);  // [word][AG]
-    unsigned *obits = reinterpret_cast<unsigned *>(smem + P.off_obits);  // [word][AG] (export launches only)
-    short *sidx = reinterpret_cast<short *>(smem + LO(sidx));          // [AG][g_stride]
+    // The LDS views of BOTH paths, each tagged with the path that reads it: [both], [gen] = generic scan only, [lat] = lattice
+    // walk only.  They stay here, in this order, one path's beside the other's: a view declared in the block that uses it
+    // takes the load of its run-time offset out of the entry block, and the order in which the regions are first named
+    // reaches the instruction schedule.  Tried view by view: the device code of every instantiation that reads the moved
+    // view's offset at run time changes, and for the lattice views that of the compile-time map's instantiations as well.
+    float *cxq = reinterpret_cast<float *>(smem + P.off_cxyf);          // [gen] fp32 cells, per PAIR {xa, xb, ya, yb} (pre-filter)
+    double *sp = reinterpret_cast<double *>(smem + LO(sp));            // [both] [4][AG]: px, py, vx, vy
+    u64 *cmask = reinterpret_cast<u64 *>(smem + P.off_cmask);            // [gen] [cell][NW]
+    float *rsum = reinterpret_cast<float *>(smem + P.off_cmask);         // [gen] [WPE][3][AG]  (aliases cmask, later phase)
+    unsigned *sbits = reinterpret_cast<unsigned *>(smem + P.off_sbits);  // [gen] [word][AG] sensed, then kept bits
+    unsigned *obits = reinterpret_cast<unsigned *>(smem + P.off_obits);  // [gen] [word][AG] (export launches only)
+    short *sidx = reinterpret_cast<short *>(smem + LO(sidx));          // [both] [AG][g_stride]
     typedef std::conditional_t<LAT, short, int> pc_t;                    // (lattice launches: 16-bit -- the kernel's LDS budget is seven workgroups per CU)
-    pc_t *part_c = reinterpret_cast<pc_t *>(smem + LO(partc));         // [WPE][AG] per-split nearest-cell candidates (cell index < 2^15)
-    u64 *pm = reinterpret_cast<u64 *>(smem + LO(sidx));                // [WPE][2 or 3][NW][AG] partial pair masks (aliases sidx, earlier phase)
-    unsigned *owords = reinterpret_cast<unsigned *>(smem + P.off_cmask); // [word][AG] occupied bits (NW == 1; aliases cmask)
-    short *snei = reinterpret_cast<short *>(smem + LO(snei));          // [AG][kTopoMax]
-    int *sncf = reinterpret_cast<int *>(smem + LO(sncf));              // [AG]: nearest cell | in_flag<<30
-    u64 *snear = reinterpret_cast<u64 *>(smem + LO(snear));            // [NW][AG] nearby-agent masks
-    u64 *lrm = reinterpret_cast<u64 *>(smem + LO(lat));                // [EPB][64] lattice row masks
-    short *lrs = reinterpret_cast<short *>(smem + LO(lat) + (size_t)EPB * 64 * 8);   // [EPB][64] row starts
-    unsigned *cov = reinterpret_cast<unsigned *>(smem + LO(cov));      // [EPB][ngw+1] cells within r_avoid/2 of ANY agent
-    int *sflag = reinterpret_cast<int *>(smem + LO(flag));             // per-lane exception flags: generic launches [AG] ints; lattice launches one BYTE per agent thread (flag_* below)
-    unsigned char *pc = smem + P.off_pc;                                 // [word][AG] kept-bit counts
+    pc_t *part_c = reinterpret_cast<pc_t *>(smem + LO(partc));         // [both] [WPE][AG] per-split nearest-cell candidates (cell index < 2^15)
+    u64 *pm = reinterpret_cast<u64 *>(smem + LO(sidx));                // [both] [WPE][2 or 3][NW][AG] partial pair masks (aliases sidx, earlier phase)
+    unsigned *owords = reinterpret_cast<unsigned *>(smem + P.off_cmask); // [gen] [word][AG] occupied bits (NW == 1; aliases cmask)
+    short *snei = reinterpret_cast<short *>(smem + LO(snei));          // [both] [AG][kTopoMax]
+    int *sncf = reinterpret_cast<int *>(smem + LO(sncf));              // [both] [AG]: nearest cell | in_flag<<30
+    u64 *snear = reinterpret_cast<u64 *>(smem + LO(snear));            // [both] [NW][AG] nearby-agent masks
+    u64 *lrm = reinterpret_cast<u64 *>(smem + LO(lat));                // [lat] [EPB][64] lattice row masks
+    short *lrs = reinterpret_cast<short *>(smem + LO(lat) + (size_t)EPB * 64 * 8);   // [lat] [EPB][64] row starts
+    int *sflag = reinterpret_cast<int *>(smem + LO(flag));             // [lat] per-lane exception flags, one BYTE per agent thread (flag_get below); generic launches: [AG] ints,
+                                                                         // cleared in the prologue and unread by the generic kernel
+    unsigned char *pc = smem + P.off_pc;                                 // [gen] [word][AG] kept-bit counts
     // row-space representation of the lattice path (LAT): window row t of agent thread `at` = lattice row b0 + t, its
     // columns are stored relative to the agent's first column ca0 (<= 17 columns are ever in range: 32-bit words)
-    constexpr int NRC = LM::NRC;                                            // window rows stored per agent (lat_nrs <= 15)
-    float4 *hdr = reinterpret_cast<float4 *>(smem + LO(hdr));          // [AG] {apr = a - ca0, bpr = b - b0, b0, ca0} (last two: ints)
-    unsigned *srow = reinterpret_cast<unsigned *>(smem + LO(srow));    // [NRC][AG] sensed, then kept columns of window row t (17 bits) | cell index of the row's column ca0 << 17
-    unsigned char *pcr = smem + LO(pcr);                               // [AG][NRC] kept cells per window row
-    u64 *covrow = reinterpret_cast<u64 *>(smem + LO(cov));             // [EPB][64] columns within r_avoid/2 of ANY agent, per lattice row
-    unsigned char *perm = smem + LO(perm);                             // [T/64][64] agent threads in ascending list length (per wave)
-    unsigned *orow = reinterpret_cast<unsigned *>(smem + P.off_orow);    // [NRC][AG] occupied columns (export launches only)
+    constexpr int NRC = LM::NRC;                                            // [lat] window rows stored per agent (lat_nrs <= 15)
+    float4 *hdr = reinterpret_cast<float4 *>(smem + LO(hdr));          // [lat] [AG] {apr = a - ca0, bpr = b - b0, b0, ca0} (last two: ints)
+    unsigned *srow = reinterpret_cast<unsigned *>(smem + LO(srow));    // [lat] [NRC][AG] sensed, then kept columns of window row t (17 bits) | cell index of the row's column ca0 << 17
+    unsigned char *pcr = smem + LO(pcr);                               // [lat] [AG][NRC] kept cells per window row
+    u64 *covrow = reinterpret_cast<u64 *>(smem + LO(cov));             // [lat] [EPB][64] columns within r_avoid/2 of ANY agent, per lattice row
+    unsigned char *perm = smem + LO(perm);                             // [lat] [T/64][64] agent threads in ascending list length (per wave; aliases part_d, later phase)
+    unsigned *orow = reinterpret_cast<unsigned *>(smem + P.off_orow);    // [lat] [NRC][AG] occupied columns (export launches only)
 
     // a mixed batch (KP::path_filter != 0) is two launches over the same grid: this workgroup belongs to the lattice launch
     // if every one of its envs has a lattice record (nrows > 0), else -- as a whole -- to the generic one.  Scalar loads and a
@@ -397,7 +422,9 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
     // ordered insertion, reward combine) -- rotating spreads that over the four SIMDs of a CU.
     const int sx = __builtin_amdgcn_readfirstlane((tid / AG + (int)blockIdx.x) % WPE);
     const int aw = at >> 6;                  // which 64-agent group of the environment
-    auto flag_get = [&]() -> bool { return LAT ? ((reinterpret_cast<const unsigned *>(sflag)[at >> 2] >> ((at & 3) * 8)) & 1u) != 0 : (sflag[at] & 1) != 0; };
+    // (lattice tail (K) only: this agent thread's byte of the exception flags.  Defined here and not beside its one call: there
+    // it changes the device code of 66 of the 162 instantiations)
+    auto flag_get = [&]() -> bool { return ((reinterpret_cast<const unsigned *>(sflag)[at >> 2] >> ((at & 3) * 8)) & 1u) != 0; };
     const bool thr_on = NPAD >= 64 || at < ACTW;         // (half-occupied geometry: agent threads ACTW..63 hold nothing)
     const int el = (NPAD < 64 && thr_on) ? at / NPAD : 0;
     const int i = NPAD < 64 ? at % NPAD : at;
@@ -465,8 +492,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
     // ---- generic (non-lattice) mode: stage an fp32 copy of the target cells (ENV: grid_center (2, n_g)) in LDS, laid
     // out per pair of cells {xa, xb, ya, yb} for packed arithmetic, padded with a sentinel (fp32: +inf).  The lattice
     // walk needs no cell coordinates except on its rare exact paths, which read the fp64 cells from global memory.
-    constexpr bool use_lat = LAT;
-    if constexpr (!use_lat)
+    if constexpr (!LAT)
     for (int rep = 0, reps = REPS(9); rep < reps; ++rep)
     for (int k = 0; k < EPB; ++k) {
         FENCE();
@@ -483,8 +509,9 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
             q[0] = (float)g.x; q[2] = (float)g.y;
         }
     }
+    // (the generic arm is a store nobody reads -- the generic kernel never looks at a flag; it stays, as the device code does)
     if (sx == 0) { if constexpr (LAT) { if ((at & 3) == 0) sflag[at >> 2] = 0; } else sflag[at] = 0; }
-    if constexpr (use_lat) {
+    if constexpr (LAT) {
         for (int q = tid; q < EPB * 64; q += T) {
             const int ek0 = blockIdx.x * EPB + (q >> 6);
             const LatEnv &Lq = P.lat[ek0 < P.n_env ? ek0 : P.n_env - 1];
@@ -635,7 +662,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
             }
         }
         STAMP(14);
-        if (use_lat && exc) atomicOr(reinterpret_cast<unsigned *>(sflag) + (at >> 2), 1u << ((at & 3) * 8));   // resolve the occupied-cell filter of this agent exactly
+        if constexpr (LAT) { if (exc) atomicOr(reinterpret_cast<unsigned *>(sflag) + (at >> 2), 1u << ((at & 3) * 8)); }   // resolve the occupied-cell filter of this agent exactly
         if constexpr (NPAD < 64) {
             // N < 64 (several environments per wavefront, JQ < 16): every split stores its partial masks, the readers OR the
             // WPE copies
@@ -844,7 +871,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
     const bool wave_exact = (P.force_exact != 0) || (__any(lane_far) != 0);
     float best32 = INFINITY, second32 = INFINITY; int bc = 0;
     const f2v pxx = {pxf, pxf}, pyy = {pyf, pyf};
-    if constexpr (use_lat) {
+    if constexpr (LAT) {
         // ---- lattice path.  Row b of the lattice holds the cells of columns rowmask[b]; the columns within
         // lattice distance rho of the agent form an interval.  Columns inside the radius shrunk by the margin lat_m
         // are in range for certain, columns outside the radius grown by lat_m are not; the (rare) columns in between
@@ -999,7 +1026,8 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
         }
         };
         if (sx != SB || WPE == 1) { if (P.lat_n32) walk(0u); else walk((u64)0); }
-    } else
+    } else {
+    // ---- generic path: every split scans its words of the env's cells, then settles its nearest-cell candidate
     for (int rep = 0, reps = REPS(3); rep < reps; ++rep) {
     FENCE();
     best32 = INFINITY; second32 = INFINITY; bc = 0;
@@ -1062,7 +1090,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
         else if (lane < 32) cmask[(size_t)(w * 32 + lane) * NW + aw] = mym;
     }
     }
-    if (!use_lat) {   // nearest cell of this split: unambiguous in fp32 unless the runner-up is within tolerance
+    {   // nearest cell of this split: unambiguous in fp32 unless the runner-up is within tolerance
         const float tol = P.min_tol_a * sqrtf(second32) + P.min_tol_b * second32 + 1e-9f;
         const bool unc_min = act && (wave_exact || (second32 < INFINITY && (second32 - best32) <= tol));
         if (__any(unc_min)) {
@@ -1084,8 +1112,9 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
             if (unc_min) bc = bcd;
         }
     }
+    }
     part_c[sx * AG + at] = (pc_t)bc;
-    double *part_d = reinterpret_cast<double *>(smem + LO(partd));     // [WPE - 1][AG] (lattice launches; the list phase's `perm` reuses it)
+    double *part_d = reinterpret_cast<double *>(smem + LO(partd));     // [lat] [WPE - 1][AG] exact distance of each walking split's candidate (the list phase's `perm` reuses it)
     if constexpr (LAT) {
         // each walking split evaluates the exact distance of ITS candidate here, before the barrier (the gather overlaps the
         // other waves' walk); the merge behind the barrier then compares values that sit in LDS instead of every split
@@ -1646,90 +1675,44 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
     } else {
     // ---- occupied-cell filter, CPP:144-216: a sensed cell is occupied iff some nearby agent is within
     // r_avoid/2 of it; only agents inside the shape filter (CPP:150).  kept = in_shape ? sensed & ~occupied : sensed.
-    // Common case (N <= 64, no index export, no agent flagged by the pair pass): the occupied bits of every word are
-    // already in LDS -- the env's covered-cell set (lattice walk) or the scan's per-agent words -- so nothing is
-    // rewritten and no barrier is needed: the readers below AND the two words on the fly.  Otherwise (N > 64: per-cell
-    // ballots; generic cell sets: the occupied words share LDS with the rank-select bits; export: the occupied bits
-    // themselves are wanted; a flagged agent: exact per-cell test) the words of the sensed set are filtered in place, dealt
-    // over the splits, behind a barrier.
-    const bool flagged = use_lat && __any((sflag[at] & 1) != 0) != 0;
-    const bool slow_filter = NW > 1 || !use_lat || P.export_idx != 0 || flagged;     // workgroup-uniform for N <= 64: every wave holds the same agents
-    if (slow_filter) {
-        {
-            u64 nearby[NW];
-    #pragma unroll
-            for (int q = 0; q < NW; ++q) nearby[q] = (NW > 1 && in_shape) ? snear[q * AG + at] : 0;
-            for (int rep = 0, reps = REPS(4); rep < reps; ++rep)
-            for (int w = 0; w < W; ++w) {
-                if (!mine(w)) continue;
-                FENCE();
-                const unsigned word = sbits[w * AG + at];
-                unsigned kw = word;
-                if (use_lat) {
-                    // occupied <=> within r_avoid/2 of ANY agent: the covering agent of a SENSED cell is "nearby"
-                    // (CPP:161) by the triangle inequality, except when its distance sits within rounding of the
-                    // nearby threshold -- those lanes were flagged by the pair pass and are resolved exactly.
-                    const unsigned cw_ = cov[el * (P.ngw + 1) + w];
-                    if (in_shape) {
-                        kw = word & ~cw_;
-                        if ((sflag[at] & 1) != 0) {
-                            unsigned it = word & cw_;
-                            kw = word;
-                            while (it) {
-                                const int b = __ffs(it) - 1; it &= it - 1;
-                                const double2 g = cell64(w * 32 + b);
-                                bool occ = false;
-                                for (int q = 0; q < NW && !occ; ++q) {
-                                    u64 nbm = NW == 1 ? (nearby1 >> (NPAD < 64 ? el * NPAD : 0)) : snear[q * AG + at];
-                                    while (nbm && !occ) {
-                                        const int j = q * 64 + __ffsll((unsigned long long)nbm) - 1; nbm &= nbm - 1;
-                                        const double ex = g.x - spx[j], ey = g.y - spy[j];
-                                        occ = ex * ex + ey * ey < P.c_occ;
-                                    }
-                                }
-                                if (occ) kw &= ~(1u << b);
-                            }
-                        }
+    // The words of the sensed set are filtered in place, dealt over the splits like the scan (each split filters the words
+    // it scanned), and counted; the barrier that follows publishes the kept words and their counts to every split.
+    {
+        u64 nearby[NW];
+#pragma unroll
+        for (int q = 0; q < NW; ++q) nearby[q] = (NW > 1 && in_shape) ? snear[q * AG + at] : 0;
+        for (int rep = 0, reps = REPS(4); rep < reps; ++rep)
+        for (int w = 0; w < W; ++w) {
+            if (!mine(w)) continue;
+            FENCE();
+            const unsigned word = sbits[w * AG + at];
+            unsigned kw = word;
+            if constexpr (NW == 1) {
+                if (in_shape) kw = word & ~owords[w * AG + at];       // occupied bits came out of the scan
+                if (rep == reps - 1) sbits[w * AG + at] = kw;
+            } else if (in_shape) {
+                unsigned it = word;
+                while (it) {
+                    int bb[4]; bool occ[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) { bb[u] = it ? __ffs(it) - 1 : -1; it &= it - 1; }   // it - 1 of 0 is harmless: it stays 0
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int c = w * 32 + (bb[u] < 0 ? 0 : bb[u]);
+                        occ[u] = false;
+#pragma unroll
+                        for (int q = 0; q < NW; ++q) occ[u] = occ[u] || ((cmask[(size_t)c * NW + q] & nearby[q]) != 0);
                     }
-                    if (rep == reps - 1) sbits[w * AG + at] = kw;
-                } else if constexpr (NW == 1) {
-                    if (in_shape) kw = word & ~owords[w * AG + at];       // occupied bits came out of the scan
-                    if (rep == reps - 1) sbits[w * AG + at] = kw;
-                } else if (in_shape) {
-                    unsigned it = word;
-                    while (it) {
-                        int bb[4]; bool occ[4];
-    #pragma unroll
-                        for (int u = 0; u < 4; ++u) { bb[u] = it ? __ffs(it) - 1 : -1; it &= it - 1; }   // it - 1 of 0 is harmless: it stays 0
-    #pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int c = w * 32 + (bb[u] < 0 ? 0 : bb[u]);
-                            occ[u] = false;
-    #pragma unroll
-                            for (int q = 0; q < NW; ++q) occ[u] = occ[u] || ((cmask[(size_t)c * NW + q] & nearby[q]) != 0);
-                        }
-    #pragma unroll
-                        for (int u = 0; u < 4; ++u) if (bb[u] >= 0 && occ[u]) kw &= ~(1u << bb[u]);
-                    }
-                    if (rep == reps - 1) sbits[w * AG + at] = kw;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) if (bb[u] >= 0 && occ[u]) kw &= ~(1u << bb[u]);
                 }
-                asm volatile("" :: "v"(kw));
-                if (P.export_idx) obits[w * AG + at] = word & ~kw;
-                pc[w * AG + at] = (unsigned char)__popc(kw);
+                if (rep == reps - 1) sbits[w * AG + at] = kw;
             }
+            asm volatile("" :: "v"(kw));
+            if (P.export_idx) obits[w * AG + at] = word & ~kw;
+            pc[w * AG + at] = (unsigned char)__popc(kw);
         }
-
     }
-    auto kept_word = [&](int w) -> unsigned {
-        const unsigned word = sbits[w * AG + at];
-        if (slow_filter || !in_shape) return word;
-        return word & ~cov[el * (P.ngw + 1) + w];
-    };
-    // kept-bit count of every word, dealt over the splits and shared through LDS: each of the WPE splits needs the counts of
-    // ALL words (list length, start of its rank range), and vector instructions -- not barriers -- are what this kernel
-    // runs out of, so nothing is counted four times
-    if (!slow_filter)
-        for (int w = sx; w < W; w += WPE) pc[w * AG + at] = (unsigned char)__popc(kept_word(w));
     __syncthreads();
     STAMP(5);
     EXIT_AT(6);
@@ -1746,10 +1729,8 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
     // round() equals the integer floor((2 s (n-1) + (G-1)) / (2 (G-1))) exactly; for even G-1 (ties possible) the
     // reference's fp64 expression is evaluated as is.
     unsigned *rsel = reinterpret_cast<unsigned *>(smem + P.off_cmask);      // [W+1][AG] (aliases cmask: consumed)
-    if (!use_lat) {                       // lattice mode cleared it up front (the region has no earlier user there)
-        for (int w = sx; w <= W; w += WPE) rsel[w * AG + at] = 0;
-        __syncthreads();
-    }
+    for (int w = sx; w <= W; w += WPE) rsel[w * AG + at] = 0;
+    __syncthreads();
     // The cap is rare (an agent deep inside a fine-celled shape): when no agent of this wave is capped -- the same
     // answer in all WPE splits, they hold the same agents -- ranks are slots and the rank-select bits are skipped.
     const bool any_sub = __any(n_kept > G) != 0;
@@ -1826,7 +1807,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
                 ww += le ? 1 : 0; within = le ? k0 - prefix : within;
             }
         }
-        unsigned it = k0 < k1 ? kept_word(ww) : 0u;
+        unsigned it = k0 < k1 ? sbits[ww * AG + at] : 0u;
         {   // drop the `within` lowest set bits: position of the within-th set bit by a binary search on popcounts
             int p = 0, left = within;
 #pragma unroll
@@ -1848,7 +1829,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
             unsigned rw = (CAP && k0 < k1) ? rsel[(k0 >> 5) * AG + at] : 0xFFFFFFFFu;      // selection bits of ranks 32 (k >> 5) ...
             while (__any(k < k1)) {
                 if (k < k1) {
-                    if (it == 0) { ++ww; it = kept_word(ww); }         // next word (more kept bits exist: k < k1 <= n_kept)
+                    if (it == 0) { ++ww; it = sbits[ww * AG + at]; }         // next word (more kept bits exist: k < k1 <= n_kept)
                     if (it != 0) {
                         const int b = __ffs(it) - 1;
                         it &= it - 1;
@@ -1886,11 +1867,8 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
             const bool va = q < lim, vb = q + 1 < lim;
             const int ca = va ? row[q] : 0, cb = vb ? row[q + 1] : 0;         // cell 0 stands in for an empty slot (weight zeroed)
             f2v gx, gy;
-            if (use_lat) { const double2 ga = gce[ca], gb = gce[cb]; gx = f2v{(float)ga.x, (float)gb.x}; gy = f2v{(float)ga.y, (float)gb.y}; }
-            else {
-                gx = f2v{cq_e[(ca >> 1) * 4 + (ca & 1)], cq_e[(cb >> 1) * 4 + (cb & 1)]};
-                gy = f2v{cq_e[(ca >> 1) * 4 + 2 + (ca & 1)], cq_e[(cb >> 1) * 4 + 2 + (cb & 1)]};
-            }
+            gx = f2v{cq_e[(ca >> 1) * 4 + (ca & 1)], cq_e[(cb >> 1) * 4 + (cb & 1)]};
+            gy = f2v{cq_e[(ca >> 1) * 4 + 2 + (ca & 1)], cq_e[(cb >> 1) * 4 + 2 + (cb & 1)]};
             const f2v x = gx - pxx2, y = gy - pyy2;
             const f2v u = __builtin_elementwise_fma(x, x, y * y) * inv2;
             f2v c = {7.969553699e-04f, 7.969553699e-04f};                      // psi_u_f32, both slots at once
@@ -2007,7 +1985,6 @@ void layout_t(KP &k)
     typedef Geo<NPAD, HALF> G_;
     constexpr int AG = G_::AG, EPB = G_::EPB, NW = G_::NW, WPE = G_::WPE, T = G_::T;
     k.ngw = (k.ng_max + 31) / 32;
-    k.cxy_stride = k.ngw * 32 + 1;            // +1 pair: envs of one wave start on different LDS banks
     int half = (k.g_max + 1) / 2;
     if ((half & 1) == 0) ++half;              // odd dword stride: lane-per-row int16 writes spread over banks
     k.g_stride = 2 * half;
@@ -2015,7 +1992,7 @@ void layout_t(KP &k)
     auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 15) & ~size_t(15); return (int)o; };
     auto max2 = [](size_t a, size_t b) { return a > b ? a : b; };
     const size_t pm_bytes = (size_t)(NW == 1 ? WPE * 4 : 5) * NW * AG * 8;   // partial pair masks (per-split copies for N <= 64, one accumulator set above)
-    k.off_cxy = 0;                             // fp64 cells are no longer staged in LDS
+    k.off_cxy = 0;                             // fp64 cells are no longer staged in LDS (cxy_stride, off_rres: dead too, left zero)
     k.off_sp = take((size_t)4 * AG * 8);
     k.cxq_stride = k.ngw * 64 + 4;             // floats: 2 per cell, +1 pair-of-pairs of padding
     if (k.lattice) {
@@ -2037,6 +2014,8 @@ void layout_t(KP &k)
     k.off_sbits = take((size_t)(k.ngw + 1) * AG * 4);
     k.off_sidx = take(max2(max2((size_t)AG * k.g_stride * 2, pm_bytes), (size_t)14 * AG * 8));
     k.off_partc = take((size_t)WPE * AG * 4);
+    // lat, cov, flag: unread by the generic kernel (flag is cleared in its prologue, by a store nobody reads).  They stay: the
+    // launch's LDS bytes decide occupancy, and a change of those wants an A/B run on hardware
     k.off_lat = take((size_t)EPB * 64 * (8 + 2));
     k.off_cov = take((size_t)EPB * (k.ngw + 1) * 4);
     k.off_flag = take((size_t)AG * 4);

@@ -1,0 +1,79 @@
+"""tools/isa_diff.py's splitter and comparer on hand-written assembly (CPU only, nothing is compiled): two files that are
+the same, one kernel changed, one kernel added."""
+import importlib.util
+import os
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def kernel(name, body, vgprs=8):
+    return """\t.globl\t%(n)s
+\t.type\t%(n)s,@function
+%(n)s:                                  ; @%(n)s
+; %%bb.0:
+%(b)s
+.LBB0_1:
+\ts_endpgm
+\t.section\t.rodata,"a",@progbits
+\t.amdhsa_kernel %(n)s
+\t\t.amdhsa_next_free_vgpr %(v)d
+\t.end_amdhsa_kernel
+\t.text
+.Lfunc_end_%(n)s:
+\t.size\t%(n)s, .Lfunc_end_%(n)s-%(n)s
+""" % {"n": name, "b": body, "v": vgprs}
+
+
+HEAD = '\t.text\n\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"\n'
+A = kernel("_Z1av", "\tv_mov_b32_e32 v0, 0\n\tv_add_u32_e32 v1, v0, v0")
+B = kernel("_Z1bv", "\ts_load_dwordx2 s[0:1], s[4:5], 0x0\n\ts_waitcnt lgkmcnt(0)")
+B_MOVED = kernel("_Z1bv", "\ts_load_dwordx2 s[0:1], s[4:5], 0x8\n\ts_waitcnt lgkmcnt(0)")
+C = kernel("_Z1cv", "\ts_nop 0")
+
+
+@pytest.fixture(scope="module")
+def tool():
+    spec = importlib.util.spec_from_file_location("isa_diff", os.path.join(ROOT, "tools", "isa_diff.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_split_takes_symbol_to_descriptor_end(tool):
+    kernels, outside = tool.split_kernels(HEAD + A + B)
+    assert sorted(kernels) == ["_Z1av", "_Z1bv"]
+    a = kernels["_Z1av"]
+    assert a[0].startswith("_Z1av:") and a[-1].strip() == ".end_amdhsa_kernel"
+    assert "\t\t.amdhsa_next_free_vgpr 8" in a and "\tv_add_u32_e32 v1, v0, v0" in a
+    assert ".LBB0_1:" in a                                   # a local label does not end a kernel
+    assert not any("v_add_u32" in l or ".amdhsa_next_free_vgpr" in l for l in outside)
+    assert len(a) + len(kernels["_Z1bv"]) + len(outside) == len((HEAD + A + B).splitlines())
+
+
+def test_identical(tool):
+    r = tool.compare(HEAD + A + B, HEAD + A + B)
+    assert r["kernels"] == 2 and r["lines"] == len((HEAD + A + B).splitlines())
+    assert r["only_base"] == [] and r["only_tree"] == [] and r["differing"] == [] and not r["outside"]
+
+
+def test_one_kernel_changed(tool):
+    r = tool.compare(HEAD + A + B, HEAD + A + B_MOVED)
+    assert r["kernels"] == 2 and r["only_base"] == [] and r["only_tree"] == [] and not r["outside"]
+    assert r["differing"] == [("_Z1bv", 3, "\ts_load_dwordx2 s[0:1], s[4:5], 0x0", "\ts_load_dwordx2 s[0:1], s[4:5], 0x8")]
+    # a descriptor line counts as much as an instruction
+    r = tool.compare(HEAD + A + B, HEAD + kernel("_Z1av", "\tv_mov_b32_e32 v0, 0\n\tv_add_u32_e32 v1, v0, v0", vgprs=9) + B)
+    assert [(d[0], d[2], d[3]) for d in r["differing"]] == [("_Z1av", "\t\t.amdhsa_next_free_vgpr 8", "\t\t.amdhsa_next_free_vgpr 9")]
+
+
+def test_one_kernel_added(tool):
+    r = tool.compare(HEAD + A + B, HEAD + A + B + C)
+    assert r["kernels"] == 3 and r["only_tree"] == ["_Z1cv"] and r["only_base"] == [] and r["differing"] == []
+    r = tool.compare(HEAD + A + B + C, HEAD + A + B)
+    assert r["only_base"] == ["_Z1cv"] and r["only_tree"] == [] and r["differing"] == []
+
+
+def test_difference_outside_the_kernels_is_reported(tool):
+    r = tool.compare(HEAD + A, HEAD + A + '\t.ident\t"other compiler"\n')
+    assert r["differing"] == [] and r["only_base"] == [] and r["only_tree"] == [] and r["outside"]
