@@ -30,8 +30,15 @@
  *
  * Memory contract of the batched ABI: every pointer passed to swarm_step / swarm_observe /
  * swarm_get_indices is a DEVICE pointer (hipMalloc / torch.Tensor.data_ptr()) valid on the handle's
- * device; the calls are asynchronous on the handle's stream (swarm_set_stream).  swarm_set_cells /
- * swarm_set_state / swarm_get_state accept host or device pointers (hipMemcpyDefault).
+ * device.  swarm_set_cells / swarm_set_state / swarm_get_state accept host or device pointers (hipMemcpyDefault).
+ *
+ * Stream contract (DESIGN.md "Stream contract"; tests/test_gpu_streams.py): all device work goes to the handle's stream
+ * (swarm_set_stream; NULL = the default stream).  swarm_step, swarm_observe, swarm_reset, swarm_select_shape, swarm_metrics
+ * and swarm_rule_action only enqueue: they return without waiting for the stream.  swarm_set_cells, swarm_set_state and the
+ * readers swarm_get_state / _get_cells / _get_shape_index / _get_indices / _get_llm_action / _path_envs, swarm_observe_host,
+ * swarm_step_host and swarm_synchronize return after the stream has run everything enqueued so far, their own work included
+ * (swarm_get_indices too, although its pointers are device pointers).  swarm_set_shapes and swarm_destroy release device
+ * memory and thereby wait for pending work that still reads it; work enqueued before them completes on what it was given.
  *
  * Layouts (E = n_env, N = n_agents, D = obs_dim = 4*(topo + 1 + with_self) + 2*num_obs_grid_max):
  *   p, dp            double [E][2][N]     component-major per env, exactly the reference's (2, n_a) arrays

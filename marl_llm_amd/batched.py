@@ -2,6 +2,11 @@
 
 Device memory, streams and tensors come from PyTorch-ROCm; all compute is in the HIP library.
 Layouts are the ones documented in include/swarm_env.h.
+
+Streams (DESIGN.md "Stream contract"): every call hands the library torch's current stream first.  step, observe, reset,
+select_shape, metrics and rule_action only enqueue on it; set_cells, set_state, the readers (get_state, get_cells,
+get_shape_index, indices, llm_action, path_envs) and the host path (observe_host, step_host) return after that stream has run
+everything enqueued so far; set_shapes and close() wait for pending work that still reads what they free.
 """
 import ctypes
 

@@ -411,6 +411,9 @@ int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
     alloc(h->d_inflag, E * N, 0); alloc(h->d_sf, E * N, 0);
     if (a == hipSuccess) a = hipEventCreate(&h->ev0);
     if (a == hipSuccess) a = hipEventCreate(&h->ev1);
+    // the fills above went to the null stream, and a first kernel on a non-blocking stream is not ordered behind it: wait
+    // for them here, once per handle (DESIGN.md "Stream contract")
+    if (a == hipSuccess) a = hipStreamSynchronize(nullptr);
     if (a != hipSuccess) {
         std::string m = std::string("device allocation failed: ") + hipGetErrorString(a);
         swarm_destroy(h);
@@ -654,6 +657,7 @@ int io_alloc(swarm_env *h)
     HIP_ALLOC(h, block, block_bytes / 8); HIP_ALLOC(h, action, EN * 16);
     HIP_ALLOC(h, hblock0, block_bytes / 8); HIP_ALLOC(h, hblock1, block_bytes / 8); HIP_ALLOC(h, haction, EN * 16);
     HIP_TRY(h, hipMemset(block.get(), 0, block_bytes));
+    HIP_TRY(h, hipStreamSynchronize(nullptr));             // a null-stream fill, as swarm_create's: complete before any stream uses it
     std::memset(hblock0.get(), 0, block_bytes); std::memset(hblock1.get(), 0, block_bytes);
     h->io_block_bytes = block_bytes;
     h->d_io_obs = std::move(obs); h->d_io_prior = std::move(prior); h->d_io_rew = std::move(rew); h->d_io_done = std::move(done);
