@@ -150,6 +150,31 @@ def pad_cells(grids, ng_max):
     return cells, n_g
 
 
+def shape_batch(shapes, E, N, dtype=None, upload=True, **kw):
+    """A SwarmBatch of E envs x N agents with room for any shape of `shapes`, the set uploaded (set_shapes) unless upload is
+    False.  dtype: the obs dtype, default torch.float32."""
+    import torch
+    from marl_llm_amd.batched import SwarmBatch
+    from marl_llm_amd.shapes import r_avoid_for
+    ng_max = max(np.asarray(g).shape[0] for g in shapes["grid_coords"])
+    sb = SwarmBatch(n_env=E, n_agents=N, n_cells_max=ng_max, r_avoid=r_avoid_for(N, shapes), obs_dtype=dtype or torch.float32, **kw)
+    if upload:
+        sb.set_shapes(shapes)
+    return sb
+
+
+def lat_nrs(cells, n_g, d_sen=0.4):
+    """The window-row count of lattice cell sets (csrc/env_api.hip: detect_lattice fits the step as the closest pair of
+    consecutive cells, stored as float; R = d_sen / step; window_rows takes floor(2 (R + 0.01)) + 1 in float).  The row walk
+    serves a cell set while this is <= 15."""
+    rmax = np.float32(0)
+    for c, n in zip(cells, n_g):
+        d = np.diff(c[:, :n], axis=1)
+        step = np.float32(np.sqrt(np.min(d[0] * d[0] + d[1] * d[1])))
+        rmax = max(rmax, np.float32(d_sen / np.float64(step)))
+    return int(np.floor(np.float32(2) * (rmax + np.float32(0.01)))) + 1
+
+
 def oracle_run(oracle, cases, acts, r_avoid, d_sen=0.4, boundary=DEFAULT_BOX, periodic=False, prior_gain=(2.0, 3.0, 2.0), *,
                topo=None, g_max=None, occ_max=None, with_self=True, feedback=None, **phys):
     """The oracle's trajectory of every case (p, dp, grid, l_cell) of `cases`: get_observation, then one step per entry of

@@ -24,12 +24,12 @@ calls.  The oracle is pinned to the reference at every row by test_step_matches_
 import numpy as np
 import pytest
 
-from helpers import (CAPS_DTYPE_NS, CAPS_DTYPE_ROWS, CAPS_NS, CAPS_ROWS, as_obs_dtype, caps_trajectory, make_case, pad_cells)
+from helpers import CAPS_DTYPE_NS, CAPS_DTYPE_ROWS, CAPS_NS, CAPS_ROWS, caps_trajectory, make_case, pad_cells
+from lockstep import hold
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-KEYS = ("neighbor_index", "in_flags", "sensed_index", "occupied_index")
 TORCH_DT = dict(f64=torch.float64, f32=torch.float32, bf16=torch.bfloat16)
 FLAG_IDS = {0: "lattice", 1: "forced", 2: "generic", 4: "fullgeo"}
 _REF = {}
@@ -43,66 +43,11 @@ def _shared(oracle, shapes, row, n_a, dtype="f64", periodic=False, with_self=Tru
     return _REF[key]
 
 
-def _np(t):
-    """A device tensor as numpy, bfloat16 widened exactly to float32."""
-    return (t.float() if t.dtype == torch.bfloat16 else t).cpu().numpy()
-
-
-def _rows(o):
-    return np.ascontiguousarray(o.T)
-
-
 def _hold(cases, ref, ra, row, dtype="f64", flags=0, periodic=False, with_self=True):
-    """Run `cases` through the HIP step at the row's caps and compare every output of every call with `ref`.  Returns the
-    state, reward and index arrays of every call (for the float64 twin of a narrower handle)."""
-    from marl_llm_amd.batched import SwarmBatch
+    """lockstep.hold at the row's caps; returns its state, reward and index arrays (for the float64 twin of a narrower handle)."""
     topo, g_max, occ_max = CAPS_ROWS[row]
-    first, steps, _ = ref
-    E, n_a = len(cases), cases[0][0].shape[1]
-    head = 4 * (topo + 1 + int(with_self))
-    cells, n_g = pad_cells([c[2] for c in cases], max(c[2].shape[1] for c in cases) + 3)
-    sb = SwarmBatch(n_env=E, n_agents=n_a, n_cells_max=cells.shape[2], r_avoid=ra, is_boundary=not periodic, with_self=with_self,
-                    topo=topo, g_max=g_max, occ_max=occ_max, obs_dtype=TORCH_DT[dtype], debug_flags=flags)
-    seen = []
-
-    def check_obs(tag, obs, idx, want):
-        assert obs.shape == (E, n_a, head + 2 * g_max)
-        for e, o in enumerate(want):
-            assert np.array_equal(obs[e], as_obs_dtype(_rows(o["obs"]), dtype)), (tag, e, "obs")
-        pad = idx["sensed_index"] < 0                                      # unused sensed slots are exactly zero
-        assert (obs[:, :, head:].reshape(E, n_a, g_max, 2)[pad] == 0).all(), (tag, "unused slots")
-
-    try:
-        sb.set_cells(cells, n_g, [c[3] for c in cases])
-        assert sb.lattice_envs() == (0 if flags & 2 else E)
-        sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
-        obs = _np(sb.observe())
-        idx = {k: v.cpu().numpy() for k, v in sb.indices().items()}
-        for e, o in enumerate(first):
-            for k in KEYS:
-                assert np.array_equal(idx[k][e], o[k]), ("observe", e, k)
-        check_obs("observe", obs, idx, first)
-        seen.append(idx)
-        for t, srow in enumerate(steps):
-            act = np.stack([s["act"] for s in srow])
-            obs, rew, done, pri = sb.step(torch.from_numpy(act).to(sb.device))
-            obs, rew, pri, done = _np(obs), rew.cpu().numpy(), _np(pri), done.cpu().numpy()
-            pg, dpg = [x.cpu().numpy() for x in sb.get_state()]
-            idx = {k: v.cpu().numpy() for k, v in sb.indices().items()}
-            assert not done.any()
-            for e, s in enumerate(srow):
-                assert np.array_equal(dpg[e], s["dp"]), (t, e, "dp")
-                assert np.array_equal(pg[e], s["p"]), (t, e, "p")
-                # the prior first: it is the next fed-back action, and the oracle was given it as this handle rounds it
-                assert np.array_equal(pri[e], as_obs_dtype(_rows(s["a_prior"]), dtype)), (t, e, "a_prior")
-                for k in KEYS:
-                    assert np.array_equal(idx[k][e], s[k]), (t, e, k)
-                assert np.array_equal(rew[e].astype(np.float64), s["reward"][0]), (t, e, "reward")
-            check_obs(t, obs, idx, srow)
-            seen.append(dict(idx, p=pg, dp=dpg, reward=rew))
-    finally:
-        sb.close()
-    return seen
+    return hold(cases, ref, lattice=0 if flags & 2 else len(cases), r_avoid=ra, is_boundary=not periodic, with_self=with_self,
+                topo=topo, g_max=g_max, occ_max=occ_max, obs_dtype=TORCH_DT[dtype], debug_flags=flags)
 
 
 # ---- a. the caps matrix, float64 ----

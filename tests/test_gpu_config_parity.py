@@ -23,13 +23,12 @@ import copy
 import numpy as np
 import pytest
 
-from helpers import (BIG_BOX, DEFAULT_BOX, DYNAMICS_ROWS, OFF_BOX, adversarial_case, config_case, oracle_run, pad_cells, physics,
-                     random_actions)
+from helpers import BIG_BOX, DEFAULT_BOX, DYNAMICS_ROWS, OFF_BOX, adversarial_case, config_case, oracle_run, physics, random_actions
+from lockstep import hold
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-KEYS = ("neighbor_index", "in_flags", "sensed_index", "occupied_index")
 _REF = {}
 
 
@@ -45,46 +44,10 @@ def _shared(key, make):
     return _REF[key]
 
 
-def _rows(o):
-    return np.ascontiguousarray(o.T)
-
-
 def _hold(cases, ref, ra, *, d_sen=0.4, boundary=DEFAULT_BOX, periodic=False, prior_gain=(2.0, 3.0, 2.0), flags=0, lattice=None, **phys):
-    """Run `cases` through the HIP step with the given constants and compare everything with `ref` = oracle_run's result."""
-    from marl_llm_amd.batched import SwarmBatch
-    first, steps, _ = ref
-    E, n_a = len(cases), cases[0][0].shape[1]
-    cells, n_g = pad_cells([c[2] for c in cases], max(c[2].shape[1] for c in cases) + 3)
-    sb = SwarmBatch(n_env=E, n_agents=n_a, n_cells_max=cells.shape[2], r_avoid=ra, d_sen=d_sen, boundary=boundary,
-                    is_boundary=not periodic, obs_dtype=torch.float64, debug_flags=flags, prior_gain=prior_gain, **physics(**phys))
-    try:
-        sb.set_cells(cells, n_g, [c[3] for c in cases])
-        if lattice is not None:
-            assert sb.lattice_envs() == lattice
-        sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
-        obs = sb.observe().cpu().numpy()
-        idx = {k: v.cpu().numpy() for k, v in sb.indices().items()}
-        for e, o in enumerate(first):
-            for k in KEYS:
-                assert np.array_equal(idx[k][e], o[k]), ("observe", e, k)
-            assert np.array_equal(obs[e], _rows(o["obs"])), ("observe", e)
-        for t, row in enumerate(steps):
-            act = np.stack([s["act"] for s in row])
-            obs, rew, done, pri = sb.step(torch.from_numpy(act).to(sb.device))
-            obs, rew, pri = obs.cpu().numpy(), rew.cpu().numpy(), pri.cpu().numpy()
-            pg, dpg = [x.cpu().numpy() for x in sb.get_state()]
-            idx = {k: v.cpu().numpy() for k, v in sb.indices().items()}
-            assert not done.any().item()
-            for e, s in enumerate(row):
-                assert np.array_equal(dpg[e], s["dp"]), (t, e, "dp")
-                assert np.array_equal(pg[e], s["p"]), (t, e, "p")
-                assert np.array_equal(pri[e], _rows(s["a_prior"])), (t, e, "a_prior")
-                for k in KEYS:
-                    assert np.array_equal(idx[k][e], s[k]), (t, e, k)
-                assert np.array_equal(obs[e], _rows(s["obs"])), (t, e, "obs")
-                assert np.array_equal(rew[e].astype(np.float64), s["reward"][0]), (t, e, "reward")
-    finally:
-        sb.close()
+    """lockstep.hold with the given constants at obs_dtype float64."""
+    hold(cases, ref, lattice=lattice, r_avoid=ra, d_sen=d_sen, boundary=boundary, is_boundary=not periodic,
+         obs_dtype=torch.float64, debug_flags=flags, prior_gain=prior_gain, **physics(**phys))
 
 
 def _free_run(oracle, shapes, seed, n_a, *, boundary=DEFAULT_BOX, periodic=False, d_sen=0.4, r_avoid=None, prior_gain=(2.0, 3.0, 2.0),

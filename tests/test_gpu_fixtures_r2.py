@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from helpers import GOLDEN_DIR, fig_shapes, load_golden
+from lockstep import Lockstep
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -27,28 +28,13 @@ def test_real_shapes_take_the_lattice_path_and_match_the_oracle(oracle):
         sy = synthetic_batch(E, n_a, fig, seed=11, assembled_fraction=0.6)
         assert len(set(sy["n_g"].tolist())) >= 5                               # several of the seven shapes are present
         sb = SwarmBatch(n_env=E, n_agents=n_a, n_cells_max=sy["cells"].shape[2], r_avoid=ra)
-        sb.set_cells(sy["cells"], sy["n_g"], sy["l_cell"]); sb.set_state(sy["p"], sy["dp"]); sb.observe()
-        assert sb.lattice_envs() == E                                          # every real shape is a lattice subset
-        p, dp = sy["p"].copy(), sy["dp"].copy()
-        nei = sb.indices(False, False)["neighbor_index"].cpu().numpy()
-        act = torch.zeros((E, n_a, 2), device=sb.device)
-        for t in range(3):
-            obs, rew, done, pri = sb.step(act)
-            a = act.cpu().numpy()
-            idx = sb.indices()
-            pg, dpg = [x.cpu().numpy() for x in sb.get_state()]
-            for e in range(E):
-                g = sy["cells"][e][:, : sy["n_g"][e]]
-                s = oracle.step(p[e], dp[e], np.ascontiguousarray(a[e].T.astype(np.float64)), g, nei[e], float(sy["l_cell"][e]), ra)
-                assert np.array_equal(pg[e], s["p"]) and np.array_equal(dpg[e], s["dp"]), (t, e)
-                assert np.array_equal(obs[e].cpu().numpy(), s["obs"].T.astype(np.float32)), (t, e)
-                assert np.array_equal(pri[e].cpu().numpy(), s["a_prior"].T.astype(np.float32)), (t, e)
-                assert np.array_equal(rew[e].cpu().numpy().astype(np.float64), s["reward"][0]), (t, e)
-                for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-                    assert np.array_equal(idx[k][e].cpu().numpy(), s[k]), (t, e, k)
-                p[e], dp[e], nei[e] = s["p"], s["dp"], s["neighbor_index"]
-            act = pri.clone()
-        sb.close()
+        sb.set_cells(sy["cells"], sy["n_g"], sy["l_cell"]); sb.set_state(sy["p"], sy["dp"])
+        ls = Lockstep(oracle, sb, sy, ra, f"fig n{n_a}", idx_every=1)          # observe, then prior-policy steps; indices every step
+        try:
+            assert sb.lattice_envs() == E                                      # every real shape is a lattice subset
+            ls.run(3)
+        finally:
+            ls.close()
     # the device-side reset on the real shape set: still lattices after rotation + offset
     sb = SwarmBatch(n_env=64, n_agents=32, n_cells_max=max(g.shape[0] for g in fig["grid_coords"]), r_avoid=r_avoid_for(32, fig))
     sb.set_shapes(fig)

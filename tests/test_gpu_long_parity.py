@@ -15,45 +15,17 @@ A mismatch names the step, the output and the envs.  With SWARM_PARITY_DUMP=<dir
 inputs (p, dp, neighbor_index, action, cells, n_g, l_cell, flags) are also written to <dir>/<case>_t<step>_e<env>.npz for
 arbitration against the oracle and the reference library on the CPU.
 """
-import os
-
 import numpy as np
 import pytest
 
-from helpers import ThreadedOracle, fig_shapes
+from helpers import ThreadedOracle, fig_shapes, lat_nrs
+from lockstep import Lockstep, Mismatch, compare, device_layout, dump, host_copy, oracle_action, to_host
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-IDX = ("neighbor_index", "in_flags", "sensed_index", "occupied_index")
-SIZE_A, D_SEN = 0.035, 0.4
 IDX_EVERY = 25            # lockstep runs compare the four index arrays every IDX_EVERY steps and on the last step
 CHUNK = 512               # whole-batch checks copy outputs to the host this many envs at a time
-
-
-class Mismatch(AssertionError):
-    def __init__(self, what, envs):
-        super().__init__(f"{what}: {len(envs)} env(s) differ, first {list(envs[:8])}")
-        self.envs = envs
-
-
-def _same(dev, ref, what, env0=0):
-    """Exact equality of [E, ...] arrays; on failure name the envs (offset by env0) that differ."""
-    if dev.shape == ref.shape and np.array_equal(dev, ref):
-        return
-    if dev.shape != ref.shape:
-        raise AssertionError(f"{what}: shape {dev.shape} != {ref.shape}")
-    bad = np.nonzero(~(dev == ref).reshape(len(dev), -1).all(1))[0] + env0
-    raise Mismatch(what, bad)
-
-
-def _rows(x):
-    """oracle [E, D, N] -> device layout [E, N, D]."""
-    return np.ascontiguousarray(np.swapaxes(x, 1, 2))
-
-
-def _host(t):
-    return t.cpu().numpy()
 
 
 def _batch(n_env, n_a, sy, shapes, **kw):
@@ -64,94 +36,6 @@ def _batch(n_env, n_a, sy, shapes, **kw):
     sb.set_cells(sy["cells"], sy["n_g"], sy["l_cell"])
     sb.set_state(sy["p"], sy["dp"])
     return sb, ra
-
-
-def _dump(tag, t, e, pre, to, flags):
-    d = os.environ.get("SWARM_PARITY_DUMP")
-    if not d:
-        return
-    os.makedirs(d, exist_ok=True)
-    np.savez(os.path.join(d, f"{tag}_t{t}_e{e}.npz"), p=pre["p"][e], dp=pre["dp"][e], neighbor_index=pre["nei"][e],
-             action=pre["a"][e], cells=to.cells[e][:, : to.n_g[e]], n_g=to.n_g[e], l_cell=to.l_cell[e],
-             r_avoid=to.r_avoid, is_boundary=to.is_boundary, with_self=to.with_self, debug_flags=flags)
-
-
-def _compare_step(out, o, f32, with_idx, idx=None, env0=0):
-    """One step's device outputs (host copies: p, dp, obs, reward, done, prior) against the oracle's."""
-    cast = (lambda x: x.astype(np.float32)) if f32 else (lambda x: x)
-    _same(out["p"], o["p"], "p", env0)
-    _same(out["dp"], o["dp"], "dp", env0)
-    _same(out["reward"].astype(np.float64), o["reward"], "reward", env0)
-    _same(out["done"], np.zeros_like(out["done"]), "done", env0)
-    _same(out["obs"], cast(_rows(o["obs"])), "obs", env0)
-    _same(out["prior"], cast(_rows(o["a_prior"])), "a_prior", env0)
-    if with_idx:
-        for k in IDX:
-            _same(idx[k], o[k], k, env0)
-
-
-class Lockstep:
-    """A SwarmBatch and the threaded oracle run side by side from the same state, prior-policy actions."""
-
-    def __init__(self, oracle, sb, sy, ra, tag, is_boundary=True, with_self=True, flags=0):
-        self.sb, self.tag, self.flags = sb, tag, flags
-        self.f32 = sb.obs_dtype == torch.float32
-        self.to = ThreadedOracle(oracle, sy["cells"], sy["n_g"], sy["l_cell"], ra, is_boundary=is_boundary, with_self=with_self)
-        self.p, self.dp = sy["p"].copy(), sy["dp"].copy()
-        self.act = torch.zeros((sb.n_env, sb.n_agents, 2), dtype=torch.float32, device=sb.device)    # bench: zero first action
-        self.t = 0
-        self.max_contacts = 0          # most colliding pairs (centre distance < 2 size_a) seen in any one step
-        self.nei = None
-        self.observe()
-
-    def observe(self):
-        """sb.observe() (needed after set_state / set_cells) against the oracle's observation of the same state."""
-        obs = _host(self.sb.observe())
-        o = self.to.observe(self.p, self.dp)
-        cast = (lambda x: x.astype(np.float32)) if self.f32 else (lambda x: x)
-        _same(obs, cast(_rows(o["obs"])), f"{self.tag} observe t={self.t}: obs")
-        idx = {k: _host(v) for k, v in self.sb.indices().items()}
-        for k in IDX:
-            _same(idx[k], o[k], f"{self.tag} observe t={self.t}: {k}")
-        if self.nei is not None:       # the list depends on the agents only: the last step's, recomputed
-            _same(o["neighbor_index"], self.nei, f"{self.tag} observe t={self.t}: neighbor_index vs the last step's")
-        self.nei = o["neighbor_index"]
-        self.act = self.act.clone()    # the step writes its prior into a ping-pong buffer that observe() has shifted
-
-    def set_cells(self, cells, n_g, l_cell, env_begin):
-        self.sb.set_cells(cells, n_g, l_cell, env_begin=env_begin)
-        c = self.to.cells.copy(); g = self.to.n_g.copy(); lc = self.to.l_cell.copy()
-        c[env_begin: env_begin + len(n_g)] = cells; g[env_begin: env_begin + len(n_g)] = n_g
-        lc[env_begin: env_begin + len(n_g)] = l_cell
-        self.to.set_cells(c, g, lc)
-
-    def run(self, steps):
-        for s in range(steps):
-            self.t += 1
-            a = np.swapaxes(_host(self.act), 1, 2).astype(np.float64)              # [E,N,2] f32 -> [E,2,N] f64, exact
-            pre = dict(p=self.p, dp=self.dp, nei=self.nei, a=a)
-            obs, rew, done, pri = self.sb.step(self.act)
-            o = self.to.step(self.p, self.dp, a, self.nei)
-            pg, dpg = self.sb.get_state()
-            out = dict(p=_host(pg), dp=_host(dpg), obs=_host(obs), reward=_host(rew), done=_host(done), prior=_host(pri))
-            with_idx = self.t % IDX_EVERY == 0 or s == steps - 1
-            idx = {k: _host(v) for k, v in self.sb.indices().items()} if with_idx else None
-            try:
-                _compare_step(out, o, self.f32, with_idx, idx)
-            except Mismatch as ex:
-                _dump(self.tag, self.t, int(ex.envs[0]), pre, self.to, self.flags)
-                raise AssertionError(f"{self.tag} step {self.t}: {ex}") from None
-            self.p, self.dp, self.nei = o["p"], o["dp"], o["neighbor_index"]
-            self.act = pri
-            if self.to.is_boundary:
-                d = self.p[:, :, :, None] - self.p[:, :, None, :]
-                dc = np.sqrt(d[:, 0] ** 2 + d[:, 1] ** 2)
-                self.max_contacts = max(self.max_contacts, int(((dc < 2 * SIZE_A).sum() - dc[..., 0].size) // 2))
-            self.last = o
-
-    def close(self):
-        self.to.close()
-        self.sb.close()
 
 
 def _synth(n_env, n_a, shapes, seed, frac):
@@ -191,7 +75,7 @@ def test_long_lockstep(oracle, shapes, tag, n_a, n_env, steps, shape_set, seed, 
     sb, ra = _batch(n_env, n_a, sy, sh, **kw)
     assert sb.lattice_envs() == (0 if kw.get("debug_flags", 0) & 2 else n_env)
     ls = Lockstep(oracle, sb, sy, ra, tag, is_boundary=kw.get("is_boundary", True), with_self=kw.get("with_self", True),
-                  flags=kw.get("debug_flags", 0))
+                  flags=kw.get("debug_flags", 0), idx_every=IDX_EVERY)
     try:
         ls.run(steps)
         inf = ls.last["in_flags"]
@@ -208,26 +92,22 @@ def test_long_lockstep(oracle, shapes, tag, n_a, n_env, steps, shape_set, seed, 
 # ------------------------------------------------------------------------------------------------------------------------
 # Whole batches at the benchmarked state
 # ------------------------------------------------------------------------------------------------------------------------
-def _check_whole_batch(sb, to, pre, outs, f32, tag, t):
+def _check_whole_batch(sb, to, pre, outs, state, tag, t):
     """Every env of one step, CHUNK envs at a time: pre = the step's inputs (host), outs = its device outputs."""
-    obs, rew, done, pri, p, dp = outs
     idx = sb.indices()
     E = sb.n_env
     for b in range(0, E, CHUNK):
         e = min(E, b + CHUNK)
         envs = np.arange(b, e)
         o = to.step(pre["p"][b:e], pre["dp"][b:e], pre["a"][b:e], pre["nei"][b:e], envs=envs)
-        out = dict(p=_host(p[b:e]), dp=_host(dp[b:e]), obs=_host(obs[b:e]), reward=_host(rew[b:e]), done=_host(done[b:e]),
-                   prior=_host(pri[b:e]))
-        ix = {k: _host(idx[k][b:e]) for k in IDX}
         try:
-            _compare_step(out, o, f32, True, ix, env0=b)
+            compare(host_copy(sb, outs, state=state, indices=idx, rows=slice(b, e)), device_layout(o, "f32"), f"{tag} step {t}", env0=b)
         except Mismatch as ex:
             sub = {k: v[b:e] for k, v in pre.items()}
-            _dump(tag, t, int(ex.envs[0]) - b, sub, _Sub(to, envs), sb.cfg.debug_flags)
-            raise AssertionError(f"{tag} step {t}: {ex}") from None
-        del o, out, ix
-    return int(_host(idx["in_flags"]).sum())
+            dump(tag, t, int(ex.envs[0]) - b, sub, _Sub(to, envs), sb.cfg.debug_flags)
+            raise
+        del o
+    return int(to_host(idx["in_flags"]).sum())
 
 
 class _Sub:
@@ -270,8 +150,8 @@ def test_whole_batch_at_bench_state(oracle, shapes, tag, n_a, n_env, env_offset,
             pre = None
             if t in checks:                    # the step's inputs, taken BEFORE any detour: the restore must not show
                 p0, dp0 = sb.get_state()
-                pre = dict(p=_host(p0), dp=_host(dp0), nei=_host(sb.indices(False, False)["neighbor_index"]),
-                           a=np.swapaxes(_host(act), 1, 2).astype(np.float64))
+                pre = dict(p=to_host(p0), dp=to_host(dp0), nei=to_host(sb.indices(False, False)["neighbor_index"]),
+                           a=oracle_action(act))
             if t - 1 in detours:
                 p0, dp0 = sb.get_state()
                 act0 = act.clone()
@@ -284,7 +164,7 @@ def test_whole_batch_at_bench_state(oracle, shapes, tag, n_a, n_env, env_offset,
             obs, rew, done, pri = sb.step(act)
             if pre is not None:
                 p, dp = sb.get_state()
-                in_shape = _check_whole_batch(sb, to, pre, (obs, rew, done, pri, p, dp), True, tag, t)
+                in_shape = _check_whole_batch(sb, to, pre, (obs, rew, done, pri), (p, dp), tag, t)
                 assert in_shape > 0
                 del pre, p, dp
             act = pri
@@ -297,34 +177,22 @@ def test_whole_batch_at_bench_state(oracle, shapes, tag, n_a, n_env, env_offset,
 # ------------------------------------------------------------------------------------------------------------------------
 # Lattice mode switching mid-trajectory
 # ------------------------------------------------------------------------------------------------------------------------
-def _lat_nrs(cells, n_g, d_sen=D_SEN):
-    """set_lattice_mode's window-row count for a batch of lattice cell sets (env_api.hip: detect_lattice fits the step as
-    the closest pair of consecutive cells, stored as float; swarm_set_cells takes R = d_sen / step; set_lattice_mode takes
-    floor(2 (max R + 0.01)) + 1 in float).  The lattice kernel runs while this is <= 15."""
-    rmax = np.float32(0)
-    for c, n in zip(cells, n_g):
-        d = np.diff(c[:, :n], axis=1)
-        step = np.float32(np.sqrt(np.min(d[0] * d[0] + d[1] * d[1])))
-        rmax = max(rmax, np.float32(d_sen / np.float64(step)))
-    return int(np.floor(np.float32(2) * (rmax + np.float32(0.01)))) + 1
-
-
 def test_lattice_mode_switches_mid_trajectory(oracle, shapes):
-    """One env's cells replaced by an off-lattice copy demotes the whole batch to the generic kernel, restoring them promotes
-    it back, and a lattice spacing on either side of the 15-window-row cap keeps or leaves the lattice kernel: the
-    trajectory stays oracle-exact across every switch."""
+    """One env's cells replaced by an off-lattice copy send that env's workgroup to the generic launch while the others keep
+    the row walk, restoring them brings it back, and a lattice spacing on either side of the 15-window-row cap keeps or
+    leaves the lattice kernel: the trajectory stays oracle-exact across every switch."""
     n_a, E, seg = 64, 16, 60
     sy = _synth(E, n_a, shapes, 5150, 0.5)
     sb, ra = _batch(E, n_a, sy, shapes)
-    ls = Lockstep(oracle, sb, sy, ra, "switch")
+    ls = Lockstep(oracle, sb, sy, ra, "switch", idx_every=IDX_EVERY)
     cells, n_g, l_cell = sy["cells"], sy["n_g"], sy["l_cell"]
     try:
-        assert sb.lattice_envs() == E and _lat_nrs(cells, n_g) <= 15
+        assert sb.lattice_envs() == E and lat_nrs(cells, n_g) <= 15
         ls.run(seg)
         jit = cells[5:6].copy()
         jit[0, :, : n_g[5]] += np.random.default_rng(5).normal(0, 0.004, (2, n_g[5]))
         ls.set_cells(jit, n_g[5:6], l_cell[5:6], env_begin=5)
-        assert sb.lattice_envs() == E - 1          # one env off the lattice: the whole batch runs the generic kernel
+        assert sb.lattice_envs() == E - 1          # one env off the lattice: its workgroup takes the generic launch
         ls.observe()
         ls.run(seg)
         ls.set_cells(cells[5:6], n_g[5:6], l_cell[5:6], env_begin=5)
@@ -339,7 +207,7 @@ def test_lattice_mode_switches_mid_trajectory(oracle, shapes):
             sc[0, :, : n_g[k]] = ctr + (g - ctr) * (spacing / l_cell[k])
             ls.set_cells(sc, n_g[k:k + 1], [spacing], env_begin=k)
             assert sb.lattice_envs() == E          # still a lattice; only the window-row count decides the kernel
-            assert _lat_nrs(ls.to.cells, ls.to.n_g) == nrs
+            assert lat_nrs(ls.to.cells, ls.to.n_g) == nrs
             ls.observe()
             ls.run(seg)
         assert ls.last["in_flags"].any() and ls.max_contacts > 0

@@ -35,13 +35,13 @@ import functools
 import numpy as np
 import pytest
 
-from helpers import ThreadedOracle, make_case, pad_cells
+from helpers import ThreadedOracle, lat_nrs, make_case, pad_cells
+from lockstep import IDX, OBSERVE, compare, device_layout, host_copy, oracle_action
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-IDX = ("neighbor_index", "in_flags", "sensed_index", "occupied_index")
-D_SEN, SIZE_A = 0.4, 0.035
+SIZE_A = 0.035
 FINE = 0.053                       # lattice spacing whose sensing window is 16 rows
 DEMOTE, SERIAL, NO_LATTICE = 8, 16, 2           # debug_flags bits 3, 4 and 1
 # test 1: (N, E, {env: kind of its non-walking cell set})
@@ -56,18 +56,6 @@ PARITY = [
     (256, 2, {1: "j"}),
 ]
 STEPS = 5
-
-
-def _lat_nrs(cells, n_g, d_sen=D_SEN):
-    """The window-row count of lattice cell sets (csrc/env_api.hip: detect_lattice fits the step as the closest pair of
-    consecutive cells, stored as float; R = d_sen / step; window_rows takes floor(2 (R + 0.01)) + 1 in float).  The row walk
-    serves a cell set while this is <= 15."""
-    rmax = np.float32(0)
-    for c, n in zip(cells, n_g):
-        d = np.diff(c[:, :n], axis=1)
-        step = np.float32(np.sqrt(np.min(d[0] * d[0] + d[1] * d[1])))
-        rmax = max(rmax, np.float32(d_sen / np.float64(step)))
-    return int(np.floor(np.float32(2) * (rmax + np.float32(0.01)))) + 1
 
 
 def _epb(n_a):
@@ -145,7 +133,7 @@ def _reference(n_a, n_env, kinds_key):
         p, dp, nei, steps = sy["p"], sy["dp"], first["neighbor_index"], []
         for _ in range(STEPS):
             act = _pair_actions(rng, p)
-            o = to.step(p, dp, np.swapaxes(act, 1, 2).astype(np.float64), nei)
+            o = to.step(p, dp, oracle_action(act), nei)
             o["act"] = act
             steps.append(o)
             p, dp, nei = o["p"], o["dp"], o["neighbor_index"]
@@ -162,14 +150,6 @@ def _assert_reached(sy, first, steps):
         d = p[:, :, :, None] - p[:, :, None, :]
         dc = np.sqrt(d[:, 0] ** 2 + d[:, 1] ** 2) + 10.0 * np.eye(p.shape[2])
         assert (dc.reshape(len(p), -1).min(axis=1) < 2 * SIZE_A).all(), ("contact", t)
-
-
-def _rows(x):
-    return np.ascontiguousarray(np.swapaxes(x, 1, 2))
-
-
-def _host(t):
-    return t.cpu().numpy()
 
 
 def _batch(sy, n_a, ra, flags=0, dtype=None):
@@ -189,20 +169,6 @@ def _nan_outputs(sb):
                 done=torch.full((E, N), 255, dtype=torch.uint8, **kw), prior=torch.full((E, N, 2), float("nan"), dtype=sb.obs_dtype, **kw))
 
 
-def _same(dev, ref, what):
-    if dev.shape == ref.shape and np.array_equal(dev, ref):
-        return
-    assert dev.shape == ref.shape, (what, dev.shape, ref.shape)
-    bad = np.nonzero(~(dev == ref).reshape(len(dev), -1).all(1))[0]
-    raise AssertionError(f"{what}: envs {list(bad[:8])} differ")
-
-
-def _same_indices(sb, o, what):
-    idx = sb.indices()
-    for k in IDX:
-        _same(_host(idx[k]), o[k], f"{what}: {k}")
-
-
 # ------------------------------------------------------------------------------------------------------------------------
 # 1. oracle parity, float64 handles
 # ------------------------------------------------------------------------------------------------------------------------
@@ -213,25 +179,18 @@ def test_oracle_parity(n_a, n_env, kinds):
     assert {"j", "s", "f"} >= set(kinds.values())
     for e, kind in kinds.items():                      # the fine lattice is a lattice whose window is 16 rows; the others walk
         if kind == "f":
-            assert _lat_nrs(sy["cells"][e:e + 1], sy["n_g"][e:e + 1]) == 16
+            assert lat_nrs(sy["cells"][e:e + 1], sy["n_g"][e:e + 1]) == 16
     walkers = [e for e in range(n_env) if e not in kinds]
-    assert walkers and _lat_nrs(sy["cells"][walkers], sy["n_g"][walkers]) <= 15
+    assert walkers and lat_nrs(sy["cells"][walkers], sy["n_g"][walkers]) <= 15
     sb = _batch(sy, n_a, ra)
     try:
         assert sb.path_envs() == _path_counts(kinds, n_env, n_a)
         assert sb.lattice_envs() == n_env - sum(k != "f" for k in kinds.values())
-        _same(_host(sb.observe()), _rows(first["obs"]), "observe: obs")
-        _same_indices(sb, first, "observe")
+        compare(host_copy(sb, sb.observe(), state=False, indices=True), device_layout(first), "observe", fields=OBSERVE)
         for t, o in enumerate(steps):
             out = _nan_outputs(sb)
             sb.step(torch.from_numpy(o["act"]).to(sb.device), out=out)
-            pg, dpg = sb.get_state()
-            _same(_host(pg), o["p"], f"step {t}: p"); _same(_host(dpg), o["dp"], f"step {t}: dp")
-            _same(_host(out["rew"]).astype(np.float64), o["reward"], f"step {t}: reward")
-            _same(_host(out["done"]), np.zeros((n_env, n_a), np.uint8), f"step {t}: done")
-            _same(_host(out["obs"]), _rows(o["obs"]), f"step {t}: obs")
-            _same(_host(out["prior"]), _rows(o["a_prior"]), f"step {t}: a_prior")
-            _same_indices(sb, o, f"step {t}")
+            compare(host_copy(sb, out, indices=True), device_layout(o), f"step {t}")
         assert sb.path_envs() == _path_counts(kinds, n_env, n_a)
     finally:
         sb.close()
@@ -352,24 +311,18 @@ def test_switching_mid_trajectory(oracle, shapes):
 
     def observe(what):
         o = to.observe(st["p"], st["dp"])
-        _same(_host(sb.observe()), _rows(o["obs"]), f"{what}: observe")
-        _same_indices(sb, o, f"{what}: observe")
+        compare(host_copy(sb, sb.observe(), state=False, indices=True), device_layout(o), f"{what}: observe", fields=OBSERVE)
         st["nei"] = o["neighbor_index"]
         st["act"] = st["act"].clone()
 
     def run(what):
         for t in range(seg):
-            a = np.swapaxes(_host(st["act"]), 1, 2).astype(np.float64)
-            obs, rew, done, pri = sb.step(st["act"])
+            a = oracle_action(st["act"])
+            out = sb.step(st["act"])
             o = to.step(st["p"], st["dp"], a, st["nei"])
-            pg, dpg = sb.get_state()
-            _same(_host(pg), o["p"], f"{what} step {t}: p"); _same(_host(dpg), o["dp"], f"{what} step {t}: dp")
-            _same(_host(rew).astype(np.float64), o["reward"], f"{what} step {t}: reward")
-            assert not done.any().item()
-            _same(_host(obs), _rows(o["obs"]), f"{what} step {t}: obs")
-            _same(_host(pri), _rows(o["a_prior"]), f"{what} step {t}: a_prior")
-            st.update(p=o["p"], dp=o["dp"], nei=o["neighbor_index"], act=pri.to(torch.float32), last=o)
-        _same_indices(sb, st["last"], f"{what}: last step")
+            last = t == seg - 1                            # the four index lists on the last step of a run
+            compare(host_copy(sb, out, indices=last), device_layout(o), f"{what} step {t}", indices=last)
+            st.update(p=o["p"], dp=o["dp"], nei=o["neighbor_index"], act=out[3].to(torch.float32), last=o)
 
     def put(envs, src):
         c = to.cells.copy()

@@ -14,8 +14,9 @@ import os
 import numpy as np
 import pytest
 
-from helpers import GOLDEN_DIR, golden_files, load_golden, make_case
+from helpers import GOLDEN_DIR, golden_files, load_golden, make_case, oracle_run, pad_cells, random_actions
 from helpers import adversarial_case as _adversarial_case
+from lockstep import compare, device_layout, hold, host_copy
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -26,19 +27,9 @@ def _batch(**kw):
     return SwarmBatch(**kw)
 
 
-def _to_rows(obs_cols):
-    """oracle obs (D, N) -> rows (N, D)."""
-    return np.ascontiguousarray(obs_cols.T)
-
-
-def _pad_cells(grids, ng_max):
-    E = len(grids)
-    cells = np.zeros((E, 2, ng_max))
-    n_g = np.zeros(E, np.int32)
-    for e, g in enumerate(grids):
-        n_g[e] = g.shape[1]
-        cells[e, :, : g.shape[1]] = g
-    return cells, n_g
+# lockstep's field -> its key in the golden files
+GOLDEN = dict(p="p_next", dp="dp_next", obs="obs", a_prior="a_prior", reward="rew", neighbor_index="nei", in_flags="in_flags",
+              sensed_index="sensed", occupied_index="occupied")
 
 
 @pytest.mark.parametrize("path", golden_files(), ids=os.path.basename)
@@ -52,29 +43,17 @@ def test_golden_steps(path, dtype):
     sb = _batch(n_env=1, n_agents=n_a, n_cells_max=n_g, r_avoid=float(z["r_avoid"]), d_sen=float(z["d_sen"]),
                 is_boundary=bool(z["is_boundary"]), with_self=bool(z["with_self"]), obs_dtype=odt,
                 boundary=tuple(z["boundary"]))
-    sb.set_cells(z["grid"][None], [n_g], [float(z["l_cell"])])
-    for t in range(T):
-        sb.set_state(z["p"][t][None], z["dp"][t][None])
-        sb.observe()
-        assert np.array_equal(sb.indices(False, False)["neighbor_index"][0].cpu().numpy(), z["nei_prev"][t])
-        act = torch.from_numpy(np.ascontiguousarray(z["a"][t].T)[None]).to(sb.device)       # (2,N) -> [1,N,2]
-        obs, rew, done, pri = sb.step(act)
-        p, dp = sb.get_state()
-        assert np.array_equal(p[0].cpu().numpy(), z["p_next"][t])
-        assert np.array_equal(dp[0].cpu().numpy(), z["dp_next"][t])
-        idx = sb.indices()
-        assert np.array_equal(idx["neighbor_index"][0].cpu().numpy(), z["nei"][t])
-        assert np.array_equal(idx["in_flags"][0].cpu().numpy(), z["in_flags"][t])
-        assert np.array_equal(idx["sensed_index"][0].cpu().numpy(), z["sensed"][t])
-        assert np.array_equal(idx["occupied_index"][0].cpu().numpy(), z["occupied"][t])
-        assert np.array_equal(rew[0].cpu().numpy().astype(np.float64), z["rew"][t][0])
-        assert not done.any().item()
-        ref_obs = _to_rows(z["obs"][t]); ref_pri = _to_rows(z["a_prior"][t])
-        if dtype == "f32":
-            ref_obs = ref_obs.astype(np.float32); ref_pri = ref_pri.astype(np.float32)
-        assert np.array_equal(obs[0].cpu().numpy(), ref_obs)
-        assert np.array_equal(pri[0].cpu().numpy(), ref_pri)
-    sb.close()
+    try:
+        sb.set_cells(z["grid"][None], [n_g], [float(z["l_cell"])])
+        for t in range(T):
+            sb.set_state(z["p"][t][None], z["dp"][t][None])
+            sb.observe()
+            assert np.array_equal(sb.indices(False, False)["neighbor_index"][0].cpu().numpy(), z["nei_prev"][t])
+            act = torch.from_numpy(np.ascontiguousarray(z["a"][t].T)[None]).to(sb.device)       # (2,N) -> [1,N,2]
+            dev = host_copy(sb, sb.step(act), indices=True)
+            compare(dev, device_layout({k: z[g][t][None] for k, g in GOLDEN.items()}, dtype), t)
+    finally:
+        sb.close()
 
 
 @pytest.mark.parametrize("n_a", [30, 100, 200])
@@ -86,32 +65,23 @@ def test_golden_batches(n_a, dtype):
     zs = [load_golden(p) for p in golden_files(f"g11_n{n_a}_s*.npz")]
     assert len(zs) == 3
     E, T = len(zs), min(z["p"].shape[0] for z in zs)
-    cells, n_g = _pad_cells([z["grid"] for z in zs], max(z["grid"].shape[1] for z in zs))
+    cells, n_g = pad_cells([z["grid"] for z in zs], max(z["grid"].shape[1] for z in zs))
     assert len({float(z["r_avoid"]) for z in zs}) == 1 and len(set(n_g.tolist())) > 1
     odt = torch.float64 if dtype == "f64" else torch.float32
     sb = _batch(n_env=E, n_agents=n_a, n_cells_max=cells.shape[2], r_avoid=float(zs[0]["r_avoid"]), d_sen=float(zs[0]["d_sen"]),
                 obs_dtype=odt, boundary=tuple(zs[0]["boundary"]))
-    sb.set_cells(cells, n_g, [float(z["l_cell"]) for z in zs])
     st = lambda k, t: np.stack([z[k][t] for z in zs])
-    for t in range(T):
-        sb.set_state(st("p", t), st("dp", t))
-        sb.observe()
-        assert np.array_equal(sb.indices(False, False)["neighbor_index"].cpu().numpy(), st("nei_prev", t))
-        act = torch.from_numpy(np.ascontiguousarray(st("a", t).transpose(0, 2, 1))).to(sb.device)      # (E,2,N) -> [E,N,2]
-        obs, rew, done, pri = sb.step(act)
-        p, dp = sb.get_state()
-        assert np.array_equal(p.cpu().numpy(), st("p_next", t)) and np.array_equal(dp.cpu().numpy(), st("dp_next", t))
-        idx = sb.indices()
-        for k_dev, k_ref in (("neighbor_index", "nei"), ("in_flags", "in_flags"), ("sensed_index", "sensed"), ("occupied_index", "occupied")):
-            assert np.array_equal(idx[k_dev].cpu().numpy(), st(k_ref, t)), (k_dev, t)
-        assert np.array_equal(rew.cpu().numpy().astype(np.float64), st("rew", t)[:, 0])
-        assert not done.any().item()
-        ref_obs = np.ascontiguousarray(st("obs", t).transpose(0, 2, 1)); ref_pri = np.ascontiguousarray(st("a_prior", t).transpose(0, 2, 1))
-        if dtype == "f32":
-            ref_obs = ref_obs.astype(np.float32); ref_pri = ref_pri.astype(np.float32)
-        assert np.array_equal(obs.cpu().numpy(), ref_obs)
-        assert np.array_equal(pri.cpu().numpy(), ref_pri)
-    sb.close()
+    try:
+        sb.set_cells(cells, n_g, [float(z["l_cell"]) for z in zs])
+        for t in range(T):
+            sb.set_state(st("p", t), st("dp", t))
+            sb.observe()
+            assert np.array_equal(sb.indices(False, False)["neighbor_index"].cpu().numpy(), st("nei_prev", t))
+            act = torch.from_numpy(np.ascontiguousarray(st("a", t).transpose(0, 2, 1))).to(sb.device)      # (E,2,N) -> [E,N,2]
+            dev = host_copy(sb, sb.step(act), indices=True)
+            compare(dev, device_layout({k: st(g, t) for k, g in GOLDEN.items()}, dtype), t)
+    finally:
+        sb.close()
 
 
 def test_known_answer_case():
@@ -127,7 +97,7 @@ def test_known_answer_case():
     assert idx["in_flags"][0].cpu().tolist() == [1, 0, 0]
     assert idx["sensed_index"][0].cpu().tolist() == [[2, -1, -1, -1], [0, 1, 2, -1], [-1, -1, -1, -1]]
     assert idx["occupied_index"][0].cpu().tolist() == [[0, 1, -1, -1, -1], [-1] * 5, [-1] * 5]
-    assert np.array_equal(obs[0].cpu().numpy(), _to_rows(z["obs"]))
+    assert np.array_equal(obs[0].cpu().numpy(), device_layout(dict(obs=z["obs"][None]))["obs"][0])
     sb.close()
 
 
@@ -148,47 +118,11 @@ def test_batched_trajectories_vs_oracle(oracle, shapes, n_a, n_env, cluster, per
     rng = np.random.default_rng(7000 + 13 * n_a + n_env)
     ra = r_avoid_for(n_a, shapes)
     cases = [make_case(rng, shapes, n_a, cluster) for _ in range(n_env)]
-    ng_max = max(c[2].shape[1] for c in cases) + 3
-    cells, n_g = _pad_cells([c[2] for c in cases], ng_max)
-    sb = _batch(n_env=n_env, n_agents=n_a, n_cells_max=ng_max, r_avoid=ra, is_boundary=not periodic,
-                with_self=with_self, obs_dtype=torch.float64, debug_flags=flags)
-    sb.set_cells(cells, n_g, [c[3] for c in cases])
+    # random float32 actions alternating with the fed-back prior (assembles the swarm; exercises the occupied filter harder)
+    ref = oracle_run(oracle, cases, random_actions(rng, steps, n_env, n_a), ra, periodic=periodic, with_self=with_self)
     # the synthetic shapes are tiled lattices like the reference's: recognised unless the path is disabled
-    assert sb.lattice_envs() == (n_env if flags == 0 else 0)
-    p = np.stack([c[0] for c in cases]); dp = np.stack([c[1] for c in cases])
-    sb.set_state(p, dp)
-    obs0 = sb.observe().cpu().numpy()
-    idx = sb.indices()
-    nei = []
-    for e, (pe, dpe, g, l_cell) in enumerate(cases):
-        o = oracle.get_observation(pe, dpe, g, l_cell, ra, is_periodic=periodic, with_self=with_self)
-        assert np.array_equal(obs0[e], _to_rows(o["obs"])), e
-        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-            assert np.array_equal(idx[k][e].cpu().numpy(), o[k]), (e, k)
-        nei.append(o["neighbor_index"])
-    state = [(c[0], c[1]) for c in cases]
-    for t in range(steps):
-        if t % 2 == 0:
-            act = rng.uniform(-1, 1, (n_env, n_a, 2)).astype(np.float32)
-        else:   # feed the prior back (assembles the swarm; exercises the occupied filter harder)
-            act = last_prior.astype(np.float32)
-        obs, rew, done, pri = sb.step(torch.from_numpy(act).to(sb.device))
-        obs, rew, pri = obs.cpu().numpy(), rew.cpu().numpy(), pri.cpu().numpy()
-        pg, dpg = [x.cpu().numpy() for x in sb.get_state()]
-        idx = sb.indices()
-        for e in range(n_env):
-            s = oracle.step(state[e][0], state[e][1], np.ascontiguousarray(act[e].T), cases[e][2], nei[e], cases[e][3],
-                            ra, is_boundary=not periodic, with_self=with_self)
-            assert np.array_equal(pg[e], s["p"]) and np.array_equal(dpg[e], s["dp"]), (t, e)
-            assert np.array_equal(obs[e], _to_rows(s["obs"])), (t, e)
-            assert np.array_equal(pri[e], _to_rows(s["a_prior"])), (t, e)
-            assert np.array_equal(rew[e].astype(np.float64), s["reward"][0]), (t, e)
-            for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-                assert np.array_equal(idx[k][e].cpu().numpy(), s[k]), (t, e, k)
-            state[e] = (s["p"], s["dp"]); nei[e] = s["neighbor_index"]
-        last_prior = pri
-        assert not done.any().item()
-    sb.close()
+    hold(cases, ref, lattice=n_env if flags == 0 else 0, r_avoid=ra, is_boundary=not periodic, with_self=with_self,
+         obs_dtype=torch.float64, debug_flags=flags)
 
 
 def test_small_caps(oracle, shapes):
@@ -198,22 +132,10 @@ def test_small_caps(oracle, shapes):
     n_a, n_env = 32, 4
     ra = r_avoid_for(n_a, shapes)
     cases = [make_case(rng, shapes, n_a, 1) for _ in range(n_env)]
-    ng_max = max(c[2].shape[1] for c in cases)
-    cells, n_g = _pad_cells([c[2] for c in cases], ng_max)
     # (G-1 odd -> integer cap arithmetic; G-1 even -> the reference's fp64 round(), ties possible)
     for topo, g_max, occ_max in ((3, 10, 7), (6, 80, 20), (1, 6, 200), (2, 5, 9), (6, 81, 33), (4, 21, 11)):
-        sb = _batch(n_env=n_env, n_agents=n_a, n_cells_max=ng_max, r_avoid=ra, topo=topo, g_max=g_max,
-                    occ_max=occ_max, obs_dtype=torch.float64)
-        sb.set_cells(cells, n_g, [c[3] for c in cases])
-        sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
-        obs = sb.observe().cpu().numpy()
-        idx = sb.indices()
-        for e, (pe, dpe, g, l_cell) in enumerate(cases):
-            o = oracle.get_observation(pe, dpe, g, l_cell, ra, topo=topo, g_max=g_max, occ_max=occ_max)
-            assert np.array_equal(obs[e], _to_rows(o["obs"]))
-            for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-                assert np.array_equal(idx[k][e].cpu().numpy(), o[k]), (e, k)
-        sb.close()
+        first = [oracle.get_observation(p, dp, g, l_cell, ra, topo=topo, g_max=g_max, occ_max=occ_max) for p, dp, g, l_cell in cases]
+        hold(cases, (first, []), pad=0, r_avoid=ra, topo=topo, g_max=g_max, occ_max=occ_max, obs_dtype=torch.float64)
 
 
 @pytest.mark.parametrize("n_a,n_env,env_offset", [
@@ -241,33 +163,23 @@ def test_full_size_properties(oracle, shapes, n_a, n_env, env_offset):
     nei0 = sb.indices(False, False)["neighbor_index"].cpu().numpy()
     rng = np.random.default_rng(1)
     act = rng.uniform(-1, 1, (n_env, n_a, 2)).astype(np.float32)
-    obs, rew, done, pri = sb.step(torch.from_numpy(act).to(sb.device))
-    obs_c, rew_c, pri_c = obs.cpu().numpy(), rew.cpu().numpy(), pri.cpu().numpy()
-    pg, dpg = [x.cpu().numpy() for x in sb.get_state()]
-    assert np.isfinite(obs_c).all() and np.isfinite(pg).all()
-    assert not done.any().item()
-    assert set(np.unique(rew_c)).issubset({0.0, 1.0})
-    assert np.abs(dpg).max() <= 0.8 and np.abs(pri_c).max() <= 1.0
-    assert (obs_c[:, :, 0] == pg[:, 0, :].astype(np.float32)).all()          # self block = absolute state
-    idx = sb.indices()
-    sen = idx["sensed_index"].cpu().numpy()
-    pad = sen < 0                                                            # unused slots are zero in obs
-    sl = obs_c[:, :, 32:].reshape(n_env, n_a, 80, 2)
-    assert (sl[pad] == 0).all()
-    assert ((sen[:, :, 1:] < 0) | (sen[:, :, :-1] >= 0)).all()               # valid slots form a prefix
-    assert (np.diff(np.where(sen >= 0, sen, 1 << 20), axis=-1) > 0)[(sen[:, :, 1:] >= 0)].all()   # ascending cell index
-    assert sb.lattice_envs() == n_env                                       # tiled shapes: the row-walk path (N <= 64)
-    sample = np.unique(np.concatenate([[0, 1, n_env - 2, n_env - 1], rng.choice(n_env, 24 if n_a <= 64 else 10, replace=False)]))
-    for e in sample:
-        g = sy["cells"][e][:, : sy["n_g"][e]]
-        s = oracle.step(sy["p"][e], sy["dp"][e], np.ascontiguousarray(act[e].T), g, nei0[e], float(sy["l_cell"][e]), ra)
-        assert np.array_equal(pg[e], s["p"]) and np.array_equal(dpg[e], s["dp"])
-        assert np.array_equal(obs_c[e], _to_rows(s["obs"]).astype(np.float32))
-        assert np.array_equal(pri_c[e], _to_rows(s["a_prior"]).astype(np.float32))
-        assert np.array_equal(rew_c[e].astype(np.float64), s["reward"][0])
-        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-            assert np.array_equal(idx[k][e].cpu().numpy(), s[k]), (e, k)
-    sb.close()
+    try:
+        dev = host_copy(sb, sb.step(torch.from_numpy(act).to(sb.device)), indices=True)
+        obs_c, pg, sen = dev["obs"], dev["p"], dev["sensed_index"]
+        assert np.isfinite(obs_c).all() and np.isfinite(pg).all()
+        assert set(np.unique(dev["reward"])).issubset({0.0, 1.0})
+        assert np.abs(dev["dp"]).max() <= 0.8 and np.abs(dev["a_prior"]).max() <= 1.0
+        assert (obs_c[:, :, 0] == pg[:, 0, :].astype(np.float32)).all()          # self block = absolute state
+        assert ((sen[:, :, 1:] < 0) | (sen[:, :, :-1] >= 0)).all()               # valid slots form a prefix
+        assert (np.diff(np.where(sen >= 0, sen, 1 << 20), axis=-1) > 0)[(sen[:, :, 1:] >= 0)].all()   # ascending cell index
+        assert sb.lattice_envs() == n_env                                       # tiled shapes: the row-walk path (N <= 64)
+        compare(dev, None, "whole batch", fields=("done", "unused"))            # no done, unused slots zero in obs: every env
+        sample = np.unique(np.concatenate([[0, 1, n_env - 2, n_env - 1], rng.choice(n_env, 24 if n_a <= 64 else 10, replace=False)]))
+        ref = [oracle.step(sy["p"][e], sy["dp"][e], np.ascontiguousarray(act[e].T), sy["cells"][e][:, : sy["n_g"][e]], nei0[e],
+                           float(sy["l_cell"][e]), ra) for e in sample]
+        compare(dev, device_layout(ref, "f32"), "sample", envs=sample)
+    finally:
+        sb.close()
 
 
 def test_error_behaviour(shapes):
@@ -296,32 +208,8 @@ def test_threshold_adversarial_inputs(oracle, shapes, n_a, n_env, force):
     rng = np.random.default_rng(4242 + n_a + force)
     ra = r_avoid_for(n_a, shapes)
     cases = [_adversarial_case(rng, shapes, n_a, ra) for _ in range(n_env)]
-    ng_max = max(c[2].shape[1] for c in cases)
-    cells, n_g = _pad_cells([c[2] for c in cases], ng_max)
-    sb = _batch(n_env=n_env, n_agents=n_a, n_cells_max=ng_max, r_avoid=ra, obs_dtype=torch.float64, debug_flags=force)
-    sb.set_cells(cells, n_g, [c[3] for c in cases])
-    sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
-    obs0 = sb.observe().cpu().numpy()
-    idx = sb.indices()
-    nei = []
-    for e, (pe, dpe, g, l_cell) in enumerate(cases):
-        o = oracle.get_observation(pe, dpe, g, l_cell, ra)
-        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-            assert np.array_equal(idx[k][e].cpu().numpy(), o[k]), (e, k)
-        assert np.array_equal(obs0[e], _to_rows(o["obs"])), e
-        nei.append(o["neighbor_index"])
-    act = np.zeros((n_env, n_a, 2), np.float32)          # zero action: the agents stay near the thresholds
-    obs, rew, done, pri = sb.step(torch.from_numpy(act).to(sb.device))
-    idx = sb.indices()
-    pg, dpg = [x.cpu().numpy() for x in sb.get_state()]
-    for e, (pe, dpe, g, l_cell) in enumerate(cases):
-        s = oracle.step(pe, dpe, np.ascontiguousarray(act[e].T), g, nei[e], l_cell, ra)
-        assert np.array_equal(pg[e], s["p"]) and np.array_equal(dpg[e], s["dp"])
-        assert np.array_equal(obs[e].cpu().numpy(), _to_rows(s["obs"]))
-        assert np.array_equal(rew[e].cpu().numpy().astype(np.float64), s["reward"][0])
-        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-            assert np.array_equal(idx[k][e].cpu().numpy(), s[k]), (e, k)
-    sb.close()
+    ref = oracle_run(oracle, cases, [np.zeros((n_env, n_a, 2), np.float32)], ra)      # zero action: the agents stay near the thresholds
+    hold(cases, ref, pad=0, r_avoid=ra, obs_dtype=torch.float64, debug_flags=force)
 
 
 def test_forced_exact_paths_equal_fast_paths(shapes):
@@ -392,20 +280,8 @@ def test_non_lattice_cells_fall_back_to_generic_path(oracle, shapes):
         else:
             g = np.ascontiguousarray(g[:, rng.permutation(g.shape[1])])   # on-lattice points, but not row-major order
         cases.append((p, dp, np.ascontiguousarray(g), l_cell))
-    ng_max = max(c[2].shape[1] for c in cases)
-    cells, n_g = _pad_cells([c[2] for c in cases], ng_max)
-    sb = _batch(n_env=n_env, n_agents=n_a, n_cells_max=ng_max, r_avoid=ra, obs_dtype=torch.float64)
-    sb.set_cells(cells, n_g, [c[3] for c in cases])
-    assert sb.lattice_envs() == 0
-    sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
-    obs0 = sb.observe().cpu().numpy()
-    idx = sb.indices()
-    for e, (pe, dpe, g, l_cell) in enumerate(cases):
-        o = oracle.get_observation(pe, dpe, g, l_cell, ra)
-        assert np.array_equal(obs0[e], _to_rows(o["obs"]))
-        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-            assert np.array_equal(idx[k][e].cpu().numpy(), o[k]), (e, k)
-    sb.close()
+    first = [oracle.get_observation(p, dp, g, l_cell, ra) for p, dp, g, l_cell in cases]
+    hold(cases, (first, []), lattice=0, pad=0, r_avoid=ra, obs_dtype=torch.float64)
 
 
 @pytest.mark.parametrize("n_a", [64, 24])
@@ -430,32 +306,9 @@ def test_wide_lattice_uses_64_bit_row_masks(oracle, n_a):
             c = int(rng.integers(0, g.shape[1])); u = rng.normal(size=2); u /= np.linalg.norm(u)
             p[:, i] = g[:, c] + u * [0.4, ra / 2, 0.5 * l_cell][i % 3] * (1 + [0.0, 1e-13, -1e-10][(i // 3) % 3])
         dp = rng.uniform(-0.3, 0.3, (2, n_a))
-        cases.append((np.ascontiguousarray(p), dp, g))
-    ng = cases[0][2].shape[1]
-    cells, n_g = _pad_cells([c[2] for c in cases], ng)
-    sb = _batch(n_env=n_env, n_agents=n_a, n_cells_max=ng, r_avoid=ra, obs_dtype=torch.float64)
-    sb.set_cells(cells, n_g, [l_cell] * n_env)
-    assert sb.lattice_envs() == n_env
-    sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
-    obs0 = sb.observe().cpu().numpy()
-    idx = sb.indices()
-    nei = []
-    for e, (pe, dpe, g) in enumerate(cases):
-        o = oracle.get_observation(pe, dpe, g, l_cell, ra)
-        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-            assert np.array_equal(idx[k][e].cpu().numpy(), o[k]), (e, k)
-        assert np.array_equal(obs0[e], _to_rows(o["obs"])), e
-        nei.append(o["neighbor_index"])
-    act = rng.uniform(-1, 1, (n_env, n_a, 2)).astype(np.float32)
-    obs, rew, done, pri = sb.step(torch.from_numpy(act).to(sb.device))
-    idx = sb.indices()
-    for e, (pe, dpe, g) in enumerate(cases):
-        s = oracle.step(pe, dpe, np.ascontiguousarray(act[e].T.astype(np.float64)), g, nei[e], l_cell, ra)
-        assert np.array_equal(obs[e].cpu().numpy(), _to_rows(s["obs"]))
-        assert np.array_equal(rew[e].cpu().numpy().astype(np.float64), s["reward"][0])
-        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-            assert np.array_equal(idx[k][e].cpu().numpy(), s[k]), (e, k)
-    sb.close()
+        cases.append((np.ascontiguousarray(p), dp, g, l_cell))
+    ref = oracle_run(oracle, cases, [rng.uniform(-1, 1, (n_env, n_a, 2)).astype(np.float32)], ra)
+    hold(cases, ref, lattice=n_env, pad=0, r_avoid=ra, obs_dtype=torch.float64)
 
 
 @pytest.mark.parametrize("n_a,periodic", [(64, False), (36, True), (200, False)])
@@ -476,34 +329,17 @@ def test_exact_distance_ties_in_the_neighbour_list(oracle, shapes, n_a, periodic
         ij = rng.permutation(side * side)[:n_a]            # random index <-> grid position assignment
         p = np.stack([(ij % side) * pitch - 1.0, (ij // side) * pitch - 1.0])
         cases.append((np.ascontiguousarray(p), dp, g, l_cell))
-    ng_max = max(c[2].shape[1] for c in cases)
-    cells, n_g = _pad_cells([c[2] for c in cases], ng_max)
-    sb = _batch(n_env=E, n_agents=n_a, n_cells_max=ng_max, r_avoid=ra, is_boundary=not periodic, obs_dtype=torch.float64)
-    sb.set_cells(cells, n_g, [c[3] for c in cases])
-    sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
-    obs = sb.observe().cpu().numpy()
-    idx = sb.indices()
+    # one free step from a zero (float64) action: rewards / priors on tied lists (collision flag = nearest listed neighbour)
+    ref = oracle_run(oracle, cases, [np.zeros((E, n_a, 2))], ra, periodic=periodic)
     ties = 0
-    for e, (p, dp, g, l_cell) in enumerate(cases):
-        o = oracle.get_observation(p, dp, g, l_cell, ra, is_periodic=periodic)
-        assert np.array_equal(idx["neighbor_index"][e].cpu().numpy(), o["neighbor_index"]), e
-        assert np.array_equal(obs[e], _to_rows(o["obs"])), e
+    for (p, dp, g, l_cell), o in zip(cases, ref[0]):
         nei = o["neighbor_index"]
         for i in range(n_a):                                # count lists that really contain a tie
             js = nei[i][nei[i] >= 0]
             d = np.sum((p[:, js] - p[:, [i]]) ** 2, axis=0)
             ties += int(len(d) > 1 and (np.diff(d) == 0).any())
     assert ties > n_a                                       # most lists do
-    # one free step: rewards / priors on tied lists (collision flag = nearest listed neighbour)
-    act = torch.zeros((E, n_a, 2), dtype=torch.float64, device=sb.device)
-    obs2, rew, done, pri = sb.step(act)
-    for e, (p, dp, g, l_cell) in enumerate(cases):
-        o = oracle.get_observation(p, dp, g, l_cell, ra, is_periodic=periodic)
-        s = oracle.step(p, dp, np.zeros((2, n_a)), g, o["neighbor_index"], l_cell, ra, is_boundary=not periodic)
-        assert np.array_equal(obs2[e].cpu().numpy(), _to_rows(s["obs"])), e
-        assert np.array_equal(rew[e].cpu().numpy().astype(np.float64), s["reward"][0]), e
-        assert np.array_equal(pri[e].cpu().numpy(), _to_rows(s["a_prior"])), e
-    sb.close()
+    hold(cases, ref, pad=0, r_avoid=ra, is_boundary=not periodic, obs_dtype=torch.float64)
 
 
 def test_near_ties_whose_norms_coincide(oracle, shapes):
@@ -536,22 +372,13 @@ def test_near_ties_whose_norms_coincide(oracle, shapes):
         far = np.sum(p[:, 3:] ** 2, axis=0) < 0.45 ** 2    # keep the others out of agent 0's sensing range
         p[:, 3:][:, far] += 1.0
         cases.append((np.ascontiguousarray(p), dp, g, l_cell))
-    ng_max = max(c[2].shape[1] for c in cases)
-    cells, n_g = _pad_cells([c[2] for c in cases], ng_max)
-    sb = _batch(n_env=E, n_agents=n_a, n_cells_max=ng_max, r_avoid=ra, obs_dtype=torch.float64)
-    sb.set_cells(cells, n_g, [c[3] for c in cases])
-    sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
-    obs = sb.observe().cpu().numpy()
-    idx = sb.indices()
-    for e, (p, dp, g, l_cell) in enumerate(cases):
-        o = oracle.get_observation(p, dp, g, l_cell, ra)
+    first = [oracle.get_observation(p, dp, g, l_cell, ra) for p, dp, g, l_cell in cases]
+    for (p, dp, g, l_cell), o in zip(cases, first):
         assert list(o["neighbor_index"][0][:2]) == [1, 2]           # the oracle (= reference rule): tie, lower index first
         d2 = np.sum(p[:, 1:3] ** 2, axis=0)
         collapsed += int(d2[0] > d2[1])
-        assert np.array_equal(idx["neighbor_index"][e].cpu().numpy(), o["neighbor_index"]), e
-        assert np.array_equal(obs[e], _to_rows(o["obs"])), e
     assert collapsed == E
-    sb.close()
+    hold(cases, (first, []), pad=0, r_avoid=ra, obs_dtype=torch.float64)
 
 
 @pytest.mark.parametrize("n_a,n_env,periodic", [(8, 37, False), (16, 9, True), (30, 21, False), (32, 64, False), (32, 5, True)])
@@ -581,19 +408,15 @@ def test_half_occupied_geometry_equals_the_full_one(oracle, shapes, n_a, n_env, 
         idx = sb.indices()
         p, dp = sb.get_state()
         outs.append((obs.clone(), torch.stack(rews), pri.clone(), p, dp, idx["sensed_index"], idx["occupied_index"],
-                     idx["neighbor_index"], idx["in_flags"], p0, dp0, nei0, a0))
+                     idx["neighbor_index"], idx["in_flags"], p0, dp0, nei0, a0,
+                     host_copy(sb, (obs, rew, done, pri), state=(p, dp), indices=idx, rows=slice(0, 6))))
         sb.close()
     for a, b in zip(outs[0][:9], outs[1][:9]):
         assert torch.equal(a, b)
-    obs, rews, pri, p, dp, sen, occ, nei, inf, p0, dp0, nei0, a0 = outs[0]
-    for e in range(min(n_env, 6)):
-        g = sy["cells"][e][:, : sy["n_g"][e]]
-        s = oracle.step(p0[e], dp0[e], np.ascontiguousarray(a0[e].T), g, nei0[e], float(sy["l_cell"][e]), ra, is_boundary=not periodic)
-        assert np.array_equal(p[e].cpu().numpy(), s["p"]) and np.array_equal(dp[e].cpu().numpy(), s["dp"])
-        assert np.array_equal(obs[e].cpu().numpy(), _to_rows(s["obs"]))
-        assert np.array_equal(rews[-1][e].cpu().numpy().astype(np.float64), s["reward"][0])
-        assert np.array_equal(pri[e].cpu().numpy(), _to_rows(s["a_prior"]))
-        assert np.array_equal(sen[e].cpu().numpy(), s["sensed_index"]) and np.array_equal(occ[e].cpu().numpy(), s["occupied_index"])
+    p0, dp0, nei0, a0, dev = outs[0][9:]
+    ref = [oracle.step(p0[e], dp0[e], np.ascontiguousarray(a0[e].T), sy["cells"][e][:, : sy["n_g"][e]], nei0[e], float(sy["l_cell"][e]),
+                       ra, is_boundary=not periodic) for e in range(min(n_env, 6))]
+    compare(dev, device_layout(ref), "last step")
 
 
 def _reward_threshold_case(oracle, rng, shapes, n_a, ra, d_sen=0.4):
@@ -667,25 +490,9 @@ def test_reward_threshold_placements(oracle, shapes, n_a, flags):
     E = 48
     cases = [_reward_threshold_case(oracle, rng, shapes, n_a, ra) for _ in range(E)]
     assert sum(c[3] for c in cases) >= 16           # agents whose crossing is the |v| test itself (not in-flag / list)
-    cells, n_g = _pad_cells([c[1] for c in cases], max(c[1].shape[1] for c in cases))
-    sb = _batch(n_env=E, n_agents=n_a, n_cells_max=cells.shape[2], r_avoid=ra, obs_dtype=torch.float64, debug_flags=flags)
-    sb.set_cells(cells, n_g, [c[2] for c in cases])
-    assert sb.lattice_envs() == (0 if flags & 2 else E)
-    p = np.stack([c[0] for c in cases])
-    sb.set_state(p, np.zeros_like(p))
-    sb.observe()
-    nei = sb.indices(False, False)["neighbor_index"].cpu().numpy()
-    obs, rew, done, pri = sb.step(torch.zeros((E, n_a, 2), dtype=torch.float64, device=sb.device))
-    pg = sb.get_state()[0].cpu().numpy()
-    idx = sb.indices()
-    assert np.array_equal(pg, p)                         # nothing moved: the reward was decided at the placed positions
-    ones = 0
-    for e, (pe, g, l_cell, _) in enumerate(cases):
-        s = oracle.step(pe, np.zeros_like(pe), np.zeros_like(pe), g, nei[e], l_cell, ra)
-        assert np.array_equal(rew[e].cpu().numpy().astype(np.float64), s["reward"][0]), e
-        assert np.array_equal(obs[e].cpu().numpy(), _to_rows(s["obs"])), e
-        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-            assert np.array_equal(idx[k][e].cpu().numpy(), s[k]), (e, k)
-        ones += int(s["reward"].sum())
-    assert ones > 0
-    sb.close()
+    # zero velocity, zero (float64) action: a step leaves every position as it is
+    cases = [(p, np.zeros_like(p), g, l_cell) for p, g, l_cell, _ in cases]
+    ref = oracle_run(oracle, cases, [np.zeros((E, n_a, 2))], ra)
+    assert sum(int(s["reward"].sum()) for s in ref[1][0]) > 0
+    seen = hold(cases, ref, lattice=0 if flags & 2 else E, pad=0, r_avoid=ra, obs_dtype=torch.float64, debug_flags=flags)
+    assert np.array_equal(seen[1]["p"], np.stack([c[0] for c in cases]))    # nothing moved: the reward was decided at the placed positions

@@ -7,18 +7,11 @@ libm differ by <= 1 ulp); then the first observation equals the oracle's on the 
 import numpy as np
 import pytest
 
+from helpers import GOLD, mix64
+from lockstep import OBSERVE, compare, device_layout, host_copy
+
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-GOLD = 0x9E3779B97F4A7C15
-M64 = (1 << 64) - 1
-
-
-def mix64(z):
-    z &= M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    return z ^ (z >> 31)
 
 
 def u01(key, k):
@@ -55,12 +48,12 @@ def test_device_reset_matches_its_restatement_and_oracle(oracle, shapes, n_a, n_
     ng_max = max(np.asarray(g).shape[0] for g in shapes["grid_coords"])
     sb = SwarmBatch(n_env=n_env, n_agents=n_a, n_cells_max=ng_max, r_avoid=ra, obs_dtype=torch.float64)
     sb.set_shapes(shapes)
-    obs = sb.reset(seed=226, episode=3, env_offset=env_offset).cpu().numpy()
+    dev = host_copy(sb, sb.reset(seed=226, episode=3, env_offset=env_offset), indices=True)
     assert sb.lattice_envs() == n_env
-    p, dp = [x.cpu().numpy() for x in sb.get_state()]
+    obs, p, dp = dev["obs"], dev["p"], dev["dp"]
     cells, n_g = sb.get_cells()
-    idx = sb.indices()
     shape_hist = np.zeros(len(shapes["l_cell"]), int)
+    first = []
     for e in range(n_env):
         s, g, pr, dpr = reset_reference(226, 3, env_offset + e, shapes, n_a)
         shape_hist[s] += 1
@@ -69,10 +62,8 @@ def test_device_reset_matches_its_restatement_and_oracle(oracle, shapes, n_a, n_
         np.testing.assert_allclose(cells[e][:, : n_g[e]], g, rtol=0, atol=2e-15)
         # first observation: the oracle on exactly the state / cells the device holds
         ge = np.ascontiguousarray(cells[e][:, : n_g[e]])
-        o = oracle.get_observation(p[e], dp[e], ge, float(shapes["l_cell"][s]), ra)
-        assert np.array_equal(obs[e], o["obs"].T)
-        for k in ("neighbor_index", "in_flags", "sensed_index", "occupied_index"):
-            assert np.array_equal(idx[k][e].cpu().numpy(), o[k]), (e, k)
+        first.append(oracle.get_observation(p[e], dp[e], ge, float(shapes["l_cell"][s]), ra))
+    compare(dev, device_layout(first), "reset", fields=OBSERVE)
     assert (np.abs(p) <= 3.4 + 1e-12).all() and (np.abs(dp) <= 0.5).all()
     # a different episode / seed gives a different draw; the same one reproduces
     obs2 = sb.reset(seed=226, episode=4, env_offset=env_offset).cpu().numpy()
@@ -190,8 +181,8 @@ def test_eval_metrics_match_wrapper_restatement(shapes, n_a, n_env):
 
 def test_partial_set_cells_after_device_reset():
     """swarm_set_cells on ONE env after a device reset, where the other envs' lattice records are the shape set's maxima and
-    not their own: an off-lattice cell set demotes the batch to the generic scan, the original cells promote it back, and
-    either way one step equals, bit for bit, the step of a twin handle that never takes the lattice path (debug_flags=2)
+    not their own: an off-lattice cell set sends that env's workgroup to the generic launch while the others keep the row walk,
+    the original cells bring it back, and either way one step equals, bit for bit, the step of a twin handle that never takes the lattice path (debug_flags=2)
     and was given the same cells and state."""
     from marl_llm_amd.batched import SwarmBatch
     from marl_llm_amd.shapes import SHAPE_NAMES, r_avoid_for, synthetic_shape_set

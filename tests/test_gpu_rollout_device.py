@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import mix64, mix64_np, noise_key
+from helpers import shape_batch as make_batch
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -23,15 +24,6 @@ def uniform_actions(seed, step, rows, row_offset=0):
         bits = (h >> np.uint64(40 - 24 * k)) & np.uint64(0xFFFFFF)
         out[:, k] = bits.astype(np.float32) * np.float32(2.0 ** -23) - np.float32(1.0)
     return out
-
-
-def make_batch(shapes, E, N, dtype=torch.float32, **kw):
-    from marl_llm_amd.batched import SwarmBatch
-    from marl_llm_amd.shapes import r_avoid_for
-    ng_max = max(np.asarray(g).shape[0] for g in shapes["grid_coords"])
-    sb = SwarmBatch(n_env=E, n_agents=N, n_cells_max=ng_max, r_avoid=r_avoid_for(N, shapes), obs_dtype=dtype, **kw)
-    sb.set_shapes(shapes)
-    return sb
 
 
 @pytest.fixture(scope="module")

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from helpers import shape_batch as make_batch
 from test_eval_boundary_cases import boundary_cases, near_tie_states
 
 torch = pytest.importorskip("torch")
@@ -24,16 +25,6 @@ def shape_arrays(shapes):
     for k, g in enumerate(grids):
         cells[k, :, : g.shape[1]] = g; n_g[k] = g.shape[1]
     return cells, n_g, np.asarray(shapes["l_cell"], np.float64)
-
-
-def make_batch(shapes, E, N, dtype=torch.float32, upload=True, **kw):
-    from marl_llm_amd.batched import SwarmBatch
-    from marl_llm_amd.shapes import r_avoid_for
-    ng_max = max(np.asarray(g).shape[0] for g in shapes["grid_coords"])
-    sb = SwarmBatch(n_env=E, n_agents=N, n_cells_max=ng_max, r_avoid=r_avoid_for(N, shapes), obs_dtype=dtype, **kw)
-    if upload:
-        sb.set_shapes(shapes)
-    return sb
 
 
 def eager_switch(sb, shapes, s):

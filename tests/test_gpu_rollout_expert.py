@@ -5,20 +5,13 @@ restatement; chains, reward statistics, rejections and the reference-shaped Asse
 import numpy as np
 import pytest
 
+from helpers import shape_batch as make_batch
+
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-12                 # test_gpu_rule.py
 RING = ("obs", "act", "rew", "done", "act_prior")
-
-
-def make_batch(shapes, E, N, dtype=torch.float32, **kw):
-    from marl_llm_amd.batched import SwarmBatch
-    from marl_llm_amd.shapes import r_avoid_for
-    ng_max = max(np.asarray(g).shape[0] for g in shapes["grid_coords"])
-    sb = SwarmBatch(n_env=E, n_agents=N, n_cells_max=ng_max, r_avoid=r_avoid_for(N, shapes), obs_dtype=dtype, **kw)
-    sb.set_shapes(shapes)
-    return sb
 
 
 def ring_for(sb, K):

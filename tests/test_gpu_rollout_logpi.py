@@ -5,20 +5,13 @@ records the same values; a ring without the column is refused before anything ru
 import numpy as np
 import pytest
 
+from helpers import shape_batch as make_batch
+
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 RING = ("obs", "act", "rew", "done", "act_prior")
 UNIFORM = np.float32(-2.0 * np.log(2.0))
-
-
-def make_batch(shapes, E, N, dtype=torch.float32):
-    from marl_llm_amd.batched import SwarmBatch
-    from marl_llm_amd.shapes import r_avoid_for
-    ng_max = max(np.asarray(g).shape[0] for g in shapes["grid_coords"])
-    sb = SwarmBatch(n_env=E, n_agents=N, n_cells_max=ng_max, r_avoid=r_avoid_for(N, shapes), obs_dtype=dtype)
-    sb.set_shapes(shapes)
-    return sb
 
 
 @pytest.fixture(scope="module")

@@ -87,7 +87,7 @@ The old tests catch every non-equivalent mutant too -- their inputs are less sat
 import numpy as np
 import pytest
 
-from helpers import (RULE_NS, assert_calm_conditions, calm_batch, calm_case, fig_shapes, make_case, rule_branch_counts,
+from helpers import (RULE_NS, assert_calm_conditions, calm_batch, calm_case, fig_shapes, make_case, pad_cells, rule_branch_counts,
                      rule_details)
 
 torch = pytest.importorskip("torch")
@@ -98,21 +98,13 @@ D_SEN = 0.4
 
 
 # ---- plumbing ----------------------------------------------------------------------------------------------------------
-def pad_cells(cases):
-    ng_max = max(c[2].shape[1] for c in cases)
-    cells = np.zeros((len(cases), 2, ng_max)); n_g = np.zeros(len(cases), np.int32)
-    for e, c in enumerate(cases):
-        n_g[e] = c[2].shape[1]; cells[e, :, : n_g[e]] = c[2]
-    return cells, n_g
-
-
 def bits_equal(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
 
 
 def make_batch(cases, r_avoid, dtype=torch.float32, **kw):
     from marl_llm_amd.batched import SwarmBatch
-    cells, n_g = pad_cells(cases)
+    cells, n_g = pad_cells([c[2] for c in cases], max(c[2].shape[1] for c in cases))
     sb = SwarmBatch(n_env=len(cases), n_agents=cases[0][0].shape[1], n_cells_max=cells.shape[2], r_avoid=r_avoid, obs_dtype=dtype, **kw)
     sb.set_cells(cells, n_g, [c[3] for c in cases])
     sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
