@@ -82,7 +82,7 @@ typedef struct swarm_env swarm_env_t;
 /* Mirrors the constants AssemblySwarmEnv hard-codes or derives (assembly.py:27-81,99-131,193-199). */
 typedef struct swarm_config {
     int32_t n_env;                  /* E >= 1 */
-    int32_t n_agents;               /* N in [1, 256] */
+    int32_t n_agents;               /* N in [1, 256]; with large_swarm in [1, 1024] */
     int32_t n_cells_max;            /* capacity of one env's cell list, >= every n_g, <= 32767 */
     int32_t topo_nei_max;           /* assembly.py:34   = 6 (1..6) */
     int32_t num_obs_grid_max;       /* assembly.py:128  = 80 */
@@ -111,7 +111,11 @@ typedef struct swarm_config {
     double llm_repulsion;           /* repulsion gain of the prior's Python twin robot_prior_policy, assembly.py:895 = 1.0 */
     int32_t llm_action;             /* 1: agent_strategy == 'llm' (assembly.py:525-529): every pass also evaluates that twin on
                                      * the new state; swarm_step(action = NULL) then applies it as the action */
-    int32_t reserved_;
+    int32_t large_swarm;            /* 0 (default): the step kernel, n_agents <= 256.  1: n_agents in [1, 1024]; every step and
+                                     * observation pass of the handle runs through the two large-swarm kernels (env_large.hip), at any
+                                     * n_agents, with the same results bit for bit.  Such a handle has no rule expert
+                                     * (swarm_rule_action, swarm_rollout_expert's rule source), reports every env as scanned
+                                     * (swarm_path_envs) and accepts debug_flags without effect */
 } swarm_config_t;
 
 int  swarm_abi_version(void);
@@ -212,7 +216,8 @@ int  swarm_metrics(swarm_env_t *h, double *out);
  * Periodic handles (is_boundary == 0): the controller takes no wrap, as assembly.py:530-601 takes none -- its distances to
  * agents and cells, the in-shape flag, the nearest cell and the sensed-cell list with its occupied-cell filter all use the
  * plain differences of the stored positions (the observation pass wraps only the topological-neighbour rows).
- * tests/test_gpu_rule_contract.py holds this call and swarm_rollout_expert's rule source to the numpy restatement. */
+ * tests/test_gpu_rule_contract.py holds this call and swarm_rollout_expert's rule source to the numpy restatement.
+ * Refused (SWARM_ERR_INVALID, nothing enqueued) on a handle created with large_swarm: the expert serves n_agents <= 256. */
 int  swarm_rule_action(swarm_env_t *h, double *action);
 
 /* Index scratch of the CURRENT state (device pointers, any may be NULL).  The step keeps neighbor_index / in_flags / the

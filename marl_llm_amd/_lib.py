@@ -19,7 +19,7 @@ class SwarmConfig(ctypes.Structure):
                 ("k_ball", ctypes.c_double), ("k_wall", ctypes.c_double), ("c_wall", ctypes.c_double),
                 ("vel_max", ctypes.c_double), ("dt", ctypes.c_double), ("boundary", ctypes.c_double * 4),
                 ("prior_gain", ctypes.c_double * 3), ("llm_repulsion", ctypes.c_double),
-                ("llm_action", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
+                ("llm_action", ctypes.c_int32), ("large_swarm", ctypes.c_int32)]
 
 
 class HostOut(ctypes.Structure):                # include/swarm_env.h swarm_host_out_t

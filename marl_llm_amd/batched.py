@@ -25,7 +25,8 @@ class SwarmBatch:
     def __init__(self, n_env, n_agents, n_cells_max, r_avoid, *, is_boundary=True, with_self=True, with_prior=True,
                  obs_dtype=torch.float32, device="cuda:0", d_sen=0.4, topo=6, g_max=80, occ_max=200,
                  boundary=(-2.4, 2.4, 2.4, -2.4), size_a=0.035, k_ball=30.0, k_wall=100.0, c_wall=5.0,
-                 vel_max=0.8, dt=0.1, debug_flags=0, llm_action=False, prior_gain=(2.0, 3.0, 2.0), llm_repulsion=1.0):
+                 vel_max=0.8, dt=0.1, debug_flags=0, llm_action=False, prior_gain=(2.0, 3.0, 2.0), llm_repulsion=1.0,
+                 large_swarm=False):
         if not torch.cuda.is_available():
             raise SwarmError("no HIP device visible to PyTorch: the env step has no CPU fallback")
         self.lib = _lib.load()
@@ -51,7 +52,9 @@ class SwarmBatch:
         for k in range(3):
             cfg.prior_gain[k] = float(prior_gain[k])
         cfg.llm_repulsion, cfg.llm_action = float(llm_repulsion), int(bool(llm_action))
+        cfg.large_swarm = int(bool(large_swarm))       # n_agents up to 1024, stepped by the large-swarm kernels (swarm_env.h)
         self.has_llm_action = bool(llm_action)
+        self.large_swarm = bool(large_swarm)
         self._host = None
         self.cfg = cfg
         self.handle = ctypes.c_void_p()

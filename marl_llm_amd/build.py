@@ -1,8 +1,9 @@
 """Build libswarmenv.so (the HIP kernels + C ABI) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED: the kernels reproduce the
-reference's IEEE-double operation order (no FMA), see csrc/swarm_env.hip.  The env library is three sources: swarm_env.hip
-(the step kernel, by far the longest compile), env_kernels.hip (the side kernels) and env_api.hip (the handle and the C ABI).
+reference's IEEE-double operation order (no FMA), see csrc/swarm_env.hip.  The env library is four sources: swarm_env.hip
+(the step kernel, by far the longest compile), env_large.hip (the two large-swarm step kernels), env_kernels.hip (the side
+kernels) and env_api.hip (the handle and the C ABI).
 """
 import os
 import shutil
@@ -10,7 +11,7 @@ import subprocess
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
-SRCS = [os.path.join(PKG, "csrc", f) for f in ("swarm_env.hip", "env_kernels.hip", "env_api.hip", "legacy_shim.hip",
+SRCS = [os.path.join(PKG, "csrc", f) for f in ("swarm_env.hip", "env_large.hip", "env_kernels.hip", "env_api.hip", "legacy_shim.hip",
                                                "policy_mlp.hip", "rollout.hip", "rule_expert.hip")]
 INC = os.path.join(ROOT, "include")
 LIB_DIR = os.path.join(PKG, "lib")

@@ -1,7 +1,8 @@
 // env_api.hip -- the host side of the env library: the swarm_env handle's bookkeeping, lattice detection and the choice of
 // the cell path, and every entry point of the C ABI (include/swarm_env.h) but the two debug ones that read the step
 // kernel's own tables.  No kernel is defined or named here: the step kernel is reached through env_layout / env_launch
-// (swarm_env.hip), the side kernels through their launchers (env_kernels.hip); env_types.h declares both.
+// (swarm_env.hip) -- on a handle created with large_swarm the two large-swarm kernels through large_launch (env_large.hip)
+// instead: step_launch below is the one place that chooses --, the side kernels through their launchers (env_kernels.hip); env_types.h declares both.
 
 #include <hip/hip_runtime.h>
 
@@ -42,6 +43,14 @@ int npad_for(int n)
     int v = 8;
     while (v < n) v <<= 1;
     return v;
+}
+
+// One step (do_step) or observation pass of the handle, on its stream: the step kernel's launch, or on a large_swarm handle
+// the large-swarm kernels' -- every pass of such a handle, at any n_agents
+int step_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior)
+{
+    return h->cfg.large_swarm ? large_launch(h, do_step, action, act_f64, obs, reward, done, a_prior)
+                              : env_launch(h, do_step, action, act_f64, obs, reward, done, a_prior);
 }
 
 // Is this cell list a row-major subset of a square lattice (<= 64 x 64)?  Fills `L` (geometry only) if so.
@@ -130,6 +139,10 @@ int window_rows(float R) { return (int)std::floor(2.0f * (R + 0.01f)) + 1; }
 void set_lattice_mode(swarm_env *h, bool any_walk, bool any_scan, float rmax, float cmax, int ncols_max)
 {
     KP &k = h->kp;
+    if (h->cfg.large_swarm) {                              // no cell path to choose: the large-swarm kernels scan every env's cells
+        h->path_mode = PATH_SCAN; h->half = false; k.lattice = 0; k.path_filter = 0;
+        return;
+    }
     k.lat_n32 = ncols_max <= 32 ? 1 : 0;
     k.lat_rw = (int)std::ceil(rmax + 0.02f);
     k.lat_cw = (int)std::ceil(cmax + 0.02f);
@@ -175,7 +188,7 @@ int export_pass(swarm_env *h, bool lists, bool cap_even)
     }
     h->kp.export_small = 1; h->kp.cap_even = cap_even;
     if (lists) { h->kp.export_idx = 1; h->kp.exp_sensed = h->d_exp_sensed.get(); h->kp.exp_occ = h->d_exp_occ.get(); }
-    const int rc = env_launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+    const int rc = step_launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
     h->kp.export_idx = 0; h->kp.export_small = 0; h->kp.cap_even = 0;
     return rc;
 }
@@ -243,6 +256,7 @@ int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out)
     out->device = h->device; out->n_env = h->cfg.n_env; out->n_agents = h->cfg.n_agents; out->obs_dim = h->kp.obs_dim;
     out->obs_dtype = h->cfg.obs_dtype; out->with_prior = h->cfg.with_prior != 0; out->observed = h->observed;
     out->g_max = h->kp.g_max; out->llm_action = h->cfg.llm_action != 0; out->n_shapes = h->n_shapes;
+    out->large_swarm = h->cfg.large_swarm != 0;
     return SWARM_OK;
 }
 
@@ -297,7 +311,10 @@ int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
     if (!cfg || !out) return fail(nullptr, SWARM_ERR_INVALID, "swarm_create: null argument");
     *out = nullptr;
     if (cfg->n_env < 1) return fail(nullptr, SWARM_ERR_INVALID, "n_env must be >= 1");
-    if (cfg->n_agents < 1 || cfg->n_agents > 256) return fail(nullptr, SWARM_ERR_INVALID, "n_agents must be in [1, 256]");
+    if (cfg->large_swarm != 0 && cfg->large_swarm != 1) return fail(nullptr, SWARM_ERR_INVALID, "large_swarm must be 0 or 1");
+    if (cfg->large_swarm) {
+        if (cfg->n_agents < 1 || cfg->n_agents > 1024) return fail(nullptr, SWARM_ERR_INVALID, "n_agents must be in [1, 1024] (large_swarm)");
+    } else if (cfg->n_agents < 1 || cfg->n_agents > 256) return fail(nullptr, SWARM_ERR_INVALID, "n_agents must be in [1, 256]");
     if (cfg->n_cells_max < 1 || cfg->n_cells_max > 32767) return fail(nullptr, SWARM_ERR_INVALID, "n_cells_max must be in [1, 32767]");
     if (cfg->topo_nei_max < 1 || cfg->topo_nei_max > kTopoMax) return fail(nullptr, SWARM_ERR_INVALID, "topo_nei_max must be in [1, 6]");
     if (cfg->num_obs_grid_max < 2 || cfg->num_obs_grid_max > 4096) return fail(nullptr, SWARM_ERR_INVALID, "num_obs_grid_max must be in [2, 4096]");
@@ -382,14 +399,15 @@ int swarm_create(const swarm_config_t *cfg, swarm_env_t **out)
         k.dbg_phase = (cfg->debug_flags >> 8) & 0xF;
         k.dbg_extra = (cfg->debug_flags >> 12) & 0xF;
     }
-    env_layout(k, h->npad, false);
+    if (!cfg->large_swarm) env_layout(k, h->npad, false);     // (describes the step kernel's LDS; the large-swarm kernels have their own)
 
     DeviceGuard g(dev);
     if (!g.ok) { delete h; return fail(nullptr, SWARM_ERR_HIP, "hipSetDevice failed"); }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { delete h; return fail(nullptr, SWARM_ERR_HIP, "hipGetDeviceProperties failed"); }
     h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if ((size_t)k.smem_generic > 160 * 1024) {
+    // the large-swarm observation kernel stays inside the LDS every kernel may have without asking for more
+    if (cfg->large_swarm ? large_lds_bytes(k.ng_max, k.n_a) > 64 * 1024 : (size_t)k.smem_generic > 160 * 1024) {
         delete h;
         return fail(nullptr, SWARM_ERR_INVALID, "configuration needs more LDS per workgroup than the device has (reduce n_cells_max / num_obs_grid_max)");
     }
@@ -622,7 +640,7 @@ int swarm_observe(swarm_env_t *h, void *obs)
     if (!h->have_cells) return fail(h, SWARM_ERR_STATE, "swarm_observe: target cells not set for every env (swarm_set_cells)");
     if (!h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_observe: state not set (swarm_set_state)");
     DeviceGuard g(h->device);
-    int rc = env_launch(h, false, nullptr, 0, obs, nullptr, nullptr, nullptr);
+    int rc = step_launch(h, false, nullptr, 0, obs, nullptr, nullptr, nullptr);
     if (rc == SWARM_OK) h->observed = true;
     return rc;
 }
@@ -639,7 +657,7 @@ int swarm_step(swarm_env_t *h, const void *action, int action_dtype, void *obs, 
     if (action_dtype != SWARM_F32 && action_dtype != SWARM_F64) return fail(h, SWARM_ERR_INVALID, "swarm_step: bad action_dtype");
     if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_step: call swarm_observe after setting cells/state (the reference's reset() ends with _get_obs())");
     DeviceGuard g(h->device);
-    return env_launch(h, true, action, action_dtype == SWARM_F64, obs, reward, done, a_prior);
+    return step_launch(h, true, action, action_dtype == SWARM_F64, obs, reward, done, a_prior);
 }
 
 // (io_alloc / io_export are in no header, yet libswarmenv.so has always exported these two names; SWARM_ABI_VERSION holds
@@ -744,7 +762,7 @@ int swarm_step_host(swarm_env_t *h, const void *action, int action_dtype, int ac
         HIP_TRY(h, hipMemcpyAsync(h->d_io_action.get(), h->h_io_action.get(), bytes, hipMemcpyHostToDevice, h->stream));
         act = h->d_io_action.get(); mode = 2 | (action_dtype == SWARM_F64 ? 1 : 0);
     }
-    rc = env_launch(h, true, act, mode, h->d_io_obs.get(), h->d_io_rew.get(), h->d_io_done.get(), h->kp.with_prior ? h->d_io_prior.get() : nullptr);
+    rc = step_launch(h, true, act, mode, h->d_io_obs.get(), h->d_io_rew.get(), h->d_io_done.get(), h->kp.with_prior ? h->d_io_prior.get() : nullptr);
     if (rc != SWARM_OK) return rc;
     return io_export(h, slot, true);
 }
@@ -770,6 +788,7 @@ int swarm_rule_action(swarm_env_t *h, double *action)
     if (!h || !action) return SWARM_ERR_INVALID;
     if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_rule_action: nothing observed yet");
     if (h->kp.g_max > 128) return fail(h, SWARM_ERR_INVALID, "swarm_rule_action: num_obs_grid_max > 128 not supported");
+    if (h->cfg.large_swarm) return fail(h, SWARM_ERR_INVALID, "swarm_rule_action: not available on a large_swarm handle (the rule expert serves n_agents <= 256 with large_swarm = 0)");
     DeviceGuard g(h->device);
     int rc = export_pass(h, true, true);
     if (rc != SWARM_OK) return rc;

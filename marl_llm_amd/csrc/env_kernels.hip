@@ -460,8 +460,9 @@ hipError_t launch_metrics(hipStream_t st, const KP &kp, double *out)
 hipError_t launch_metrics_step(hipStream_t st, const KP &kp, int n_cu, double *out)
 {
     const int stride = (36 * kp.n_a + 4 + 15) & ~15;             // per env: xy[N], val[N], tmp[N], cnt[N + 1]
-    // one wave per env needs about two waves per SIMD (4 SIMDs per CU) to hide its latencies; below that, four waves per env
-    if ((long long)kp.n_env >= 8LL * n_cu)
+    // one wave per env needs about two waves per SIMD (4 SIMDs per CU) to hide its latencies; below that, four waves per env.
+    // Above 256 agents (large_swarm handles) always four waves per env: four envs' stride would not fit a workgroup's LDS
+    if (kp.n_a <= 256 && (long long)kp.n_env >= 8LL * n_cu)
         hipLaunchKernelGGL(k_metrics_step<1>, dim3((unsigned)((kp.n_env + kMsEnvs - 1) / kMsEnvs)), dim3(64 * kMsEnvs),
                            (size_t)stride * kMsEnvs, st, kp, out, stride);
     else

@@ -1,6 +1,6 @@
-// Private to the three translation units of the env library -- swarm_env.hip (the step kernel and its launch),
-// env_kernels.hip (the side kernels) and env_api.hip (the handle and the C ABI): the kernel-argument types, the handle and
-// the functions through which the three call each other.  Not installed, not exported: the namespace has hidden visibility,
+// Private to the four translation units of the env library -- swarm_env.hip (the step kernel and its launch), env_large.hip
+// (the large-swarm step kernels), env_kernels.hip (the side kernels) and env_api.hip (the handle and the C ABI): the
+// kernel-argument types, the handle and the functions through which they call each other.  Not installed, not exported: the namespace has hidden visibility,
 // so the public ABI (swarm_env.h) does not change.  What the OTHER translation units of libswarmenv.so may ask of an env
 // handle is in swarm_internal.h.
 #ifndef SWARM_ENV_TYPES_H
@@ -187,6 +187,12 @@ int fail(swarm_env *h, int code, const std::string &msg);
 void env_layout(KP &k, int npad, bool half);
 // enqueue one step (do_step) or observation pass of the handle's current cell path on its stream
 int env_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior);
+
+// ---- env_large.hip: the two kernels of a handle created with swarm_config_t.large_swarm (any n_agents in [1, 1024])
+// dynamic LDS per workgroup of the observation kernel
+int large_lds_bytes(int n_cells_max, int n_agents);
+// env_launch's contract for such a handle: the move kernel (do_step) and the observation kernel, both on the handle's stream
+int large_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior);
 
 // ---- env_kernels.hip: one launcher per side kernel; each enqueues on `st` and returns the launch's hipGetLastError()
 hipError_t launch_reset(hipStream_t st, const KP &kp, const ShapeSet &S, unsigned long long seed, unsigned long long episode,

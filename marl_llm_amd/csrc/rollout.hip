@@ -343,6 +343,8 @@ int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t ste
         if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
     }
     if (ei.n_agents > 256) return fail(SWARM_ERR_INVALID, "n_agents > 256", who);
+    if (source == SWARM_EXPERT_RULE && ei.large_swarm)
+        return fail(SWARM_ERR_INVALID, "the rule expert is not available on a large_swarm handle (it serves n_agents <= 256 with large_swarm = 0)", who);
     if (source == SWARM_EXPERT_RULE && ei.g_max > 128)
         return fail(SWARM_ERR_INVALID, "the rule expert needs num_obs_grid_max <= 128 (as swarm_rule_action)", who);
     if (source == SWARM_EXPERT_LLM && !ei.llm_action)

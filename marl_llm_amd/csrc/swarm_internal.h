@@ -107,6 +107,7 @@ public:
 struct swarm_env_info {
     int device, n_env, n_agents, obs_dim, obs_dtype, g_max, n_shapes;
     bool with_prior, observed, llm_action;
+    bool large_swarm;             // created with swarm_config_t.large_swarm: stepped by env_large.hip, no rule expert
 };
 SWARM_HIDDEN int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out);
 

@@ -148,7 +148,9 @@ class AssemblySwarmEnv(_EnvBase):
                                      boundary=(-self.boundary_width_half, self.boundary_height_half,
                                                self.boundary_width_half, -self.boundary_height_half),
                                      size_a=self.size_a, k_ball=self.k_ball, k_wall=self.k_wall, c_wall=self.c_wall,
-                                     vel_max=self.Vel_max, dt=self.dt)
+                                     vel_max=self.Vel_max, dt=self.dt,
+                                     # the reference takes any n_a; above the step kernel's 256 the large-swarm kernels step it
+                                     large_swarm=self.n_agents_per_env > 256)
         return self._batch
 
     # ------------------------------------------------------------------ reset (assembly.py:156-223)

@@ -17,9 +17,9 @@ for SYM in $(grep -o "^_ZN12_GLOBAL__N_15k_envI[A-Za-z0-9_]*:" $S | tr -d : | so
   E=$(awk -v L=$L 'NR>L && /\.end_amdhsa_kernel/{print NR; exit}' $S)
   echo "k_env<$K>" $(awk -v L=$L 'NR>L && /; (NumVgprs|ScratchSize|Occupancy|codeLenInByte)/{printf "%s ", $0; n++} n>=4{exit}' $S) "; spill instructions:" $(sed -n "${L},${E}p" $S | grep -c "Folded Spill\|Folded Reload")
 done
-# the env's side kernels, the policy kernel (VGPRs must not move: 218 for the bf16 instantiations), the rollout loop's kernels
+# the large-swarm step kernels (env_large: no scratch, no spill in the pair, cell or filter loops), the env's side kernels, the policy kernel (VGPRs must not move: 218 for the bf16 instantiations), the rollout loop's kernels
 # and the rule expert (no scratch)
-for F in env_kernels policy_mlp rollout rule_expert; do
+for F in env_large env_kernels policy_mlp rollout rule_expert; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -I$R/include -c $R/marl_llm_amd/csrc/$F.hip -o $T/$F.o \
       -Rpass-analysis=kernel-resource-usage 2>&1 | sed -n 's/.*remark: *//p' | sed 's/ \[-Rpass-analysis.*//' |
     awk '/^Function Name:/{if (l) print l; l=$3; next} /^(VGPRs|AGPRs|ScratchSize|Occupancy)/{l=l" ; "$0} END{if (l) print l}'
