@@ -91,6 +91,35 @@ int  swarm_policy_forward_explore_logpi(swarm_policy_t *p, const void *obs, int 
 #define SWARM_POLICY_BF16X3 1
 int  swarm_policy_set_precision(swarm_policy_t *p, int precision);
 
+/* New weights for an existing handle, from fp32 DEVICE arrays on the handle's device (torch.nn.Linear layout, the shapes the
+ * handle was created with: the learner's parameters where torch keeps them).  One launch of a packing kernel on `stream`
+ * (a hipStream_t; NULL: the default stream) rewrites the handle's packed weights in place: the high bf16 parts bf(v), the low
+ * parts bf(v - bf(v)), the fp32 b1, the biases of layers 2-4 in the constant-one column, the constant-one feature itself and
+ * the permuted k order of layers 2-4 -- everything swarm_policy_create packs on the host.
+ *   Enqueue only: no host synchronisation, no allocation, no copy of the weights through the host.
+ *   Stream order: a forward or rollout enqueued on the same stream before the call uses the old weights, one enqueued after
+ *     it the new ones.  The eight arrays are read when the kernel RUNS, not when the call is made: they must stay valid and
+ *     hold the intended values until then (writes enqueued on the same stream before the call are seen).  Work on other
+ *     streams that uses the handle or writes the arrays is the caller's to order with events.
+ *   Same bytes as the host packer: for finite weights whose bf16 rounding is finite, the packed weights after the call equal,
+ *     byte for byte, what swarm_policy_create builds from the same fp32 values on the host (swarm_policy_read_packed reads
+ *     them).  Denormals, +-0, exact bf16 values and round-to-even ties are inside that contract: v - bf(v) is the IEEE fp32
+ *     difference and is not flushed.  Non-finite weights are outside it: a weight that is Inf, or rounds to Inf, gives
+ *     Inf - Inf, a NaN whose sign differs between an x86 host and the GPU (and NaN payloads are not pinned either).
+ *   Validation first: a NULL handle or a NULL array returns SWARM_POLICY_ERR_INVALID with a message that starts
+ *     "swarm_policy_load_device:", and nothing is enqueued; a launch error returns SWARM_POLICY_ERR_HIP.
+ * The precision setting is kept.  One handle holds one set of weights: a caller who learns and rolls out on different streams
+ * keeps two handles. */
+int  swarm_policy_load_device(swarm_policy_t *p, const float *w1, const float *b1, const float *w2, const float *b2,
+                              const float *w3, const float *b3, const float *w4, const float *b4, void *stream);
+
+/* The handle's packed weights, exactly the bytes the kernel reads (what holds swarm_policy_load_device to the host packer, and
+ * what a checkpoint of the actor as evaluated would store).  Returns their size in bytes.  host_dst != NULL and capacity >=
+ * that size: copies them to host_dst on `stream` (behind the loads enqueued there) and waits for it: complete on return;
+ * host_dst == NULL or a smaller capacity: nothing is copied and nothing waits -- the size alone.  A NULL handle or a
+ * negative capacity returns -SWARM_POLICY_ERR_INVALID, a HIP error -SWARM_POLICY_ERR_HIP, with a message. */
+int64_t swarm_policy_read_packed(swarm_policy_t *p, void *host_dst, int64_t capacity, void *stream);
+
 const char *swarm_policy_last_error(void);
 
 #ifdef __cplusplus

@@ -51,7 +51,7 @@ BATCHED_SYMBOLS = ("swarm_abi_version", "swarm_default_config", "swarm_create", 
                    "swarm_host_outputs", "swarm_observe_host", "swarm_step_host", "swarm_get_llm_action", "swarm_select_shape", "swarm_path_envs")
 POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_destroy", "swarm_policy_forward", "swarm_policy_forward_bf16",
                   "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_forward_explore_logpi",
-                  "swarm_policy_set_precision",
+                  "swarm_policy_set_precision", "swarm_policy_load_device", "swarm_policy_read_packed",
                   "swarm_policy_last_error")   # include/swarm_policy.h
 ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_logpi", "swarm_rollout_expert", "swarm_rollout_eval",
                    "swarm_rollout_last_error")   # include/swarm_rollout.h
@@ -112,6 +112,8 @@ def load():
     lib.swarm_select_shape.argtypes = [vp, ctypes.c_int32, vp]; lib.swarm_select_shape.restype = i32
     lib.swarm_rollout_last_error.argtypes = []; lib.swarm_rollout_last_error.restype = ctypes.c_char_p
     lib.swarm_policy_set_precision.argtypes = [vp, i32]; lib.swarm_policy_set_precision.restype = i32
+    lib.swarm_policy_load_device.argtypes = [vp] * 10; lib.swarm_policy_load_device.restype = i32
+    lib.swarm_policy_read_packed.argtypes = [vp, vp, ctypes.c_int64, vp]; lib.swarm_policy_read_packed.restype = ctypes.c_int64
     lib.swarm_policy_last_error.argtypes = []; lib.swarm_policy_last_error.restype = ctypes.c_char_p
     lib.swarm_observe.argtypes = [vp, vp]; lib.swarm_observe.restype = i32
     lib.swarm_step.argtypes = [vp, vp, i32, vp, vp, vp, vp]; lib.swarm_step.restype = i32

@@ -268,6 +268,68 @@ k_policy_mlp(const MlpParams P, const void *__restrict__ obs_, float *__restrict
     }
 }
 
+// swarm_policy_load_device's packer: the whole blob of a handle re-written from fp32 DEVICE weights (torch.nn.Linear layout),
+// in the layout swarm_policy_create packs on the host -- which stays the independent witness: tests/test_gpu_policy_load.py
+// compares the two blobs byte for byte.  One thread per 16-byte piece (fragment x lane: 8 bf16 of one output feature), writing
+// the piece's high and low parts; the threads behind them write the fp32 bias block.  The padded [out][in] matrices the host
+// code materialises for layers 2-4 are evaluated per element: the weight where both indices are live, the bias in column
+// `hidden`, the 1.0 that carries the constant-one feature at (hidden, hidden) of layers 2-3, zero elsewhere.
+struct PackParams {
+    const float *w1, *b1, *w2, *b2, *w3, *b3, *w4, *b4;      // fc1..fc4, device
+    uint4 *hi, *lo;                    // the blob's high and low parts, kPackPieces 16-byte pieces each
+    float *bias;                       // the blob's fp32 block, kPackBias floats
+    int in_dim, hidden, act_dim;
+};
+constexpr int kPackPieces = (3 * kMT * kKS + kKS) * 64;                     // 228 fragments x 64 lanes
+constexpr int kPackBias = 3 * kKP + 32;
+constexpr int kPackThreads = 256;
+
+// round-to-nearest-even on the bit pattern, as the host packer's bf16_rne (integer: no conversion's denormal mode to trust)
+__device__ __forceinline__ unsigned pack_bf16(float f)
+{
+    unsigned u = __float_as_uint(f);
+    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (u >> 16) | 0x40u;     // NaN (outside the contract)
+    u += 0x7FFFu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+
+// (A template, launched through launch_pack at the end of the file, only so that the compiler emits it behind the
+// k_policy_mlp instantiations: their code, local labels included, stays what it was -- tools/isa_diff.py.)
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) k_policy_pack(const PackParams P)
+{
+    const int q = blockIdx.x * THREADS + threadIdx.x;
+    if (q >= kPackPieces) {
+        const int t = q - kPackPieces;                                      // bias block: b1, the constant one, zeros
+        if (t < kPackBias) P.bias[t] = t < P.hidden ? P.b1[t] : (t == P.hidden ? 1.0f : 0.0f);
+        return;
+    }
+    const int f = q >> 6, lane = q & 63, h = lane >> 5;
+    const int layer = f < 3 * kMT * kKS ? f / (kMT * kKS) : 3;              // 0..3 = fc1..fc4
+    const int fl = f - layer * (kMT * kKS), mt = fl / kKS, ks = fl - mt * kKS;
+    const int o = 32 * mt + (lane & 31), one = P.hidden;
+    const float *__restrict__ w = layer == 0 ? P.w1 : layer == 1 ? P.w2 : layer == 2 ? P.w3 : P.w4;
+    const float *__restrict__ b = layer == 1 ? P.b2 : layer == 2 ? P.b3 : P.b4;       // layer 1's bias stays fp32, in the bias block
+    const int n_out = layer == 3 ? P.act_dim : P.hidden;                    // live output features of this layer
+    unsigned hv[8], lv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float v = 0.0f;
+        if (layer == 0) {                                                   // natural k order, fp32 bias kept apart
+            const int k = 16 * ks + 8 * h + j;
+            if (o < n_out && k < P.in_dim) v = w[(size_t)o * P.in_dim + k];
+        } else {                                                            // the accumulator tile's k order
+            const int k = 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+            if (o < n_out) { if (k < one) v = w[(size_t)o * one + k]; else if (k == one) v = b[o]; }
+            else if (layer != 3 && o == one && k == one) v = 1.0f;
+        }
+        hv[j] = pack_bf16(v);
+        lv[j] = pack_bf16(v - __uint_as_float(hv[j] << 16));                // the IEEE fp32 difference, denormals kept
+    }
+    P.hi[q] = make_uint4(hv[0] | hv[1] << 16, hv[2] | hv[3] << 16, hv[4] | hv[5] << 16, hv[6] | hv[7] << 16);
+    P.lo[q] = make_uint4(lv[0] | lv[1] << 16, lv[2] | lv[3] << 16, lv[4] | lv[5] << 16, lv[6] | lv[7] << 16);
+}
+
 uint16_t bf16_rne(float f)
 {
     uint32_t u;
@@ -295,12 +357,20 @@ void set_smem()
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<IN_BF16, TPW, X3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
 }
 
+template <int THREADS>
+void launch_pack(const PackParams &q, hipStream_t st)
+{
+    const unsigned grid = (kPackPieces + kPackBias + THREADS - 1) / THREADS;
+    hipLaunchKernelGGL(k_policy_pack<THREADS>, dim3(grid), dim3(THREADS), 0, st, q);
+}
+
 }  // namespace
 
 struct SWARM_HIDDEN swarm_policy {     // hidden: its implicit destructor must not become an exported weak symbol
     int device, in_dim, hidden, act_dim;
     int precision = 0;             // 0 = bf16 (default), 1 = bf16x3
     swarm_internal::DevBuf<unsigned char> d_blob;     // the packed weights and biases p points into
+    size_t blob_bytes = 0;
     MlpParams p;
     bool smem_set = false;
 };
@@ -381,7 +451,7 @@ int swarm_policy_create(const float *w1, const float *b1, const float *w2, const
 
     swarm_policy *p = new (std::nothrow) swarm_policy;
     if (!p) return SWARM_POLICY_ERR_INVALID;
-    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim;
+    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim; p->blob_bytes = bytes;
     if (p->d_blob.alloc(bytes) != hipSuccess || hipMemcpy(p->d_blob.get(), blob.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
         delete p;
         g_policy_error = "swarm_policy_create: device allocation / upload failed";
@@ -487,6 +557,41 @@ int swarm_policy_forward_explore_logpi(swarm_policy_t *p, const void *obs, int o
 {
     if (!log_pi) { g_policy_error = "swarm_policy_forward_explore_logpi: null log_pi (a [rows] fp32 device array is required)"; return SWARM_POLICY_ERR_INVALID; }
     return policy_forward(p, obs, obs_is_bf16 != 0, rows, act, stream, noise_scale, seed, step, row_offset, log_pi);
+}
+
+int swarm_policy_load_device(swarm_policy_t *p, const float *w1, const float *b1, const float *w2, const float *b2,
+                             const float *w3, const float *b3, const float *w4, const float *b4, void *stream)
+{
+    if (!p) { g_policy_error = "swarm_policy_load_device: null handle"; return SWARM_POLICY_ERR_INVALID; }
+    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_load_device: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
+    const DeviceGuard guard(p->device);
+    if (!guard.ok) { g_policy_error = "swarm_policy_load_device: hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
+    static_assert(kPackPieces % 64 == 0 && sizeof(bf8) == sizeof(uint4), "one 16-byte piece per fragment lane");
+    PackParams q;
+    q.w1 = w1; q.b1 = b1; q.w2 = w2; q.b2 = b2; q.w3 = w3; q.b3 = b3; q.w4 = w4; q.b4 = b4;
+    q.hi = reinterpret_cast<uint4 *>(p->d_blob.get());
+    q.lo = q.hi + kPackPieces;
+    q.bias = reinterpret_cast<float *>(q.lo + kPackPieces);
+    q.in_dim = p->in_dim; q.hidden = p->hidden; q.act_dim = p->act_dim;
+    launch_pack<kPackThreads>(q, static_cast<hipStream_t>(stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_policy_error = std::string("swarm_policy_load_device: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
+    return SWARM_POLICY_OK;
+}
+
+int64_t swarm_policy_read_packed(swarm_policy_t *p, void *host_dst, int64_t capacity, void *stream)
+{
+    if (!p) { g_policy_error = "swarm_policy_read_packed: null handle"; return -SWARM_POLICY_ERR_INVALID; }
+    if (capacity < 0) { g_policy_error = "swarm_policy_read_packed: negative capacity"; return -SWARM_POLICY_ERR_INVALID; }
+    const int64_t bytes = (int64_t)p->blob_bytes;
+    if (!host_dst || capacity < bytes) return bytes;
+    const DeviceGuard guard(p->device);
+    if (!guard.ok) { g_policy_error = "swarm_policy_read_packed: hipSetDevice failed"; return -SWARM_POLICY_ERR_HIP; }
+    hipStream_t st = static_cast<hipStream_t>(stream);          // the copy on the stream, behind the loads enqueued there; then the wait
+    hipError_t e = hipMemcpyAsync(host_dst, p->d_blob.get(), p->blob_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { g_policy_error = std::string("swarm_policy_read_packed: ") + hipGetErrorString(e); return -SWARM_POLICY_ERR_HIP; }
+    return bytes;
 }
 
 }  // extern "C"

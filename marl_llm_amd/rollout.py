@@ -48,7 +48,8 @@ class FusedPolicy:
     """The same actor evaluated by ONE hand-written HIP kernel (csrc/policy_mlp.hip: bf16 MFMA, fp32 accumulate, the four
     layers chained through the accumulator registers) instead of four hipBLASLt GEMMs + elementwise kernels.  Inference
     only (rollouts); numerics = torch.autocast(bfloat16) on the module.  Built from a PolicyMLP (or any module with
-    fc1..fc4); call `refresh()` after the learner updated the weights.  No CPU path."""
+    fc1..fc4); after the learner updated the weights call `sync()` (device parameters, in stream order, no host wait) or
+    `refresh()` (a new handle from a host copy; blocks).  No CPU path."""
 
     def __init__(self, module, device="cuda:0", precision="bf16"):
         """precision: "bf16" (operands rounded to bfloat16: torch.autocast's contract, ~4e-2 from the fp32 module) or "bf16x3"
@@ -84,6 +85,35 @@ class FusedPolicy:
         self.handle = h
         if self.lib.swarm_policy_set_precision(self.handle, 1 if self.precision == "bf16x3" else 0) != 0:
             raise RuntimeError("swarm_policy_set_precision failed: " + self.lib.swarm_policy_last_error().decode())
+
+    def sync(self):
+        """Load the module's current parameters into the existing handle, in stream order (swarm_policy_load_device,
+        include/swarm_policy.h): one packing kernel enqueued on torch's current stream of the device, the stream `__call__`
+        uses.  Enqueue only -- no host synchronisation, no allocation in the library, nothing goes through the host: a
+        forward or rollout enqueued before the call uses the old weights, one enqueued after it the new ones, and the
+        parameters are read when the kernel runs (in-place updates enqueued on that stream before sync() are seen).
+        The packed weights are byte for byte those of `refresh()`.  A parameter that is float32, contiguous and on the
+        device is read in place; another dtype or layout is converted on the device first.  The parameters must be on the
+        policy's device and of the shapes the handle was built with: otherwise ValueError, before any library call -- use
+        `refresh()`, which takes host weights and new shapes."""
+        ct = self._ctypes
+        m = self.module
+        ps = [m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, m.fc3.weight, m.fc3.bias, m.fc4.weight, m.fc4.bias]
+        want = [(self.hidden, self.in_dim), (self.hidden,), (self.hidden, self.hidden), (self.hidden,),
+                (self.hidden, self.hidden), (self.hidden,), (self.act_dim, self.hidden), (self.act_dim,)]
+        if any(tuple(t.shape) != w for t, w in zip(ps, want)):
+            raise ValueError("sync(): the module's (in_dim, hidden, act_dim) are not the handle's (%d, %d, %d); refresh() builds "
+                             "a handle for new shapes" % (self.in_dim, self.hidden, self.act_dim))
+        if any(t.device != self.device for t in ps):
+            raise ValueError("sync() reads the parameters on %s; refresh() loads parameters kept on another device" % (self.device,))
+        # a conversion runs on the current stream of the device, where the kernel goes; the caching allocator hands the staging
+        # tensor's memory to later work of that stream only, so it may be dropped on return
+        ws = [t.detach() if t.dtype == torch.float32 and t.is_contiguous() else t.detach().to(torch.float32).contiguous()
+              for t in ps]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self.lib.swarm_policy_load_device(self.handle, *[ct.c_void_p(w.data_ptr()) for w in ws], ct.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("swarm_policy_load_device failed: " + self.lib.swarm_policy_last_error().decode())
 
     def __call__(self, obs, out=None, noise_scale=0.0, seed=0, step=0, log_pi=None, row_offset=0):
         """obs [rows, in_dim] float32 or bfloat16 on the device (contiguous) -> actions [rows, act_dim] float32.
