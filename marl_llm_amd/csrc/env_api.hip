@@ -45,12 +45,11 @@ int npad_for(int n)
     return v;
 }
 
-// One step (do_step) or observation pass of the handle, on its stream: the step kernel's launch, or on a large_swarm handle
-// the large-swarm kernels' -- every pass of such a handle, at any n_agents
-int step_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior)
+// One pass of the handle, on its stream: the step kernel's launch, or on a large_swarm handle the large-swarm kernels' --
+// every pass of such a handle, at any n_agents
+int step_launch(swarm_env *h, const Pass &ps)
 {
-    return h->cfg.large_swarm ? large_launch(h, do_step, action, act_f64, obs, reward, done, a_prior)
-                              : env_launch(h, do_step, action, act_f64, obs, reward, done, a_prior);
+    return h->cfg.large_swarm ? large_launch(h, ps) : env_launch(h, ps);
 }
 
 // Is this cell list a row-major subset of a square lattice (<= 64 x 64)?  Fills `L` (geometry only) if so.
@@ -166,7 +165,7 @@ void set_lattice_mode(swarm_env *h, bool any_walk, bool any_scan, float rmax, fl
     // half-occupied geometry (Geo<NPAD, true>) -- twice the workgroups, eight lanes per agent in the list phase.  It exists
     // for the lattice kernel only, and the two launches of a mixed batch must share one workgroup -> env map: all-walk only
     {
-        const int epb_full = h->npad < 64 ? 64 / h->npad : 1;
+        const int epb_full = env_geometry(h->npad, false).envs;
         const long long grid_full = ((long long)h->cfg.n_env + epb_full - 1) / epb_full;
         h->half = h->path_mode == PATH_WALK && h->npad < 64 && epb_full >= 2 && !(h->cfg.debug_flags & 4) && 2 * grid_full <= (long long)h->n_cu * 6;
     }
@@ -186,11 +185,9 @@ int export_pass(swarm_env *h, bool lists, bool cap_even)
         HIP_ALLOC(h, occ, EN * (size_t)h->kp.occ_max);
         h->d_exp_sensed = std::move(sensed); h->d_exp_occ = std::move(occ);
     }
-    h->kp.export_small = 1; h->kp.cap_even = cap_even;
-    if (lists) { h->kp.export_idx = 1; h->kp.exp_sensed = h->d_exp_sensed.get(); h->kp.exp_occ = h->d_exp_occ.get(); }
-    const int rc = step_launch(h, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-    h->kp.export_idx = 0; h->kp.export_small = 0; h->kp.cap_even = 0;
-    return rc;
+    Pass ps;
+    ps.export_small = true; ps.export_lists = lists; ps.cap_even = cap_even;
+    return step_launch(h, ps);
 }
 
 // Classify one cell set: is it a lattice subset (and is the lattice path allowed on this handle), and does it walk?  If it
@@ -640,7 +637,9 @@ int swarm_observe(swarm_env_t *h, void *obs)
     if (!h->have_cells) return fail(h, SWARM_ERR_STATE, "swarm_observe: target cells not set for every env (swarm_set_cells)");
     if (!h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_observe: state not set (swarm_set_state)");
     DeviceGuard g(h->device);
-    int rc = step_launch(h, false, nullptr, 0, obs, nullptr, nullptr, nullptr);
+    Pass ps;
+    ps.obs = obs;
+    int rc = step_launch(h, ps);
     if (rc == SWARM_OK) h->observed = true;
     return rc;
 }
@@ -657,7 +656,7 @@ int swarm_step(swarm_env_t *h, const void *action, int action_dtype, void *obs, 
     if (action_dtype != SWARM_F32 && action_dtype != SWARM_F64) return fail(h, SWARM_ERR_INVALID, "swarm_step: bad action_dtype");
     if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_step: call swarm_observe after setting cells/state (the reference's reset() ends with _get_obs())");
     DeviceGuard g(h->device);
-    return step_launch(h, true, action, action_dtype == SWARM_F64, obs, reward, done, a_prior);
+    return step_launch(h, Pass{true, action, action_dtype == SWARM_F64 ? ACT_F64 : 0, obs, reward, done, a_prior});
 }
 
 // (io_alloc / io_export are in no header, yet libswarmenv.so has always exported these two names; SWARM_ABI_VERSION holds
@@ -666,7 +665,7 @@ int io_alloc(swarm_env *h)
 {
     if (h->h_io_action) return SWARM_OK;
     const size_t EN = (size_t)h->cfg.n_env * h->cfg.n_agents, D = (size_t)h->kp.obs_dim;
-    const size_t so = h->cfg.obs_dtype == SWARM_F64 ? 8 : h->cfg.obs_dtype == SWARM_BF16 ? 2 : 4;
+    const size_t so = obs_elem_bytes(h->cfg.obs_dtype);
     const size_t block_bytes = (D * EN + 2 * EN + EN) * 8 + ((EN + 15) & ~size_t(15));
     // built aside and handed to the handle complete (h_io_action last, which the test above reads): a failure leaves nothing
     DevBuf<char> obs, prior, action; DevBuf<float> rew; DevBuf<uint8_t> done; DevBuf<double> block;
@@ -752,17 +751,17 @@ int swarm_step_host(swarm_env_t *h, const void *action, int action_dtype, int ac
     const void *act = action; int mode = 0;
     if (!action) {
         if (!h->cfg.llm_action) return fail(h, SWARM_ERR_INVALID, "swarm_step_host: null action");
-        act = h->d_act_next.get(); mode = 1;                                   // agent-major doubles
+        act = h->d_act_next.get(); mode = ACT_F64;                             // agent-major doubles
     } else if (action_on_device) {
-        mode = action_dtype == SWARM_F64 ? 1 : 0;                        // [E][N][2] device tensor, as swarm_step
+        mode = action_dtype == SWARM_F64 ? ACT_F64 : 0;                  // [E][N][2] device tensor, as swarm_step
     } else {
         // the reference's (2, n_a) host array: through the pinned staging buffer, read component-major by the kernel
         const size_t bytes = EN * 2 * (action_dtype == SWARM_F64 ? 8 : 4);
         std::memcpy(h->h_io_action.get(), action, bytes);
         HIP_TRY(h, hipMemcpyAsync(h->d_io_action.get(), h->h_io_action.get(), bytes, hipMemcpyHostToDevice, h->stream));
-        act = h->d_io_action.get(); mode = 2 | (action_dtype == SWARM_F64 ? 1 : 0);
+        act = h->d_io_action.get(); mode = ACT_COMPONENT_MAJOR | (action_dtype == SWARM_F64 ? ACT_F64 : 0);
     }
-    rc = step_launch(h, true, act, mode, h->d_io_obs.get(), h->d_io_rew.get(), h->d_io_done.get(), h->kp.with_prior ? h->d_io_prior.get() : nullptr);
+    rc = step_launch(h, Pass{true, act, mode, h->d_io_obs.get(), h->d_io_rew.get(), h->d_io_done.get(), h->kp.with_prior ? h->d_io_prior.get() : nullptr});
     if (rc != SWARM_OK) return rc;
     return io_export(h, slot, true);
 }
@@ -821,7 +820,7 @@ int swarm_path_envs(swarm_env_t *h, int32_t *walk_envs, int32_t *scan_envs)
         std::vector<int> nrows((size_t)E);
         HIP_TRY(h, hipMemcpy2D(nrows.data(), sizeof(int), reinterpret_cast<const char *>(h->d_lat.get()) + offsetof(LatEnv, nrows), sizeof(LatEnv),
                                sizeof(int), (size_t)E, hipMemcpyDeviceToHost));
-        const int epb = h->npad < 64 ? 64 / h->npad : 1;
+        const int epb = env_geometry(h->npad, false).envs;
         for (int e0 = 0; e0 < E; e0 += epb) {
             bool any_zero = false;
             for (int k = 0; k < epb; ++k) any_zero = any_zero || nrows[(size_t)std::min(e0 + k, E - 1)] == 0;
@@ -837,7 +836,7 @@ double swarm_step_algorithmic_bytes(const swarm_env_t *h)
     if (!h) return 0.0;
     // Per agent-step: action 2*4 r, state p/dp 4*8 r + 4*8 w (fp64 here), obs D*sizeof w, reward 4 + done 1 +
     // prior 2*sizeof w; per env: target cells 2*n_g_max*8 r.  (with this build's dtypes.)
-    const double so = h->cfg.obs_dtype == SWARM_F64 ? 8.0 : h->cfg.obs_dtype == SWARM_BF16 ? 2.0 : 4.0;
+    const double so = (double)obs_elem_bytes(h->cfg.obs_dtype);
     const double per_agent = 8.0 + 64.0 + h->kp.obs_dim * so + 5.0 + 2.0 * so;
     return (double)h->cfg.n_env * (h->cfg.n_agents * per_agent + 2.0 * h->kp.ng_max * 8.0);
 }

@@ -475,13 +475,11 @@ hipError_t launch_export(hipStream_t st, int obs_dtype, const void *obs, const f
                          const void *prior, double *out, int D, long long EN, int with_prior)
 {
     const unsigned grid = (unsigned)((EN + 63) / 64);
-    if (obs_dtype == SWARM_F64)
-        hipLaunchKernelGGL(k_export<double>, dim3(grid), dim3(256), 0, st, (const double *)obs, reward, done, (const double *)prior, out, D, EN, with_prior);
-    else if (obs_dtype == SWARM_BF16)
-        hipLaunchKernelGGL(k_export<__bf16>, dim3(grid), dim3(256), 0, st, (const __bf16 *)obs, reward, done, (const __bf16 *)prior, out, D, EN, with_prior);
-    else
-        hipLaunchKernelGGL(k_export<float>, dim3(grid), dim3(256), 0, st, (const float *)obs, reward, done, (const float *)prior, out, D, EN, with_prior);
-    return hipGetLastError();
+    return with_obs_type(obs_dtype, [&](auto t) {
+        typedef typename decltype(t)::type OT;
+        hipLaunchKernelGGL(k_export<OT>, dim3(grid), dim3(256), 0, st, (const OT *)obs, reward, done, (const OT *)prior, out, D, EN, with_prior);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace swarm_internal

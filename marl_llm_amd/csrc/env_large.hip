@@ -511,21 +511,21 @@ namespace swarm_internal {
 
 int large_lds_bytes(int n_cells_max, int n_agents) { return kWaves * WaveLds(n_cells_max, n_agents).bytes(); }
 
-int large_launch(swarm_env *h, bool do_step, const void *action, int act_mode, void *obs, float *reward, uint8_t *done, void *a_prior)
+int large_launch(swarm_env *h, const Pass &ps)
 {
-    const KP &kp = h->kp;
+    KP tmp;
+    const KP &kp = launch_kp(h, ps, 0, tmp);
     const long long EN = (long long)kp.n_env * kp.n_a;
-    const int dt = h->cfg.obs_dtype;
-    if (do_step) {
-        const int pair_bytes = dt == SWARM_F64 ? 16 : dt == SWARM_BF16 ? 4 : 8;
-        hipLaunchKernelGGL(k_large_move, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0, h->stream, kp, action, act_mode,
-                           kp.with_prior ? a_prior : nullptr, pair_bytes);
+    if (ps.do_step) {
+        const int pair_bytes = 2 * (int)obs_elem_bytes(h->cfg.obs_dtype);
+        hipLaunchKernelGGL(k_large_move, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0, h->stream, kp, ps.action, ps.act_mode,
+                           kp.with_prior ? ps.a_prior : nullptr, pair_bytes);
         HIP_TRY(h, hipGetLastError());
     }
     const int smem = large_lds_bytes(kp.ng_max, kp.n_a);
-    HIP_LAUNCHED(h, dt == SWARM_F64 ? launch_observe<double>(h->stream, kp, smem, obs, reward, done)
-                  : dt == SWARM_BF16 ? launch_observe<__bf16>(h->stream, kp, smem, obs, reward, done)
-                                     : launch_observe<float>(h->stream, kp, smem, obs, reward, done));
+    HIP_LAUNCHED(h, with_obs_type(h->cfg.obs_dtype, [&](auto t) {
+        return launch_observe<typename decltype(t)::type>(h->stream, kp, smem, ps.obs, ps.reward, ps.done);
+    }));
     return SWARM_OK;
 }
 

@@ -1,13 +1,14 @@
 // Private to the four translation units of the env library -- swarm_env.hip (the step kernel and its launch), env_large.hip
 // (the large-swarm step kernels), env_kernels.hip (the side kernels) and env_api.hip (the handle and the C ABI): the
-// kernel-argument types, the handle and the functions through which they call each other.  Not installed, not exported: the namespace has hidden visibility,
-// so the public ABI (swarm_env.h) does not change.  What the OTHER translation units of libswarmenv.so may ask of an env
-// handle is in swarm_internal.h.
+// kernel-argument types, the handle, the description of one pass (Pass: what a launch's KP is derived from) and the functions
+// through which they call each other.  Not installed, not exported: the namespace has hidden visibility, so the public ABI
+// (swarm_env.h) does not change.  What the OTHER translation units of libswarmenv.so may ask of an env handle is in swarm_internal.h.
 #ifndef SWARM_ENV_TYPES_H
 #define SWARM_ENV_TYPES_H
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -35,7 +36,8 @@ struct LatEnv {
 
 // The kernel argument of every env kernel.  Field order, types and size are part of the step kernel's device code (the
 // scalar loads address the fields by offset): append, never move.  cxy_stride, off_cxy and off_rres are dead -- no kernel
-// reads them and the host leaves them zero; they keep their places for the fields behind them.
+// reads them and the host leaves them zero; they keep their places for the fields behind them.  export_idx, export_small,
+// cap_even, exp_sensed, exp_occ, stamps and path_filter are zero in the handle's KP: launch_kp sets them in a launch's copy.
 struct KP {
     int n_env, n_a, ng_max, ngw, topo, g_max, occ_max, obs_dim;
     int with_self, periodic, boundary, with_prior, export_idx;
@@ -94,6 +96,9 @@ struct KP {
                                // The host picks the filtered instantiation of the kernel by it (k_env's FILT); the kernel's own
                                // test is compiled in, by the launch kind
 };
+static_assert(sizeof(KP) == 632, "KP: append, never move -- and a new field changes this size on purpose");
+static_assert(offsetof(KP, n_env) == 0 && offsetof(KP, dbg_phase) == 232 && offsetof(KP, lat) == 336 && offsetof(KP, p) == 464 &&
+              offsetof(KP, path_filter) == 624, "KP: a field moved");
 
 // The uploaded shape set, as the reset and shape-switch kernels read it
 struct ShapeSet {
@@ -119,6 +124,29 @@ struct LatInfo {
 // The cell path of the next launches (set_lattice_mode): one lattice launch, one generic launch, or both with KP::path_filter
 enum PathMode { PATH_SCAN = 0, PATH_WALK = 1, PATH_MIXED = 2 };
 
+// Layout of a pass's action array: doubles (else floats); the reference's (2, n_a) host array with the envs side by side
+// (else agent-major pairs [E][N][2])
+enum ActMode { ACT_F64 = 1, ACT_COMPONENT_MAJOR = 2 };
+
+// One step (do_step) or observation pass of a handle: its arrays, and the switches that hold for this pass alone (launch_kp)
+struct Pass {
+    bool do_step = false;
+    const void *action = nullptr; int act_mode = 0;   // ActMode bits
+    void *obs = nullptr; float *reward = nullptr; uint8_t *done = nullptr; void *a_prior = nullptr;
+    bool export_small = false, cap_even = false;      // KP's fields of these names
+    bool export_lists = false;                        // KP::export_idx, into the handle's export lists (allocated by the caller)
+    long long *stamps = nullptr;                      // KP::stamps (diagnostic build)
+};
+
+// What the host needs to know of the step kernel's Geo<NPAD, HALF>: environments and threads per workgroup
+struct GeoInfo { int envs, threads; };
+
+// slot of one k_env instantiation of the handle's agent count in swarm_env::attr_smem
+constexpr int attr_slot(size_t obs_elem, bool do_step, bool lat, bool half, bool filt)
+{
+    return (do_step ? 1 : 0) + (obs_elem == 8 ? 2 : obs_elem == 2 ? 4 : 0) + (lat ? 6 : 0) + (half ? 12 : 0) + (filt ? 24 : 0);
+}
+
 }  // namespace swarm_internal
 
 struct swarm_env {
@@ -129,7 +157,7 @@ struct swarm_env {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_cells = false, have_state = false, observed = false;
-    int attr_smem[48];
+    int attr_smem[swarm_internal::attr_slot(2, true, true, true, true) + 1];   // dynamic-LDS cap raised so far, per instantiation
     bool half = false;             // the half-occupied geometry is in use (set_lattice_mode; all-walk batches only)
     int path_mode = swarm_internal::PATH_SCAN;
     // the generic launch of a mixed batch runs beside the lattice launch on this stream, forked from and joined to the
@@ -185,14 +213,19 @@ int fail(swarm_env *h, int code, const std::string &msg);
 // ---- swarm_env.hip: the step kernel
 // lay out the dynamic LDS of the launches of geometry (npad, half) for k.lattice / k.ng_max / k.g_max: KP's strides, off_*, smem_*
 void env_layout(KP &k, int npad, bool half);
-// enqueue one step (do_step) or observation pass of the handle's current cell path on its stream
-int env_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior);
+GeoInfo env_geometry(int npad, bool half);
+// The KP of one launch of `ps`: the handle's with the pass's switches applied.  filter = KP::path_filter: 0, or 1 / 2 for the
+// lattice / generic launch of a mixed batch (2: with the generic LDS layout).  The result is the handle's own (a plain step
+// copies nothing) or `tmp`.
+const KP &launch_kp(const swarm_env *h, const Pass &ps, int filter, KP &tmp);
+// enqueue the pass on the handle's current cell path, on its stream
+int env_launch(swarm_env *h, const Pass &ps);
 
 // ---- env_large.hip: the two kernels of a handle created with swarm_config_t.large_swarm (any n_agents in [1, 1024])
 // dynamic LDS per workgroup of the observation kernel
 int large_lds_bytes(int n_cells_max, int n_agents);
 // env_launch's contract for such a handle: the move kernel (do_step) and the observation kernel, both on the handle's stream
-int large_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior);
+int large_launch(swarm_env *h, const Pass &ps);
 
 // ---- env_kernels.hip: one launcher per side kernel; each enqueues on `st` and returns the launch's hipGetLastError()
 hipError_t launch_reset(hipStream_t st, const KP &kp, const ShapeSet &S, unsigned long long seed, unsigned long long episode,

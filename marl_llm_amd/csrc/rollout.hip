@@ -18,6 +18,7 @@
 namespace {
 
 using swarm_internal::DeviceGuard;
+using swarm_internal::obs_elem_bytes;
 using swarm_internal::np_sum_stream;
 using swarm_internal::np_clip1;
 using swarm_internal::pmix64;
@@ -201,7 +202,7 @@ struct Loop {
 
     Loop(const char *who_, swarm_env_t *env_, const swarm_env_info &ei, const swarm_ring_t *ring, void *stream_)
         : who(who_), env(env_), dev(ei.device), stream(stream_), st(static_cast<hipStream_t>(stream_)), rows(ring->rows),
-          bf16(ei.obs_dtype == SWARM_BF16), obs_slot((size_t)rows * ei.obs_dim * (bf16 ? 2 : 4)), pri_slot((size_t)rows * 2 * (bf16 ? 2 : 4)),
+          bf16(ei.obs_dtype == SWARM_BF16), obs_slot((size_t)rows * ei.obs_dim * obs_elem_bytes(ei.obs_dtype)), pri_slot((size_t)rows * 2 * obs_elem_bytes(ei.obs_dtype)),
           obs_base(static_cast<char *>(ring->obs)), pri_base(static_cast<char *>(ring->prior)), act_base(ring->act), rew_base(ring->rew),
           done_base(ring->done), cur(ring->cur), n_slots(ring->n_slots), rc(SWARM_OK)
     {

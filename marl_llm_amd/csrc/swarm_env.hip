@@ -354,7 +354,7 @@ __device__ __forceinline__ float psi5_u_f32(float u)
 //                   ends with its slowest wave.  The lattice kernel runs them at the end of part 5, ahead of part 6.
 template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF = false, bool FILT = false>
 __global__ void __launch_bounds__((Geo<NPAD, HALF>::T), (LAT ? Geo<NPAD, HALF>::WPS_LAT : Geo<NPAD, HALF>::WPS_GEN))
-k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__restrict__ obs,
+k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__restrict__ obs,
       float *__restrict__ reward, uint8_t *__restrict__ done, OT *__restrict__ a_prior)
 {
     typedef Geo<NPAD, HALF> G_;
@@ -474,14 +474,14 @@ k_env(const KP P, const void *__restrict__ action, const int act_f64, OT *__rest
         px = P.p[sbase + i]; py = P.p[sbase + n_a + i];
         vx = P.dp[sbase + i]; vy = P.dp[sbase + n_a + i];
         if (DO_STEP) {
-            // act_f64 bit 0: doubles; bit 1: the reference's (2, n_a) component-major layout with the envs side by side on
+            // act_mode bit 0: doubles; bit 1: the reference's (2, n_a) component-major layout with the envs side by side on
             // the agent axis (the numpy API, ENV:487), else agent-major pairs [E][N][2]
-            if (act_f64 & 2) {
+            if (act_mode & 2) {
                 const size_t a0 = (size_t)e * n_a + i, a1 = a0 + (size_t)P.n_env * n_a;
-                if (act_f64 & 1) { ax = ((const double *)action)[a0]; ay = ((const double *)action)[a1]; }
+                if (act_mode & 1) { ax = ((const double *)action)[a0]; ay = ((const double *)action)[a1]; }
                 else { ax = (double)((const float *)action)[a0]; ay = (double)((const float *)action)[a1]; }
             }
-            else if (act_f64 & 1) { const size_t ab = ((size_t)e * n_a + i) * 2; ax = ((const double *)action)[ab]; ay = ((const double *)action)[ab + 1]; }
+            else if (act_mode & 1) { const size_t ab = ((size_t)e * n_a + i) * 2; ax = ((const double *)action)[ab]; ay = ((const double *)action)[ab + 1]; }
             else { const float2 af = reinterpret_cast<const float2 *>(action)[(size_t)e * n_a + i]; ax = (double)af.x; ay = (double)af.y; }
             // the prior policy of THIS step (CPP:1061-1196 via ENV:605-624) is a function of the pre-integration state and
             // of the neighbour list / nearest cell of the previous observation: the previous launch evaluated it at its end,
@@ -2053,7 +2053,7 @@ struct Launch {
 };
 
 template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF, bool FILT = false>
-int launch_t(swarm_env *h, const Launch &l, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior)
+int launch_t(swarm_env *h, const Launch &l, const Pass &ps)
 {
     constexpr int T = Geo<NPAD, HALF>::T, EPB = Geo<NPAD, HALF>::EPB;
     auto kern = k_env<NPAD, OT, DO_STEP, LAT, HALF, FILT>;
@@ -2062,57 +2062,45 @@ int launch_t(swarm_env *h, const Launch &l, const void *action, int act_f64, voi
 #ifdef SWARM_EXTRA_SMEM
     smem += SWARM_EXTRA_SMEM;                            // occupancy experiments only
 #endif
-    int &attr = h->attr_smem[(DO_STEP ? 1 : 0) + (sizeof(OT) == 8 ? 2 : sizeof(OT) == 2 ? 4 : 0) + (LAT ? 6 : 0) + (HALF ? 12 : 0) + (FILT ? 24 : 0)];   // raise the dynamic-LDS cap once per instantiation
+    int &attr = h->attr_smem[attr_slot(sizeof(OT), DO_STEP, LAT, HALF, FILT)];   // raise the dynamic-LDS cap once per instantiation
     if (attr < smem) {
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr = smem;
     }
     const int grid = (h->cfg.n_env + EPB - 1) / EPB;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T), smem, l.st, kp, action, act_f64,
-                       static_cast<OT *>(obs), reward, done, static_cast<OT *>(a_prior));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(T), smem, l.st, kp, ps.action, ps.act_mode,
+                       static_cast<OT *>(ps.obs), ps.reward, ps.done, static_cast<OT *>(ps.a_prior));
     HIP_TRY(h, hipGetLastError());
     return SWARM_OK;
 }
 
-template <int NPAD, typename OT, bool DO_STEP>
-int launch_l(swarm_env *h, const Launch &l, const void *action, int act_f64, void *obs, float *reward, uint8_t *done, void *a_prior)
+// The instantiation of one agent count that l and ps ask for.  The kernels stand in the code object in the order of
+// instantiation: steps before observation passes (launch_one), then with_obs_type's order, then the order below.
+template <int NPAD, bool DO_STEP>
+int launch_n(swarm_env *h, const Launch &l, const Pass &ps)
 {
-    if constexpr (NPAD < 64) {
-        if (l.kp->lattice && l.half) return launch_t<NPAD, OT, DO_STEP, true, true>(h, l, action, act_f64, obs, reward, done, a_prior);
-    }
-    if (l.kp->path_filter != 0) {              // a launch of a mixed batch: 1 = its lattice launch, 2 = its generic launch
-        if (l.kp->path_filter != (l.kp->lattice ? 1 : 2) || l.half) return fail(h, SWARM_ERR_INVALID, "env_launch: path_filter does not match the launch");
-        return l.kp->lattice ? launch_t<NPAD, OT, DO_STEP, true, false, true>(h, l, action, act_f64, obs, reward, done, a_prior)
-                             : launch_t<NPAD, OT, DO_STEP, false, false, true>(h, l, action, act_f64, obs, reward, done, a_prior);
-    }
-    return l.kp->lattice ? launch_t<NPAD, OT, DO_STEP, true, false>(h, l, action, act_f64, obs, reward, done, a_prior)
-                         : launch_t<NPAD, OT, DO_STEP, false, false>(h, l, action, act_f64, obs, reward, done, a_prior);
-}
-
-template <int NPAD>
-int launch_n(swarm_env *h, const Launch &l, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done,
-             void *a_prior)
-{
-    const int dt = h->cfg.obs_dtype;
-    if (do_step) {
-        return dt == SWARM_F64 ? launch_l<NPAD, double, true>(h, l, action, act_f64, obs, reward, done, a_prior)
-             : dt == SWARM_BF16 ? launch_l<NPAD, __bf16, true>(h, l, action, act_f64, obs, reward, done, a_prior)
-                                : launch_l<NPAD, float, true>(h, l, action, act_f64, obs, reward, done, a_prior);
-    }
-    return dt == SWARM_F64 ? launch_l<NPAD, double, false>(h, l, action, act_f64, obs, reward, done, a_prior)
-         : dt == SWARM_BF16 ? launch_l<NPAD, __bf16, false>(h, l, action, act_f64, obs, reward, done, a_prior)
-                            : launch_l<NPAD, float, false>(h, l, action, act_f64, obs, reward, done, a_prior);
+    return with_obs_type(h->cfg.obs_dtype, [&](auto t) {
+        typedef typename decltype(t)::type OT;
+        const bool lat = l.kp->lattice != 0;
+        if constexpr (NPAD < 64) {
+            if (lat && l.half) return launch_t<NPAD, OT, DO_STEP, true, true>(h, l, ps);
+        }
+        if (l.kp->path_filter != 0) {              // a launch of a mixed batch: 1 = its lattice launch, 2 = its generic launch
+            if (l.kp->path_filter != (lat ? 1 : 2) || l.half) return fail(h, SWARM_ERR_INVALID, "env_launch: path_filter does not match the launch");
+            return lat ? launch_t<NPAD, OT, DO_STEP, true, false, true>(h, l, ps) : launch_t<NPAD, OT, DO_STEP, false, false, true>(h, l, ps);
+        }
+        return lat ? launch_t<NPAD, OT, DO_STEP, true, false>(h, l, ps) : launch_t<NPAD, OT, DO_STEP, false, false>(h, l, ps);
+    });
 }
 
 // one launch of the step kernel: the instantiation of the handle's agent count and obs dtype that l asks for
-int launch_one(swarm_env *h, const Launch &l, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done,
-               void *a_prior)
+int launch_one(swarm_env *h, const Launch &l, const Pass &ps)
 {
     // (SWARM_ONLY_NPAD: development builds with a single instantiation -- quick register / code-size checks and A/B runs)
 #ifndef SWARM_ONLY_NPAD
 #define SWARM_ONLY_NPAD 0
 #endif
-#define SWARM_CASE(n) case n: if (SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) return launch_n<(SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) ? n : (SWARM_ONLY_NPAD)>(h, l, do_step, action, act_f64, obs, reward, done, a_prior); break
+#define SWARM_CASE(n) case n: if (SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) { constexpr int N = (SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) ? n : (SWARM_ONLY_NPAD); return ps.do_step ? launch_n<N, true>(h, l, ps) : launch_n<N, false>(h, l, ps); } break
     switch (h->npad) {
     SWARM_CASE(8); SWARM_CASE(16); SWARM_CASE(32); SWARM_CASE(64); SWARM_CASE(128); SWARM_CASE(256);
     }
@@ -2129,24 +2117,40 @@ void env_layout(KP &k, int npad, bool half)
     for_geometry(npad, half, [&](auto g) { layout_t<decltype(g)::NPAD_, decltype(g)::HALF_>(k); });
 }
 
-int env_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void *obs, float *reward, uint8_t *done,
-               void *a_prior)
+GeoInfo env_geometry(int npad, bool half)
 {
+    GeoInfo r = {};
+    for_geometry(npad, half, [&](auto g) { r = GeoInfo{decltype(g)::EPB, decltype(g)::T}; });
+    return r;
+}
+
+const KP &launch_kp(const swarm_env *h, const Pass &ps, int filter, KP &tmp)
+{
+    if (filter == 0 && !ps.export_small && !ps.export_lists && !ps.cap_even && !ps.stamps) return h->kp;
+    tmp = h->kp;
+    tmp.export_small = ps.export_small; tmp.cap_even = ps.cap_even; tmp.stamps = ps.stamps;
+    if (ps.export_lists) { tmp.export_idx = 1; tmp.exp_sensed = h->d_exp_sensed.get(); tmp.exp_occ = h->d_exp_occ.get(); }
+    tmp.path_filter = filter;
+    if (filter == 2) { tmp.lattice = 0; env_layout(tmp, h->npad, false); }
+    return tmp;
+}
+
+int env_launch(swarm_env *h, const Pass &ps)
+{
+    KP tmp, tmp_gen;
     if (h->path_mode != PATH_MIXED)          // one kernel for the whole batch, as the handle's KP describes it
-        return launch_one(h, Launch{&h->kp, h->stream, h->half}, do_step, action, act_f64, obs, reward, done, a_prior);
+        return launch_one(h, Launch{&launch_kp(h, ps, 0, tmp), h->stream, h->half}, ps);
     // A mixed batch: the generic kernel steps the workgroups that hold an env without a lattice record, the lattice kernel the
     // others; both over the full geometry, so that they agree on which envs a workgroup holds, and each returns at once from
-    // the other's workgroups (KP::path_filter).  The generic launch's KP is the handle's (export switches, pointers and all)
-    // with the generic LDS layout.  The launches touch disjoint envs, so the generic one runs beside the lattice one on the
+    // the other's workgroups (KP::path_filter).  The generic launch's KP is the lattice launch's (the pass's switches and
+    // all) with the generic LDS layout.  The launches touch disjoint envs, so the generic one runs beside the lattice one on the
     // handle's auxiliary stream, forked from and joined to the handle's stream by events -- no host synchronisation;
     // debug_flags bit 4: one after the other on the handle's stream.
-    KP gen = h->kp, lat = h->kp;
-    gen.lattice = 0; env_layout(gen, h->npad, false); gen.path_filter = 2;
-    lat.path_filter = 1;
+    const KP *lat = &launch_kp(h, ps, 1, tmp), *gen = &launch_kp(h, ps, 2, tmp_gen);
     if (h->cfg.debug_flags & 16) {
-        const int rc = launch_one(h, Launch{&gen, h->stream, false}, do_step, action, act_f64, obs, reward, done, a_prior);
+        const int rc = launch_one(h, Launch{gen, h->stream, false}, ps);
         if (rc != SWARM_OK) return rc;
-        return launch_one(h, Launch{&lat, h->stream, false}, do_step, action, act_f64, obs, reward, done, a_prior);
+        return launch_one(h, Launch{lat, h->stream, false}, ps);
     }
     if (!h->aux_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
     if (!h->ev_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
@@ -2154,9 +2158,9 @@ int env_launch(swarm_env *h, bool do_step, const void *action, int act_f64, void
     HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
     HIP_TRY(h, hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
     // from here the aux stream may hold work: nothing returns before the streams are joined again
-    const int rc_gen = launch_one(h, Launch{&gen, h->aux_stream, false}, do_step, action, act_f64, obs, reward, done, a_prior);
+    const int rc_gen = launch_one(h, Launch{gen, h->aux_stream, false}, ps);
     hipError_t e_join = hipEventRecord(h->ev_join, h->aux_stream);
-    const int rc_lat = launch_one(h, Launch{&lat, h->stream, false}, do_step, action, act_f64, obs, reward, done, a_prior);
+    const int rc_lat = launch_one(h, Launch{lat, h->stream, false}, ps);
     if (e_join == hipSuccess) e_join = hipStreamWaitEvent(h->stream, h->ev_join, 0);
     if (e_join != hipSuccess) {                  // no event to wait on: the host waits for the generic launch instead (under a
                                                  // graph capture that wait fails too; the call is failing already and says so)
@@ -2202,16 +2206,16 @@ int swarm_debug_stamps(swarm_env_t *h, const void *action, int action_dtype, voi
 {
     if (!h || !out) return -1;
     DeviceGuard g(h->device);
-    const int epb = h->npad < 64 ? (64 / h->npad) / (h->half ? 2 : 1) : 1;
-    const int grid = (h->cfg.n_env + epb - 1) / epb;   // same for every Geo<NPAD>
-    const int wpb = (h->npad < 64 ? 64 : h->npad) * 4 / 64;      // waves per workgroup
+    const GeoInfo geo = env_geometry(h->npad, h->half);
+    const int grid = (h->cfg.n_env + geo.envs - 1) / geo.envs;
+    const int wpb = geo.threads / 64;                  // waves per workgroup
     if (grid > max_blocks) return -1;
     DevBuf<long long> d;
     if (d.alloc((size_t)grid * wpb * 24) != hipSuccess) return -1;
     (void)hipMemset(d.get(), 0, (size_t)grid * wpb * 24 * sizeof(long long));
-    h->kp.stamps = d.get();
-    int rc = env_launch(h, true, action, action_dtype == SWARM_F64, obs, reward, done, a_prior);
-    h->kp.stamps = nullptr;
+    Pass ps = {true, action, action_dtype == SWARM_F64 ? ACT_F64 : 0, obs, reward, done, a_prior};
+    ps.stamps = d.get();
+    int rc = env_launch(h, ps);
     if (rc == SWARM_OK && hipMemcpy(out, d.get(), (size_t)grid * wpb * 24 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
     return rc == SWARM_OK ? grid : -1;
 }

@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "swarm_env.h"
@@ -101,6 +102,16 @@ public:
     T *get() const { return p_; }
     explicit operator bool() const { return p_ != nullptr; }
 };
+
+// The one switch over an obs dtype code (swarm_config_t.obs_dtype): f(TypeTag<T>{}) with T the type of an observation
+// element -- double, __bf16 or float.  f returns the same type for all three.
+template <class T> struct TypeTag { typedef T type; };
+template <class F>
+inline auto with_obs_type(int dtype, F &&f)
+{
+    return dtype == SWARM_F64 ? f(TypeTag<double>{}) : dtype == SWARM_BF16 ? f(TypeTag<__bf16>{}) : f(TypeTag<float>{});
+}
+inline size_t obs_elem_bytes(int dtype) { return with_obs_type(dtype, [](auto t) { return sizeof(typename decltype(t)::type); }); }
 
 }  // namespace swarm_internal
 
