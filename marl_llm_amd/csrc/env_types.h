@@ -1,4 +1,4 @@
-// Private to the four translation units of the env library -- swarm_env.hip (the step kernel and its launch), env_large.hip
+// Private to the four sources of the env library -- swarm_env.hip (the step kernel and its launch; compiled as seven units), env_large.hip
 // (the large-swarm step kernels), env_kernels.hip (the side kernels) and env_api.hip (the handle and the C ABI): the
 // kernel-argument types, the handle, the description of one pass (Pass: what a launch's KP is derived from) and the functions
 // through which they call each other.  Not installed, not exported: the namespace has hidden visibility, so the public ABI
@@ -220,6 +220,22 @@ GeoInfo env_geometry(int npad, bool half);
 const KP &launch_kp(const swarm_env *h, const Pass &ps, int filter, KP &tmp);
 // enqueue the pass on the handle's current cell path, on its stream
 int env_launch(swarm_env *h, const Pass &ps);
+// What one launch of the step kernel takes from its caller: the kernel argument (kp->lattice chooses the kernel), the stream,
+// and whether the lattice kernel runs in the half-occupied geometry
+struct Launch {
+    const KP *kp;
+    hipStream_t st;
+    bool half;
+};
+// One launch of the k_env instantiation of padded agent count NPAD that l and ps ask for.  swarm_env.hip is compiled once
+// per agent count (its kernel units); each defines the launch_npad of its own count, and the file's host unit calls them.
+template <int NPAD> int launch_npad(swarm_env *h, const Launch &l, const Pass &ps);
+extern template int launch_npad<8>(swarm_env *, const Launch &, const Pass &);
+extern template int launch_npad<16>(swarm_env *, const Launch &, const Pass &);
+extern template int launch_npad<32>(swarm_env *, const Launch &, const Pass &);
+extern template int launch_npad<64>(swarm_env *, const Launch &, const Pass &);
+extern template int launch_npad<128>(swarm_env *, const Launch &, const Pass &);
+extern template int launch_npad<256>(swarm_env *, const Launch &, const Pass &);
 
 // ---- env_large.hip: the two kernels of a handle created with swarm_config_t.large_swarm (any n_agents in [1, 1024])
 // dynamic LDS per workgroup of the observation kernel

@@ -45,6 +45,24 @@
 
 using namespace swarm_internal;
 
+// One source, several objects (marl_llm_amd/build.py: UNITS).  SWARM_ENV_UNIT chooses what a compile of this file holds:
+//   8, 16, 32, 64, 128, 256   a KERNEL unit: the k_env instantiations of that padded agent count, launch_t / launch_n and
+//                             the one function the rest of the library calls, swarm_internal::launch_npad<NPAD>
+//   0                         the HOST unit: layout_t, the geometries, env_launch, the swarm_debug_* entry points; no kernel
+//   (not defined)             everything, as one translation unit -- what an ad-hoc hipcc line gets, and the witness that the
+//                             cut changes no kernel (tools/isa_diff.py)
+// The kernel's text is in this file alone, whatever the cut.  Geo and LatMap are visible to every unit.
+#if !defined(SWARM_ENV_UNIT)
+#define SWARM_UNIT_KERNELS 1
+#define SWARM_UNIT_HOST 1
+#elif SWARM_ENV_UNIT == 0
+#define SWARM_UNIT_KERNELS 0
+#define SWARM_UNIT_HOST 1
+#else
+#define SWARM_UNIT_KERNELS 1
+#define SWARM_UNIT_HOST 0
+#endif
+
 namespace {
 
 typedef unsigned long long u64;
@@ -1979,6 +1997,86 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
 
 #undef LO
 
+}  // namespace
+
+#if SWARM_UNIT_KERNELS
+// ---- the kernel part: the instantiations of one agent count (a kernel unit) or of all six (the whole file), with their
+// launch -- hipFuncSetAttribute wants the kernel's address, which only the unit that instantiates the kernel has
+
+namespace {
+
+template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF, bool FILT = false>
+int launch_t(swarm_env *h, const Launch &l, const Pass &ps)
+{
+    constexpr int T = Geo<NPAD, HALF>::T, EPB = Geo<NPAD, HALF>::EPB;
+    auto kern = k_env<NPAD, OT, DO_STEP, LAT, HALF, FILT>;
+    const KP &kp = *l.kp;
+    int smem = !LAT ? kp.smem_generic : (kp.export_idx ? kp.smem_lat_export : kp.smem_lat);
+#ifdef SWARM_EXTRA_SMEM
+    smem += SWARM_EXTRA_SMEM;                            // occupancy experiments only
+#endif
+    int &attr = h->attr_smem[attr_slot(sizeof(OT), DO_STEP, LAT, HALF, FILT)];   // raise the dynamic-LDS cap once per instantiation
+    if (attr < smem) {
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        attr = smem;
+    }
+    const int grid = (h->cfg.n_env + EPB - 1) / EPB;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(T), smem, l.st, kp, ps.action, ps.act_mode,
+                       static_cast<OT *>(ps.obs), ps.reward, ps.done, static_cast<OT *>(ps.a_prior));
+    HIP_TRY(h, hipGetLastError());
+    return SWARM_OK;
+}
+
+// The instantiation of one agent count that l and ps ask for.  The kernels stand in the code object in the order of
+// instantiation: steps before observation passes (launch_npad), then with_obs_type's order, then the order below.
+template <int NPAD, bool DO_STEP>
+int launch_n(swarm_env *h, const Launch &l, const Pass &ps)
+{
+    return with_obs_type(h->cfg.obs_dtype, [&](auto t) {
+        typedef typename decltype(t)::type OT;
+        const bool lat = l.kp->lattice != 0;
+        if constexpr (NPAD < 64) {
+            if (lat && l.half) return launch_t<NPAD, OT, DO_STEP, true, true>(h, l, ps);
+        }
+        if (l.kp->path_filter != 0) {              // a launch of a mixed batch: 1 = its lattice launch, 2 = its generic launch
+            if (l.kp->path_filter != (lat ? 1 : 2) || l.half) return fail(h, SWARM_ERR_INVALID, "env_launch: path_filter does not match the launch");
+            return lat ? launch_t<NPAD, OT, DO_STEP, true, false, true>(h, l, ps) : launch_t<NPAD, OT, DO_STEP, false, false, true>(h, l, ps);
+        }
+        return lat ? launch_t<NPAD, OT, DO_STEP, true, false>(h, l, ps) : launch_t<NPAD, OT, DO_STEP, false, false>(h, l, ps);
+    });
+}
+
+}  // namespace
+
+namespace swarm_internal {
+
+template <int NPAD>
+int launch_npad(swarm_env *h, const Launch &l, const Pass &ps)
+{
+    return ps.do_step ? launch_n<NPAD, true>(h, l, ps) : launch_n<NPAD, false>(h, l, ps);
+}
+
+#ifdef SWARM_ENV_UNIT
+template int launch_npad<SWARM_ENV_UNIT>(swarm_env *, const Launch &, const Pass &);
+#else
+template int launch_npad<8>(swarm_env *, const Launch &, const Pass &);
+template int launch_npad<16>(swarm_env *, const Launch &, const Pass &);
+template int launch_npad<32>(swarm_env *, const Launch &, const Pass &);
+template int launch_npad<64>(swarm_env *, const Launch &, const Pass &);
+template int launch_npad<128>(swarm_env *, const Launch &, const Pass &);
+template int launch_npad<256>(swarm_env *, const Launch &, const Pass &);
+#endif
+
+}  // namespace swarm_internal
+
+#endif  // SWARM_UNIT_KERNELS
+
+#if SWARM_UNIT_HOST
+// ---- the host part: the LDS layout, the geometries, the choice of the launch, the diagnostic entry points.  No kernel is
+// instantiated here.
+
+namespace {
+
 template <int NPAD, bool HALF>
 void layout_t(KP &k)
 {
@@ -2044,67 +2142,17 @@ void for_geometry(int npad, bool half, F &&f)
     }
 }
 
-// What one launch of the step kernel takes from its caller: the kernel argument (kp->lattice chooses the kernel), the stream,
-// and whether the lattice kernel runs in the half-occupied geometry
-struct Launch {
-    const KP *kp;
-    hipStream_t st;
-    bool half;
-};
-
-template <int NPAD, typename OT, bool DO_STEP, bool LAT, bool HALF, bool FILT = false>
-int launch_t(swarm_env *h, const Launch &l, const Pass &ps)
-{
-    constexpr int T = Geo<NPAD, HALF>::T, EPB = Geo<NPAD, HALF>::EPB;
-    auto kern = k_env<NPAD, OT, DO_STEP, LAT, HALF, FILT>;
-    const KP &kp = *l.kp;
-    int smem = !LAT ? kp.smem_generic : (kp.export_idx ? kp.smem_lat_export : kp.smem_lat);
-#ifdef SWARM_EXTRA_SMEM
-    smem += SWARM_EXTRA_SMEM;                            // occupancy experiments only
-#endif
-    int &attr = h->attr_smem[attr_slot(sizeof(OT), DO_STEP, LAT, HALF, FILT)];   // raise the dynamic-LDS cap once per instantiation
-    if (attr < smem) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr = smem;
-    }
-    const int grid = (h->cfg.n_env + EPB - 1) / EPB;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T), smem, l.st, kp, ps.action, ps.act_mode,
-                       static_cast<OT *>(ps.obs), ps.reward, ps.done, static_cast<OT *>(ps.a_prior));
-    HIP_TRY(h, hipGetLastError());
-    return SWARM_OK;
-}
-
-// The instantiation of one agent count that l and ps ask for.  The kernels stand in the code object in the order of
-// instantiation: steps before observation passes (launch_one), then with_obs_type's order, then the order below.
-template <int NPAD, bool DO_STEP>
-int launch_n(swarm_env *h, const Launch &l, const Pass &ps)
-{
-    return with_obs_type(h->cfg.obs_dtype, [&](auto t) {
-        typedef typename decltype(t)::type OT;
-        const bool lat = l.kp->lattice != 0;
-        if constexpr (NPAD < 64) {
-            if (lat && l.half) return launch_t<NPAD, OT, DO_STEP, true, true>(h, l, ps);
-        }
-        if (l.kp->path_filter != 0) {              // a launch of a mixed batch: 1 = its lattice launch, 2 = its generic launch
-            if (l.kp->path_filter != (lat ? 1 : 2) || l.half) return fail(h, SWARM_ERR_INVALID, "env_launch: path_filter does not match the launch");
-            return lat ? launch_t<NPAD, OT, DO_STEP, true, false, true>(h, l, ps) : launch_t<NPAD, OT, DO_STEP, false, false, true>(h, l, ps);
-        }
-        return lat ? launch_t<NPAD, OT, DO_STEP, true, false>(h, l, ps) : launch_t<NPAD, OT, DO_STEP, false, false>(h, l, ps);
-    });
-}
-
 // one launch of the step kernel: the instantiation of the handle's agent count and obs dtype that l asks for
 int launch_one(swarm_env *h, const Launch &l, const Pass &ps)
 {
-    // (SWARM_ONLY_NPAD: development builds with a single instantiation -- quick register / code-size checks and A/B runs)
-#ifndef SWARM_ONLY_NPAD
-#define SWARM_ONLY_NPAD 0
-#endif
-#define SWARM_CASE(n) case n: if (SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) { constexpr int N = (SWARM_ONLY_NPAD == 0 || SWARM_ONLY_NPAD == n) ? n : (SWARM_ONLY_NPAD); return ps.do_step ? launch_n<N, true>(h, l, ps) : launch_n<N, false>(h, l, ps); } break
     switch (h->npad) {
-    SWARM_CASE(8); SWARM_CASE(16); SWARM_CASE(32); SWARM_CASE(64); SWARM_CASE(128); SWARM_CASE(256);
+    case 8: return launch_npad<8>(h, l, ps);
+    case 16: return launch_npad<16>(h, l, ps);
+    case 32: return launch_npad<32>(h, l, ps);
+    case 64: return launch_npad<64>(h, l, ps);
+    case 128: return launch_npad<128>(h, l, ps);
+    case 256: return launch_npad<256>(h, l, ps);
     }
-#undef SWARM_CASE
     return fail(h, SWARM_ERR_INVALID, "unsupported agent count");
 }
 
@@ -2222,3 +2270,5 @@ int swarm_debug_stamps(swarm_env_t *h, const void *action, int action_dtype, voi
 #endif
 
 }  // extern "C"
+
+#endif  // SWARM_UNIT_HOST

@@ -77,3 +77,46 @@ def test_one_kernel_added(tool):
 def test_difference_outside_the_kernels_is_reported(tool):
     r = tool.compare(HEAD + A, HEAD + A + '\t.ident\t"other compiler"\n')
     assert r["differing"] == [] and r["only_base"] == [] and r["only_tree"] == [] and r["outside"]
+
+
+# ---- one source cut into different units in the two trees: kernel by kernel over all units, local labels and comments normalised
+
+def metadata(entries):
+    return "\t.amdgpu_metadata\n---\namdhsa.kernels:\n" + "".join(
+        "  - .args:\n      - .name:           P\n        .size:           %d\n    .name:           %s\n    .symbol:         %s.kd\n"
+        % (size, n, n) for n, size in entries) + "amdhsa.target:   amdgcn-amd-amdhsa--gfx950\n...\n\n\t.end_amdgpu_metadata\n"
+
+
+def test_units_function_number_and_comments_do_not_count(tool):
+    # the same kernel as the first function of a unit and as the eighth of the whole file
+    whole = HEAD + B + A + metadata([("_Z1bv", 8), ("_Z1av", 8)])
+    a_unit = HEAD + A.replace(".LBB0_1", ".LBB7_1").replace("; @_Z1av", "; -- Begin function _Z1av").replace("; %bb.0:", "") + metadata([("_Z1av", 8)])
+    b_unit = HEAD + B + metadata([("_Z1bv", 8)])
+    assert ".LBB7_1:" in a_unit and "; @_Z1av" not in a_unit
+    r = tool.compare_units([whole], [a_unit, b_unit])
+    assert r["kernels"] == 2 and r["differing"] == [] and r["only_base"] == [] and r["only_tree"] == [] and r["duplicates"] == []
+    assert r["lines"] == len(a_unit.splitlines()) + len(b_unit.splitlines())
+    assert tool.normalise(["\ts_cbranch_scc1 .LBB12_3 ; taken", ".LJTI4_0:", "\t.long .Ltmp9-.Lfunc_end33", "; only a comment"]) == \
+        ["\ts_cbranch_scc1 .LBB_3", ".LJTI_0:", "\t.long .Ltmp-.Lfunc_end"]
+
+
+def test_units_branch_target_counts(tool):
+    r = tool.compare_units([HEAD + A], [HEAD + A.replace(".LBB0_1", ".LBB0_2")])
+    assert [(d[0], d[2], d[3]) for d in r["differing"]] == [("_Z1av", ".LBB_1:", ".LBB_2:")]
+    branch = kernel("_Z1dv", "\ts_cbranch_scc1 .LBB0_1\n.LBB0_2:")
+    r = tool.compare_units([HEAD + branch], [HEAD + branch.replace("scc1 .LBB0_1", "scc1 .LBB0_2")])
+    assert [(d[0], d[2], d[3]) for d in r["differing"]] == [("_Z1dv", "\ts_cbranch_scc1 .LBB_1", "\ts_cbranch_scc1 .LBB_2")]
+
+
+def test_units_descriptor_and_metadata_count(tool):
+    r = tool.compare_units([HEAD + A + B], [HEAD + B, HEAD + kernel("_Z1av", "\tv_mov_b32_e32 v0, 0\n\tv_add_u32_e32 v1, v0, v0", vgprs=9)])
+    assert [(d[0], d[2], d[3]) for d in r["differing"]] == [("_Z1av", "\t\t.amdhsa_next_free_vgpr 8", "\t\t.amdhsa_next_free_vgpr 9")]
+    r = tool.compare_units([HEAD + A + B + metadata([("_Z1av", 8), ("_Z1bv", 8)])], [HEAD + A + metadata([("_Z1av", 8)]), HEAD + B + metadata([("_Z1bv", 16)])])
+    assert [(d[0], d[2], d[3]) for d in r["differing"]] == [("_Z1bv", "        .size:           8", "        .size:           16")]
+
+
+def test_units_duplicate_kernel_is_reported(tool):
+    r = tool.compare_units([HEAD + A + B], [HEAD + A + B, HEAD + A])
+    assert r["duplicates"] == [("tree", "_Z1av")] and r["differing"] == [] and r["only_base"] == [] and r["only_tree"] == []
+    r = tool.compare_units([HEAD + A, HEAD + A + B], [HEAD + A + B])
+    assert r["duplicates"] == [("base", "_Z1av")]

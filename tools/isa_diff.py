@@ -3,17 +3,28 @@
 
     python3 tools/isa_diff.py BASE_REF [-DNAME[=VALUE] ...] [source ...]
 
-Checks BASE_REF out into a temporary directory, compiles every source (default: the library's, marl_llm_amd.build.SRCS) from
-both trees to gfx950 assembly with the library's own flags (marl_llm_amd.build.HIPCC_FLAGS) and compares the text: whole
-files first; where two files differ, kernel by kernel -- from `<symbol>:` to `.end_amdhsa_kernel`, so a kernel's register
-counts, LDS and scratch sizes (.amdhsa_*) are compared with its instructions.  Prints the kernels that are only in the
-base, only in the tree, or different (with the first differing line), then `kernels N, lines M, differing K`, and exits
-non-zero if K > 0, the sets of names differ, or two files differ outside their kernels.  Arguments that start with `-` go
-to the compiler (-DSWARM_STAMPS, -DSWARM_ONLY_NPAD=64).  No GPU is needed: hipcc cross-compiles.
+Checks BASE_REF out into a temporary directory and compiles, for each tree, the units that tree's own marl_llm_amd/build.py
+lists (UNITS; a base without it: its SRCS, one unit each) to gfx950 assembly with that file's flags (HIPCC_FLAGS), all in
+parallel, and compares the text source by source (default: every source of the library).
 
-One name is taken out of both texts before they are compared: `__hip_cuid_<hash>`, a one-byte object that hipcc names after
-a hash of the SOURCE text, comments included -- it differs whenever the source does and says nothing about the code."""
+Where both trees compile a source as the same unit(s), unit by unit: whole files first; where two files differ, kernel by kernel -- from
+`<symbol>:` to `.end_amdhsa_kernel`, so a kernel's register counts, LDS and scratch sizes (.amdhsa_*) are compared with its
+instructions.  One name is taken out of both texts before they are compared: `__hip_cuid_<hash>`, a one-byte object that
+hipcc names after a hash of the SOURCE text, comments included -- it differs whenever the source does and says nothing about
+the code.
+
+Where the trees cut a source into different units, the kernels of all of the source's units are compared one by one, each with
+its entry of the `amdhsa.kernels` metadata (arguments, segment sizes); a kernel found in two units of one tree is an error,
+and the text outside the kernels is not compared.  Two things are taken out of a kernel's text first (normalise): the number
+that the local labels .LBB<k>_, .Lfunc_end<k>, .LJTI<k>_ and .Ltmp<k> carry -- the function's position in its translation
+unit -- and the `;` comments.  Nothing else.
+
+Prints the kernels that are only in the base, only in the tree, or different (with the first differing line), then
+`kernels N, lines M, differing K`, and exits non-zero if K > 0, the sets of names differ, a kernel is there twice, or two
+files differ outside their kernels.  Arguments that start with `-` go to the compiler, for every unit (-DSWARM_STAMPS).  No
+GPU is needed: hipcc cross-compiles."""
 import concurrent.futures
+import importlib.util
 import os
 import re
 import shutil
@@ -23,9 +34,6 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-MAX_JOBS = 16
-
 
 def split_kernels(text):
     """{kernel symbol: its lines, `<symbol>:` .. `.end_amdhsa_kernel`} of one assembly file, and the lines outside them."""
@@ -47,6 +55,17 @@ def strip_cuid(text):
     return re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_", text)
 
 
+def by_name(kb, kt, res):
+    """fill res with the names only in kb, only in kt, and the first differing line of those in both"""
+    res["only_base"] = sorted(set(kb) - set(kt))
+    res["only_tree"] = sorted(set(kt) - set(kb))
+    for name in sorted(set(kb) & set(kt)):
+        a, b = kb[name], kt[name]
+        if a != b:
+            n = next((q for q in range(min(len(a), len(b))) if a[q] != b[q]), min(len(a), len(b)))
+            res["differing"].append((name, n + 1, a[n] if n < len(a) else None, b[n] if n < len(b) else None))
+
+
 def compare(base_text, tree_text):
     """Compare two assembly files.  Returns a dict: kernels (names in either), lines (of tree_text), only_base, only_tree
     (sorted names), differing ([(name, line number inside the kernel from 1, base line, tree line)]; a missing line is
@@ -56,14 +75,61 @@ def compare(base_text, tree_text):
     res["kernels"] = len(set(kb) | set(kt))
     if base_text == tree_text:
         return res
-    res["only_base"] = sorted(set(kb) - set(kt))
-    res["only_tree"] = sorted(set(kt) - set(kb))
-    for name in sorted(set(kb) & set(kt)):
-        a, b = kb[name], kt[name]
-        if a != b:
-            n = next((q for q in range(min(len(a), len(b))) if a[q] != b[q]), min(len(a), len(b)))
-            res["differing"].append((name, n + 1, a[n] if n < len(a) else None, b[n] if n < len(b) else None))
+    by_name(kb, kt, res)
     res["outside"] = not (res["only_base"] or res["only_tree"] or res["differing"])
+    return res
+
+
+def normalise(lines):
+    """a kernel's lines without the function number of its local labels and without `;` comments (lines that held only a
+    comment go)"""
+    out = []
+    for l in lines:
+        l = re.sub(r"\s*;.*$", "", l)
+        l = re.sub(r"\.(LBB|LJTI)\d+_", r".\1_", l)
+        l = re.sub(r"\.(Lfunc_end|Ltmp)\d+", r".\1", l)
+        if l.strip():
+            out.append(l)
+    return out
+
+
+def kernel_metadata(text):
+    """{kernel symbol: the lines of its entry under `amdhsa.kernels:` in the file's metadata}"""
+    lines = text.splitlines()
+    entries, cur = {}, None
+    try:
+        q = lines.index("amdhsa.kernels:") + 1
+    except ValueError:
+        return entries
+    while q < len(lines) and (lines[q].startswith("  ") or not lines[q].strip()):
+        if lines[q].startswith("  - "):
+            cur = []
+        if cur is not None:
+            cur.append(lines[q])
+            m = re.match(r"    \.name:\s+(\S+)", lines[q])
+            if m:
+                entries[m.group(1)] = cur
+        q += 1
+    return entries
+
+
+def compare_units(base_texts, tree_texts):
+    """Compare one source's kernels over all of its units in each tree (lists of assembly files).  compare()'s dict, with
+    `duplicates`: [(which tree, name)] of kernels that two units of one tree hold; `outside` is False, not compared."""
+    res = {"lines": sum(len(t.splitlines()) for t in tree_texts), "only_base": [], "only_tree": [], "differing": [],
+           "outside": False, "duplicates": []}
+    sides = {}
+    for side, texts in (("base", base_texts), ("tree", tree_texts)):
+        ks = sides[side] = {}
+        for t in texts:
+            meta = kernel_metadata(t)
+            for name, body in split_kernels(t)[0].items():
+                if name in ks:
+                    res["duplicates"].append((side, name))
+                ks[name] = normalise(body) + meta.get(name, [])
+    kb, kt = sides["base"], sides["tree"]
+    res["kernels"] = len(set(kb) | set(kt))
+    by_name(kb, kt, res)
     return res
 
 
@@ -76,10 +142,23 @@ def checkout(ref, dst):
         raise RuntimeError("git archive %s failed" % ref)
 
 
+def tree_units(root):
+    """(HIPCC_FLAGS, {source relative to root: [(unit name, its defines)]}) as root's own marl_llm_amd/build.py has them"""
+    spec = importlib.util.spec_from_file_location("build_of_" + re.sub(r"\W", "_", root), os.path.join(root, "marl_llm_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    units = {}
+    if hasattr(mod, "UNITS"):
+        for name, src, defines in mod.UNITS:
+            units.setdefault(os.path.join("marl_llm_amd", "csrc", src), []).append((name, list(defines)))
+    else:
+        for src in mod.SRCS:
+            units[os.path.relpath(src, root)] = [(os.path.splitext(os.path.basename(src))[0], [])]
+    return mod.HIPCC_FLAGS, units
+
+
 def compile_asm(hipcc, flags, root, rel, out):
     """rel (relative to root) -> device assembly `out`; run from the tree's root so that both trees' .file lines agree"""
-    if not os.path.exists(os.path.join(root, rel)):
-        return None
     cmd = [hipcc] + flags + ["-Iinclude", "--cuda-device-only", "-S", rel, "-o", out]
     p = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
     if p.returncode != 0:
@@ -89,44 +168,56 @@ def compile_asm(hipcc, flags, root, rel, out):
 
 
 def main(argv):
-    from marl_llm_amd.build import HIPCC_FLAGS, SRCS, hipcc_path
+    from marl_llm_amd.build import hipcc_path, jobs
     args = [a for a in argv if not a.startswith("-")]
     extra = [a for a in argv if a.startswith("-")]
     if not args or "-h" in extra or "--help" in extra:
         print(__doc__)
         return 2
     base_ref = args[0]
-    rels = [os.path.relpath(os.path.abspath(s), ROOT) for s in args[1:]] or [os.path.relpath(s, ROOT) for s in SRCS]
-    hipcc, flags = hipcc_path(), HIPCC_FLAGS + extra
+    hipcc = hipcc_path()
     tmp = tempfile.mkdtemp(prefix="isa_diff_")
     try:
         base_root, out = os.path.join(tmp, "base"), os.path.join(tmp, "out")
         os.makedirs(base_root)
         os.makedirs(out)
         checkout(base_ref, base_root)
-        jobs = max(1, min(MAX_JOBS, os.cpu_count() or 1))
-        with concurrent.futures.ThreadPoolExecutor(jobs) as pool:
-            # the longest compile (the step kernel, first in SRCS) is started first, for both trees
-            fut = {(side, rel): pool.submit(compile_asm, hipcc, flags, root, rel,
-                                            os.path.join(out, "%s_%d.s" % (side, q)))
-                   for q, rel in enumerate(rels) for side, root in (("base", base_root), ("tree", ROOT))}
-            asm = {k: f.result() for k, f in fut.items()}
+        trees = {"base": (base_root,) + tree_units(base_root), "tree": (ROOT,) + tree_units(ROOT)}
+        rels = [os.path.relpath(os.path.abspath(s), ROOT) for s in args[1:]] or list(trees["tree"][2])
+        with concurrent.futures.ThreadPoolExecutor(jobs()) as pool:
+            # (both build.py list the longest compiles first)
+            fut = {(side, rel): [pool.submit(compile_asm, hipcc, flags + extra + defines, root, rel,
+                                             os.path.join(out, "%s_%s.s" % (side, name)))
+                                 for name, defines in units.get(rel, [])]
+                   for rel in rels for side, (root, flags, units) in trees.items()}
+            asm = {k: [f.result() for f in fs] for k, fs in fut.items()}
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     kernels = lines = differing = 0
     bad = False
     for rel in rels:
         b, t = asm[("base", rel)], asm[("tree", rel)]
-        if b is None and t is None:
+        if not b and not t:
             print("%s: in neither tree" % rel)
             bad = True
             continue
-        r = compare(b or "", t or "")
+        cut_b, cut_t = ([d for _, d in trees[side][2].get(rel, [])] for side in ("base", "tree"))
+        if cut_b == cut_t or not b or not t:
+            # the same units in both trees (or a source that one tree lacks): unit by unit, whole files first
+            rs = [compare(x, y) for x, y in zip(b, t)] if cut_b == cut_t else [compare(x, "") for x in b] + [compare("", y) for y in t]
+            r = {k: sum((q[k] for q in rs), type(rs[0][k])()) for k in rs[0]}
+            print("%s: %s" % (rel, "identical" if b == t else "DIFFERENT"))
+        else:
+            r = compare_units(b, t)
+            same = not (r["only_base"] or r["only_tree"] or r["differing"] or r["duplicates"])
+            print("%s: %d unit(s) in %s, %d in the tree: kernels %s; the text outside the kernels was not compared"
+                  % (rel, len(b), base_ref, len(t), "identical" if same else "DIFFERENT"))
         kernels += r["kernels"]
         lines += r["lines"]
         differing += len(r["differing"])
-        bad = bad or bool(r["only_base"] or r["only_tree"] or r["differing"] or r["outside"])
-        print("%s: %s" % (rel, "identical" if b == t else "DIFFERENT"))
+        bad = bad or bool(r["only_base"] or r["only_tree"] or r["differing"] or r["outside"] or r.get("duplicates"))
+        for side, name in r.get("duplicates", []):
+            print("  in two units of %s: %s" % (base_ref if side == "base" else "the tree", name))
         for name in r["only_base"]:
             print("  only in %s: %s" % (base_ref, name))
         for name in r["only_tree"]:

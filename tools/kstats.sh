@@ -2,13 +2,19 @@
 # Register / scratch / code-size statistics of the k_env instantiations (cross-compiled, no GPU needed).  The headline
 # kernel sits at 80 VGPRs (6 waves per SIMD) and ~58 KB of code (64 KB instruction cache): a change that spills or pushes
 # the code past the cache costs far more than it saves -- check after every kernel edit.
+# The compile commands are marl_llm_amd/build.py's (--cmd UNIT); the six kernel units of the step kernel are compiled side by
+# side, as many at a time as the build allows itself.
 R=$(cd $(dirname $0)/.. && pwd)
 T=$(mktemp -d)
+cd $R
+CMD() { python3 -m marl_llm_amd.build --cmd $1; }
+JOBS=$(python3 -c "from marl_llm_amd.build import jobs; print(jobs())")
 # every k_env instantiation is listed, by its template arguments as the symbol spells them: I Li<NPAD>E <f|d|DF16b = OBS_T>
 # Lb<DO_STEP>E Lb<LAT>E Lb<HALF>E Lb<FILT>E.  USE_ASM=<file>: read a kept assembly (KEEP_ASM) instead of compiling the step kernel.
-S=$T/swarm_env-hip-amdgcn-amd-amdhsa-gfx950.s
+S=$T/swarm_env.s
 if [ -n "$USE_ASM" ]; then cp $USE_ASM $S; else
-cd $T && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -I$R/include --save-temps -c $R/marl_llm_amd/csrc/swarm_env.hip -o $T/o.o 2>/dev/null
+for N in 256 128 64 32 16 8; do mkdir $T/n$N; echo "cd $T/n$N && $(CMD swarm_env_n$N) --save-temps -c -o o.o 2>/dev/null"; done | xargs -P $JOBS -d '\n' -n 1 bash -c
+cat $T/n*/swarm_env-hip-amdgcn-amd-amdhsa-gfx950.s > $S
 fi
 cd $T
 for SYM in $(grep -o "^_ZN12_GLOBAL__N_15k_envI[A-Za-z0-9_]*:" $S | tr -d : | sort); do
@@ -20,7 +26,7 @@ done
 # the large-swarm step kernels (env_large: no scratch, no spill in the pair, cell or filter loops), the env's side kernels, the policy kernel (VGPRs must not move: 218 for the bf16 instantiations), the rollout loop's kernels
 # and the rule expert (no scratch)
 for F in env_large env_kernels policy_mlp rollout rule_expert; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -I$R/include -c $R/marl_llm_amd/csrc/$F.hip -o $T/$F.o \
+  $(cd $R && CMD $F) -c -o $T/$F.o \
       -Rpass-analysis=kernel-resource-usage 2>&1 | sed -n 's/.*remark: *//p' | sed 's/ \[-Rpass-analysis.*//' |
     awk '/^Function Name:/{if (l) print l; l=$3; next} /^(VGPRs|AGPRs|ScratchSize|Occupancy)/{l=l" ; "$0} END{if (l) print l}'
 done
