@@ -28,12 +28,12 @@
  *
  * There is no CPU fallback anywhere in this library: without a HIP device every call fails.
  *
- * Memory contract of the batched ABI: every pointer passed to swarm_step / swarm_observe /
+ * Memory contract of the batched ABI: every pointer passed to swarm_step / swarm_observe / swarm_select_shapes /
  * swarm_get_indices is a DEVICE pointer (hipMalloc / torch.Tensor.data_ptr()) valid on the handle's
  * device.  swarm_set_cells / swarm_set_state / swarm_get_state accept host or device pointers (hipMemcpyDefault).
  *
  * Stream contract (DESIGN.md "Stream contract"; tests/test_gpu_streams.py): all device work goes to the handle's stream
- * (swarm_set_stream; NULL = the default stream).  swarm_step, swarm_observe, swarm_reset, swarm_select_shape, swarm_metrics
+ * (swarm_set_stream; NULL = the default stream).  swarm_step, swarm_observe, swarm_reset, swarm_select_shape(s), swarm_metrics
  * and swarm_rule_action only enqueue: they return without waiting for the stream.  swarm_set_cells, swarm_set_state and the
  * readers swarm_get_state / _get_cells / _get_shape_index / _get_indices / _get_llm_action / _path_envs, swarm_observe_host,
  * swarm_step_host and swarm_synchronize return after the stream has run everything enqueued so far, their own work included
@@ -152,9 +152,37 @@ int  swarm_reset(swarm_env_t *h, uint64_t seed, uint64_t episode, int64_t env_of
  * shape_index instead of -1).  No host synchronisation, no host-to-device copy, no allocation.
  * SWARM_ERR_STATE without a shape set or a state, SWARM_ERR_INVALID for an index outside [0, n_shapes): nothing is enqueued. */
 int  swarm_select_shape(swarm_env_t *h, int32_t shape_index, void *obs);
+/* Per-env device-side shape switch (process_shape per env, eval_assembly.py:34-57, with its rand_angle / rand_target_offset):
+ * each env takes its own shape at its own pose, or keeps what it has.  The agents (p / dp) stay where they are.
+ *   shape_index  DEVICE int32 [E].  s in [0, n_shapes): env e takes shape s of the set uploaded by swarm_set_shapes.  Any other
+ *     value (-1 is the documented "keep"): nothing of env e is written -- its cells, n_g, in-shape cut-off, lattice record and
+ *     shape index stay as they are.  The kernel tests the range before it reads the set: an out-of-range index is a kept env.
+ *   pose  DEVICE double [E][4] = (c, s, off_x, off_y) per env, or NULL.  NULL: the shape's own doubles, the whole row, padding
+ *     included -- with all indices equal the call is bit for bit swarm_select_shape.  Given: cell k < n_g becomes
+ *         x = c*sx + s*sy + off_x,   y = -s*sx + c*sy + off_y
+ *     in IEEE double, in this order, without FMA contraction (swarm_reset's expression; rotate_matrix = [[c, s], [-s, c]],
+ *     assembly.py:177-178,187), cells k >= n_g become 0.0, and a lattice record's frame is moved the same way.  c and s are the
+ *     caller's cos / sin of the angle: the kernel evaluates no trigonometric function, so the cells are reproducible from numpy bit
+ *     for bit.  The contract is this ELEMENTWISE expression, not np.dot: np.dot(R, g) + off goes through BLAS, which contracts,
+ *     and differs from it in the last bit of a good part of the values (so does swarm_reset's transform).  At the reference's
+ *     live setting (angle 0, offset 0) both are the identity.
+ * One kernel on the handle's stream writes, per switched env, both cell layouts, n_g, the in-shape cut-off, the lattice record
+ * and the shape index; then the observation pass runs (obs may be NULL, as in swarm_select_shape).  Afterwards every output of
+ * every later call is bit for bit what it is on a handle that was given those cells through swarm_set_cells + swarm_observe
+ * (swarm_get_shape_index reports the indices instead of -1); a kept env continues exactly as if nothing had been called.
+ *   Enqueue only: no host synchronisation, no allocation, no host-to-device copy.
+ *   Stream order: the two arrays are read when the kernel RUNS, not when the call is made: they must stay valid and hold the
+ *     intended values until then (writes enqueued on the same stream before the call are seen).  Work on other streams that
+ *     writes the arrays is the caller's to order with events.
+ *   Validation first: a NULL handle or a NULL shape_index returns SWARM_ERR_INVALID; no shape set, no state, or cells not set
+ *     for every env (a kept env needs cells) returns SWARM_ERR_STATE; the message starts "swarm_select_shapes:" and nothing is
+ *     enqueued.
+ * The host does not learn which env took what (as after swarm_reset): it plans the cell path for the envs' present cell sets
+ * and every shape of the set together; swarm_path_envs reads the device records and stays exact. */
+int  swarm_select_shapes(swarm_env_t *h, const int32_t *shape_index, const double *pose, void *obs);
 int  swarm_get_state(swarm_env_t *h, double *p, double *dp);
 int  swarm_get_cells(swarm_env_t *h, double *cells, int32_t *n_g);        /* [E][2][n_cells_max], [E]; host or device */
-/* Shape index each env drew in the last swarm_reset (assembly.py:160 `rand_shape_index`) or was given by swarm_select_shape,
+/* Shape index each env drew in the last swarm_reset (assembly.py:160 `rand_shape_index`) or was given by swarm_select_shape(s),
  * [E] host or device; -1 for envs whose cells were set through swarm_set_cells.  The host needs it for l_cell / shape_frequency (assembly.py:161-163). */
 int  swarm_get_shape_index(swarm_env_t *h, int32_t *shape_index);
 

@@ -48,7 +48,8 @@ BATCHED_SYMBOLS = ("swarm_abi_version", "swarm_default_config", "swarm_create", 
                    "swarm_set_stream", "swarm_synchronize", "swarm_obs_dim", "swarm_set_cells", "swarm_set_state",
                    "swarm_get_state", "swarm_observe", "swarm_step", "swarm_get_indices",
                    "swarm_step_algorithmic_bytes", "swarm_timer_start", "swarm_timer_stop", "swarm_lattice_envs", "swarm_set_shapes", "swarm_reset", "swarm_get_cells", "swarm_get_shape_index", "swarm_metrics", "swarm_rule_action",
-                   "swarm_host_outputs", "swarm_observe_host", "swarm_step_host", "swarm_get_llm_action", "swarm_select_shape", "swarm_path_envs")
+                   "swarm_host_outputs", "swarm_observe_host", "swarm_step_host", "swarm_get_llm_action", "swarm_select_shape", "swarm_path_envs",
+                   "swarm_select_shapes")
 POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_destroy", "swarm_policy_forward", "swarm_policy_forward_bf16",
                   "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_forward_explore_logpi",
                   "swarm_policy_set_precision", "swarm_policy_load_device", "swarm_policy_read_packed",
@@ -110,6 +111,7 @@ def load():
     lib.swarm_rollout_eval.argtypes = [vp, vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, vp, ctypes.POINTER(SwarmEvalOut), vp]
     lib.swarm_rollout_eval.restype = i32
     lib.swarm_select_shape.argtypes = [vp, ctypes.c_int32, vp]; lib.swarm_select_shape.restype = i32
+    lib.swarm_select_shapes.argtypes = [vp, vp, vp, vp]; lib.swarm_select_shapes.restype = i32
     lib.swarm_rollout_last_error.argtypes = []; lib.swarm_rollout_last_error.restype = ctypes.c_char_p
     lib.swarm_policy_set_precision.argtypes = [vp, i32]; lib.swarm_policy_set_precision.restype = i32
     lib.swarm_policy_load_device.argtypes = [vp] * 10; lib.swarm_policy_load_device.restype = i32

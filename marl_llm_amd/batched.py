@@ -4,9 +4,10 @@ Device memory, streams and tensors come from PyTorch-ROCm; all compute is in the
 Layouts are the ones documented in include/swarm_env.h.
 
 Streams (DESIGN.md "Stream contract"): every call hands the library torch's current stream first.  step, observe, reset,
-select_shape, metrics and rule_action only enqueue on it; set_cells, set_state, the readers (get_state, get_cells,
-get_shape_index, indices, llm_action, path_envs) and the host path (observe_host, step_host) return after that stream has run
-everything enqueued so far; set_shapes and close() wait for pending work that still reads what they free.
+select_shape, select_shapes (given device tensors), metrics and rule_action only enqueue on it; set_cells, set_state, the
+readers (get_state, get_cells, get_shape_index, indices, llm_action, path_envs) and the host path (observe_host, step_host)
+return after that stream has run everything enqueued so far; set_shapes and close() wait for pending work that still reads
+what they free.
 """
 import ctypes
 
@@ -75,6 +76,8 @@ class SwarmBatch:
         self._flip = 0
         self.n_shapes = 0                # shapes of the uploaded set (set_shapes)
         self.shape_in_force = -1         # the shape every env was switched to (select_shape / rollout_eval), else -1
+        self.shape_env_in_force = None   # host int64 [E]: the shape each env was switched to (-1: not known), None: none known
+        self._posed_env = None           # bool [E]: that env's shape was given a pose (select_shapes)
 
     # -- plumbing -----------------------------------------------------------------------------------
     def _sync_stream(self):
@@ -112,7 +115,7 @@ class SwarmBatch:
         check(self.lib, self.handle, self.lib.swarm_set_cells(self.handle, int(env_begin), count, cptr,
                                                               n_g.ctypes.data_as(ctypes.c_void_p),
                                                               l_cell.ctypes.data_as(ctypes.c_void_p)))
-        self.shape_in_force = -1
+        self.shape_in_force, self.shape_env_in_force, self._posed_env = -1, None, None
 
     def set_shapes(self, results):
         """Upload a shape set (the reference's results.pkl layout: 'grid_coords' list of (n_g, 2), 'l_cell' list)
@@ -145,7 +148,100 @@ class SwarmBatch:
         if out is None:
             self._flip ^= 1
         self.shape_in_force = int(index)
+        self.shape_env_in_force = np.full(self.n_env, int(index), np.int64)
+        self._posed_env = np.zeros(self.n_env, bool)
         return obs
+
+    def _shapes_args(self, index, angle=None, offset=None, pose=None):
+        """The arguments of select_shapes, checked on the host: (index, pose), each a host array (int32 [E] / float64 [E, 4]
+        or None) or the caller's device tensor.  Raises ValueError; touches neither the device nor the library."""
+        E = self.n_env
+        if isinstance(index, torch.Tensor) and index.is_cuda:
+            if index.dtype != torch.int32 or tuple(index.shape) != (E,) or not index.is_contiguous() or index.device != self.device:
+                raise ValueError(f"a device index must be a contiguous int32 tensor [{E}] on {self.device}")
+        else:
+            a = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
+            if a.shape != (E,) or a.dtype.kind not in "iu":
+                raise ValueError(f"index must be an int array [{E}]")
+            if self.n_shapes < 1 or ((a < -1) | (a >= self.n_shapes)).any():
+                raise ValueError(f"host indices must lie in [-1, n_shapes = {self.n_shapes}) (-1: the env keeps its shape)")
+            index = np.ascontiguousarray(a, dtype=np.int32)
+        if pose is not None and (angle is not None or offset is not None):
+            raise ValueError("give either angle / offset or pose, not both")
+        if isinstance(pose, torch.Tensor) and pose.is_cuda:
+            if pose.dtype != torch.float64 or tuple(pose.shape) != (E, 4) or not pose.is_contiguous() or pose.device != self.device:
+                raise ValueError(f"a device pose must be a contiguous float64 tensor [{E}, 4] on {self.device}")
+        elif pose is not None:
+            pose = np.ascontiguousarray(pose.cpu() if isinstance(pose, torch.Tensor) else pose, dtype=np.float64)
+            if pose.shape != (E, 4):
+                raise ValueError(f"pose must be [{E}, 4] = (cos, sin, off_x, off_y)")
+        elif angle is not None or offset is not None:
+            ang = np.zeros(E) if angle is None else np.asarray(angle, dtype=np.float64)
+            off = np.zeros((E, 2)) if offset is None else np.asarray(offset, dtype=np.float64)
+            if ang.shape != (E,) or off.shape != (E, 2):
+                raise ValueError(f"angle must be [{E}] and offset [{E}, 2]")
+            pose = np.ascontiguousarray(np.column_stack([np.cos(ang), np.sin(ang), off]))   # process_shape's matrix entries
+        return index, pose
+
+    def select_shapes(self, index, angle=None, offset=None, pose=None, out=None):
+        """Per-env device-side shape switch (swarm_select_shapes): env e takes shape index[e] of the uploaded set, or keeps
+        what it has (index[e] == -1); the agents stay where they are, and the observation pass runs.
+
+        index: int array-like [E] on the host, or an int32 cuda tensor [E].  Host indices outside [-1, n_shapes) raise
+        ValueError before anything is enqueued; a device tensor is passed through unvalidated, and the kernel treats every
+        value outside [0, n_shapes) as "keep".
+        Pose, per env: none (the set's own pose: the shape's doubles as they are), or angle [E] and / or offset [E, 2] (host
+        float64; the kernel gets (cos(angle), sin(angle), offset), the entries of process_shape's matrix,
+        eval_assembly.py:40-46,55), or pose [E, 4] = (cos, sin, off_x, off_y) as an array or a float64 cuda tensor.  Cell k
+        becomes x = c*sx + s*sy + off_x, y = -s*sx + c*sy + off_y, elementwise in float64 -- not np.dot, whose BLAS
+        contracts (include/swarm_env.h).  Giving pose together with angle / offset raises ValueError.
+        With device tensors the call only enqueues, and the tensors are read when the kernel runs (stream order); host
+        arrays are uploaded first.  Returns the observation tensor, like select_shape."""
+        return self._select_shapes_ready(self._shapes_ready(index, angle, offset, pose), out)
+
+    def _shapes_ready(self, index, angle=None, offset=None, pose=None):
+        """select_shapes' arguments checked (_shapes_args) and on the device (_shapes_upload)."""
+        return self._shapes_upload(*self._shapes_args(index, angle, offset, pose))
+
+    def _shapes_upload(self, index, pose):
+        """_shapes_args' result on the device: (index tensor, pose tensor or None, the host index or None).  rollout_eval
+        checks a whole schedule, then uploads it, before it enqueues anything."""
+        host_index = index if isinstance(index, np.ndarray) else None
+        if host_index is not None:
+            index = torch.from_numpy(host_index).to(self.device)
+        if isinstance(pose, np.ndarray):
+            pose = torch.from_numpy(pose).to(self.device)
+        return index, pose, host_index
+
+    def _select_shapes_ready(self, ready, out=None):
+        """The switch itself, for arguments that are checked and on the device (_shapes_upload's result): enqueue only."""
+        index, pose, host_index = ready
+        if out is not None:
+            obs = self._out_ptrs(dict(obs=out))["obs"].view(self.n_env, self.n_agents, self.obs_dim)
+        else:
+            obs = self._obs[self._flip ^ 1]
+        self._sync_stream()
+        check(self.lib, self.handle, self.lib.swarm_select_shapes(self.handle, _ptr(index), _ptr(pose), _ptr(obs)))
+        if out is None:
+            self._flip ^= 1
+        self._note_shapes(host_index, pose is not None)
+        return obs
+
+    def _note_shapes(self, host_index, posed):
+        """Host bookkeeping of a per-env switch: shape_env_in_force (None: nothing known), which envs hold a posed shape, and
+        shape_in_force (the common shape when every env is known to hold one shape at the set's own pose, else -1)."""
+        if host_index is None:           # a device index: the host does not know who took what
+            self.shape_env_in_force, self._posed_env, self.shape_in_force = None, None, -1
+            return
+        E = self.n_env
+        prev = self.shape_env_in_force if self.shape_env_in_force is not None else np.full(E, -1, np.int64)
+        prev_posed = self._posed_env if self._posed_env is not None else np.zeros(E, bool)
+        took = host_index >= 0
+        s = np.where(took, host_index, prev).astype(np.int64)
+        self._posed_env = np.where(took, posed, prev_posed)
+        self.shape_env_in_force = s if (s >= 0).any() else None
+        plain = bool((s >= 0).all() and (s == s[0]).all() and not self._posed_env.any())
+        self.shape_in_force = int(s[0]) if plain else -1
 
     def reset(self, seed, episode=0, env_offset=0, out=None):
         """Batched device-side reset (swarm_reset): returns the first observation tensor.  out: a caller-owned obs tensor
@@ -157,7 +253,7 @@ class SwarmBatch:
             obs = self._obs[self._flip]
         self._sync_stream()
         check(self.lib, self.handle, self.lib.swarm_reset(self.handle, int(seed), int(episode), int(env_offset), _ptr(obs)))
-        self.shape_in_force = -1         # every env drew its own shape
+        self.shape_in_force, self.shape_env_in_force, self._posed_env = -1, None, None      # every env drew its own shape
         return obs
 
     def get_cells(self):

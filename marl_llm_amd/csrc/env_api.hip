@@ -210,7 +210,7 @@ LatInfo classify_cells(const swarm_env *h, const double *gx, const double *gy, i
 // Choose the cell path for the cell sets [first, last) (envs, or the shapes of the set a reset draws from): are all
 // lattices, does any walk, does any scan, and the largest R / Rc / column count among those that walk.  Returns that
 // summary, which is what it handed to set_lattice_mode.
-LatInfo lattice_mode_of(swarm_env *h, const LatInfo *first, const LatInfo *last)
+LatInfo lattice_summary(const LatInfo *first, const LatInfo *last)
 {
     LatInfo m = {true, false, false, 0.0f, 0.0f, 0};
     for (; first != last; ++first) {
@@ -220,6 +220,12 @@ LatInfo lattice_mode_of(swarm_env *h, const LatInfo *first, const LatInfo *last)
         m.R = std::max(m.R, first->R); m.Rc = std::max(m.Rc, first->Rc);
         m.ncols = std::max(m.ncols, first->ncols);
     }
+    return m;
+}
+
+LatInfo lattice_mode_of(swarm_env *h, const LatInfo *first, const LatInfo *last)
+{
+    const LatInfo m = lattice_summary(first, last);
     set_lattice_mode(h, m.walk, m.scan, m.R, m.Rc, m.ncols);
     return m;
 }
@@ -574,6 +580,28 @@ int swarm_select_shape(swarm_env_t *h, int32_t shape_index, void *obs)
     std::fill(h->env_lat.begin(), h->env_lat.end(), *one);
     h->have_cells = true;
     lattice_mode_of(h, one, one + 1);
+    h->observed = false;
+    return swarm_observe(h, obs);
+}
+
+int swarm_select_shapes(swarm_env_t *h, const int32_t *shape_index, const double *pose, void *obs)
+{
+    if (!h) return SWARM_ERR_INVALID;
+    if (!shape_index) return fail(h, SWARM_ERR_INVALID, "swarm_select_shapes: null shape_index");
+    if (h->n_shapes < 1) return fail(h, SWARM_ERR_STATE, "swarm_select_shapes: no shape set (swarm_set_shapes)");
+    if (!h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_select_shapes: state not set (swarm_set_state / swarm_reset)");
+    if (!h->have_cells) return fail(h, SWARM_ERR_STATE, "swarm_select_shapes: target cells not set for every env (a kept env needs them)");
+    DeviceGuard g(h->device);
+    HIP_LAUNCHED(h, launch_select_shapes(h->stream, shape_set(h), shape_index, pose, h->kp.ng_max, h->cfg.n_env, h->d_cells.get(), h->d_cells_xy.get(),
+                                         h->d_ng.get(), h->d_cin.get(), h->d_lat.get(), h->d_shape_idx.get()));
+    // which env took which shape only the device knows (as after swarm_reset): every env's record becomes what holds for its
+    // present cells AND for any shape of the set; the device records stay exact, and they are what the kernels' filters read
+    const LatInfo set = lattice_summary(h->shape_lat.data(), h->shape_lat.data() + h->shape_lat.size());
+    for (LatInfo &i : h->env_lat) {
+        const LatInfo both[2] = {i, set};
+        i = lattice_summary(both, both + 2);
+    }
+    lattice_mode_of(h, h->env_lat.data(), h->env_lat.data() + h->env_lat.size());
     h->observed = false;
     return swarm_observe(h, obs);
 }

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 #include "swarm_env.h"
@@ -37,6 +38,32 @@ __host__ __device__ inline double reset_u01(unsigned long long key, unsigned k)
     return (double)(mix64(key + 0x9E3779B97F4A7C15ull * (unsigned long long)(k + 1)) >> 11) * (1.0 / 9007199254740992.0);
 }
 
+// Cell c of a shape (shape-frame rows sx, sy; ng cells) at the pose (cs, sn, off): rotate_matrix = [[c, s], [-s, c]] applied to
+// the cell, then the offset (ENV:177-178,187) -- this expression, elementwise, in this order; padding cells (c >= ng) are 0.0.
+// Shared by the reset and the per-env shape switch.
+__device__ __forceinline__ double2 pose_cell(const double *__restrict__ sx, const double *__restrict__ sy, const int c, const int ng,
+                                             const double cs, const double sn, const double offx, const double offy)
+{
+    double2 g; g.x = 0.0; g.y = 0.0;
+    if (c < ng) { g.x = cs * sx[c] + sn * sy[c] + offx; g.y = -sn * sx[c] + cs * sy[c] + offy; }
+    return g;
+}
+
+// The frame of a shape's lattice record (LatEnv's origin and inverse basis; nrows > 0) at that pose: u' = R u, v' = R v,
+// o' = R o + offset.  Rows, masks and radii do not change under a rigid motion.
+__device__ __forceinline__ void pose_lattice(double &ox, double &oy, double &uxi, double &uyi, double &vxi, double &vyi,
+                                             const double cs, const double sn, const double offx, const double offy)
+{
+    // shape-frame basis from the stored inverse basis: u = uxi / |uxi|^2
+    const double iu = 1.0 / (uxi * uxi + uyi * uyi), iv = 1.0 / (vxi * vxi + vyi * vyi);
+    const double ux = uxi * iu, uy = uyi * iu, vx = vxi * iv, vy = vyi * iv;
+    const double rux = cs * ux + sn * uy, ruy = -sn * ux + cs * uy;
+    const double rvx = cs * vx + sn * vy, rvy = -sn * vx + cs * vy;
+    const double rox = cs * ox + sn * oy + offx, roy = -sn * ox + cs * oy + offy;
+    ox = rox; oy = roy;
+    uxi = rux / iu; uyi = ruy / iu; vxi = rvx / iv; vyi = rvy / iv;
+}
+
 __global__ void __launch_bounds__(256)
 k_reset(const KP P, const ShapeSet S, const unsigned long long seed, const unsigned long long episode,
         const long long env_offset, double *cells_out, int *ng_out, double *cin_out, LatEnv *lat_out, int *shape_out)
@@ -54,23 +81,13 @@ k_reset(const KP P, const ShapeSet S, const unsigned long long seed, const unsig
     const double *sx_ = S.cells + (size_t)s * 2 * P.ng_max, *sy_ = sx_ + P.ng_max;
     double *gx = cells_out + (size_t)e * 2 * P.ng_max, *gy = gx + P.ng_max;
     for (int c = tid; c < P.ng_max; c += blockDim.x) {
-        double x = 0.0, y = 0.0;
-        if (c < ng) { x = cs * sx_[c] + sn * sy_[c] + offx; y = -sn * sx_[c] + cs * sy_[c] + offy; }   // ENV:178,187
-        gx[c] = x; gy[c] = y;
+        const double2 g = pose_cell(sx_, sy_, c, ng, cs, sn, offx, offy);
+        gx[c] = g.x; gy[c] = g.y;
     }
     if (tid == 0) {
         ng_out[e] = ng; cin_out[e] = S.c_in[s]; shape_out[e] = s;
         LatEnv L = S.lat[s];
-        if (L.nrows > 0) {          // rotate / shift the shape's lattice: u' = R u, v' = R v, o' = R o + offset
-            // shape-frame basis from the stored inverse basis: u = uxi / |uxi|^2
-            const double iu = 1.0 / (L.uxi * L.uxi + L.uyi * L.uyi), iv = 1.0 / (L.vxi * L.vxi + L.vyi * L.vyi);
-            const double ux = L.uxi * iu, uy = L.uyi * iu, vx = L.vxi * iv, vy = L.vyi * iv;
-            const double rux = cs * ux + sn * uy, ruy = -sn * ux + cs * uy;
-            const double rvx = cs * vx + sn * vy, rvy = -sn * vx + cs * vy;
-            const double rox = cs * L.ox + sn * L.oy + offx, roy = -sn * L.ox + cs * L.oy + offy;
-            L.ox = rox; L.oy = roy;
-            L.uxi = rux / iu; L.uyi = ruy / iu; L.vxi = rvx / iv; L.vyi = rvy / iv;
-        }
+        if (L.nrows > 0) pose_lattice(L.ox, L.oy, L.uxi, L.uyi, L.vxi, L.vyi, cs, sn, offx, offy);
         lat_out[e] = L;
     }
     // agents (ENV:202-215)
@@ -371,6 +388,50 @@ k_select_shape(const ShapeSet S, const int s, const int ng_max, double *__restri
     if (c == 0) { ng_out[e] = S.n_g[s]; cin_out[e] = S.c_in[s]; shape_out[e] = s; lat_out[e] = S.lat[s]; }
 }
 
+// The per-env shape switch (swarm_select_shapes; eval_assembly.py:34-57 process_shape with its rand_angle / rand_target_offset):
+// env e takes shape shape_index[e] of the uploaded set -- at the set's own pose (pose == NULL: the whole row, the same doubles,
+// padding included, as k_select_shape) or at pose[e] = (c, s, off_x, off_y) (k_reset's transform of cells and lattice frame;
+// no trigonometric function is evaluated here).  An index outside [0, n_shapes) keeps the env: the range is tested before the
+// set is read, and nothing of that env is written.  p / dp are not touched.
+constexpr int kLatWords = (int)(sizeof(LatEnv) / 8), kLatFrameWords = 6;      // LatEnv in 8-byte words; ox .. vyi come first
+static_assert(sizeof(LatEnv) % 8 == 0 && kLatWords <= 256 && offsetof(LatEnv, vyi) == 8 * (kLatFrameWords - 1) &&
+              offsetof(LatEnv, nrows) >= 8 * kLatFrameWords, "k_select_shapes copies LatEnv by words behind its six frame doubles");
+
+__global__ void __launch_bounds__(256)
+k_select_shapes(const ShapeSet S, const int *__restrict__ shape_index, const double *__restrict__ pose, const int ng_max,
+                double *__restrict__ cells_out, double2 *__restrict__ cells_xy, int *__restrict__ ng_out,
+                double *__restrict__ cin_out, LatEnv *__restrict__ lat_out, int *__restrict__ shape_out)
+{
+    const int e = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;         // grid (ceil(ng_max / 256), n_env)
+    const int s = shape_index[e];
+    if (s < 0 || s >= S.n_shapes) return;                                 // keep
+    const double *sx = S.cells + (size_t)s * 2 * ng_max, *sy = sx + ng_max;
+    double cs = 1.0, sn = 0.0, offx = 0.0, offy = 0.0;
+    if (pose != nullptr) { cs = pose[4 * (size_t)e]; sn = pose[4 * (size_t)e + 1]; offx = pose[4 * (size_t)e + 2]; offy = pose[4 * (size_t)e + 3]; }
+    if (c < ng_max) {
+        double2 g;
+        if (pose != nullptr) g = pose_cell(sx, sy, c, S.n_g[s], cs, sn, offx, offy);
+        else { g.x = sx[c]; g.y = sy[c]; }
+        cells_out[(size_t)e * 2 * ng_max + c] = g.x; cells_out[(size_t)e * 2 * ng_max + ng_max + c] = g.y;
+        cells_xy[(size_t)e * ng_max + c] = g;
+    }
+    if (blockIdx.x != 0) return;
+    // the lattice record: one word per thread; with a pose thread 0 writes the frame of a record that has one
+    const LatEnv *src = S.lat + s;
+    const bool framed = pose != nullptr && src->nrows > 0;
+    if (c < kLatWords && !(framed && c < kLatFrameWords))
+        reinterpret_cast<unsigned long long *>(lat_out + e)[c] = reinterpret_cast<const unsigned long long *>(src)[c];
+    if (c == 0) {
+        ng_out[e] = S.n_g[s]; cin_out[e] = S.c_in[s]; shape_out[e] = s;
+        if (framed) {
+            double ox = src->ox, oy = src->oy, uxi = src->uxi, uyi = src->uyi, vxi = src->vxi, vyi = src->vyi;
+            pose_lattice(ox, oy, uxi, uyi, vxi, vyi, cs, sn, offx, offy);
+            LatEnv *dst = lat_out + e;
+            dst->ox = ox; dst->oy = oy; dst->uxi = uxi; dst->uyi = uyi; dst->vxi = vxi; dst->vyi = vyi;
+        }
+    }
+}
+
 // -------------------------------------------------------------------------------------------------
 // The reference-shaped host outputs ("a single host-side gather of obs / reward"): the step
 // leaves obs [E][N][D], reward [E][N], done [E][N], a_prior [E][N][2] on the device; the numpy API of
@@ -439,6 +500,14 @@ hipError_t launch_select_shape(hipStream_t st, const ShapeSet &S, int s, int ng_
 {
     hipLaunchKernelGGL(k_select_shape, dim3((unsigned)((ng_max + 255) / 256), (unsigned)n_env), dim3(256), 0, st, S, s, ng_max,
                        cells, cells_xy, n_g, c_in, lat, shape_idx);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_shapes(hipStream_t st, const ShapeSet &S, const int *shape_index, const double *pose, int ng_max, int n_env,
+                                double *cells, double2 *cells_xy, int *n_g, double *c_in, LatEnv *lat, int *shape_idx)
+{
+    hipLaunchKernelGGL(k_select_shapes, dim3((unsigned)((ng_max + 255) / 256), (unsigned)n_env), dim3(256), 0, st, S, shape_index, pose,
+                       ng_max, cells, cells_xy, n_g, c_in, lat, shape_idx);
     return hipGetLastError();
 }
 

@@ -248,6 +248,9 @@ hipError_t launch_reset(hipStream_t st, const KP &kp, const ShapeSet &S, unsigne
                         long long env_offset, double *cells, int *n_g, double *c_in, LatEnv *lat, int *shape_idx);
 hipError_t launch_select_shape(hipStream_t st, const ShapeSet &S, int s, int ng_max, int n_env, double *cells, double2 *cells_xy,
                                int *n_g, double *c_in, LatEnv *lat, int *shape_idx);
+// shape_index [E] and pose [E][4] (or NULL) are device arrays, read when the kernel runs
+hipError_t launch_select_shapes(hipStream_t st, const ShapeSet &S, const int *shape_index, const double *pose, int ng_max, int n_env,
+                                double *cells, double2 *cells_xy, int *n_g, double *c_in, LatEnv *lat, int *shape_idx);
 hipError_t launch_interleave(hipStream_t st, const double *cells, double2 *cells_xy, int ng_max, int e0, int count);
 hipError_t launch_metrics(hipStream_t st, const KP &kp, double *out);
 hipError_t launch_metrics_step(hipStream_t st, const KP &kp, int n_cu, double *out);

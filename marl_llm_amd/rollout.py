@@ -668,30 +668,54 @@ class EvalTrace:
     voronoi_based_uniformity of the state BEFORE step t against the cells in force at step t), p / dp [steps, E, 2, N]
     float64 (that state) or None, reward_stats [steps, 2] float64 or None -- device tensors, valid once the stream has run --
     and shape [steps], a host int array: the shape index every env was switched to and that is in force at step t, or -1
-    while no switch has happened (cells set by hand, or drawn per env by a reset)."""
+    while no switch has happened (cells set by hand, or drawn per env by a reset) and at steps where the envs differ (per-env
+    switches).  shape_env [steps, E], a host int array: the shape env e was switched to and holds at step t, -1 where that is
+    not known; None if a per-env entry's index was a device tensor."""
 
-    def __init__(self, metrics, p=None, dp=None, reward_stats=None, shape=None):
+    def __init__(self, metrics, p=None, dp=None, reward_stats=None, shape=None, shape_env=None):
         self.metrics, self.p, self.dp, self.reward_stats = metrics, p, dp, reward_stats
         self.shape = np.full(len(metrics), -1, np.int64) if shape is None else np.asarray(shape, dtype=np.int64)
+        self.shape_env = None if shape_env is None else np.asarray(shape_env, dtype=np.int64)
 
 
-def _switch_schedule(switch, steps):
-    """switch= of rollout_eval as the int32 [steps] array swarm_rollout_eval takes (-1 = keep), or None without a switch:
-    a {step: shape_index} dict, or a sequence of length `steps` (-1 / None = keep)."""
+def _per_env_entry(sh):
+    """An entry of switch= that names a shape per env: a dict of select_shapes' arguments, or an array-like / tensor [E]."""
+    return isinstance(sh, dict) or (sh is not None and (isinstance(sh, torch.Tensor) and sh.dim() > 0 or
+                                                        not isinstance(sh, torch.Tensor) and np.ndim(sh) > 0))
+
+
+def _switch_schedule(switch, steps, per_env=None):
+    """switch= of rollout_eval as the int32 [steps] array swarm_rollout_eval takes (-1 = keep), or None without a batch-wide
+    switch: a {step: shape_index} dict, or a sequence of length `steps` (-1 / None = keep).  per_env: a dict that receives
+    the per-env entries as {step: dict of select_shapes' arguments} (an array entry becomes {"index": array}); without it
+    such an entry is a ValueError."""
     if switch is None:
         return None
     sched = np.full(steps, -1, np.int32)
+
+    def entry(t, sh, keep_ok):
+        if _per_env_entry(sh):
+            if per_env is None:
+                raise ValueError("switch: a per-env entry at step %d where only shape indices are taken" % t)
+            kw = dict(sh) if isinstance(sh, dict) else {"index": sh}
+            if "index" not in kw or set(kw) - {"index", "angle", "offset", "pose"}:
+                raise ValueError("switch: a per-env entry takes index and angle / offset / pose, got %r" % sorted(kw))
+            per_env[t] = kw
+        else:
+            sched[t] = _shape_entry(sh, keep_ok)
+
     if isinstance(switch, dict):
         for t, sh in switch.items():
             if int(t) != t or not 0 <= int(t) < steps:
                 raise ValueError("switch: step %r outside [0, %d)" % (t, steps))
-            sched[int(t)] = _shape_entry(sh)
+            entry(int(t), sh, False)
     else:
         seq = list(switch)
         if len(seq) != steps:
             raise ValueError("switch: a sequence must have one entry per step (%d), got %d" % (steps, len(seq)))
         for t, sh in enumerate(seq):
-            sched[t] = -1 if sh is None else _shape_entry(sh, keep_ok=True)
+            if sh is not None:
+                entry(t, sh, True)
     return sched if (sched >= 0).any() else None
 
 
@@ -710,11 +734,16 @@ def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=N
 
     env / policy / replay / obs / reset : exactly as rollout_device (the ring records the evaluation transitions; the
              private two-slot ring is enough for evaluation).
-    switch : {step: shape_index} or a sequence of length `steps` (-1 / None = keep): at that step every env takes that shape
-             of the uploaded set (SwarmBatch.set_shapes) at the set's own pose, before the step's metrics -- process_shape of
-             eval_assembly.py:34-57.  The actor at a switch step still sees the observation the previous step returned
-             (computed against the old shape), as the reference's does.  Needs a SwarmBatch; ValueError with an
-             AssemblySwarmEnv (assign its grid_center / n_g / l_cell between calls instead).
+    switch : {step: entry} or a sequence of length `steps` (-1 / None = keep).  An int entry: at that step every env takes
+             that shape of the uploaded set (SwarmBatch.set_shapes) at the set's own pose, before the step's metrics --
+             process_shape of eval_assembly.py:34-57.  A per-env entry -- an int array-like / tensor [E], or a dict with
+             select_shapes' keys (index, angle, offset, pose) -- gives every env its own shape and pose, or lets it keep what
+             it has (SwarmBatch.select_shapes).  The actor at a switch step still sees the observation the previous step
+             returned (computed against the old shape), as the reference's does.  A schedule of ints is one library call; one
+             with per-env entries is split at those steps -- select_shapes, then swarm_rollout_eval for the stretch up to the
+             next -- with the same results as the eager loop, bit for bit.  Every host array of the schedule is checked and
+             uploaded before the first stretch is enqueued.  Needs a SwarmBatch; ValueError with an AssemblySwarmEnv (assign
+             its grid_center / n_g / l_cell between calls instead).
     trace_state : also record p / dp before every step.
     Returns (obs [E,N,D] -- the ring slot of the last next_obs --, EvalTrace).  On error nothing is enqueued, the ring and
     the env are unchanged, and SwarmError / ValueError raises."""
@@ -732,39 +761,52 @@ def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=N
     steps = int(steps)
     if steps < 0:
         raise ValueError("steps must be >= 0")
-    sched = _switch_schedule(switch, steps)
-    if sched is not None:
+    per_env = {}
+    sched = _switch_schedule(switch, steps, per_env)
+    if sched is not None or per_env:
         if sb.n_shapes < 1:
             raise _lib.SwarmError("rollout_eval: switch= needs a shape set (SwarmBatch.set_shapes)")
-        if int(sched.max()) >= sb.n_shapes:
+        if sched is not None and int(sched.max()) >= sb.n_shapes:
             raise ValueError("switch: shape index %d outside [0, %d)" % (int(sched.max()), sb.n_shapes))
+    checked = {t: sb._shapes_args(**kw) for t, kw in sorted(per_env.items())}     # every entry, before any upload
     E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
     replay = _device_ring(sb, replay)
     lib = _lib.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
 
-    def call(k, sw, out):
+    def call(k, sw, out, done=0):
         ring = _ring_struct(sb, replay)
+        ring.cur = (replay.cur + done) % replay.S         # the stretch behind `done` steps of this call
         rc = lib.swarm_rollout_eval(sb.handle, policy.handle, ctypes.byref(ring), k,
                                     sw.ctypes.data_as(ctypes.c_void_p) if sw is not None else None,
                                     ctypes.byref(out) if out is not None else None, stream)
         _check_rollout(lib, rc, k, reset)
 
     _begin_chain(sb, replay, obs, reset, lambda: call(0, None, None), "rollout_eval")
+    ready = {t: sb._shapes_upload(*args) for t, args in checked.items()}          # uploads: before the first stretch
     f64 = dict(dtype=torch.float64, device=sb.device)
     metrics = torch.empty((steps, E, 3), **f64)
     p = torch.empty((steps, E, 2, N), **f64) if trace_state else None
     dp = torch.empty((steps, E, 2, N), **f64) if trace_state else None
     stats = torch.empty((steps, 2), **f64) if track_reward else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    call(steps, sched, _lib.SwarmEvalOut(ptr(metrics), ptr(p), ptr(dp), ptr(stats)))
-    shape = np.full(steps, sb.shape_in_force, np.int64)
-    if sched is not None:
-        for t in np.nonzero(sched >= 0)[0]:
-            shape[t:] = sched[t]
-        sb.shape_in_force = int(shape[-1])
+    ptr = lambda t, a: t[a:].data_ptr() if t is not None else None
+    shape, shape_env = np.full(steps, -1, np.int64), np.full((steps, E), -1, np.int64)
+    cuts = sorted(set(ready) | {0, steps})
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        if a in ready:
+            sb._select_shapes_ready(ready[a])             # out=None: the ring slot the actor reads is not rewritten
+        for t in range(a, b):
+            if sched is not None and sched[t] >= 0:       # the library's own switch at step t: select_shape's bookkeeping
+                sb._note_shapes(np.full(E, sched[t], np.int32), False)
+            shape[t] = sb.shape_in_force
+            if sb.shape_env_in_force is not None:
+                shape_env[t] = sb.shape_env_in_force
+        call(b - a, np.ascontiguousarray(sched[a:b]) if sched is not None else None,
+             _lib.SwarmEvalOut(ptr(metrics, a), ptr(p, a), ptr(dp, a), ptr(stats, a)), done=a)
+    if any(host is None for _, _, host in ready.values()):
+        shape_env = None                                  # a device index: who took what is not known on the host
     _finish_chain(aenv, replay, steps)
-    return replay.obs[replay.cur].view(E, N, D), EvalTrace(metrics, p, dp, stats, shape)
+    return replay.obs[replay.cur].view(E, N, D), EvalTrace(metrics, p, dp, stats, shape, shape_env)
 
 
 def _host_array(x):
@@ -777,7 +819,8 @@ def save_eval_results(trace, file_dir, env=0):
 
     metrics.pkl      : the reference's list, one dict per step: coverage_rate, uniformity_degree, voronoi_uniformity (floats),
                        et_index, shape_count.  The reference logs shape_count after its increment, so shape_count = the
-                       shape index in force + 1 (0 while no switch has happened).
+                       shape index in force + 1 (0 while no switch has happened); with per-env switches (trace.shape_env) it is
+                       env `env`'s own shape.
     state_data.npz   : pos, vel [2, N, T] float64 and t_step = T - 1 (the reference saves its loop variable).  Needs a trace
                        recorded with trace_state=True (ValueError otherwise, before anything is written).
     metrics_batch.npz: what the batch adds -- mean, std [T, 3] over the envs, NaN-aware (distribution_uniformity is 0/0 when
@@ -799,13 +842,16 @@ def save_eval_results(trace, file_dir, env=0):
     shape = np.asarray(trace.shape).reshape(-1)
     if shape.shape[0] != T:
         raise ValueError("trace.shape must have one entry per step")
+    shape_env = getattr(trace, "shape_env", None)          # per-env switches: env e's own shape
+    if shape_env is not None and np.shape(shape_env) != (T, E):
+        raise ValueError("trace.shape_env must be [steps, E]")
     p, dp = _host_array(trace.p), _host_array(trace.dp)
     os.makedirs(file_dir, exist_ok=True)
     rows = []
     for t in range(T):
         d = {k: float(m[t, e, j]) for j, k in enumerate(METRIC_KEYS)}
         d["et_index"] = t
-        d["shape_count"] = int(shape[t]) + 1
+        d["shape_count"] = int(shape_env[t, e] if shape_env is not None else shape[t]) + 1
         rows.append(d)
     paths = [os.path.join(file_dir, f) for f in ("metrics.pkl", "state_data.npz", "metrics_batch.npz")]
     with open(paths[0], "wb") as f:
@@ -817,3 +863,39 @@ def save_eval_results(trace, file_dir, env=0):
         mean, std = np.nanmean(m, axis=1), np.nanstd(m, axis=1)
     np.savez(paths[2], mean=mean, std=std, nan_count=np.isnan(m).sum(axis=1), metrics=m)
     return tuple(paths)
+
+
+def save_eval_by_shape(trace, file_dir, n_shapes):
+    """Write metrics_by_shape.npz for a trace of per-env shapes (rollout_eval with per-env switch entries, or any trace whose
+    shape_env is set) and return its path: mean, std [T, S, 3] of the three metrics over the envs that hold shape s at step t,
+    NaN-aware exactly as metrics_batch.npz (a NaN metric of an env is left out; all NaN stays NaN), and count [T, S], the
+    number of those envs.  A shape nobody holds at a step has count 0 and NaN mean / std.  Envs whose shape is not known
+    (-1) are in no group.  Waits for the GPU (it reads the trace back)."""
+    import os
+    import warnings
+    shape_env = getattr(trace, "shape_env", None)
+    if shape_env is None:
+        raise ValueError("save_eval_by_shape: the trace has no shape_env (a per-env entry's index was a device tensor)")
+    m = _host_array(trace.metrics).astype(np.float64, copy=False)
+    if m.ndim != 3 or m.shape[2] != 3:
+        raise ValueError("trace.metrics must be [steps, E, 3]")
+    T, E, _ = m.shape
+    shape_env = np.asarray(shape_env)
+    if shape_env.shape != (T, E):
+        raise ValueError("trace.shape_env must be [steps, E]")
+    S = int(n_shapes)
+    if S < 1:
+        raise ValueError("n_shapes must be >= 1")
+    mean, std = np.full((T, S, 3), np.nan), np.full((T, S, 3), np.nan)
+    count = np.zeros((T, S), np.int64)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)            # all-NaN groups: the mean / std stay NaN
+        for s in range(S):
+            held = shape_env == s
+            count[:, s] = held.sum(axis=1)
+            for t in np.nonzero(count[:, s])[0]:
+                mean[t, s], std[t, s] = np.nanmean(m[t, held[t]], axis=0), np.nanstd(m[t, held[t]], axis=0)
+    os.makedirs(file_dir, exist_ok=True)
+    path = os.path.join(file_dir, "metrics_by_shape.npz")
+    np.savez(path, mean=mean, std=std, count=count)
+    return path

@@ -8,14 +8,17 @@ of every path and on the assembled state the warm-up leaves, alternating `--reps
   b  device     rollout_device(noise_scale=0): the loop without evaluation
   c  eval       rollout_eval with metrics
   d  eval+trace rollout_eval with metrics and the state trace
-  e  switch     one shape switch: SwarmBatch.select_shape against the eager set_cells + observe (host upload + synchronise)
+  e  switch     one shape switch: SwarmBatch.select_shape against the eager set_cells + observe (host upload + synchronise);
+                switch_shapes / switch_shapes_pose: the per-env switch, SwarmBatch.select_shapes with device tensors (every env
+                the next shape of the set; without a pose, and at a per-env rotation and offset)
 
 No path records reward statistics (track_reward=False in b, c, d).  (a) is what a user of the eager entry points runs: its
 get_state() copies the state and synchronises every step, so (a) includes the host-bound gaps that (c) and (d) do not have.
 
 --config 64x4096 restricts the run to one size and --paths eager,eval to some paths: under
 `rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --config 64x4096 --paths eager,eval` the kernel statistics
-then hold k_metrics (launched by a) and k_metrics_step (launched by c) on the same trajectory at one size.
+then hold k_metrics (launched by a) and k_metrics_step (launched by c) on the same trajectory at one size.  --fig-shapes runs
+on the reference's seven fig/*.png shapes (tests/golden/fig_cells.npz) instead of the synthetic set.
 
 Output: a table, and one JSON line per config."""
 import argparse
@@ -75,6 +78,16 @@ def measure(n_a, E, steps, reps, shapes, module, paths=None):
             sb.set_cells(np.repeat(cells[s][None], E, 0), np.full(E, grids[s].shape[1], np.int32), np.full(E, shapes["l_cell"][s]))
             sb.observe()
 
+    rng = np.random.default_rng(226)
+    ang = rng.uniform(-np.pi, np.pi, E)
+    pose = torch.from_numpy(np.column_stack([np.cos(ang), np.sin(ang), rng.uniform(-1, 1, (E, 2))])).to(sb.device)
+    index = [torch.full((E,), s, dtype=torch.int32, device=sb.device) for s in range(len(grids))]
+
+    def switch_shapes(k, pose=None):
+        for _ in range(k):
+            state["shape"] = (state["shape"] + 1) % len(grids)
+            sb.select_shapes(index[state["shape"]], pose=pose)
+
     def timed(fn, k):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
@@ -86,7 +99,8 @@ def measure(n_a, E, steps, reps, shapes, module, paths=None):
 
     k_sw = 4
     cases = [("eager", eager, steps), ("device", device, steps), ("eval", evaluate, steps),
-             ("eval_trace", lambda k: evaluate(k, True), steps), ("switch_device", switch_device, k_sw), ("switch_eager", switch_eager, k_sw)]
+             ("eval_trace", lambda k: evaluate(k, True), steps), ("switch_device", switch_device, k_sw), ("switch_eager", switch_eager, k_sw),
+             ("switch_shapes", switch_shapes, k_sw), ("switch_shapes_pose", lambda k: switch_shapes(k, pose), k_sw)]
     if paths:
         cases = [c for c in cases if c[0] in paths]
     for _, fn, k in cases:                                       # warm-up: code objects, allocator, LDS attributes; the swarm assembles
@@ -112,15 +126,21 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--config", default=None, help="one size only, AGENTSxENVS (e.g. 64x4096)")
-    ap.add_argument("--paths", default=None, help="comma-separated subset of eager,device,eval,eval_trace,switch_device,switch_eager")
+    ap.add_argument("--paths", default=None, help="comma-separated subset of eager,device,eval,eval_trace,switch_device,switch_eager,"
+                                                 "switch_shapes,switch_shapes_pose")
+    ap.add_argument("--fig-shapes", action="store_true", help="the reference's fig/*.png shapes instead of the synthetic set")
     ap.add_argument("--out", default=None, help="also write the table and the JSON lines to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench: no HIP device (this is a GPU measurement)")
-    shapes = synthetic_shape_set()
+    if args.fig_shapes:
+        from marl_llm_amd.shape_images import unpack_cells_npz
+        shapes = unpack_cells_npz(os.path.join(ROOT, "tests", "golden", "fig_cells.npz"))
+    else:
+        shapes = synthetic_shape_set()
     torch.manual_seed(0)
     module = PolicyMLP(192, 2, 180).cuda()
-    names = ("eager", "device", "eval", "eval_trace", "switch_device", "switch_eager")
+    names = ("eager", "device", "eval", "eval_trace", "switch_device", "switch_eager", "switch_shapes", "switch_shapes_pose")
     paths = args.paths.split(",") if args.paths else None
     if paths:
         if set(paths) - set(names):

@@ -5,6 +5,10 @@ state_data.npz for one env plus metrics_batch.npz (mean / std of the three metri
 
   python tools/eval_device.py --random-actor --envs 64 --episode_length 300 --switch 0:0,150:1
   python tools/eval_device.py --model models/run/model.pt --results_file results.pkl --switch 0:4,300:5 --episode_length 600
+  python tools/eval_device.py --random-actor --envs 70 --all-shapes
+
+--all-shapes evaluates the actor on every shape of the set in one batch: env e takes shape e % S at step 0 (a per-env switch,
+SwarmBatch.select_shapes), the final per-shape table is printed and save_eval_by_shape writes metrics_by_shape.npz.
 
 --model reads the actor's fc1..fc4 tensors from a MADDPG checkpoint (torch.save of {'init_dict', 'agent_params': [{'policy':
 state_dict, ...}]}; a bare state dict works too) into a PolicyMLP.  The file is read with torch.load(weights_only=True): tensors
@@ -19,7 +23,7 @@ import numpy as np
 import torch
 
 from marl_llm_amd.batched import SwarmBatch
-from marl_llm_amd.rollout import FusedPolicy, PolicyMLP, rollout_eval, save_eval_results
+from marl_llm_amd.rollout import FusedPolicy, PolicyMLP, rollout_eval, save_eval_by_shape, save_eval_results
 from marl_llm_amd.shapes import load_results, r_avoid_for, synthetic_shape_set
 
 FC = ("fc1", "fc2", "fc3", "fc4")
@@ -32,6 +36,19 @@ def parse_switch(text):
         t, s = item.split(":")
         sched[int(t)] = int(s)
     return sched
+
+
+def all_shapes_switch(n_env, n_shapes):
+    """The schedule of --all-shapes: at step 0 env e takes shape e % S."""
+    return {0: np.arange(n_env) % n_shapes}
+
+
+def by_shape_table(mean, count):
+    """The per-shape table of one step: mean [S, 3], count [S] of metrics_by_shape.npz."""
+    lines = ["shape | envs | coverage | distribution uniformity | voronoi uniformity"]
+    for s in range(len(count)):
+        lines.append("%5d | %4d | %8.4f | %23.4f | %18.4f" % (s, count[s], mean[s, 0], mean[s, 1], mean[s, 2]))
+    return "\n".join(lines)
 
 
 def actor_state(ckpt):
@@ -65,6 +82,7 @@ def main():
     ap.add_argument("--envs", type=int, default=64)
     ap.add_argument("--episode_length", type=int, default=300)
     ap.add_argument("--switch", default="0:0", help="step:shape pairs, e.g. 0:4,300:5")
+    ap.add_argument("--all-shapes", action="store_true", help="env e takes shape e %% S at step 0 (instead of --switch)")
     ap.add_argument("--model", default=None, help="MADDPG checkpoint (model.pt)")
     ap.add_argument("--random-actor", action="store_true", help="a randomly initialised actor instead of --model")
     ap.add_argument("--precision", default="bf16x3", choices=("bf16", "bf16x3"),
@@ -88,9 +106,14 @@ def main():
     else:
         module = load_actor(args.model)
     policy = FusedPolicy(module.to(sb.device), device=sb.device, precision=args.precision)
-    _, trace = rollout_eval(sb, policy, args.episode_length, reset=(args.seed, 0, 0), switch=parse_switch(args.switch),
-                            trace_state=True)
+    S = len(shapes["l_cell"])
+    switch = all_shapes_switch(args.envs, S) if args.all_shapes else parse_switch(args.switch)
+    _, trace = rollout_eval(sb, policy, args.episode_length, reset=(args.seed, 0, 0), switch=switch, trace_state=True)
     paths = save_eval_results(trace, args.out, env=args.env)
+    if args.all_shapes:
+        paths += (save_eval_by_shape(trace, args.out, S),)
+        with np.load(paths[-1]) as z:
+            print(by_shape_table(z["mean"][-1], z["count"][-1]))
     m = trace.metrics[-1].cpu().numpy()
     with np.errstate(all="ignore"):
         print("last step over %d envs: coverage %.4f, distribution uniformity %.4f, voronoi uniformity %.4f | mean reward %.4f"
