@@ -1342,10 +1342,16 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             FENCE();
             const int Gp = P.g_max;
             const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = T >> 6;
+            // PIPE: the lattice kernels of 64 agents write their rows as a pipeline (below); every other instantiation keeps
+            // the pass-by-pass loop and its register allocation (profiles/r14/kstats.txt).  There the wave's row slots in its
+            // permutation are addressed by scalars: pw is the same bytes through a per-lane pointer that would have to stay in
+            // a register from the ranking on.
+            constexpr bool PIPE = NPAD == 64 && !HALF;
+            const unsigned char *pws = !own ? pw : (PIPE ? perm + wv * 64 : pw) + (64 - ACTW) + sx * AGW;
             // row slot k of this wave -> agent thread tr, environment in the workgroup elr, output row r, "row exists"
             auto locate = [&](int k, int &tr, int &elr, int &r) -> bool {
                 if (own) {
-                    const int ta = (at & ~63) + pw[(64 - ACTW) + sx * AGW + k];
+                    const int ta = (at & ~63) + pws[k];
                     const int ii = NPAD < 64 ? (ta & 63) % NPAD : ta;
                     elr = NPAD < 64 ? (ta & 63) / NPAD : 0;
                     tr = ta; r = elr * n_a + ii;
@@ -1363,39 +1369,140 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
                 // consecutive addresses -- half the store instructions of the pair-per-lane form.  A row has 40 two-slot
                 // chunks; 8 rows = 320 chunks = 5 full passes.
                 typedef OT OT4 __attribute__((ext_vector_type(4)));
-                const int ngrp = own ? AGW / 8 : (rows + nwv * 8 - 1) / (nwv * 8);
-                for (int g8 = 0; g8 < ngrp; ++g8) {
+                if (!own || !PIPE) {
+                    // pass by pass.  Generic path: the waves deal the groups of eight rows (the staged form below put a thousand
+                    // more scalar spill reloads into the generic step kernels, which sit at their SGPR limit: DESIGN section 5, v53)
+                    const int ngrp = own ? AGW / 8 : (rows + nwv * 8 - 1) / (nwv * 8);
+                    for (int g8 = 0; g8 < ngrp; ++g8) {
 #pragma unroll
-                    for (int ps = 0; ps < 5; ++ps) {
-                        const int ch = ps * 64 + lane;                   // 0..319
-                        const int rl = (ch * 205) >> 13;                 // ch / 40 (exact for ch < 320)
-                        const int m = ch - rl * 40;
-                        // straight-line: both gathers of every pass are issued unconditionally (an empty slot reads cell 0
-                        // and stores zeros), so the five passes' loads are in flight together instead of one wait each
-                        int tr, elr, r;
-                        const bool ok = locate(own ? g8 * 8 + rl : (wv + g8 * nwv) * 8 + rl, tr, elr, r);
-                        const double2 *gr = P.cells_xy + (size_t)(blockIdx.x * EPB + elr) * P.ng_max;
-                        const double qx = sp[tr], qy = sp[AG + tr];
-                        const int cc = *reinterpret_cast<const int *>(sidx + (size_t)tr * P.g_stride + 2 * m);
-                        const int c0 = (int)(short)(cc & 0xFFFF), c1 = cc >> 16;
-                        const double2 g0 = gr[c0 < 0 ? 0 : c0], g1 = gr[c1 < 0 ? 0 : c1];
-                        const OT z = to_out<OT>(0.0);
-                        const OT a0 = to_out<OT>(g0.x - qx), b0 = to_out<OT>(g0.y - qy);
-                        const OT a1 = to_out<OT>(g1.x - qx), b1 = to_out<OT>(g1.y - qy);
-                        OT4 o = {c0 >= 0 ? a0 : z, c0 >= 0 ? b0 : z, c1 >= 0 ? a1 : z, c1 >= 0 ? b1 : z};
-                        if (ok) __builtin_nontemporal_store(o, reinterpret_cast<OT4 *>(out + (size_t)r * PPR + HP + 2 * m));
+                        for (int ps = 0; ps < 5; ++ps) {
+                            const int ch = ps * 64 + lane;               // 0..319
+                            const int rl = (ch * 205) >> 13;             // ch / 40 (exact for ch < 320)
+                            const int m = ch - rl * 40;
+                            int tr, elr, r;
+                            const bool ok = locate(own ? g8 * 8 + rl : (wv + g8 * nwv) * 8 + rl, tr, elr, r);
+                            const double2 *gr = P.cells_xy + (size_t)(blockIdx.x * EPB + elr) * P.ng_max;
+                            const double qx = sp[tr], qy = sp[AG + tr];
+                            const int cc = *reinterpret_cast<const int *>(sidx + (size_t)tr * P.g_stride + 2 * m);
+                            const int c0 = (int)(short)(cc & 0xFFFF), c1 = cc >> 16;
+                            const double2 g0 = gr[c0 < 0 ? 0 : c0], g1 = gr[c1 < 0 ? 0 : c1];
+                            const OT z = to_out<OT>(0.0);
+                            const OT a0 = to_out<OT>(g0.x - qx), b0 = to_out<OT>(g0.y - qy);
+                            const OT a1 = to_out<OT>(g1.x - qx), b1 = to_out<OT>(g1.y - qy);
+                            OT4 o = {c0 >= 0 ? a0 : z, c0 >= 0 ? b0 : z, c1 >= 0 ? a1 : z, c1 >= 0 ? b1 : z};
+                            if (ok) __builtin_nontemporal_store(o, reinterpret_cast<OT4 *>(out + (size_t)r * PPR + HP + 2 * m));
+                        }
                     }
+                } else {
+                // Lattice path: the wave's 5 AGW / 8 passes are a PIPELINE four passes deep, not one round trip each.  Per pass:
+                // (1) the LDS reads that lead to an address -- permutation byte, list word --, (2) its two 16-byte gathers into
+                // registers of their own, (3) subtract / convert / select / store behind a COUNTED wait, four passes later.
+                // Nothing on the load path depends on "row exists": a row that does not (padding lane, env past n_env) reads
+                // cell 0 of an env that does, and only its STORE is predicated -- a load whose only use sits under `if (ok)`
+                // is sunk into that branch by the compiler and waited for alone, one dependent LDS -> LDS -> HBM chain per pass
+                // (ten per wave).  When every row of the workgroup exists (wave-uniform; every full batch) stage 3 has no
+                // branch at all.  The gathers of pass t + 4 are issued BEFORE the store of pass t: the wait for a gather (the
+                // counter retires in order) then never includes the acknowledgement of the row store next to it.
+                // The passes run chunk-major -- pass t is chunk t / ngrp of group t % ngrp -- so that the groups share a
+                // chunk's lane arithmetic; a wave writes only its own rows, so their order is free.  The phase costs vector
+                // instructions like any other: what is uniform over the wave is computed on the scalar side, the products are
+                // 24-bit, gathers and stores address base + 32-bit offset.  Kept per pass: LDS offset of the agent thread's
+                // position, byte offset of the store (bit 31: row exists), the list word, the gathered cells.
+                constexpr int ngrp = AGW / 8, NPASS = 5 * ngrp, DEPTH = 4;
+                constexpr int S = (int)sizeof(OT2);
+                const char *gbase = reinterpret_cast<const char *>(P.cells_xy + (size_t)(blockIdx.x * EPB) * P.ng_max);
+                const int e_last = (P.n_env - 1) - (int)(blockIdx.x * EPB);       // (a workgroup's last envs may not exist: never gather past the batch)
+                const int a64 = __builtin_amdgcn_readfirstlane(at & ~63);
+                const unsigned row_b = PPR * S, head_b = HP * S, list_b = P.g_stride * 2;
+                int rl = 0, m = 0;                                       // the chunk's row in its group and two-slot column
+                auto stage1 = [&](bool pred, int t, int &qo, int &so, int &cc, unsigned &eo) {
+                    if (t % ngrp == 0) {
+                        int ln = lane;
+                        asm volatile("" : "+v"(ln));                     // (recomputed per chunk, not carried in registers through the phase)
+                        const int ch = (t / ngrp) * 64 + ln;             // 0..319
+                        rl = (int)(__umul24(ch, 205) >> 13);             // ch / 40 (exact for ch < 320)
+                        m = ch - rl * 40;
+                    }
+                    const int ta = a64 + pws[(t % ngrp) * 8 + rl];       // locate(), own rows
+                    int elr = NPAD < 64 ? ta / NPAD : 0, r = ta;         // every row exists: n_a == NPAD, row = agent thread
+                    bool ok = true;
+                    if (pred) {
+                        const int ii = NPAD < 64 ? ta % NPAD : ta;
+                        r = elr * n_a + ii;
+                        ok = elr <= e_last && ii < n_a;
+                    }
+                    cc = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(sidx) + (__umul24(ta, list_b) + m * 4));
+                    if (pred) {
+                        asm volatile("" : "+v"(cc));                     // (the list word is read whether the row exists or not)
+                        if (!ok) cc = -1;                                // no row: both gathers read cell 0
+                        if (EPB > 1 && elr > e_last) elr = e_last;
+                    }
+                    eo = EPB > 1 ? (unsigned)elr * (unsigned)P.ng_max : 0u;
+                    qo = ta * 8;
+                    so = (int)(__umul24(r, row_b) + (head_b + m * (2 * S)));
+                    if (pred && ok) so |= (int)0x80000000;
+                    asm volatile("" : "+v"(qo), "+v"(so));
+                };
+                auto stage2 = [&](int cc, unsigned eo, double2 &g0, double2 &g1) {
+                    const int c0 = (int)(short)(cc & 0xFFFF), c1 = cc >> 16;
+                    g0 = *reinterpret_cast<const double2 *>(gbase + ((eo + (unsigned)(c0 < 0 ? 0 : c0)) << 4));
+                    g1 = *reinterpret_cast<const double2 *>(gbase + ((eo + (unsigned)(c1 < 0 ? 0 : c1)) << 4));
+                };
+                auto stage3 = [&](int qo, int cc, double2 g0, double2 g1, OT4 &o) {
+                    const int c0 = (int)(short)(cc & 0xFFFF), c1 = cc >> 16;
+                    const char *q = reinterpret_cast<const char *>(sp) + qo;
+                    const double qx = *reinterpret_cast<const double *>(q), qy = *reinterpret_cast<const double *>(q + AG * 8);
+                    const OT z = to_out<OT>(0.0);
+                    const OT a0 = to_out<OT>(g0.x - qx), b0 = to_out<OT>(g0.y - qy);
+                    const OT a1 = to_out<OT>(g1.x - qx), b1 = to_out<OT>(g1.y - qy);
+                    o = OT4{c0 >= 0 ? a0 : z, c0 >= 0 ? b0 : z, c1 >= 0 ? a1 : z, c1 >= 0 ? b1 : z};
+                };
+                typedef std::integral_constant<bool, true> pred_yes;
+                typedef std::integral_constant<bool, false> pred_no;
+                auto groups = [&](auto PRED) {
+                    constexpr bool pred = decltype(PRED)::value;
+                    int qo[DEPTH], so[DEPTH], cc[DEPTH];
+                    double2 ga[DEPTH], gb[DEPTH];
+                    {
+                        unsigned eo[DEPTH];
+#pragma unroll
+                        for (int t = 0; t < DEPTH; ++t) stage1(pred, t, qo[t], so[t], cc[t], eo[t]);
+#pragma unroll
+                        for (int t = 0; t < DEPTH; ++t) stage2(cc[t], eo[t], ga[t], gb[t]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);                   // the first gathers stay ahead of the first wait
+#pragma unroll
+                    for (int t = 0; t < NPASS; ++t) {
+                        const int k = t % DEPTH;
+                        const bool more = t + DEPTH < NPASS;
+                        int qn = 0, sn = 0, cn = 0;
+                        unsigned en = 0;
+                        if (more) stage1(pred, t + DEPTH, qn, sn, cn, en);
+                        // predicated stores: the gathered values are "used" here, outside the branch, so the loads stay put
+                        if constexpr (pred) asm volatile("" : "+v"(ga[k].x), "+v"(ga[k].y), "+v"(gb[k].x), "+v"(gb[k].y));
+                        OT4 o;
+                        stage3(qo[k], cc[k], ga[k], gb[k], o);
+                        const int sk = so[k];
+                        if (more) { qo[k] = qn; so[k] = sn; cc[k] = cn; stage2(cn, en, ga[k], gb[k]); }
+                        OT4 *dst = reinterpret_cast<OT4 *>(reinterpret_cast<char *>(out) + (unsigned)(pred ? sk & 0x7FFFFFFF : sk));
+                        if (!pred || sk < 0) __builtin_nontemporal_store(o, dst);
+                    }
+                };
+                if (n_a == NPAD && (int)(blockIdx.x * EPB) + EPB <= P.n_env) groups(pred_no{});
+                else groups(pred_yes{});
                 }
             } else {
                 // any other list length / f64 rows: wave per row, lane = slot
                 const int nrow = own ? AGW : (rows - wv + nwv - 1) / nwv;
+                int l0 = lane;
+                if constexpr (PIPE) asm volatile("" : "+v"(l0));          // (this branch's per-lane addresses are not kept in registers beside the other's)
                 for (int k = 0; k < nrow; ++k) {
                     int tr, elr, r;
                     const bool ok = locate(own ? k : wv + k * nwv, tr, elr, r);
                     const double2 *gr = P.cells_xy + (size_t)(blockIdx.x * EPB + elr) * P.ng_max;
                     const double qx = sp[tr], qy = sp[AG + tr];
                     const short *srw = sidx + (size_t)tr * P.g_stride;
-                    for (int q = lane; q < Gp; q += 64) {
+                    for (int q = l0; q < Gp; q += 64) {
                         const int c = srw[q];
                         const double2 g = gr[c < 0 ? 0 : c];
                         OT2 o; o.x = c >= 0 ? to_out<OT>(g.x - qx) : to_out<OT>(0.0); o.y = c >= 0 ? to_out<OT>(g.y - qy) : to_out<OT>(0.0);
