@@ -296,10 +296,11 @@ class SwarmBatch:
         return p, dp
 
     # -- hot path -----------------------------------------------------------------------------------
-    def observe(self):
-        """Recompute obs + caches from the current state (the tail of the reference's reset())."""
+    def observe(self, out=None):
+        """Recompute obs + caches from the current state (the tail of the reference's reset()).  out: optional caller-owned
+        obs tensor (as step's out["obs"]) written instead of the batch's own ping-pong buffer."""
         self._flip ^= 1
-        obs = self._obs[self._flip]
+        obs = self._out_ptrs({"obs": out})["obs"].view(self.n_env, self.n_agents, self.obs_dim) if out is not None else self._obs[self._flip]
         self._sync_stream()
         check(self.lib, self.handle, self.lib.swarm_observe(self.handle, _ptr(obs)))
         return obs

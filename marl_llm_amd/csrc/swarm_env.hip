@@ -1342,16 +1342,13 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             FENCE();
             const int Gp = P.g_max;
             const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = T >> 6;
-            // PIPE: the lattice kernels of 64 agents write their rows as a pipeline (below); every other instantiation keeps
-            // the pass-by-pass loop and its register allocation (profiles/r14/kstats.txt).  There the wave's row slots in its
-            // permutation are addressed by scalars: pw is the same bytes through a per-lane pointer that would have to stay in
-            // a register from the ranking on.
-            constexpr bool PIPE = NPAD == 64 && !HALF;
-            const unsigned char *pws = !own ? pw : (PIPE ? perm + wv * 64 : pw) + (64 - ACTW) + sx * AGW;
+            // (N = 8: the wave's row slots through one pointer formed here -- the same bytes, and 12 to 20 B of scratch less in
+            // those lattice kernels; at N = 32 that form measured 0.8 % slower, profiles/r14 and r15)
+            const unsigned char *pws = !own ? pw : pw + (64 - ACTW) + sx * AGW;
             // row slot k of this wave -> agent thread tr, environment in the workgroup elr, output row r, "row exists"
             auto locate = [&](int k, int &tr, int &elr, int &r) -> bool {
                 if (own) {
-                    const int ta = (at & ~63) + pws[k];
+                    const int ta = (at & ~63) + (NPAD == 8 ? pws[k] : pw[(64 - ACTW) + sx * AGW + k]);
                     const int ii = NPAD < 64 ? (ta & 63) % NPAD : ta;
                     elr = NPAD < 64 ? (ta & 63) / NPAD : 0;
                     tr = ta; r = elr * n_a + ii;
@@ -1369,140 +1366,39 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
                 // consecutive addresses -- half the store instructions of the pair-per-lane form.  A row has 40 two-slot
                 // chunks; 8 rows = 320 chunks = 5 full passes.
                 typedef OT OT4 __attribute__((ext_vector_type(4)));
-                if (!own || !PIPE) {
-                    // pass by pass.  Generic path: the waves deal the groups of eight rows (the staged form below put a thousand
-                    // more scalar spill reloads into the generic step kernels, which sit at their SGPR limit: DESIGN section 5, v53)
-                    const int ngrp = own ? AGW / 8 : (rows + nwv * 8 - 1) / (nwv * 8);
-                    for (int g8 = 0; g8 < ngrp; ++g8) {
+                const int ngrp = own ? AGW / 8 : (rows + nwv * 8 - 1) / (nwv * 8);
+                for (int g8 = 0; g8 < ngrp; ++g8) {
 #pragma unroll
-                        for (int ps = 0; ps < 5; ++ps) {
-                            const int ch = ps * 64 + lane;               // 0..319
-                            const int rl = (ch * 205) >> 13;             // ch / 40 (exact for ch < 320)
-                            const int m = ch - rl * 40;
-                            int tr, elr, r;
-                            const bool ok = locate(own ? g8 * 8 + rl : (wv + g8 * nwv) * 8 + rl, tr, elr, r);
-                            const double2 *gr = P.cells_xy + (size_t)(blockIdx.x * EPB + elr) * P.ng_max;
-                            const double qx = sp[tr], qy = sp[AG + tr];
-                            const int cc = *reinterpret_cast<const int *>(sidx + (size_t)tr * P.g_stride + 2 * m);
-                            const int c0 = (int)(short)(cc & 0xFFFF), c1 = cc >> 16;
-                            const double2 g0 = gr[c0 < 0 ? 0 : c0], g1 = gr[c1 < 0 ? 0 : c1];
-                            const OT z = to_out<OT>(0.0);
-                            const OT a0 = to_out<OT>(g0.x - qx), b0 = to_out<OT>(g0.y - qy);
-                            const OT a1 = to_out<OT>(g1.x - qx), b1 = to_out<OT>(g1.y - qy);
-                            OT4 o = {c0 >= 0 ? a0 : z, c0 >= 0 ? b0 : z, c1 >= 0 ? a1 : z, c1 >= 0 ? b1 : z};
-                            if (ok) __builtin_nontemporal_store(o, reinterpret_cast<OT4 *>(out + (size_t)r * PPR + HP + 2 * m));
-                        }
+                    for (int ps = 0; ps < 5; ++ps) {
+                        const int ch = ps * 64 + lane;                   // 0..319
+                        const int rl = (ch * 205) >> 13;                 // ch / 40 (exact for ch < 320)
+                        const int m = ch - rl * 40;
+                        // straight-line: both gathers of every pass are issued unconditionally (an empty slot reads cell 0
+                        // and stores zeros), so the five passes' loads are in flight together instead of one wait each
+                        int tr, elr, r;
+                        const bool ok = locate(own ? g8 * 8 + rl : (wv + g8 * nwv) * 8 + rl, tr, elr, r);
+                        const double2 *gr = P.cells_xy + (size_t)(blockIdx.x * EPB + elr) * P.ng_max;
+                        const double qx = sp[tr], qy = sp[AG + tr];
+                        const int cc = *reinterpret_cast<const int *>(sidx + (size_t)tr * P.g_stride + 2 * m);
+                        const int c0 = (int)(short)(cc & 0xFFFF), c1 = cc >> 16;
+                        const double2 g0 = gr[c0 < 0 ? 0 : c0], g1 = gr[c1 < 0 ? 0 : c1];
+                        const OT z = to_out<OT>(0.0);
+                        const OT a0 = to_out<OT>(g0.x - qx), b0 = to_out<OT>(g0.y - qy);
+                        const OT a1 = to_out<OT>(g1.x - qx), b1 = to_out<OT>(g1.y - qy);
+                        OT4 o = {c0 >= 0 ? a0 : z, c0 >= 0 ? b0 : z, c1 >= 0 ? a1 : z, c1 >= 0 ? b1 : z};
+                        if (ok) __builtin_nontemporal_store(o, reinterpret_cast<OT4 *>(out + (size_t)r * PPR + HP + 2 * m));
                     }
-                } else {
-                // Lattice path: the wave's 5 AGW / 8 passes are a PIPELINE four passes deep, not one round trip each.  Per pass:
-                // (1) the LDS reads that lead to an address -- permutation byte, list word --, (2) its two 16-byte gathers into
-                // registers of their own, (3) subtract / convert / select / store behind a COUNTED wait, four passes later.
-                // Nothing on the load path depends on "row exists": a row that does not (padding lane, env past n_env) reads
-                // cell 0 of an env that does, and only its STORE is predicated -- a load whose only use sits under `if (ok)`
-                // is sunk into that branch by the compiler and waited for alone, one dependent LDS -> LDS -> HBM chain per pass
-                // (ten per wave).  When every row of the workgroup exists (wave-uniform; every full batch) stage 3 has no
-                // branch at all.  The gathers of pass t + 4 are issued BEFORE the store of pass t: the wait for a gather (the
-                // counter retires in order) then never includes the acknowledgement of the row store next to it.
-                // The passes run chunk-major -- pass t is chunk t / ngrp of group t % ngrp -- so that the groups share a
-                // chunk's lane arithmetic; a wave writes only its own rows, so their order is free.  The phase costs vector
-                // instructions like any other: what is uniform over the wave is computed on the scalar side, the products are
-                // 24-bit, gathers and stores address base + 32-bit offset.  Kept per pass: LDS offset of the agent thread's
-                // position, byte offset of the store (bit 31: row exists), the list word, the gathered cells.
-                constexpr int ngrp = AGW / 8, NPASS = 5 * ngrp, DEPTH = 4;
-                constexpr int S = (int)sizeof(OT2);
-                const char *gbase = reinterpret_cast<const char *>(P.cells_xy + (size_t)(blockIdx.x * EPB) * P.ng_max);
-                const int e_last = (P.n_env - 1) - (int)(blockIdx.x * EPB);       // (a workgroup's last envs may not exist: never gather past the batch)
-                const int a64 = __builtin_amdgcn_readfirstlane(at & ~63);
-                const unsigned row_b = PPR * S, head_b = HP * S, list_b = P.g_stride * 2;
-                int rl = 0, m = 0;                                       // the chunk's row in its group and two-slot column
-                auto stage1 = [&](bool pred, int t, int &qo, int &so, int &cc, unsigned &eo) {
-                    if (t % ngrp == 0) {
-                        int ln = lane;
-                        asm volatile("" : "+v"(ln));                     // (recomputed per chunk, not carried in registers through the phase)
-                        const int ch = (t / ngrp) * 64 + ln;             // 0..319
-                        rl = (int)(__umul24(ch, 205) >> 13);             // ch / 40 (exact for ch < 320)
-                        m = ch - rl * 40;
-                    }
-                    const int ta = a64 + pws[(t % ngrp) * 8 + rl];       // locate(), own rows
-                    int elr = NPAD < 64 ? ta / NPAD : 0, r = ta;         // every row exists: n_a == NPAD, row = agent thread
-                    bool ok = true;
-                    if (pred) {
-                        const int ii = NPAD < 64 ? ta % NPAD : ta;
-                        r = elr * n_a + ii;
-                        ok = elr <= e_last && ii < n_a;
-                    }
-                    cc = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(sidx) + (__umul24(ta, list_b) + m * 4));
-                    if (pred) {
-                        asm volatile("" : "+v"(cc));                     // (the list word is read whether the row exists or not)
-                        if (!ok) cc = -1;                                // no row: both gathers read cell 0
-                        if (EPB > 1 && elr > e_last) elr = e_last;
-                    }
-                    eo = EPB > 1 ? (unsigned)elr * (unsigned)P.ng_max : 0u;
-                    qo = ta * 8;
-                    so = (int)(__umul24(r, row_b) + (head_b + m * (2 * S)));
-                    if (pred && ok) so |= (int)0x80000000;
-                    asm volatile("" : "+v"(qo), "+v"(so));
-                };
-                auto stage2 = [&](int cc, unsigned eo, double2 &g0, double2 &g1) {
-                    const int c0 = (int)(short)(cc & 0xFFFF), c1 = cc >> 16;
-                    g0 = *reinterpret_cast<const double2 *>(gbase + ((eo + (unsigned)(c0 < 0 ? 0 : c0)) << 4));
-                    g1 = *reinterpret_cast<const double2 *>(gbase + ((eo + (unsigned)(c1 < 0 ? 0 : c1)) << 4));
-                };
-                auto stage3 = [&](int qo, int cc, double2 g0, double2 g1, OT4 &o) {
-                    const int c0 = (int)(short)(cc & 0xFFFF), c1 = cc >> 16;
-                    const char *q = reinterpret_cast<const char *>(sp) + qo;
-                    const double qx = *reinterpret_cast<const double *>(q), qy = *reinterpret_cast<const double *>(q + AG * 8);
-                    const OT z = to_out<OT>(0.0);
-                    const OT a0 = to_out<OT>(g0.x - qx), b0 = to_out<OT>(g0.y - qy);
-                    const OT a1 = to_out<OT>(g1.x - qx), b1 = to_out<OT>(g1.y - qy);
-                    o = OT4{c0 >= 0 ? a0 : z, c0 >= 0 ? b0 : z, c1 >= 0 ? a1 : z, c1 >= 0 ? b1 : z};
-                };
-                typedef std::integral_constant<bool, true> pred_yes;
-                typedef std::integral_constant<bool, false> pred_no;
-                auto groups = [&](auto PRED) {
-                    constexpr bool pred = decltype(PRED)::value;
-                    int qo[DEPTH], so[DEPTH], cc[DEPTH];
-                    double2 ga[DEPTH], gb[DEPTH];
-                    {
-                        unsigned eo[DEPTH];
-#pragma unroll
-                        for (int t = 0; t < DEPTH; ++t) stage1(pred, t, qo[t], so[t], cc[t], eo[t]);
-#pragma unroll
-                        for (int t = 0; t < DEPTH; ++t) stage2(cc[t], eo[t], ga[t], gb[t]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);                   // the first gathers stay ahead of the first wait
-#pragma unroll
-                    for (int t = 0; t < NPASS; ++t) {
-                        const int k = t % DEPTH;
-                        const bool more = t + DEPTH < NPASS;
-                        int qn = 0, sn = 0, cn = 0;
-                        unsigned en = 0;
-                        if (more) stage1(pred, t + DEPTH, qn, sn, cn, en);
-                        // predicated stores: the gathered values are "used" here, outside the branch, so the loads stay put
-                        if constexpr (pred) asm volatile("" : "+v"(ga[k].x), "+v"(ga[k].y), "+v"(gb[k].x), "+v"(gb[k].y));
-                        OT4 o;
-                        stage3(qo[k], cc[k], ga[k], gb[k], o);
-                        const int sk = so[k];
-                        if (more) { qo[k] = qn; so[k] = sn; cc[k] = cn; stage2(cn, en, ga[k], gb[k]); }
-                        OT4 *dst = reinterpret_cast<OT4 *>(reinterpret_cast<char *>(out) + (unsigned)(pred ? sk & 0x7FFFFFFF : sk));
-                        if (!pred || sk < 0) __builtin_nontemporal_store(o, dst);
-                    }
-                };
-                if (n_a == NPAD && (int)(blockIdx.x * EPB) + EPB <= P.n_env) groups(pred_no{});
-                else groups(pred_yes{});
                 }
             } else {
                 // any other list length / f64 rows: wave per row, lane = slot
                 const int nrow = own ? AGW : (rows - wv + nwv - 1) / nwv;
-                int l0 = lane;
-                if constexpr (PIPE) asm volatile("" : "+v"(l0));          // (this branch's per-lane addresses are not kept in registers beside the other's)
                 for (int k = 0; k < nrow; ++k) {
                     int tr, elr, r;
                     const bool ok = locate(own ? k : wv + k * nwv, tr, elr, r);
                     const double2 *gr = P.cells_xy + (size_t)(blockIdx.x * EPB + elr) * P.ng_max;
                     const double qx = sp[tr], qy = sp[AG + tr];
                     const short *srw = sidx + (size_t)tr * P.g_stride;
-                    for (int q = l0; q < Gp; q += 64) {
+                    for (int q = lane; q < Gp; q += 64) {
                         const int c = srw[q];
                         const double2 g = gr[c < 0 ? 0 : c];
                         OT2 o; o.x = c >= 0 ? to_out<OT>(g.x - qx) : to_out<OT>(0.0); o.y = c >= 0 ? to_out<OT>(g.y - qy) : to_out<OT>(0.0);
@@ -1512,6 +1408,115 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             }
         }
     };
+
+    // The same rows in the lattice kernels of 64 agents (ROWS_LIVE; g_max == 80, rows of at most 4-byte elements): a writer
+    // of its own, so that every other instantiation keeps sensed_rows() and its code as they are.  Same values, same
+    // stores, another order; only passes that hold a cell do the work.
+    //   Slot-aligned passes.  A wave's sixteen rows are two groups of eight, in its permutation's order: ascending list
+    // length.  In a group, lane = 8 * row + column: pass p is slots [16 p, 16 p + 16) of the group's eight rows, 8 lanes x
+    // 16 B (f32) of consecutive addresses per row.  Everything that belongs to a row -- permutation byte, position, list
+    // address, store address -- is computed once per group; a pass adds constants, which sit in the instructions' offsets.
+    //   Live and dead passes.  The group's longest list is its last agent's (nmax, capped); passes p >= ceil(nmax / 16) hold
+    // no cell in any of the eight rows (the list region beyond a list's end is -1): they store zeros and read nothing.
+    // `live` carries the two groups' live-pass counts, four bits each, taken on the scalar side in the reward block.
+    //   The live passes of a group are a pipeline as before (profiles/r14): list words and gathers of up to four passes in
+    // flight (bf16 rows: three), subtract / convert / select / store behind COUNTED waits, the gathers of pass t + 4 ahead of
+    // the store of pass t.  One statically unrolled pipeline per live-pass count, picked by a scalar switch, run once per
+    // group -- a group's fill is not overlapped with the other's drain.  A wave-uniform branch around a
+    // load INSIDE one pipeline would make every wait behind it a full one.  The zero stores go behind the group's first
+    // gathers: younger than those, they are in no gather's wait, and they fill the time the first gathers take.
+    //   Nothing on the load path depends on "row exists" (n_a < 64): such a row reads cell 0 and only its stores are
+    // predicated; a workgroup whose every row exists takes the twin without predicates.
+    constexpr bool ROWS_LIVE = LAT && NPAD == 64 && !HALF && sizeof(OT) <= 4;
+    auto sensed_rows_live = [&](const int live) {
+        typedef OT OT4 __attribute__((ext_vector_type(4)));
+        typedef std::integral_constant<bool, true> pred_yes;
+        typedef std::integral_constant<bool, false> pred_no;
+        // NP passes of 16 slots: g_max == 80.  DEPTH passes in flight; the bf16 rows' conversion takes registers of its own
+        constexpr int S = (int)sizeof(OT2), DEPTH = sizeof(OT) == 2 ? 3 : 4, NP = 5;
+        static_assert(!ROWS_LIVE || (EPB == 1 && AG == 64), "one env per workgroup, row = agent thread");
+        for (int rep = 0, reps = REPS(8); rep < reps; ++rep) {
+            FENCE();
+            const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+            const unsigned char *pws = perm + wv * 64 + (64 - ACTW) + sx * AGW;
+            const char *gbase = reinterpret_cast<const char *>(P.cells_xy + (size_t)blockIdx.x * P.ng_max);
+            const unsigned row_b = PPR * S, head_b = HP * S, list_b = P.g_stride * 2;
+            auto group = [&](auto PRED, auto LIVE, const int g) {
+                constexpr bool pred = decltype(PRED)::value;
+                constexpr int L = decltype(LIVE)::value, F = L < DEPTH ? L : DEPTH;
+                const int ta = pws[g * 8 + (lane >> 3)], col = lane & 7;  // the row's agent thread; the lane's two-slot column in a pass
+                const bool ok = !pred || ((int)blockIdx.x < P.n_env && ta < n_a);
+                char *dst = reinterpret_cast<char *>(out) + (__umul24(ta, row_b) + (head_b + col * (2 * S)));
+                const OT z = to_out<OT>(0.0);
+                auto gather = [&](int cc, double2 &g0, double2 &g1) {
+                    const int c0 = (int)(short)(cc & 0xFFFF), c1 = cc >> 16;
+                    g0 = *reinterpret_cast<const double2 *>(gbase + ((unsigned)(c0 < 0 ? 0 : c0) << 4));
+                    g1 = *reinterpret_cast<const double2 *>(gbase + ((unsigned)(c1 < 0 ? 0 : c1) << 4));
+                };
+                auto put = [&](int p, OT4 o) {
+                    OT4 *d = reinterpret_cast<OT4 *>(dst + p * (16 * S));
+                    if constexpr (pred) { if (ok) __builtin_nontemporal_store(o, d); }
+                    else __builtin_nontemporal_store(o, d);
+                };
+                if constexpr (L == 0) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) put(p, OT4{z, z, z, z});
+                } else {
+                    const char *lp = reinterpret_cast<const char *>(sidx) + (__umul24(ta, list_b) + col * 4);
+                    auto word = [&](int p) -> int {
+                        int cc = *reinterpret_cast<const int *>(lp + p * 32);
+                        if constexpr (pred) {
+                            asm volatile("" : "+v"(cc));                 // (the list word is read whether the row exists or not)
+                            if (!ok) cc = -1;                            // no row: both gathers read cell 0
+                        }
+                        return cc;
+                    };
+                    const double qx = sp[ta], qy = sp[AG + ta];
+                    int cc[DEPTH];
+                    double2 ga[DEPTH], gb[DEPTH];
+#pragma unroll
+                    for (int t = 0; t < F; ++t) cc[t] = word(t);
+#pragma unroll
+                    for (int t = 0; t < F; ++t) gather(cc[t], ga[t], gb[t]);
+                    __builtin_amdgcn_sched_barrier(0);                   // the first gathers stay ahead of the zero stores and of the first wait
+#pragma unroll
+                    for (int p = L; p < NP; ++p) put(p, OT4{z, z, z, z});
+                    if constexpr (L < NP) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int t = 0; t < L; ++t) {
+                        const int k = t % DEPTH;
+                        const bool more = t + DEPTH < L;
+                        int cn = 0;
+                        if (more) cn = word(t + DEPTH);
+                        // predicated stores: the gathered values are "used" here, outside the branch, so the loads stay put
+                        if constexpr (pred) asm volatile("" : "+v"(ga[k].x), "+v"(ga[k].y), "+v"(gb[k].x), "+v"(gb[k].y));
+                        const int c0 = (int)(short)(cc[k] & 0xFFFF), c1 = cc[k] >> 16;
+                        const OT a0 = to_out<OT>(ga[k].x - qx), b0 = to_out<OT>(ga[k].y - qy);
+                        const OT a1 = to_out<OT>(gb[k].x - qx), b1 = to_out<OT>(gb[k].y - qy);
+                        const OT4 o = {c0 >= 0 ? a0 : z, c0 >= 0 ? b0 : z, c1 >= 0 ? a1 : z, c1 >= 0 ? b1 : z};
+                        if (more) { cc[k] = cn; gather(cn, ga[k], gb[k]); }
+                        put(t, o);
+                    }
+                }
+            };
+            auto groups = [&](auto PRED) {
+#pragma unroll 1
+                for (int g = 0; g < AGW / 8; ++g) {
+                    switch ((live >> (4 * g)) & 15) {
+                    case 0: group(PRED, std::integral_constant<int, 0>{}, g); break;
+                    case 1: group(PRED, std::integral_constant<int, 1>{}, g); break;
+                    case 2: group(PRED, std::integral_constant<int, 2>{}, g); break;
+                    case 3: group(PRED, std::integral_constant<int, 3>{}, g); break;
+                    case 4: group(PRED, std::integral_constant<int, 4>{}, g); break;
+                    default: group(PRED, std::integral_constant<int, NP>{}, g); break;
+                    }
+                }
+            };
+            if (n_a == NPAD && (int)blockIdx.x < P.n_env) groups(pred_no{});
+            else groups(pred_yes{});
+        }
+    };
+    int row_live = 0;                               // ROWS_LIVE: live passes of the wave's two row groups (sensed_rows_live)
 
     const int G = P.g_max;
     int n_sel = 0;                                   // length of this agent thread's capped list
@@ -1761,6 +1766,12 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     {
         const int nsl = qnk > G ? G : qnk;
+        if constexpr (ROWS_LIVE) {
+            // the longest list of each group of eight rows is its last agent's (ranking: key (length, lane)); taken here, on the
+            // scalar side, while the lengths are in a register
+            const int n0 = __builtin_amdgcn_readlane(nsl, 7 * LPA), n1 = __builtin_amdgcn_readlane(nsl, 15 * LPA);
+            row_live = ((n0 + 15) >> 4) | (((n1 + 15) >> 4) << 4);
+        }
         const bool in_a = (sncf[ea] >> 30) != 0;
         const int ael = NPAD < 64 ? (ea & 63) / NPAD : 0, ai = NPAD < 64 ? (ea & 63) % NPAD : ea;
         const int ae = blockIdx.x * EPB + ael;
@@ -1795,7 +1806,10 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
         head_blocks(NW == 1);                        // (N > 64: dealt over all splits but B; the early A / C deal measured +15 % at N = 256)
         STAMP(9);
         EXIT_AT(11);
-        sensed_rows(true, perm + (tid >> 6) * 64);
+        if constexpr (ROWS_LIVE) {
+            if (G == 80) sensed_rows_live(row_live);
+            else sensed_rows(true, perm + (tid >> 6) * 64);
+        } else sensed_rows(true, perm + (tid >> 6) * 64);
     }
     } else {
     // ---- occupied-cell filter, CPP:144-216: a sensed cell is occupied iff some nearby agent is within
