@@ -244,6 +244,9 @@ template <int NPAD, bool HALF = false> struct Geo {
 // share bytes, and why they may:
 //   pm   over sidx   the partial pair masks are consumed two barriers before the first list slot is written
 //   perm over part_d written two barriers after the walking splits' distances were consumed
+//   tgt  over part_d behind perm's bytes: the nearest cell relative to its agent, {x, y} in fp64 (N = 64: the kernels whose
+//                    heads and prior read it, TGT_LDS).  Written behind the barrier that ends (K) -- until then another split
+//                    may still be merging the distances -- and read behind the one that ends (S)
 //   prk  over part_c the partial ranks: the nearest-cell candidates are consumed by the merge, a barrier earlier
 //   the exact reward's scratch (N > 64) over srow
 template <int NPAD, bool HALF> struct LatMap {
@@ -282,11 +285,14 @@ template <int NPAD, bool HALF> struct LatMap {
     static constexpr int sidx = snear + al(snear_bytes);
     static constexpr int perm = partd;
     static constexpr int perm_bytes = T, prk_bytes = WPE * AG * 2;
+    static constexpr int tgt = partd + al(perm_bytes);                    // behind perm: the two are live together
+    static constexpr int tgt_bytes = AG * 16;
     static constexpr int sidx_bytes(int g_stride) { return al(mx(AG * g_stride * 2, pm_bytes)); }
     static constexpr int total(int g_stride) { return sidx + sidx_bytes(g_stride); }                  // a step launch
     static constexpr int orow_off(int g_stride) { return total(g_stride); }
     static constexpr int total_export(int g_stride) { return orow_off(g_stride) + al(orow_bytes); }   // a launch that exports the lists
     static_assert(perm_bytes <= partd_bytes, "perm must fit the distance array it reuses");
+    static_assert(tgt % 16 == 0 && tgt - partd + tgt_bytes <= partd_bytes, "perm and the relative targets must fit the distance array they reuse, side by side");
     static_assert(prk_bytes <= partc_bytes, "the partial ranks must fit the nearest-cell candidates they reuse");
     static_assert(rew_scratch_bytes <= srow_bytes, "the exact reward's scratch must fit the window rows it reuses");
     static_assert(pm_bytes <= sidx_bytes(0), "the pair masks must fit the list region they reuse");
@@ -1133,6 +1139,14 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
     }
     part_c[sx * AG + at] = (pc_t)bc;
     double *part_d = reinterpret_cast<double *>(smem + LO(partd));     // [lat] [WPE - 1][AG] exact distance of each walking split's candidate (the list phase's `perm` reuses it)
+    // TGT_LDS (the lattice kernels of 64 agents): the candidate's offset from the agent stays in registers past the merge, and
+    // the split whose candidate wins publishes it in LDS (`tgt`, behind the barrier that ends (K)).  It is, bit for bit, the
+    // target block of the agent's observation head and the prior policy's attraction vector -- the same cell, the same
+    // position, the same subtraction -- so neither gathers the cell again.
+    constexpr bool TGT_LDS = LAT && NPAD == 64 && !HALF;
+    double2 *tgt = reinterpret_cast<double2 *>(smem + LM::tgt);          // [lat, TGT_LDS] [AG] nearest cell - own position (aliases part_d, later phase)
+    double cand_x = 0.0, cand_y = 0.0;
+    int win = 0;                                                         // TGT_LDS: the split whose candidate the merge picked
     if constexpr (LAT) {
         // each walking split evaluates the exact distance of ITS candidate here, before the barrier (the gather overlaps the
         // other waves' walk); the merge behind the barrier then compares values that sit in LDS instead of every split
@@ -1141,6 +1155,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             const double2 g = cell64(bc);
             const double ex = g.x - px, ey = g.y - py;
             part_d[(WPE > 1 && sx > SB ? sx - 1 : sx) * AG + at] = ex * ex + ey * ey;      // [walking split][AG]
+            if constexpr (TGT_LDS) { cand_x = ex; cand_y = ey; }
         }
     }
     STAMP(16);
@@ -1159,10 +1174,11 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
         double d;
         if constexpr (LAT) d = part_d[(WPE > 1 && s > SB ? s - 1 : s) * AG + at];
         else { const double2 g = cell64(c); const double ex = g.x - px, ey = g.y - py; d = ex * ex + ey * ey; }
-        if (d < best || (d == best && c < bc)) { best = d; bc = c; }
+        if (d < best || (d == best && c < bc)) { best = d; bc = c; if constexpr (TGT_LDS) win = s; }
     }
     }
     const bool in_shape = act && best < P.c_in[es];                    // CPP:889
+    const bool tgt_mine = TGT_LDS && win == sx;                        // (a lane mask: scalar registers across (K))
     if (sx == 0) {
         sncf[at] = bc | (in_shape ? (1 << 30) : 0);
         if (P.export_small && act) {
@@ -1192,7 +1208,8 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             const int ncf = sncf[at];
             // target: own position when in shape (CPP:889-897) => zero attraction; else the nearest cell
             double tx = px - px, ty = py - py;
-            if (!(ncf >> 30)) { const double2 g = cell64(ncf & 0xFFFF); tx = g.x - px; ty = g.y - py; }
+            if constexpr (TGT_LDS) { const double2 t = tgt[at]; if (!(ncf >> 30)) { tx = t.x; ty = t.y; } }      // the merge's winner: that cell - (px, py)
+            else if (!(ncf >> 30)) { const double2 g = cell64(ncf & 0xFFFF); tx = g.x - px; ty = g.y - py; }
             const double dt_ = sqrt(tx * tx + ty * ty);
             if (dt_ > 0) { qx += P.pk_att * tx / dt_; qy += P.pk_att * ty / dt_; }
             lx = qx; ly = qy;
@@ -1290,6 +1307,83 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
                         OT2 o0, o1;
                         o0.x = to_out<OT>(a); o0.y = to_out<OT>(b); o1.x = to_out<OT>(mu - qu); o1.y = to_out<OT>(mv - qv);
                         store_nt(dst, o0); store_nt(dst + 1, o1);
+                    }
+                }
+            }
+        }
+    };
+
+    // The same heads in the kernels that hold every agent's relative target in LDS (TGT_LDS): a writer of its own, so that
+    // every other instantiation keeps head_blocks() and its code.  Same values, same stores, the early deal's chunks of 64
+    // items; nothing is read from global memory, and the block kind selects ADDRESSES, not values.  A value is M - Q:
+    //   own block        own - 0
+    //   neighbour k      neighbour - own; no neighbour: own - own (+0 for every finite value: the reference's zeros)
+    //   target           inside the shape own - own; outside: position tgt - 0, velocity 0 - own
+    // M is one LDS read per value at `has ? neighbour : own` (positions of a target outside the shape: at its `tgt` entry);
+    // Q is `own` or 0.  (Zeros are selected, never made by a product: (-0) - (-0) is not (-0) - 0.)  With eight blocks to a
+    // row -- the reference's topology -- a lane's block and its kind are fixed over the chunks.
+    // Chunks c of every eight: A takes [0, SWARM_HEAD_A), C the rest but the last SWARM_HEAD_B, which B takes behind its prior
+    // (5 / 3 / 0 as in head_blocks; 4 / 4, 4 / 3 / 1 and 5 / 2 / 1 measured the same: profiles/r16).
+#ifndef SWARM_HEAD_A
+#define SWARM_HEAD_A 5
+#endif
+#ifndef SWARM_HEAD_B
+#define SWARM_HEAD_B 0
+#endif
+    auto head_blocks_tgt = [&]() {
+        static_assert(!TGT_LDS || (EPB == 1 && NW == 1), "one env per workgroup, row = agent thread");
+        typedef OT OT4 __attribute__((ext_vector_type(4)));
+        for (int rep = 0, reps = REPS(7); rep < reps; ++rep) {
+            FENCE();
+            const int NB = P.with_self + P.topo + 1;
+            const int total = rows * NB, n_it = (total + 63) >> 6;
+            auto owner = [](int it_) -> int { const int c8 = it_ & 7; return c8 < SWARM_HEAD_A ? 0 : (c8 < 8 - SWARM_HEAD_B ? 2 : SB); };
+            // a wave without chunks leaves here: the set-up below and the induction registers of the chunk loop are vector
+            // instructions too (about 80 per wave on B and D, which own nothing)
+            if (!(sx == 0 || sx == 2 || (SWARM_HEAD_B > 0 && sx == SB))) continue;
+            // block blk (of the kind the flags say) of row r
+            auto put = [&](const int r, const int blk, const bool is_self, const bool is_nei, const bool is_tgt) {
+                const int j = snei[r * kNeiStride + (is_nei ? blk - P.with_self : 0)];
+                const int ncf = sncf[r];
+                const bool has = is_nei && j >= 0, out_t = is_tgt && !(ncf >> 30);
+                const int m = has ? j : r;
+                const double *tq = reinterpret_cast<const double *>(tgt + r);
+                const double *mpx = out_t ? tq : sp + m, *mpy = out_t ? tq + 1 : sp + AG + m;
+                const double ox = sp[r], oy = sp[AG + r], ou = sp[2 * AG + r], ov = sp[3 * AG + r];
+                const double mx = *mpx, my = *mpy, mu_ = sp[2 * AG + m], mv_ = sp[3 * AG + m];
+                const bool q0 = is_self || out_t;
+                const double qx = q0 ? 0.0 : ox, qy = q0 ? 0.0 : oy, qu = is_self ? 0.0 : ou, qv = is_self ? 0.0 : ov;
+                const double mu = out_t ? 0.0 : mu_, mv = out_t ? 0.0 : mv_;
+                double a = mx - qx, b = my - qy;
+                if (P.periodic && is_nei) wrap_rel(a, b, P.w_half, P.h_half);
+                OT2 *dst = out + (size_t)r * PPR + 2 * blk;
+                if ((PPR & 1) == 0) {                                    // rows are a whole number of blocks: 4-value stores stay aligned
+                    const OT4 o = {to_out<OT>(a), to_out<OT>(b), to_out<OT>(mu - qu), to_out<OT>(mv - qv)};
+                    __builtin_nontemporal_store(o, reinterpret_cast<OT4 *>(dst));
+                } else {                                                 // odd list length (non-reference configs)
+                    OT2 o0, o1;
+                    o0.x = to_out<OT>(a); o0.y = to_out<OT>(b); o1.x = to_out<OT>(mu - qu); o1.y = to_out<OT>(mv - qv);
+                    store_nt(dst, o0); store_nt(dst + 1, o1);
+                }
+            };
+            if (NB == 8) {
+                const int blk = lane & 7;
+                const bool is_tgt = blk == 7, is_self = P.with_self && blk == 0, is_nei = !is_tgt && !is_self;
+                // (a rolled loop: unrolled over the eight chunks, with or without a scheduling barrier between them, every
+                // TGT_LDS kernel takes 64 - 84 B of scratch)
+                for (int it_ = 0; it_ < n_it; ++it_) {
+                    if (sx != owner(it_)) continue;
+                    const int r = it_ * 8 + (lane >> 3);
+                    if (r < rows) put(r, blk, is_self, is_nei, is_tgt);
+                }
+            } else {
+                for (int it_ = 0; it_ < n_it; ++it_) {
+                    if (sx != owner(it_)) continue;
+                    const int item = it_ * 64 + lane;
+                    if (item < total) {
+                        const int r = item / NB, blk = item - r * NB;
+                        const bool is_tgt = blk == NB - 1, is_self = P.with_self && blk == 0;
+                        put(r, blk, is_self, !is_tgt && !is_self, is_tgt);
                     }
                 }
             }
@@ -1586,6 +1680,9 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
     __syncthreads();
     STAMP(5);
     EXIT_AT(6);
+    // every split is past its merge: the distances are dead, and the winning split's lane publishes the agent's relative
+    // target over them (read by the prior policy and the heads, behind the next barrier)
+    if constexpr (TGT_LDS) { if (tgt_mine) tgt[at] = double2{cand_x, cand_y}; }
 
     // ---- (S) rank of every agent thread by (list length, index) inside its 64-group: each split compares against a quarter
     // of the group (the other agents' keys come from the wave's own lanes), the partial counts are summed through LDS
@@ -1803,7 +1900,8 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
     // lists were shortest (A and C); the split with the longest lists (D) goes straight to its rows.
     prior_policy();
     if (obs != nullptr) {
-        head_blocks(NW == 1);                        // (N > 64: dealt over all splits but B; the early A / C deal measured +15 % at N = 256)
+        if constexpr (TGT_LDS) head_blocks_tgt();
+        else head_blocks(NW == 1);                   // (N > 64: dealt over all splits but B; the early A / C deal measured +15 % at N = 256)
         STAMP(9);
         EXIT_AT(11);
         if constexpr (ROWS_LIVE) {
