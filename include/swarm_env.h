@@ -99,7 +99,9 @@ typedef struct swarm_config {
                                      * that holds both cell sets the lattice walk serves and cell sets it does not runs the generic scan
                                      * for every env (one launch) instead of one launch of each kernel; bit 4: those two launches run
                                      * one after the other on the handle's stream instead of side by side -- results are identical
-                                     * with any of them; bits 8..15: diagnostics (tools/ablate.py) */
+                                     * with any of them; bits 8..15: diagnostics (tools/ablate.py) -- the lattice kernels of 64 agent
+                                     * threads (N in 33..64, full geometry) act on them only in a library built with -DSWARM_DIAG and
+                                     * ignore them otherwise; every other kernel always acts on them */
     double d_sen;                   /* assembly.py:199  = 0.4 */
     double r_avoid;                 /* assembly.py:124 */
     double size_a;                  /* assembly.py:44   = 0.035 */

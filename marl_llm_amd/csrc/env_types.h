@@ -60,7 +60,8 @@ struct KP {
     int cap_even;              // the expert's export pass: ties of round(i*step) go to even, as np.round sends them (assembly.py:564);
                                // the observation itself rounds them away from zero (std::round, CPP:223).  Ties need G-1 even.
     int dbg_phase, dbg_extra;  // diagnostics only (tools/ablate.py): run phase dbg_phase dbg_extra EXTRA times; the
-                               // phases are idempotent, so results are unchanged and the extra cost is the phase's cost
+                               // phases are idempotent, so results are unchanged and the extra cost is the phase's cost.
+                               // (The N = 64 lattice kernels read them only in a -DSWARM_DIAG build: swarm_env.hip, DIAG.)
     int off_cxyf, off_partc, off_lat, off_cov, off_flag;
     // lattice (row-space) launches only: per-agent frame, per (window row, agent) column masks / first cell index, per-agent
     // row counts, the agent permutation of the list phase, the fp32 reward verdicts, the occupied columns (export only)

@@ -180,11 +180,20 @@ __device__ __forceinline__ double clamp_ref(double v, double lo, double hi)
     return (lo < m) ? m : lo;
 }
 
-#define REPS(k) ((P.dbg_phase == (k)) ? P.dbg_extra + 1 : 1)
+// The ablation hooks (tools/ablate.py): run phase k EXTRA more times; leave the kernel after segment k.  DIAG is a constexpr
+// of the instantiation (k_env): the lattice kernels of 64 agents carry the hooks only in a library built with -DSWARM_DIAG
+// -- there REPS(k) is the constant 1 and EXIT_AT(k) is empty, and KP::dbg_phase / dbg_extra are never read -- every other
+// kernel always does.
+#ifdef SWARM_DIAG
+constexpr bool kDiagBuild = true;
+#else
+constexpr bool kDiagBuild = false;
+#endif
+#define REPS(k) (DIAG ? ((P.dbg_phase == (k)) ? P.dbg_extra + 1 : 1) : 1)
 #define FENCE() asm volatile("" ::: "memory")
 // diagnostics only (tools/ablate.py --cumulative): leave the kernel after segment k (debug phase 15, extra = k); outputs
 // are then incomplete, so only timing / counter runs use it
-#define EXIT_AT(k) do { if (P.dbg_phase == 15 && P.dbg_extra == (k)) return; } while (0)
+#define EXIT_AT(k) do { if constexpr (DIAG) { if (P.dbg_phase == 15 && P.dbg_extra == (k)) return; } } while (0)
 
 #ifdef SWARM_STAMPS
 // written straight to global memory by lane 0 of every wave (no registers held across the kernel)
@@ -386,6 +395,10 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
     constexpr int ACTW = G_::ACTW, LPA = G_::LPA, AGW = G_::AGW;
     static_assert(!HALF || LAT, "the half-occupied geometry exists for the lattice path only");
     static_assert(!HALF || !FILT, "the launches of a mixed batch use the full geometry");
+    // ablation hooks (REPS / EXIT_AT): compiled out of the N = 64 lattice kernels of the full geometry -- the TGT_LDS kernels
+    // below -- unless the library is a diagnostic build.  They sit at the 72-VGPR limit of seven workgroups per CU, and the
+    // hooks cost them an SGPR pair held across the kernel, a run-time loop around every phase and twelve edges to the end.
+    constexpr bool DIAG = kDiagBuild || !(LAT && NPAD == 64 && !HALF);
     typedef typename Pair<OT>::type OT2;
 
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1322,13 +1335,18 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
     // M is one LDS read per value at `has ? neighbour : own` (positions of a target outside the shape: at its `tgt` entry);
     // Q is `own` or 0.  (Zeros are selected, never made by a product: (-0) - (-0) is not (-0) - 0.)  With eight blocks to a
     // row -- the reference's topology -- a lane's block and its kind are fixed over the chunks.
-    // Chunks c of every eight: A takes [0, SWARM_HEAD_A), C the rest but the last SWARM_HEAD_B, which B takes behind its prior
-    // (5 / 3 / 0 as in head_blocks; 4 / 4, 4 / 3 / 1 and 5 / 2 / 1 measured the same: profiles/r16).
+    // Chunks c of every eight: A takes [0, SWARM_HEAD_A), C the rest but the last SWARM_HEAD_B + SWARM_HEAD_D: B takes
+    // SWARM_HEAD_B of them behind its prior, D the last SWARM_HEAD_D ahead of its rows
+    // (5 / 3 / 0 / 0 as in head_blocks; 4 / 4, 4 / 3 / 1 and 5 / 2 / 1 measured the same: profiles/r16; with the straight-line
+    // chunks 4 / 4 is 0.3 us behind and 3 / 3 / 0 / 2 1 us -- D has the longest lists: profiles/r17).
 #ifndef SWARM_HEAD_A
 #define SWARM_HEAD_A 5
 #endif
 #ifndef SWARM_HEAD_B
 #define SWARM_HEAD_B 0
+#endif
+#ifndef SWARM_HEAD_D
+#define SWARM_HEAD_D 0
 #endif
     auto head_blocks_tgt = [&]() {
         static_assert(!TGT_LDS || (EPB == 1 && NW == 1), "one env per workgroup, row = agent thread");
@@ -1337,14 +1355,16 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             FENCE();
             const int NB = P.with_self + P.topo + 1;
             const int total = rows * NB, n_it = (total + 63) >> 6;
-            auto owner = [](int it_) -> int { const int c8 = it_ & 7; return c8 < SWARM_HEAD_A ? 0 : (c8 < 8 - SWARM_HEAD_B ? 2 : SB); };
+            auto owner = [](int it_) -> int { const int c8 = it_ & 7; return c8 < SWARM_HEAD_A ? 0 : (c8 < 8 - SWARM_HEAD_B - SWARM_HEAD_D ? 2 : (c8 < 8 - SWARM_HEAD_D ? SB : 3)); };
             // a wave without chunks leaves here: the set-up below and the induction registers of the chunk loop are vector
             // instructions too (about 80 per wave on B and D, which own nothing)
-            if (!(sx == 0 || sx == 2 || (SWARM_HEAD_B > 0 && sx == SB))) continue;
-            // block blk (of the kind the flags say) of row r
-            auto put = [&](const int r, const int blk, const bool is_self, const bool is_nei, const bool is_tgt) {
-                const int j = snei[r * kNeiStride + (is_nei ? blk - P.with_self : 0)];
-                const int ncf = sncf[r];
+            if (!(sx == 0 || sx == 2 || (SWARM_HEAD_B > 0 && sx == SB) || (SWARM_HEAD_D > 0 && sx == 3))) continue;
+            // block blk (of the kind the flags say) of row r, from its two index words: j, the neighbour slot (slot_of), and ncf
+            // (plain: the caller has checked that the arena is not periodic and that rows are a whole number of blocks -- a
+            // constant at each call, so that such a chunk is one basic block)
+            auto slot_of = [&](const int r, const int blk, const bool is_nei) -> int { return snei[r * kNeiStride + (is_nei ? blk - P.with_self : 0)]; };
+            auto emit = [&](const int r, const int blk, const bool is_self, const bool is_nei, const bool is_tgt, const bool plain,
+                            const int j, const int ncf) {
                 const bool has = is_nei && j >= 0, out_t = is_tgt && !(ncf >> 30);
                 const int m = has ? j : r;
                 const double *tq = reinterpret_cast<const double *>(tgt + r);
@@ -1355,9 +1375,9 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
                 const double qx = q0 ? 0.0 : ox, qy = q0 ? 0.0 : oy, qu = is_self ? 0.0 : ou, qv = is_self ? 0.0 : ov;
                 const double mu = out_t ? 0.0 : mu_, mv = out_t ? 0.0 : mv_;
                 double a = mx - qx, b = my - qy;
-                if (P.periodic && is_nei) wrap_rel(a, b, P.w_half, P.h_half);
+                if (!plain && P.periodic && is_nei) wrap_rel(a, b, P.w_half, P.h_half);
                 OT2 *dst = out + (size_t)r * PPR + 2 * blk;
-                if ((PPR & 1) == 0) {                                    // rows are a whole number of blocks: 4-value stores stay aligned
+                if (plain || (PPR & 1) == 0) {                           // rows are a whole number of blocks: 4-value stores stay aligned
                     const OT4 o = {to_out<OT>(a), to_out<OT>(b), to_out<OT>(mu - qu), to_out<OT>(mv - qv)};
                     __builtin_nontemporal_store(o, reinterpret_cast<OT4 *>(dst));
                 } else {                                                 // odd list length (non-reference configs)
@@ -1366,15 +1386,40 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
                     store_nt(dst, o0); store_nt(dst + 1, o1);
                 }
             };
+            auto put = [&](const int r, const int blk, const bool is_self, const bool is_nei, const bool is_tgt) {
+                emit(r, blk, is_self, is_nei, is_tgt, false, slot_of(r, blk, is_nei), sncf[r]);
+            };
             if (NB == 8) {
                 const int blk = lane & 7;
                 const bool is_tgt = blk == 7, is_self = P.with_self && blk == 0, is_nei = !is_tgt && !is_self;
-                // (a rolled loop: unrolled over the eight chunks, with or without a scheduling barrier between them, every
-                // TGT_LDS kernel takes 64 - 84 B of scratch)
-                for (int it_ = 0; it_ < n_it; ++it_) {
-                    if (sx != owner(it_)) continue;
-                    const int r = it_ * 8 + (lane >> 3);
-                    if (r < rows) put(r, blk, is_self, is_nei, is_tgt);
+                if (!DIAG && rows == 64 && !P.periodic && (PPR & 1) == 0) {
+                    // Every row of the env, the plain case, without the ablation hooks: the wave's chunks [F, F + C) are
+                    // straight-line code -- no branch and no induction arithmetic between them, and nothing paid for the chunks
+                    // of the other waves.  The index words of all of them are read first, so that the reads of a chunk's values
+                    // are issued ahead of the previous chunk's conversion and store.
+                    const int r0 = lane >> 3;
+                    auto run = [&](auto first, auto count) {
+                        constexpr int F = decltype(first)::value, C = decltype(count)::value;
+                        int j[C > 0 ? C : 1], ncf[C > 0 ? C : 1];
+                        static_for<C>([&](auto c) { constexpr int k = decltype(c)::value; const int r = (F + k) * 8 + r0; j[k] = slot_of(r, blk, is_nei); ncf[k] = sncf[r]; });
+                        static_for<C>([&](auto c) { constexpr int k = decltype(c)::value; emit((F + k) * 8 + r0, blk, is_self, is_nei, is_tgt, true, j[k], ncf[k]); });
+                    };
+                    typedef std::integral_constant<int, SWARM_HEAD_A> nA;
+                    typedef std::integral_constant<int, SWARM_HEAD_B> nB;
+                    typedef std::integral_constant<int, SWARM_HEAD_D> nD;
+                    typedef std::integral_constant<int, 8 - SWARM_HEAD_A - SWARM_HEAD_B - SWARM_HEAD_D> nC;
+                    if (sx == 0) run(std::integral_constant<int, 0>{}, nA{});
+                    else if (sx == 2) run(nA{}, nC{});
+                    else if (sx == SB) run(std::integral_constant<int, 8 - SWARM_HEAD_B - SWARM_HEAD_D>{}, nB{});
+                    else run(std::integral_constant<int, 8 - SWARM_HEAD_D>{}, nD{});
+                } else {
+                    // (a rolled loop: unrolled over the eight chunks behind their owner tests, with the hooks every TGT_LDS kernel
+                    // takes 64 - 84 B of scratch, and without them it measures the same as the loop: profiles/r17)
+                    for (int it_ = 0; it_ < n_it; ++it_) {
+                        if (sx != owner(it_)) continue;
+                        const int r = it_ * 8 + (lane >> 3);
+                        if (r < rows) put(r, blk, is_self, is_nei, is_tgt);
+                    }
                 }
             } else {
                 for (int it_ = 0; it_ < n_it; ++it_) {

@@ -41,7 +41,22 @@ def run(skip, n_a, E, sy, ra, state, steps=int(os.environ.get('ABLATE_STEPS', '6
     return ms
 
 
+def use_diag_library():
+    """The hooks this tool drives are compiled out of the N = 64 lattice kernels of the shipped library (csrc/swarm_env.hip,
+    DIAG): run against the DIAGNOSTIC library, built with -DSWARM_DIAG (here if it is missing or stale -- on a GPU box build
+    it beforehand: marl_llm_amd.build.build_lib(defines=["-DSWARM_DIAG"])).  SWARM_LIB overrides the choice.  Returns whether
+    the library in use is that build.  Call before the first SwarmBatch: the library is loaded once."""
+    from marl_llm_amd.build import build_lib, variant
+    defines = ["-DSWARM_DIAG"]
+    if "SWARM_LIB" not in os.environ:
+        os.environ["SWARM_LIB"] = build_lib(defines=defines)
+    return os.path.realpath(os.environ["SWARM_LIB"]) == os.path.realpath(variant(defines)[1])
+
+
 def main():
+    if not use_diag_library():
+        print(f"note: {os.environ['SWARM_LIB']} is not the -DSWARM_DIAG library: unless it was built with that define, the N = 64 "
+              "lattice kernels ignore debug_flags bits 8-15 and every row below is the full kernel")
     dbg = sys.argv[sys.argv.index("--dbg") + 1] if "--dbg" in sys.argv else None
     pos = [a for a in sys.argv[1:] if not a.startswith('--') and a != dbg]
     n_a = int(pos[0]) if len(pos) > 0 else 64

@@ -2,6 +2,9 @@
 """Parse a rocprofv3 --pmc counter CSV of tools/ablate.py: per-variant mean of a counter over the timed step dispatches
 (each variant = 5 warm-up + k timed launches of k_env<..., true>).
 
+tools/ablate.py loads the diagnostic library (-DSWARM_DIAG): the shipped N = 64 lattice kernels have no repeat hooks, and a
+CSV taken against them shows the full kernel in every row.
+
 Collect it like this (GPU box): the step count is exported in the CALLING shell and python3 comes directly after `--` -- on
 this pool nothing may sit between the profiler and the interpreter (no `env VAR=...`, no shebang hop), because the
 profiler's preloaded library has already initialised the GPU and every such hop is an exec:

@@ -3,7 +3,8 @@
 (marl_llm_amd.build.build_lib(stamps=True): in-kernel clock64 stamps at every barrier and phase boundary, one record per
 wave) and prints, for each role (split A = forces / reward combine, B = prior / insertion, C and D = walk only), the mean
 cycles between consecutive stamp points.  Read SHARES, not absolute time: the stamps fence the scheduler
-(cdna_hip_programming.md section 7).  Usage: python3 tools/phase_profile.py [agents] [envs]"""
+(cdna_hip_programming.md section 7).  The stamps are independent of the ablation hooks (-DSWARM_DIAG): the stamped library
+has none in the N = 64 lattice kernels, like the shipped one.  Usage: python3 tools/phase_profile.py [agents] [envs]"""
 import ctypes
 import os
 import sys
