@@ -360,6 +360,76 @@ __device__ __forceinline__ float psi5_u_f32(float u)
     return c;
 }
 
+// The nearest-cell candidates of the lattice rows b = wr, wr + WS, ... < nrows of one env for the WALK_LEAN kernels (k_env,
+// part 3): per row the nearest set column below the split column a_r (`dn`) and from it on (`up`), best and runner-up d2
+// in lattice units, and the cell index of the best (0 when the lane is inactive or saw no cell).  MT: the row-mask word.
+// What row_cands + the plain loop of k_env compute, in fewer instructions per row:
+//  - A side without a set column is not selected to +inf: the raw first-bit instructions answer 0xFFFFFFFF for a zero word,
+//    which the saturating adds (up) and the xor (down) keep >= 0xFFFFFFC0, so the column converts to ~4.29e9 and the
+//    candidate's d2 is >= 1.8e19 whatever the agent's coordinates within coord_lim (lanes outside it take the exact scan).
+//    Every real candidate has the operands and the operations of row_cands, so its d2 is that bit for bit.  A second32
+//    at or above kNoCand means that no second candidate was seen.
+//  - The loop tracks WHICH candidate leads (its trip, row in the trip and side), not its cell index: the winner's
+//    rowstart + popcount is worked out once behind the loop.
+//  - Four rows a trip: one address, the rows of the trip in the reads' offset fields; the candidate number 0..7 is an inline
+//    constant of the select, the trip is noted once, behind its rows.  The last trip holds one to three rows: the rows past
+//    the lattice's last are empty words there, candidates at the sentinel distance.
+//  - Inactive lanes walk along (their coordinates are whatever the state buffer holds) and are set to +inf / cell 0 behind it.
+constexpr float kNoCand = 1e18f;
+template <typename MT, int WS>
+__device__ __forceinline__ void nearest_rows_lean(const u64 *rm, const short *rs, const int nrows, const int wr, const float apf,
+                                                  const float bpf, const int a_r, const MT lowm, const bool act,
+                                                  float &best32, float &second32, int &bc)
+{
+    constexpr int MB = (int)sizeof(MT) * 8;
+    auto rowmask = [&](int b) -> MT { return MB == 32 ? (MT)reinterpret_cast<const unsigned *>(rm)[2 * b] : (MT)rm[b]; };
+    // lowest / highest set bit of a 32-bit word, 0xFFFFFFFF for zero (the plain builtins are undefined there)
+    auto ffbl = [](unsigned v) -> unsigned { unsigned r; asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(v)); return r; };
+    auto ffbh = [](unsigned v) -> unsigned { unsigned r; asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(v)); return r; };
+    auto sat = [](unsigned x, unsigned y) -> unsigned { return __builtin_elementwise_add_sat(x, y); };
+    int lead = 0, lead_b = 0;
+    auto cand_row = [&](int b, MT rowm, auto kc) {
+        constexpr int k = decltype(kc)::value;
+        const float dy = (float)b - bpf, dy2 = dy * dy;
+        const MT up = rowm >> a_r, dn = rowm & lowm;
+        unsigned fu, fd;                                         // first column of `up`, last of `dn` counted from the top bit
+        if constexpr (MB == 32) { fu = ffbl((unsigned)up); fd = ffbh((unsigned)dn); }
+        else {
+            fu = min(ffbl((unsigned)up), sat(ffbl((unsigned)((u64)up >> 32)), 32u));
+            fd = min(ffbh((unsigned)((u64)dn >> 32)), sat(ffbh((unsigned)dn), 32u));
+        }
+        const unsigned a_up = sat((unsigned)a_r, fu), a_dn = fd ^ (unsigned)(MB - 1);
+        const float dxu = (float)a_up - apf, dxd = (float)a_dn - apf;
+        const float d2u = fmaf(dxu, dxu, dy2), d2d = fmaf(dxd, dxd, dy2);
+        // lower cell index first: on an exact tie the strict compare keeps it (and the tie is re-done exactly)
+        second32 = __builtin_amdgcn_fmed3f(best32, second32, d2d);
+        bool lt = d2d < best32;
+        best32 = lt ? d2d : best32; lead = lt ? 2 * k : lead;
+        second32 = __builtin_amdgcn_fmed3f(best32, second32, d2u);
+        lt = d2u < best32;
+        best32 = lt ? d2u : best32; lead = lt ? 2 * k + 1 : lead;
+    };
+    auto trip = [&](int b, auto tail) {
+        constexpr bool TAIL = decltype(tail)::value;
+        const MT m0 = rowmask(b), m1 = (!TAIL || b + WS < nrows) ? rowmask(b + WS) : (MT)0;
+        const MT m2 = (!TAIL || b + 2 * WS < nrows) ? rowmask(b + 2 * WS) : (MT)0;
+        const float best_in = best32;
+        cand_row(b, m0, std::integral_constant<int, 0>{}); cand_row(b + WS, m1, std::integral_constant<int, 1>{});
+        cand_row(b + 2 * WS, m2, std::integral_constant<int, 2>{});
+        if constexpr (!TAIL) cand_row(b + 3 * WS, rowmask(b + 3 * WS), std::integral_constant<int, 3>{});
+        lead_b = best32 < best_in ? b : lead_b;
+    };
+    int b = wr;
+    for (; b + 3 * WS < nrows; b += 4 * WS) trip(b, std::false_type{});
+    if (b < nrows) trip(b, std::true_type{});
+    const bool found = act && best32 < kNoCand;                  // (a split always has a row with a cell)
+    const int lrow = found ? lead_b + (lead >> 1) * WS : 0;
+    const MT below = rowmask(lrow) & lowm;
+    const int lc = rs[lrow] + (MB == 32 ? __popc((unsigned)below) : __popcll((unsigned long long)below)) - 1 + (lead & 1);
+    bc = found ? lc : 0;
+    if (!act) { best32 = INFINITY; second32 = INFINITY; }
+}
+
 // LAT: every env's target cells are a lattice subset (host-detected, KP::lattice) -- a compile-time switch, so that each
 // instantiation carries ONE cell path and stays inside the 64 KB instruction cache: the row-space lattice walk, or the
 // generic scan of all cells.
@@ -399,6 +469,14 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
     // below -- unless the library is a diagnostic build.  They sit at the 72-VGPR limit of seven workgroups per CU, and the
     // hooks cost them an SGPR pair held across the kernel, a run-time loop around every phase and twelve edges to the end.
     constexpr bool DIAG = kDiagBuild || !(LAT && NPAD == 64 && !HALF);
+    // the same twelve kernels walk the lattice rows in fewer instructions (part 3): the nearest-cell loop takes empty sides by
+    // a sentinel distance, four rows a trip and the winner's cell index once; an env picks the 32-bit walk by its own width;
+    // split B leaves out the lattice coordinates that only the walking splits read.  The switch below exists for A/B builds
+    // (profiles/r18).
+    constexpr bool WALK_LEAN = LAT && NPAD == 64 && !HALF;
+#ifndef SWARM_WALK_ENV32
+#define SWARM_WALK_ENV32 1                     // an env of <= 32 columns takes the 32-bit walk whatever the batch's widest (0: lat_n32 alone)
+#endif
     typedef typename Pair<OT>::type OT2;
 
     extern __shared__ __align__(16) unsigned char smem[];
@@ -917,8 +995,10 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
         // tolerance of detect_lattice) + ~1e-6 (fp32 radius / sqrt roundings), i.e. < 2e-5 steps for |coordinate| <= 128.
         // The sets stay in ROW space: window row t of an agent is lattice row b0 + t, its in-range columns are kept as a
         // 32-bit word relative to the agent's first possible column ca0 (the window is <= 17 columns wide).
+        // (split B does not walk and is not split 0: in the WALK_LEAN kernels it passes all of this by)
+        if (!(WALK_LEAN && WPE > 1) || sx != SB) {
         const LatEnv &L = P.lat[es];
-        const double apd = (px - L.ox) * L.uxi + (py - L.oy) * L.uyi;
+        const double apd =(px - L.ox) * L.uxi + (py - L.oy) * L.uyi;
         const double bpd = (px - L.ox) * L.vxi + (py - L.oy) * L.vyi;
         const float apf = (float)apd, bpf = (float)bpd;
         const int nrows = L.nrows, ncols = L.ncols;
@@ -952,13 +1032,16 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
         auto range = [](int lo, int hi) -> MT { return hi >= lo ? (MT)((~(MT)0 >> (MB - 1 - hi)) & (~(MT)0 << lo)) : (MT)0; };
         auto row_sel = [&](int b, float rho, double cut) -> MT {
             // columns of row b within lattice distance rho of (apf, bpf); exact test d2 < cut on the boundary columns
-            const bool rowok = act && b >= 0 && b < nrows;
+            // (LEAN: one unsigned compare for both ends of the row range, and the clamp of ho2 as one v_med3 -- fmaxf costs
+            // a canonicalising v_max in front of its own; the same values)
+            constexpr bool LEAN = WALK_LEAN;
+            const bool rowok = LEAN ? act && (unsigned)b < (unsigned)nrows : act && b >= 0 && b < nrows;
             const float dy = (float)b - bpf, dy2 = dy * dy;
             const float ro = rho + lat_m, ri = rho - lat_m, ri2 = ri > 0.0f ? ri * ri : 0.0f;
             const float ho2 = ro * ro - dy2;
             const bool any_o = rowok && ho2 > 0.0f;
             // raw v_sqrt_f32 (1 ulp): its error is far inside the margin
-            const float ho = __builtin_amdgcn_sqrtf(fmaxf(ho2, 0.0f));
+            const float ho = __builtin_amdgcn_sqrtf(LEAN ? __builtin_amdgcn_fmed3f(ho2, 0.0f, INFINITY) : fmaxf(ho2, 0.0f));
             int ao0 = (int)ceilf(apf - ho), ao1 = (int)floorf(apf + ho);     // columns that may be in range
             ao0 = ao0 < 0 ? 0 : ao0; ao1 = ao1 > ncols - 1 ? ncols - 1 : ao1;
             const int bq = b < 0 ? 0 : (b > 63 ? 63 : b);
@@ -1024,6 +1107,15 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
                 d2d = (act && dn != 0) ? fmaf(dxd, dxd, dy2) : INFINITY;
                 c_dn = rs[b] + popc(dn) - 1;                                 // the `up` candidate is cell c_dn + 1
             };
+            // `no_cand`: a second32 at or above it means that no second candidate was seen (the sentinel walk below
+            // gives a side without a set column a finite distance above it instead of +inf)
+            // (switched by WALK_LEAN alone: a condition that also names MB here moves registers in the other 150 kernels)
+            float no_cand = INFINITY;
+            if constexpr (WALK_LEAN) no_cand = kNoCand;
+            if constexpr (WALK_LEAN) {
+                // the same candidates in fewer instructions per row: nearest_rows_lean, above the kernel
+                nearest_rows_lean<MT, WS>(rm, rs, nrows, wr, apf, bpf, a_r, lowm, act, best32, second32, bc);
+            } else
             for (int b = wr; b < nr_hi; b += WS) {
                 float d2d, d2u; int c_dn;
                 row_cands(b, d2d, d2u, c_dn);
@@ -1040,7 +1132,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             // fp64 distances, first minimum in ascending cell order (rows ascending, left candidate before right).
             const float lat_dlt = 1.2e-7f * fmaxf(fabsf(apf), fabsf(bpf)) + 2e-6f;
             const float tol = 6.0f * sqrtf(second32) * lat_dlt + 1e-9f;
-            const bool unc_min = act && (wave_exact || (second32 < INFINITY && (second32 - best32) <= tol));
+            const bool unc_min = act && (wave_exact || (second32 < no_cand && (second32 - best32) <= tol));
             if (__any(unc_min)) {
                 if (unc_min) {
                     const float thr = wave_exact ? INFINITY : best32 + tol;
@@ -1062,7 +1154,10 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             }
         }
         };
-        if (sx != SB || WPE == 1) { if (P.lat_n32) walk(0u); else walk((u64)0); }
+        // (WALK_LEAN, one env per workgroup: the env's OWN column count picks the walk -- a batch with one wider shape
+        // keeps the 32-bit walk for the others)
+        if (sx != SB || WPE == 1) { if (P.lat_n32 || (WALK_LEAN && SWARM_WALK_ENV32 && ncols <= 32)) walk(0u); else walk((u64)0); }
+        }
     } else {
     // ---- generic path: every split scans its words of the env's cells, then settles its nearest-cell candidate
     for (int rep = 0, reps = REPS(3); rep < reps; ++rep) {
