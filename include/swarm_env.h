@@ -99,7 +99,10 @@ typedef struct swarm_config {
                                      * that holds both cell sets the lattice walk serves and cell sets it does not runs the generic scan
                                      * for every env (one launch) instead of one launch of each kernel; bit 4: those two launches run
                                      * one after the other on the handle's stream instead of side by side -- results are identical
-                                     * with any of them; bits 8..15: diagnostics (tools/ablate.py) -- the lattice kernels of 64 agent
+                                     * with any of them; bit 5: the rule expert (swarm_rule_action, swarm_rollout_expert's rule source)
+                                     * runs k_rule_large, the kernel of large_swarm handles above 256 agents, instead of k_rule -- the
+                                     * same bits, and no other effect: the in-binary stand-in that lets the two kernels be compared on
+                                     * the same export lists (tests/test_gpu_large_rule.py); bits 8..15: diagnostics (tools/ablate.py) -- the lattice kernels of 64 agent
                                      * threads (N in 33..64, full geometry) act on them only in a library built with -DSWARM_DIAG and
                                      * ignore them otherwise; every other kernel always acts on them */
     double d_sen;                   /* assembly.py:199  = 0.4 */
@@ -115,9 +118,10 @@ typedef struct swarm_config {
                                      * the new state; swarm_step(action = NULL) then applies it as the action */
     int32_t large_swarm;            /* 0 (default): the step kernel, n_agents <= 256.  1: n_agents in [1, 1024]; every step and
                                      * observation pass of the handle runs through the two large-swarm kernels (env_large.hip), at any
-                                     * n_agents, with the same results bit for bit.  Such a handle has no rule expert
-                                     * (swarm_rule_action, swarm_rollout_expert's rule source), reports every env as scanned
-                                     * (swarm_path_envs) and accepts debug_flags without effect */
+                                     * n_agents, with the same results bit for bit.  Above 256 agents such a handle has the rule expert
+                                     * (swarm_rule_action, swarm_rollout_expert: k_rule_large); with n_agents <= 256 it refuses both
+                                     * (the default handle serves those counts).  It reports every env as scanned (swarm_path_envs)
+                                     * and accepts debug_flags, bit 5 included, without effect */
 } swarm_config_t;
 
 int  swarm_abi_version(void);
@@ -247,7 +251,11 @@ int  swarm_metrics(swarm_env_t *h, double *out);
  * agents and cells, the in-shape flag, the nearest cell and the sensed-cell list with its occupied-cell filter all use the
  * plain differences of the stored positions (the observation pass wraps only the topological-neighbour rows).
  * tests/test_gpu_rule_contract.py holds this call and swarm_rollout_expert's rule source to the numpy restatement.
- * Refused (SWARM_ERR_INVALID, nothing enqueued) on a handle created with large_swarm: the expert serves n_agents <= 256. */
+ * Handles created with large_swarm: with n_agents in [257, 1024] the cap_even export pass of the large-swarm kernels, then
+ * k_rule_large (rule_expert.hip: one wave per env and 64 agents, k_rule's arithmetic and operation order; on the same lists
+ * the same bits as k_rule, which debug_flags bit 5 lets a default handle show) -- enqueued on the handle's stream like the
+ * default handle's.  tests/test_gpu_large_rule.py holds it to the same restatement.  With n_agents <= 256 a large_swarm
+ * handle is refused (SWARM_ERR_INVALID, nothing enqueued): the default handle serves n_agents <= 256. */
 int  swarm_rule_action(swarm_env_t *h, double *action);
 
 /* Index scratch of the CURRENT state (device pointers, any may be NULL).  The step keeps neighbor_index / in_flags / the

@@ -86,8 +86,10 @@ int swarm_rollout_logpi(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_
  * Why f32 rows suffice: ReplayBufferExpert.sample hands its rows out through torch.Tensor, i.e. as fp32, and the step's f32
  * observation is the f32 rounding of the fp64 one (the env's parity contract), so AIRL sees the same bits as from the
  * reference's fp64 buffer.
- * Checks as swarm_rollout minus the policy's; n_agents <= 256 for both sources; SWARM_EXPERT_RULE also needs num_obs_grid_max <= 128
- * and a handle without large_swarm (as swarm_rule_action).
+ * Checks as swarm_rollout minus the policy's; SWARM_EXPERT_RULE also needs num_obs_grid_max <= 128 and, as swarm_rule_action,
+ * refuses a large_swarm handle with n_agents <= 256 (the default handle serves those counts).  A large_swarm handle with
+ * n_agents in [257, 1024] is served for both sources: RULE by k_rule_large behind the large-swarm export pass, LLM by the
+ * large-swarm kernels' own act_next.
  * The first RULE call allocates the handle's fp64 action scratch and, unless swarm_rule_action or swarm_get_indices already
  * did, its list scratch (once each); later calls allocate nothing.  A rejected
  * call enqueues nothing; the message is in swarm_rollout_last_error. */

@@ -431,7 +431,9 @@ class SwarmBatch:
         return out
 
     def rule_action(self):
-        """[E, N, 2] float64 tensor: the rule-based expert's action for the current state (assembly.py:530-601)."""
+        """[E, N, 2] float64 tensor: the rule-based expert's action for the current state (assembly.py:530-601).  Default
+        handles (n_agents <= 256) and large_swarm handles of 257 to 1024 agents; a large_swarm handle with n_agents <= 256
+        refuses (SwarmError): the default handle serves those counts."""
         out = torch.empty((self.n_env, self.n_agents, 2), dtype=torch.float64, device=self.device)
         self._sync_stream()
         check(self.lib, self.handle, self.lib.swarm_rule_action(self.handle, _ptr(out)))

@@ -25,16 +25,6 @@ namespace {
 
 thread_local std::string g_create_error;
 
-// smallest double x with sqrt(x) >= t (IEEE sqrt is correctly rounded and monotonic), so that
-// sqrt(d2) < t  <=>  d2 < x  for every d2 >= 0.
-double cut_lt(double t)
-{
-    if (!(t > 0)) return 0.0;
-    double x = t * t;
-    while (x > 0 && std::sqrt(x) >= t) x = std::nextafter(x, 0.0);
-    while (std::sqrt(x) < t) x = std::nextafter(x, INFINITY);
-    return x;
-}
 // sqrt(d2) <= t  <=>  d2 < cut_le(t)
 double cut_le(double t) { return cut_lt(std::nextafter(t, INFINITY)); }
 
@@ -245,6 +235,13 @@ int interleave(swarm_env *h, int e0, int count)
     return SWARM_OK;
 }
 
+// Does the rule expert of this handle run k_rule_large (rule_expert.hip)?  Above k_rule's 256 agents always; on a default handle
+// also with debug_flags bit 5, the in-binary stand-in that lets the two kernels be compared on the same export lists.
+bool rule_tiled(const swarm_env *h)
+{
+    return h->cfg.n_agents > 256 || (!h->cfg.large_swarm && (h->cfg.debug_flags & 32) != 0);
+}
+
 }  // namespace
 
 int swarm_internal::fail(swarm_env *h, int code, const std::string &msg)
@@ -260,6 +257,7 @@ int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out)
     out->obs_dtype = h->cfg.obs_dtype; out->with_prior = h->cfg.with_prior != 0; out->observed = h->observed;
     out->g_max = h->kp.g_max; out->llm_action = h->cfg.llm_action != 0; out->n_shapes = h->n_shapes;
     out->large_swarm = h->cfg.large_swarm != 0;
+    out->rule_tiled = rule_tiled(h);
     return SWARM_OK;
 }
 
@@ -815,14 +813,14 @@ int swarm_rule_action(swarm_env_t *h, double *action)
     if (!h || !action) return SWARM_ERR_INVALID;
     if (!h->observed) return fail(h, SWARM_ERR_STATE, "swarm_rule_action: nothing observed yet");
     if (h->kp.g_max > 128) return fail(h, SWARM_ERR_INVALID, "swarm_rule_action: num_obs_grid_max > 128 not supported");
-    if (h->cfg.large_swarm) return fail(h, SWARM_ERR_INVALID, "swarm_rule_action: not available on a large_swarm handle (the rule expert serves n_agents <= 256 with large_swarm = 0)");
+    if (h->cfg.large_swarm && h->cfg.n_agents <= 256) return fail(h, SWARM_ERR_INVALID, "swarm_rule_action: not available on a large_swarm handle (the rule expert serves n_agents <= 256 with large_swarm = 0)");
     DeviceGuard g(h->device);
     int rc = export_pass(h, true, true);
     if (rc != SWARM_OK) return rc;
     swarm_expert_view v;
     rc = swarm_internal_expert_view(h, false, &v);
     if (rc != SWARM_OK) return rc;
-    HIP_TRY(h, swarm_internal_launch_rule(v, action, nullptr, h->stream));       // k_rule (rule_expert.hip)
+    HIP_TRY(h, swarm_internal_launch_rule(v, action, nullptr, h->stream, rule_tiled(h)));       // k_rule / k_rule_large (rule_expert.hip)
     return SWARM_OK;
 }
 

@@ -343,8 +343,8 @@ int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t ste
         if (m.empty()) m = check_ring_slots(ei, ring);
         if (!m.empty()) return fail(SWARM_ERR_INVALID, m, who);
     }
-    if (ei.n_agents > 256) return fail(SWARM_ERR_INVALID, "n_agents > 256", who);
-    if (source == SWARM_EXPERT_RULE && ei.large_swarm)
+    // (a large_swarm handle above 256 agents is served for both sources: k_rule_large, and act_next of the large-swarm kernels)
+    if (source == SWARM_EXPERT_RULE && ei.large_swarm && ei.n_agents <= 256)
         return fail(SWARM_ERR_INVALID, "the rule expert is not available on a large_swarm handle (it serves n_agents <= 256 with large_swarm = 0)", who);
     if (source == SWARM_EXPERT_RULE && ei.g_max > 128)
         return fail(SWARM_ERR_INVALID, "the rule expert needs num_obs_grid_max <= 128 (as swarm_rule_action)", who);
@@ -361,7 +361,7 @@ int swarm_rollout_expert(swarm_env_t *env, const swarm_ring_t *ring, int32_t ste
         const int rc = swarm_internal_expert_view(env, source == SWARM_EXPERT_RULE, &v);
         if (rc != SWARM_OK) return fail(rc, swarm_last_error(env), who);
         if (source == SWARM_EXPERT_RULE) {
-            if (int e = L.check(swarm_internal_launch_rule(v, reinterpret_cast<double *>(v.act64), L.act(t), L.st), "k_rule")) return e;
+            if (int e = L.check(swarm_internal_launch_rule(v, reinterpret_cast<double *>(v.act64), L.act(t), L.st, ei.rule_tiled), "k_rule")) return e;
             return L.step(v.act64, SWARM_F64, t);
         }
         hipLaunchKernelGGL(k_act_f32, dim3(L.row_grid()), dim3(kThreads), 0, L.st, v.act_next, reinterpret_cast<float2 *>(L.act(t)), L.rows);

@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -54,6 +55,17 @@ __device__ inline double np_sum_stream(int n, F f)
     double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
     for (; i < n; ++i) res += f(i);
     return res;
+}
+
+// smallest double x with sqrt(x) >= t (IEEE sqrt is correctly rounded and monotonic), so that
+// sqrt(d2) < t  <=>  d2 < x  for every d2 >= 0 (and for a NaN d2: both false).  Host code: the kernels get the cut.
+inline double cut_lt(double t)
+{
+    if (!(t > 0)) return 0.0;
+    double x = t * t;
+    while (x > 0 && std::sqrt(x) >= t) x = std::nextafter(x, 0.0);
+    while (std::sqrt(x) < t) x = std::nextafter(x, INFINITY);
+    return x;
 }
 
 // np.clip(v, -1, 1): NaN compares false both ways and passes through (fmin / fmax would return the bound); every other
@@ -118,7 +130,9 @@ inline size_t obs_elem_bytes(int dtype) { return with_obs_type(dtype, [](auto t)
 struct swarm_env_info {
     int device, n_env, n_agents, obs_dim, obs_dtype, g_max, n_shapes;
     bool with_prior, observed, llm_action;
-    bool large_swarm;             // created with swarm_config_t.large_swarm: stepped by env_large.hip, no rule expert
+    bool large_swarm;             // created with swarm_config_t.large_swarm: stepped by env_large.hip; the expert (rule and 'llm')
+                                  // serves such a handle above 256 agents only -- at 256 or fewer the default handle does
+    bool rule_tiled;              // the rule expert runs k_rule_large, not k_rule: n_agents > 256, or debug_flags bit 5 on a default handle
 };
 SWARM_HIDDEN int swarm_internal_env_info(const swarm_env_t *h, swarm_env_info *out);
 
@@ -142,8 +156,9 @@ SWARM_HIDDEN int swarm_internal_expert_view(swarm_env_t *h, bool lists, swarm_ex
 
 // Enqueue the rule-expert kernel (rule_expert.hip) on `st` for the lists in `v`: the fp64 action into act64 [E][N][2] (8-byte
 // aligned; 16-byte aligned when act32 is given, as v.act64 is) and, act32 != NULL, its f32 rounding into act32 [E][N][2].
-// Returns the launch's hipGetLastError().
-SWARM_HIDDEN hipError_t swarm_internal_launch_rule(const swarm_expert_view &v, double *act64, float *act32, hipStream_t st);
+// The kernel is k_rule (one workgroup per env, n_agents <= 256) unless n_agents > 256 or `tiled` (swarm_env_info.rule_tiled):
+// then k_rule_large, one wave per (env, 64 agents), the same arithmetic.  Returns the launch's hipGetLastError().
+SWARM_HIDDEN hipError_t swarm_internal_launch_rule(const swarm_expert_view &v, double *act64, float *act32, hipStream_t st, bool tiled);
 
 // The evaluation loop's per-step metrics launch: out[E][3] (DEVICE), bit for bit what swarm_metrics writes (k_metrics_step in
 // env_kernels.hip).  Enqueued on the handle's stream; no host synchronisation.

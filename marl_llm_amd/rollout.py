@@ -582,7 +582,8 @@ def rollout_expert(env, steps, obs=None, replay=None, reset=None, source="rule",
     collect_expert_data.py's loop (agent_strategy 'rule' / 'llm' with is_collected).  Enqueued on torch's current stream;
     returns without a host synchronisation.
 
-    env    : a SwarmBatch, or an AssemblySwarmEnv whose agent_strategy is `source` (its float32 / bfloat16 backend).
+    env    : a SwarmBatch, or an AssemblySwarmEnv whose agent_strategy is `source` (its float32 / bfloat16 backend).  Up to
+             256 agents on a default batch, 257 to 1024 on a large_swarm one (both sources).
     source : "rule" -- the rule-based expert (assembly.py:530-601) computed on the device in fp64 (bit-identical to
              SwarmBatch.rule_action()); the env steps with that fp64 action and the ring's act row holds its f32 rounding.
              "llm"  -- the prior policy's twin (a batch created with llm_action): the ring's act row is the applied action,

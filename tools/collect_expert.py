@@ -26,7 +26,7 @@ from marl_llm_amd.shapes import load_results, r_avoid_for, synthetic_shape_set
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--n_a", type=int, default=30)
+    ap.add_argument("--n_a", type=int, default=30, help="agents per episode, 1 to 1024")
     ap.add_argument("--n_episodes", type=int, default=500)
     ap.add_argument("--episode_length", type=int, default=200)
     ap.add_argument("--envs-per-call", type=int, default=500, help="episodes per rollout_expert call (must divide n_episodes)")
@@ -47,7 +47,9 @@ def main():
     shapes = load_results(args.shapes) if args.shapes else synthetic_shape_set()
     ng_max = max(np.asarray(g).shape[0] for g in shapes["grid_coords"])
     dtype = torch.float32 if args.obs_dtype == "float32" else torch.bfloat16
-    sb = SwarmBatch(n_env=E, n_agents=args.n_a, n_cells_max=ng_max, r_avoid=r_avoid_for(args.n_a, shapes), obs_dtype=dtype)
+    # (above the step kernel's 256 agents the large-swarm kernels step the envs and k_rule_large is the expert; up to 1024)
+    sb = SwarmBatch(n_env=E, n_agents=args.n_a, n_cells_max=ng_max, r_avoid=r_avoid_for(args.n_a, shapes), obs_dtype=dtype,
+                    large_swarm=args.n_a > 256)
     sb.set_shapes(shapes)
     ring = ChainedReplay(calls * (L + 1) - 1, E * args.n_a, sb.obs_dim, 2, sb.device, obs_dtype=dtype)   # every transition
     print(f"expert collection: {args.n_episodes} episodes x {L} steps x {args.n_a} agents, {E} envs per call, "
