@@ -29,12 +29,12 @@
  * There is no CPU fallback anywhere in this library: without a HIP device every call fails.
  *
  * Memory contract of the batched ABI: every pointer passed to swarm_step / swarm_observe / swarm_select_shapes /
- * swarm_get_indices is a DEVICE pointer (hipMalloc / torch.Tensor.data_ptr()) valid on the handle's
+ * swarm_reset_envs / swarm_get_indices is a DEVICE pointer (hipMalloc / torch.Tensor.data_ptr()) valid on the handle's
  * device.  swarm_set_cells / swarm_set_state / swarm_get_state accept host or device pointers (hipMemcpyDefault).
  *
  * Stream contract (DESIGN.md "Stream contract"; tests/test_gpu_streams.py): all device work goes to the handle's stream
- * (swarm_set_stream; NULL = the default stream).  swarm_step, swarm_observe, swarm_reset, swarm_select_shape(s), swarm_metrics
- * and swarm_rule_action only enqueue: they return without waiting for the stream.  swarm_set_cells, swarm_set_state and the
+ * (swarm_set_stream; NULL = the default stream).  swarm_step, swarm_observe, swarm_reset, swarm_reset_envs, swarm_select_shape(s),
+ * swarm_metrics and swarm_rule_action only enqueue: they return without waiting for the stream.  swarm_set_cells, swarm_set_state and the
  * readers swarm_get_state / _get_cells / _get_shape_index / _get_indices / _get_llm_action / _path_envs, swarm_observe_host,
  * swarm_step_host and swarm_synchronize return after the stream has run everything enqueued so far, their own work included
  * (swarm_get_indices too, although its pointers are device pointers).  swarm_set_shapes and swarm_destroy release device
@@ -149,6 +149,24 @@ int  swarm_set_state(swarm_env_t *h, const double *p, const double *dp);   /* [E
  * env range reproducible on any rank -- and runs the observation pass (obs may be NULL). */
 int  swarm_set_shapes(swarm_env_t *h, int n_shapes, const double *shape_cells, const int32_t *n_g, const double *l_cell);
 int  swarm_reset(swarm_env_t *h, uint64_t seed, uint64_t episode, int64_t env_offset, void *obs);
+/* Per-env device-side reset: the envs named by `episode` start a new episode, the others go on.
+ *   episode  DEVICE int64 [E].  ep >= 0: env e is redrawn exactly as swarm_reset(seed, ep, env_offset) draws env e -- shape index,
+ *     pose, cells (both layouts, padding 0.0), n_g, in-shape cut-off, lattice record, p and dp: the same draws, expressions and
+ *     order, hence the same bits.  A negative entry (-1 is the documented "keep"): nothing of env e is written.
+ * One kernel on the handle's stream, one workgroup per env; then the observation pass runs over the whole batch (obs may be
+ * NULL), as in swarm_select_shapes -- it is idempotent on an env that did not change.  Afterwards a reset env is, for every later
+ * call, bit for bit the env of a handle that ran swarm_reset with that episode, and a kept env continues exactly as if nothing
+ * had been called.
+ *   Enqueue only: no host synchronisation, no allocation, no host-to-device copy.
+ *   Stream order: episode is read when the kernel RUNS, not when the call is made: it must stay valid and hold the intended
+ *     values until then (writes enqueued on the same stream before the call are seen).  Work on other streams that writes it is
+ *     the caller's to order with events.
+ *   Validation first: a NULL handle or a NULL episode returns SWARM_ERR_INVALID; no shape set, no state, or cells not set for
+ *     every env (a kept env needs both) returns SWARM_ERR_STATE; the message starts "swarm_reset_envs:" and nothing is enqueued.
+ * The host does not learn which env was reset: it plans the cell path for the envs' present cell sets and every shape of the set
+ * together (as swarm_select_shapes does); swarm_path_envs reads the device records and stays exact.  Default and large_swarm
+ * handles alike. */
+int  swarm_reset_envs(swarm_env_t *h, uint64_t seed, const int64_t *episode, int64_t env_offset, void *obs);
 /* Device-side shape switch (what eval_assembly.py:34-57 process_shape does in mid-episode, with its rotation 0 and offset 0):
  * every env takes shape `shape_index` of the set uploaded by swarm_set_shapes, at the set's own pose -- the env's cells are the
  * shape's cells, the same doubles.  One kernel on the handle's stream writes the cells, n_g, the in-shape cut-off, the lattice

@@ -49,7 +49,7 @@ BATCHED_SYMBOLS = ("swarm_abi_version", "swarm_default_config", "swarm_create", 
                    "swarm_get_state", "swarm_observe", "swarm_step", "swarm_get_indices",
                    "swarm_step_algorithmic_bytes", "swarm_timer_start", "swarm_timer_stop", "swarm_lattice_envs", "swarm_set_shapes", "swarm_reset", "swarm_get_cells", "swarm_get_shape_index", "swarm_metrics", "swarm_rule_action",
                    "swarm_host_outputs", "swarm_observe_host", "swarm_step_host", "swarm_get_llm_action", "swarm_select_shape", "swarm_path_envs",
-                   "swarm_select_shapes")
+                   "swarm_select_shapes", "swarm_reset_envs")
 POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_destroy", "swarm_policy_forward", "swarm_policy_forward_bf16",
                   "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_forward_explore_logpi",
                   "swarm_policy_set_precision", "swarm_policy_load_device", "swarm_policy_read_packed",
@@ -125,6 +125,7 @@ def load():
     lib.swarm_path_envs.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]; lib.swarm_path_envs.restype = i32
     lib.swarm_set_shapes.argtypes = [vp, i32, vp, vp, vp]; lib.swarm_set_shapes.restype = i32
     lib.swarm_reset.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, vp]; lib.swarm_reset.restype = i32
+    lib.swarm_reset_envs.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_int64, vp]; lib.swarm_reset_envs.restype = i32
     lib.swarm_host_outputs.argtypes = [vp, i32, ctypes.POINTER(HostOut)]; lib.swarm_host_outputs.restype = i32
     lib.swarm_observe_host.argtypes = [vp, i32]; lib.swarm_observe_host.restype = i32
     lib.swarm_step_host.argtypes = [vp, vp, i32, i32, i32]; lib.swarm_step_host.restype = i32

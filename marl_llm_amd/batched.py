@@ -4,7 +4,7 @@ Device memory, streams and tensors come from PyTorch-ROCm; all compute is in the
 Layouts are the ones documented in include/swarm_env.h.
 
 Streams (DESIGN.md "Stream contract"): every call hands the library torch's current stream first.  step, observe, reset,
-select_shape, select_shapes (given device tensors), metrics and rule_action only enqueue on it; set_cells, set_state, the
+select_shape, select_shapes and reset_envs (given device tensors), metrics and rule_action only enqueue on it; set_cells, set_state, the
 readers (get_state, get_cells, get_shape_index, indices, llm_action, path_envs) and the host path (observe_host, step_host)
 return after that stream has run everything enqueued so far; set_shapes and close() wait for pending work that still reads
 what they free.
@@ -255,6 +255,68 @@ class SwarmBatch:
         check(self.lib, self.handle, self.lib.swarm_reset(self.handle, int(seed), int(episode), int(env_offset), _ptr(obs)))
         self.shape_in_force, self.shape_env_in_force, self._posed_env = -1, None, None      # every env drew its own shape
         return obs
+
+    def _episode_args(self, episode):
+        """reset_envs' episode vector, checked on the host: a contiguous int64 host array [E], or the caller's int64 cuda
+        tensor [E].  Raises ValueError; touches neither the device nor the library."""
+        E = self.n_env
+        if isinstance(episode, torch.Tensor) and episode.is_cuda:
+            if episode.dtype != torch.int64 or tuple(episode.shape) != (E,) or not episode.is_contiguous() or episode.device != self.device:
+                raise ValueError(f"a device episode vector must be a contiguous int64 tensor [{E}] on {self.device}")
+            return episode
+        a = np.asarray(episode.cpu() if isinstance(episode, torch.Tensor) else episode)
+        if a.shape != (E,) or a.dtype.kind not in "iu":
+            raise ValueError(f"episode must be an int array [{E}] (a negative entry keeps that env)")
+        if a.dtype.kind == "u" and a.size and int(a.max()) >= 2 ** 63:
+            raise ValueError("episode numbers must fit int64")
+        return np.ascontiguousarray(a, dtype=np.int64)
+
+    def _episode_upload(self, episode):
+        """_episode_args' result on the device: (int64 tensor [E], the host array or None).  The device loops check a whole
+        schedule, then upload it, before they enqueue anything."""
+        host = episode if isinstance(episode, np.ndarray) else None
+        return (torch.from_numpy(host).to(self.device) if host is not None else episode), host
+
+    def _reset_envs_ready(self, seed, ready, env_offset=0, out=None):
+        """The per-env reset itself, for an episode vector that is checked and on the device (_episode_upload's result):
+        enqueue only."""
+        episode, host = ready
+        if out is not None:
+            obs = self._out_ptrs(dict(obs=out))["obs"].view(self.n_env, self.n_agents, self.obs_dim)
+        else:
+            obs = self._obs[self._flip ^ 1]
+        self._sync_stream()
+        check(self.lib, self.handle, self.lib.swarm_reset_envs(self.handle, int(seed) & (2 ** 64 - 1), _ptr(episode), int(env_offset), _ptr(obs)))
+        if out is None:
+            self._flip ^= 1
+        self._note_reset_envs(host)
+        return obs
+
+    def _note_reset_envs(self, host):
+        """Host bookkeeping of a per-env reset: a reset env drew its own shape and pose (unknown shape, posed); with a device
+        episode vector the host does not know who was reset, and everything becomes unknown."""
+        if host is None:
+            self.shape_env_in_force, self._posed_env, self.shape_in_force = None, None, -1
+            return
+        took = host >= 0
+        if not took.any():
+            return
+        if self.shape_env_in_force is not None:
+            s = np.where(took, -1, self.shape_env_in_force).astype(np.int64)
+            self.shape_env_in_force = s if (s >= 0).any() else None
+        prev_posed = self._posed_env if self._posed_env is not None else np.zeros(self.n_env, bool)
+        self._posed_env = np.where(took, True, prev_posed) if self.shape_env_in_force is not None else None
+        self.shape_in_force = -1
+
+    def reset_envs(self, seed, episode, env_offset=0, out=None):
+        """Per-env device-side reset (swarm_reset_envs): env e starts episode episode[e] -- redrawn bit for bit as
+        reset(seed, episode[e], env_offset) draws env e -- or, with a negative entry (-1: keep), goes on untouched.  The
+        observation pass then runs over the whole batch; returns the observation tensor (out as in reset()).
+
+        episode: int array-like [E] on the host (wrong length or a non-integer dtype: ValueError before anything runs; then
+        uploaded), or an int64 cuda tensor [E], passed through: the call then only enqueues, and the tensor is read when
+        the kernel runs (stream order).  Needs a shape set, a state and cells for every env (a kept env needs both)."""
+        return self._reset_envs_ready(seed, self._episode_upload(self._episode_args(episode)), env_offset, out)
 
     def get_cells(self):
         """(cells [E,2,n_cells_max] float64, n_g [E] int32) currently on the device (numpy copies)."""

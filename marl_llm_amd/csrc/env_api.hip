@@ -563,6 +563,28 @@ int swarm_reset(swarm_env_t *h, uint64_t seed, uint64_t episode, int64_t env_off
     return swarm_observe(h, obs);
 }
 
+int swarm_reset_envs(swarm_env_t *h, uint64_t seed, const int64_t *episode, int64_t env_offset, void *obs)
+{
+    if (!h) return SWARM_ERR_INVALID;
+    if (!episode) return fail(h, SWARM_ERR_INVALID, "swarm_reset_envs: null episode");
+    if (h->n_shapes < 1) return fail(h, SWARM_ERR_STATE, "swarm_reset_envs: no shape set (swarm_set_shapes)");
+    if (!h->have_state) return fail(h, SWARM_ERR_STATE, "swarm_reset_envs: state not set (a kept env needs it: swarm_set_state / swarm_reset)");
+    if (!h->have_cells) return fail(h, SWARM_ERR_STATE, "swarm_reset_envs: target cells not set for every env (a kept env needs them)");
+    DeviceGuard g(h->device);
+    HIP_LAUNCHED(h, launch_reset_envs(h->stream, h->kp, shape_set(h), seed, reinterpret_cast<const long long *>(episode), env_offset,
+                                      h->d_cells.get(), h->d_cells_xy.get(), h->d_ng.get(), h->d_cin.get(), h->d_lat.get(), h->d_shape_idx.get()));
+    // which env was reset, and to which shape, only the device knows (as after swarm_select_shapes): every env's record becomes
+    // what holds for its present cells AND for any shape of the set; the device records stay exact
+    const LatInfo set = lattice_summary(h->shape_lat.data(), h->shape_lat.data() + h->shape_lat.size());
+    for (LatInfo &i : h->env_lat) {
+        const LatInfo both[2] = {i, set};
+        i = lattice_summary(both, both + 2);
+    }
+    lattice_mode_of(h, h->env_lat.data(), h->env_lat.data() + h->env_lat.size());
+    h->observed = false;
+    return swarm_observe(h, obs);
+}
+
 int swarm_select_shape(swarm_env_t *h, int32_t shape_index, void *obs)
 {
     if (!h) return SWARM_ERR_INVALID;

@@ -1,6 +1,6 @@
 // env_kernels.hip -- the env library's side kernels: batched reset, shape switch, cell interleave, the evaluation metrics
-// (reference form and per-step form) and the reference-shaped host export.  Each sits behind a launcher declared in
-// env_types.h; the host side (env_api.hip) names no kernel.  The step kernel itself is swarm_env.hip.
+// (reference form and per-step form), the reference-shaped host export and the per-env reset.  Each sits behind a launcher
+// declared in env_types.h; the host side (env_api.hip) names no kernel.  The step kernel itself is swarm_env.hip.
 //
 // Like the step kernel these reproduce the reference's fp64 operation order: compile with -ffp-contract=off.
 
@@ -484,6 +484,70 @@ k_export(const OT *__restrict__ obs, const float *__restrict__ reward, const uin
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// The per-env reset (swarm_reset_envs): env e is redrawn for episode[e] >= 0 exactly as k_reset draws it for (seed, episode[e],
+// env_offset + e) -- the same draw slots, expressions and order, the device cos / sin, pose_cell / pose_lattice, padding cells
+// 0.0: the same bits -- and is left alone for episode[e] < 0 (keep): the block reads its entry first and returns before it
+// writes anything of that env (the test is block-uniform and sits in front of everything else; the kernel has no barrier and
+// no LDS).  episode is a device array, read when the kernel runs.  A reset env's cells go into both layouts here, as in
+// k_select_shapes: no interleave pass follows, and a kept env's cells_xy row is neither read nor written.
+// Its own text, behind every other kernel of the file, so that k_reset's device code and the other kernels' stay what they
+// were.  Unlike k_reset it holds no LatEnv in registers: the record is copied by words (one per thread, as k_select_shapes
+// does) and thread 0 writes the posed frame of a record that has one -- no scratch.
+// -------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_reset_envs(const KP P, const ShapeSet S, const unsigned long long seed, const long long *__restrict__ episode,
+             const long long env_offset, double *__restrict__ cells_out, double2 *__restrict__ cells_xy, int *__restrict__ ng_out,
+             double *__restrict__ cin_out, LatEnv *__restrict__ lat_out, int *__restrict__ shape_out)
+{
+    const int e = blockIdx.x, tid = threadIdx.x;
+    const long long ep = episode[e];
+    if (ep < 0) return;                                                   // keep
+    const unsigned long long key = mix64(mix64(seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)ep + 1)) ^ (unsigned long long)(env_offset + e));
+    const double W = P.w_half, H = P.h_half;
+    int s = (int)(reset_u01(key, 0) * S.n_shapes);
+    s = s >= S.n_shapes ? S.n_shapes - 1 : s;
+    const double ang = M_PI * (2.0 * reset_u01(key, 1) - 1.0);
+    const double cs = cos(ang), sn = sin(ang);                       // rotate_matrix = [[c, s], [-s, c]], ENV:177
+    const double offx = (-W + 1) + reset_u01(key, 4) * (2 * W - 2);
+    const double offy = (-H + 1) + reset_u01(key, 5) * (2 * H - 2);
+    const int ng = S.n_g[s];
+    const double *sx_ = S.cells + (size_t)s * 2 * P.ng_max, *sy_ = sx_ + P.ng_max;
+    double *gx = cells_out + (size_t)e * 2 * P.ng_max, *gy = gx + P.ng_max;
+    double2 *gxy = cells_xy + (size_t)e * P.ng_max;
+    for (int c = tid; c < P.ng_max; c += blockDim.x) {
+        const double2 g = pose_cell(sx_, sy_, c, ng, cs, sn, offx, offy);
+        gx[c] = g.x; gy[c] = g.y; gxy[c] = g;
+    }
+    // the lattice record: one word per thread; thread 0 writes the frame of a record that has one (k_reset: pose_lattice iff nrows > 0)
+    const LatEnv *src = S.lat + s;
+    const bool framed = src->nrows > 0;
+    if (tid < kLatWords && !(framed && tid < kLatFrameWords))
+        reinterpret_cast<unsigned long long *>(lat_out + e)[tid] = reinterpret_cast<const unsigned long long *>(src)[tid];
+    if (tid == 0) {
+        ng_out[e] = ng; cin_out[e] = S.c_in[s]; shape_out[e] = s;
+        if (framed) {
+            double ox = src->ox, oy = src->oy, uxi = src->uxi, uyi = src->uyi, vxi = src->vxi, vyi = src->vyi;
+            pose_lattice(ox, oy, uxi, uyi, vxi, vyi, cs, sn, offx, offy);
+            LatEnv *dst = lat_out + e;
+            dst->ox = ox; dst->oy = oy; dst->uxi = uxi; dst->uyi = uyi; dst->vxi = vxi; dst->vyi = vyi;
+        }
+    }
+    // agents (ENV:202-215)
+    const int N = P.n_a;
+    const bool spread = (2.0 * reset_u01(key, 6) - 1.0) > 0;
+    const double cx = (-W + 1) + reset_u01(key, 7) * (2 * W - 2), cy = (-H + 1) + reset_u01(key, 8) * (2 * H - 2);
+    for (int i = tid; i < N; i += blockDim.x) {
+        const double ux_ = reset_u01(key, 16 + i), uy_ = reset_u01(key, 16 + N + i);
+        double x, y;
+        if (spread) { x = -W + ux_ * (2 * W); y = -H + uy_ * (2 * H); }
+        else { x = (2.0 * ux_ - 1.0) + cx; y = (2.0 * uy_ - 1.0) + cy; }
+        P.p[(size_t)e * 2 * N + i] = x; P.p[(size_t)e * 2 * N + N + i] = y;
+        P.dp[(size_t)e * 2 * N + i] = -0.5 + reset_u01(key, 16 + 2 * N + i);
+        P.dp[(size_t)e * 2 * N + N + i] = -0.5 + reset_u01(key, 16 + 3 * N + i);
+    }
+}
+
 }  // namespace
 
 namespace swarm_internal {
@@ -492,6 +556,14 @@ hipError_t launch_reset(hipStream_t st, const KP &kp, const ShapeSet &S, unsigne
                         long long env_offset, double *cells, int *n_g, double *c_in, LatEnv *lat, int *shape_idx)
 {
     hipLaunchKernelGGL(k_reset, dim3(kp.n_env), dim3(256), 0, st, kp, S, seed, episode, env_offset, cells, n_g, c_in, lat, shape_idx);
+    return hipGetLastError();
+}
+
+hipError_t launch_reset_envs(hipStream_t st, const KP &kp, const ShapeSet &S, unsigned long long seed, const long long *episode,
+                             long long env_offset, double *cells, double2 *cells_xy, int *n_g, double *c_in, LatEnv *lat, int *shape_idx)
+{
+    hipLaunchKernelGGL(k_reset_envs, dim3(kp.n_env), dim3(256), 0, st, kp, S, seed, episode, env_offset, cells, cells_xy, n_g, c_in, lat,
+                       shape_idx);
     return hipGetLastError();
 }
 

@@ -247,6 +247,9 @@ int large_launch(swarm_env *h, const Pass &ps);
 // ---- env_kernels.hip: one launcher per side kernel; each enqueues on `st` and returns the launch's hipGetLastError()
 hipError_t launch_reset(hipStream_t st, const KP &kp, const ShapeSet &S, unsigned long long seed, unsigned long long episode,
                         long long env_offset, double *cells, int *n_g, double *c_in, LatEnv *lat, int *shape_idx);
+// episode [E] is a device array, read when the kernel runs; an env with a negative entry is kept (nothing of it is written)
+hipError_t launch_reset_envs(hipStream_t st, const KP &kp, const ShapeSet &S, unsigned long long seed, const long long *episode,
+                             long long env_offset, double *cells, double2 *cells_xy, int *n_g, double *c_in, LatEnv *lat, int *shape_idx);
 hipError_t launch_select_shape(hipStream_t st, const ShapeSet &S, int s, int ng_max, int n_env, double *cells, double2 *cells_xy,
                                int *n_g, double *c_in, LatEnv *lat, int *shape_idx);
 // shape_index [E] and pose [E][4] (or NULL) are device arrays, read when the kernel runs

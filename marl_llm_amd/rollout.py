@@ -14,6 +14,8 @@ ring buffer (train_assembly.py:91-111, maddpg.py:72-87, agents.py:69-96, buffer_
                      log_pi=True also each action's log-probability (swarm_rollout_logpi), the AIRL agent side's log_pi.
 * `rollout_expert`-- expert rollouts (rule-based expert or the prior's 'llm' twin) into the same ring, one library call per
                      episode batch: swarm_rollout_expert (collect_expert_data.py's loop on the device).
+* `EpisodeClock`  -- staggered episodes for the device loops: the resets= schedule (whole-batch and per-env resets inside a
+                     call, SwarmBatch.reset_envs) that keeps the envs of a batch out of phase.
 * `save_expert_data` -- a ring's transitions as the expert_data.npz that ReplayBufferExpert.load reads (train_assembly_airl.py).
 * `rollout_eval`  -- evaluation rollouts (eval_assembly.py's loop on the device), one library call: swarm_rollout_eval -- the
                      actor without noise, per step the three wrapper metrics of every env, a state trace and target-shape
@@ -440,7 +442,7 @@ def _is_view_of(t, slot):
 
 @torch.no_grad()
 def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, epsilon=0.0, host_rng=None, seed=0, step0=0,
-                   row_offset=0, reset=None, track_reward=True, log_pi=False):
+                   row_offset=0, reset=None, track_reward=True, log_pi=False, resets=None):
     """`steps` exploring-actor + env steps in ONE library call (swarm_rollout, include/swarm_rollout.h): the launches are
     enqueued on torch's current stream and the call returns without a host synchronisation.
 
@@ -454,6 +456,16 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
                starts a new chain through replay.new_chain(): the stored transitions keep their true next_obs.
     epsilon  : the coin of agents.py:89-91, drawn on the host before the call, one host_rng.random() per step (the order and
                count rollout() uses); a coin step takes counter-based uniform actions instead of the policy.
+    resets   : {step: (seed, episode[, env_offset])} with 0 <= step < steps -- episode boundaries inside the call (SwarmBatch
+               only; EpisodeClock writes such schedules).  An int episode is the whole-batch reset, an int array-like /
+               int64 cuda tensor [E] the per-env one (SwarmBatch.reset_envs: -1 keeps the env).  The reset of step t comes
+               before everything else of step t.  It ends a chain: the slot that holds step t-1's next_obs is sealed
+               (new_chain) and the reset writes its observation of all envs into the slot behind it, so every stored
+               transition keeps its true next_obs and each cut costs ONE ring slot for the whole batch -- group the envs
+               (EpisodeClock's groups) to keep that small.  The call is split into stretches: a reset, then one library call
+               up to the next reset (noise keyed by step0 + t as ever); without entries it stays one library call.
+               resets={0: (seed, ep)} is reset=(seed, ep); both together are a ValueError.  The whole schedule is checked
+               and uploaded before anything is enqueued.
     log_pi   : also record each transition's log-probability of its exploring action (swarm_rollout_logpi) in the ring's
                log-pi column: the policy kernel's (include/swarm_policy.h) or LOG_PI_UNIFORM on a coin step -- what
                train_assembly_airl.py pushes as log_pi_orig.  The ring must be built with log_pi=True (the private ring
@@ -466,12 +478,14 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
     from . import _lib
     aenv, sb = _device_env(env, "rollout_device", lambda e: e.agent_strategy == "input" and not e.is_collected,
                            "rollout_device drives the env with the policy's actions: needs agent_strategy 'input' and not is_collected",
-                           reset)
+                           reset if reset is not None else (resets or None))
     if not isinstance(policy, FusedPolicy):
         raise TypeError("rollout_device needs a FusedPolicy (the device loop runs the fused policy kernel)")
     steps = int(steps)
     if steps < 0:
         raise ValueError("steps must be >= 0")
+    plan = _reset_plan(sb, resets, steps, reset, "rollout_device")
+    first = reset if reset is not None else plan.get(0)
     E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
     replay = _device_ring(sb, replay, log_pi)
     if log_pi and replay.log_pi is None:
@@ -479,25 +493,24 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
     lib = _lib.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
 
-    def call(k, coins, stats):
+    def call(k, coins, stats, a=0):
         ring = _ring_struct(sb, replay)
         tail = (k, coins.ctypes.data_as(ctypes.c_void_p) if coins is not None else None, float(noise_scale),
-                int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1),
-                ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, stream)
+                int(seed) & (2 ** 64 - 1), (int(step0) + a) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1),
+                ctypes.c_void_p(stats[a:].data_ptr()) if stats is not None else None, stream)
         if log_pi:
             rc = lib.swarm_rollout_logpi(sb.handle, policy.handle, ctypes.byref(ring), ctypes.c_void_p(replay.log_pi.data_ptr()), *tail)
         else:
             rc = lib.swarm_rollout(sb.handle, policy.handle, ctypes.byref(ring), *tail)
-        _check_rollout(lib, rc, k, reset)
+        _check_rollout(lib, rc, k, first)
 
-    _begin_chain(sb, replay, obs, reset, lambda: call(0, None, None), "rollout_device")
     coins = None
     if epsilon > 0:
         coin = host_rng if host_rng is not None else np.random
         coins = np.array([coin.random() < epsilon for _ in range(steps)], dtype=np.uint8)          # agents.py:89
     stats = torch.empty((steps, 2), dtype=torch.float64, device=sb.device) if track_reward else None
-    call(steps, coins, stats)
-    _finish_chain(aenv, replay, steps)
+    _run_stretches(aenv, sb, replay, obs, reset, plan, steps, lambda: call(0, None, None),
+                   lambda a, b: call(b - a, np.ascontiguousarray(coins[a:b]) if coins is not None else None, stats, a), "rollout_device")
     return replay.obs[replay.cur].view(E, N, D), stats
 
 
@@ -543,9 +556,11 @@ def _check_rollout(lib, rc, k, reset):
         raise _lib.SwarmError(f"libswarmenv error {rc}: {lib.swarm_rollout_last_error().decode()}")
 
 
-def _begin_chain(sb, replay, obs, reset, validate, who):
+def _begin_chain(sb, replay, obs, reset, validate, who, upload=None):
     """Continue the ring's chain, or start a new one from `obs` / reset=(seed, episode[, env_offset]) through
-    replay.new_chain().  `validate()` (a zero-step library call) runs first: a rejected call leaves the ring as it was."""
+    replay.new_chain().  `validate()` (a zero-step library call) runs first: a rejected call leaves the ring as it was.
+    reset may also be a callable that returns the (uploaded) step-0 entry of a resets= schedule; upload() -- the uploads of
+    that schedule -- runs behind validate() and before anything is enqueued."""
     E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
     n = E * N
     cont = reset is None and (obs is None or _is_view_of(obs, replay.obs[replay.cur]))
@@ -555,13 +570,13 @@ def _begin_chain(sb, replay, obs, reset, validate, who):
                                          or obs.numel() != n * D):
         raise ValueError(f"obs must be a {sb.obs_dtype} tensor [{E}, {N}, {D}] on {sb.device}")
     validate()                              # validation only: a rejected call raises before the ring is touched
+    if upload is not None:
+        upload()
     if not cont:
         kept = (replay.cur, replay.count, replay._chained, set(replay._sealed))
         try:
             if reset is not None:
-                r = tuple(reset)
-                slot = replay.new_chain()
-                sb.reset(r[0], r[1], r[2] if len(r) > 2 else 0, out=replay.obs[slot])
+                _chain_reset(sb, replay, reset() if callable(reset) else reset)
             else:
                 replay.new_chain(obs)
         except Exception:
@@ -569,15 +584,127 @@ def _begin_chain(sb, replay, obs, reset, validate, who):
             raise
 
 
-def _finish_chain(aenv, replay, steps):
-    replay._advance(steps)
+def _chain_reset(sb, replay, entry):
+    """An episode boundary in the ring: seal the slot that holds the last next_obs (new_chain) and let the reset -- the whole
+    batch's for an int episode, the per-env one for an uploaded episode vector (SwarmBatch._episode_upload's pair) -- write
+    its observation of ALL envs into the slot behind it.  A kept env's row there equals its row in the sealed slot."""
+    r = tuple(entry)
+    seed, episode, env_offset = r[0], r[1], r[2] if len(r) > 2 else 0
+    slot = replay.new_chain()
+    if isinstance(episode, tuple):
+        sb._reset_envs_ready(seed, episode, env_offset, out=replay.obs[slot])
+    else:
+        sb.reset(seed, episode, env_offset, out=replay.obs[slot])
+
+
+def _reset_plan(sb, resets, steps, reset, who):
+    """resets= of the device loops, checked on the host: {step: (seed, episode, env_offset)} in step order, where episode is
+    an int (a whole-batch swarm_reset) or SwarmBatch._episode_args' checked vector (reset_envs).  Raises before anything
+    is uploaded or enqueued."""
+    if resets is None:
+        return {}
+    if not isinstance(resets, dict):
+        raise ValueError(f"{who}: resets= must be a dict {{step: (seed, episode[, env_offset])}}")
+    plan = {}
+    for t, entry in resets.items():
+        if int(t) != t or not 0 <= int(t) < steps:
+            raise ValueError("resets: step %r outside [0, %d)" % (t, steps))
+        r = tuple(entry)
+        if len(r) not in (2, 3):
+            raise ValueError("resets: the entry of step %d must be (seed, episode[, env_offset])" % int(t))
+        episode = r[1]
+        if (isinstance(episode, torch.Tensor) and episode.dim() > 0) or (not isinstance(episode, torch.Tensor) and np.ndim(episode) > 0):
+            episode = sb._episode_args(episode)
+        else:
+            if int(episode) != episode or int(episode) < 0:
+                raise ValueError("resets: the whole-batch episode of step %d must be an int >= 0, got %r" % (int(t), episode))
+            episode = int(episode)
+        plan[int(t)] = (int(r[0]), episode, int(r[2]) if len(r) > 2 else 0)
+    if reset is not None and 0 in plan:
+        raise ValueError(f"{who}: reset= and resets[0] both reset the envs at step 0; give one")
+    if plan and sb.n_shapes < 1:
+        from . import _lib
+        raise _lib.SwarmError(f"{who}: resets= needs a shape set (SwarmBatch.set_shapes)")
+    return dict(sorted(plan.items()))
+
+
+def _run_stretches(aenv, sb, replay, obs, reset, plan, steps, validate, stretch, who, splits=()):
+    """The chain of one device-loop call with a resets= plan: begin the chain (obs / reset= / the plan's step 0), then for
+    every stretch between two resets the reset (_chain_reset) and ONE library call, stretch(a, b), for steps [a, b) with
+    the ring at replay.cur; the ring advances by the stretch and its seal.  Without a plan that is one call.  splits:
+    further steps at which the caller wants a stretch to end (rollout_eval's per-env switches).  Everything is checked and
+    uploaded before the first enqueue; if anything raises the ring is put back exactly as it was."""
+    kept = (replay.cur, replay.count, replay._chained, set(replay._sealed))
+
+    def upload():
+        for t, (seed, episode, off) in plan.items():
+            if not isinstance(episode, int):
+                plan[t] = (seed, sb._episode_upload(episode), off)
+
+    try:
+        _begin_chain(sb, replay, obs, (lambda: plan[0]) if 0 in plan else reset, validate, who, upload)
+        starts = sorted(set(plan) | set(splits) | {0})
+        for a, b in zip(starts, starts[1:] + [steps]):
+            if a > 0 and a in plan:
+                _chain_reset(sb, replay, plan[a])
+            stretch(a, b)
+            replay._advance(b - a)
+    except Exception:
+        replay.cur, replay.count, replay._chained, replay._sealed = kept
+        raise
     if aenv is not None:
         aenv.simulation_time += aenv.dt * steps
         aenv._state_version += 1
 
 
+class EpisodeClock:
+    """Staggered episodes for the device loops, host only: which env starts which episode at which global step.
+
+    Env e belongs to group e % groups and starts q_e = (group * episode_len) // groups steps into its episode 0.  At global
+    step t it resets iff t == 0 or (t + q_e) % episode_len == 0, and its episode number then is (t + q_e) // episode_len.
+    resets(steps) returns the resets= dict of the next `steps` global steps and advances the clock: an int entry (the
+    whole-batch reset) where every env resets with one episode number, an int64 vector (-1 = keep) elsewhere.  groups=1 is
+    today's in-phase batch: int entries every episode_len steps.  Each cut costs the ring one slot for the whole batch
+    (rollout_device), i.e. groups slots per episode_len steps.
+
+        clock = EpisodeClock(E, 200, groups=8, seed=7)
+        obs, stats = rollout_device(sb, pol, K, replay=ring, resets=clock.resets(K))"""
+
+    def __init__(self, n_env, episode_len, groups=1, seed=0, env_offset=0):
+        n_env, episode_len, groups = int(n_env), int(episode_len), int(groups)
+        if n_env < 1 or episode_len < 1 or not 1 <= groups <= episode_len:
+            raise ValueError("EpisodeClock needs n_env >= 1, episode_len >= 1 and 1 <= groups <= episode_len")
+        self.n_env, self.episode_len, self.groups = n_env, episode_len, groups
+        self.seed, self.env_offset = int(seed), int(env_offset)
+        self.t = 0
+
+    def resets(self, steps):
+        steps, L, t0 = int(steps), self.episode_len, self.t
+        groups = min(self.groups, self.n_env)                  # the groups that hold an env
+        due = {}                                               # global step -> {group: episode}; the work is per group, not per step
+        for g in range(groups):
+            q = (g * L) // self.groups
+            t = t0 + (-(t0 + q)) % L                           # the first t >= t0 with (t + q) % L == 0
+            while t < t0 + steps:
+                due.setdefault(t, {})[g] = (t + q) // L
+                t += L
+        if t0 == 0 and steps > 0:
+            due[0] = {g: 0 for g in range(groups)}             # every env starts its episode 0 at t = 0
+        out = {}
+        for t in sorted(due):
+            episode = due[t]
+            if len(episode) == groups and len(set(episode.values())) == 1:
+                out[t - t0] = (self.seed, episode[0], self.env_offset)
+            else:
+                by_group = np.full(self.groups, -1, np.int64)
+                by_group[list(episode)] = list(episode.values())
+                out[t - t0] = (self.seed, by_group[np.arange(self.n_env) % self.groups], self.env_offset)
+        self.t += steps
+        return out
+
+
 @torch.no_grad()
-def rollout_expert(env, steps, obs=None, replay=None, reset=None, source="rule", track_reward=True):
+def rollout_expert(env, steps, obs=None, replay=None, reset=None, source="rule", track_reward=True, resets=None):
     """`steps` expert steps in ONE library call (swarm_rollout_expert, include/swarm_rollout.h): the device counterpart of
     collect_expert_data.py's loop (agent_strategy 'rule' / 'llm' with is_collected).  Enqueued on torch's current stream;
     returns without a host synchronisation.
@@ -588,7 +715,8 @@ def rollout_expert(env, steps, obs=None, replay=None, reset=None, source="rule",
              SwarmBatch.rule_action()); the env steps with that fp64 action and the ring's act row holds its f32 rounding.
              "llm"  -- the prior policy's twin (a batch created with llm_action): the ring's act row is the applied action,
              what the eager path returns as its fifth value with is_collected.
-    replay / obs / reset : the chain, exactly as rollout_device (reset= seals the boundary slot through new_chain()).
+    replay / obs / reset / resets : the chain, exactly as rollout_device (reset= seals the boundary slot through new_chain();
+             resets= puts whole-batch and per-env episode boundaries inside the call, one library call per stretch).
     Returns (obs [E,N,D] -- the ring slot of the last next_obs --, reward_stats [steps, 2] float64 or None).  On error
     nothing is enqueued, the ring and the env state are unchanged, and SwarmError / ValueError raises."""
     import ctypes
@@ -596,26 +724,27 @@ def rollout_expert(env, steps, obs=None, replay=None, reset=None, source="rule",
     if source not in ("rule", "llm"):
         raise ValueError("source must be 'rule' or 'llm'")
     aenv, sb = _device_env(env, "rollout_expert", lambda e: e.agent_strategy == source,
-                           f"rollout_expert(source={source!r}) needs an AssemblySwarmEnv with agent_strategy {source!r}", reset)
+                           f"rollout_expert(source={source!r}) needs an AssemblySwarmEnv with agent_strategy {source!r}",
+                           reset if reset is not None else (resets or None))
     steps = int(steps)
     if steps < 0:
         raise ValueError("steps must be >= 0")
+    plan = _reset_plan(sb, resets, steps, reset, "rollout_expert")
+    first = reset if reset is not None else plan.get(0)
     E, N, D = sb.n_env, sb.n_agents, sb.obs_dim
     replay = _device_ring(sb, replay)
     lib = _lib.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
     src = _lib.EXPERT_RULE if source == "rule" else _lib.EXPERT_LLM
 
-    def call(k, stats):
+    def call(k, stats, a=0):
         ring = _ring_struct(sb, replay)
         rc = lib.swarm_rollout_expert(sb.handle, ctypes.byref(ring), k, src,
-                                      ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, stream)
-        _check_rollout(lib, rc, k, reset)
+                                      ctypes.c_void_p(stats[a:].data_ptr()) if stats is not None else None, stream)
+        _check_rollout(lib, rc, k, first)
 
-    _begin_chain(sb, replay, obs, reset, lambda: call(0, None), "rollout_expert")
     stats = torch.empty((steps, 2), dtype=torch.float64, device=sb.device) if track_reward else None
-    call(steps, stats)
-    _finish_chain(aenv, replay, steps)
+    _run_stretches(aenv, sb, replay, obs, reset, plan, steps, lambda: call(0, None), lambda a, b: call(b - a, stats, a), "rollout_expert")
     return replay.obs[replay.cur].view(E, N, D), stats
 
 
@@ -727,7 +856,8 @@ def _shape_entry(sh, keep_ok=False):
 
 
 @torch.no_grad()
-def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=None, trace_state=False, track_reward=True):
+def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=None, trace_state=False, track_reward=True,
+                 resets=None):
     """`steps` evaluation steps in ONE library call (swarm_rollout_eval, include/swarm_rollout.h): the device counterpart of
     eval_assembly.py:145-186 for every env of the batch.  Per step: the state trace, an optional target-shape switch on the
     device, the three wrapper metrics, the actor WITHOUT noise (explore=False) at the policy's precision, the env step.
@@ -745,6 +875,9 @@ def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=N
              next -- with the same results as the eager loop, bit for bit.  Every host array of the schedule is checked and
              uploaded before the first stretch is enqueued.  Needs a SwarmBatch; ValueError with an AssemblySwarmEnv (assign
              its grid_center / n_g / l_cell between calls instead).
+    resets : episode boundaries inside the call, as rollout_device's resets= (SwarmBatch only).  The reset of step t comes
+             before the state trace, the switch and the metrics of step t: p[t] is the fresh state, metrics[t] what metrics()
+             gives behind the reset.  The call is split at those steps as it is at per-env switches.
     trace_state : also record p / dp before every step.
     Returns (obs [E,N,D] -- the ring slot of the last next_obs --, EvalTrace).  On error nothing is enqueued, the ring and
     the env are unchanged, and SwarmError / ValueError raises."""
@@ -756,12 +889,14 @@ def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=N
                              "n_g / l_cell attributes between calls")
     aenv, sb = _device_env(env, "rollout_eval", lambda e: e.agent_strategy == "input" and not e.is_collected,
                            "rollout_eval drives the env with the policy's actions: needs agent_strategy 'input' and not is_collected",
-                           reset)
+                           reset if reset is not None else (resets or None))
     if not isinstance(policy, FusedPolicy):
         raise TypeError("rollout_eval needs a FusedPolicy (the device loop runs the fused policy kernel)")
     steps = int(steps)
     if steps < 0:
         raise ValueError("steps must be >= 0")
+    plan = _reset_plan(sb, resets, steps, reset, "rollout_eval")
+    first = reset if reset is not None else plan.get(0)
     per_env = {}
     sched = _switch_schedule(switch, steps, per_env)
     if sched is not None or per_env:
@@ -775,16 +910,14 @@ def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=N
     lib = _lib.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
 
-    def call(k, sw, out, done=0):
-        ring = _ring_struct(sb, replay)
-        ring.cur = (replay.cur + done) % replay.S         # the stretch behind `done` steps of this call
+    def call(k, sw, out):
+        ring = _ring_struct(sb, replay)                   # (the ring advances with every stretch: _run_stretches)
         rc = lib.swarm_rollout_eval(sb.handle, policy.handle, ctypes.byref(ring), k,
                                     sw.ctypes.data_as(ctypes.c_void_p) if sw is not None else None,
                                     ctypes.byref(out) if out is not None else None, stream)
-        _check_rollout(lib, rc, k, reset)
+        _check_rollout(lib, rc, k, first)
 
-    _begin_chain(sb, replay, obs, reset, lambda: call(0, None, None), "rollout_eval")
-    ready = {t: sb._shapes_upload(*args) for t, args in checked.items()}          # uploads: before the first stretch
+    ready = {}
     f64 = dict(dtype=torch.float64, device=sb.device)
     metrics = torch.empty((steps, E, 3), **f64)
     p = torch.empty((steps, E, 2, N), **f64) if trace_state else None
@@ -792,8 +925,12 @@ def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=N
     stats = torch.empty((steps, 2), **f64) if track_reward else None
     ptr = lambda t, a: t[a:].data_ptr() if t is not None else None
     shape, shape_env = np.full(steps, -1, np.int64), np.full((steps, E), -1, np.int64)
-    cuts = sorted(set(ready) | {0, steps})
-    for a, b in zip(cuts[:-1], cuts[1:]):
+
+    def validate():
+        call(0, None, None)
+        ready.update({t: sb._shapes_upload(*args) for t, args in checked.items()})     # uploads: before the first stretch
+
+    def stretch(a, b):                                    # steps [a, b): behind the reset of step a, if it has one
         if a in ready:
             sb._select_shapes_ready(ready[a])             # out=None: the ring slot the actor reads is not rewritten
         for t in range(a, b):
@@ -803,10 +940,11 @@ def rollout_eval(env, policy, steps, obs=None, replay=None, reset=None, switch=N
             if sb.shape_env_in_force is not None:
                 shape_env[t] = sb.shape_env_in_force
         call(b - a, np.ascontiguousarray(sched[a:b]) if sched is not None else None,
-             _lib.SwarmEvalOut(ptr(metrics, a), ptr(p, a), ptr(dp, a), ptr(stats, a)), done=a)
-    if any(host is None for _, _, host in ready.values()):
-        shape_env = None                                  # a device index: who took what is not known on the host
-    _finish_chain(aenv, replay, steps)
+             _lib.SwarmEvalOut(ptr(metrics, a), ptr(p, a), ptr(dp, a), ptr(stats, a)))
+
+    _run_stretches(aenv, sb, replay, obs, reset, plan, steps, validate, stretch, "rollout_eval", splits=checked)
+    if any(host is None for _, _, host in ready.values()) or any(isinstance(ep, tuple) and ep[1] is None for _, ep, _ in plan.values()):
+        shape_env = None                                  # a device index / episode vector: who holds what is not known on the host
     return replay.obs[replay.cur].view(E, N, D), EvalTrace(metrics, p, dp, stats, shape, shape_env)
 
 

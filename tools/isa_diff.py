@@ -11,7 +11,9 @@ Where both trees compile a source as the same unit(s), unit by unit: whole files
 `<symbol>:` to `.end_amdhsa_kernel`, so a kernel's register counts, LDS and scratch sizes (.amdhsa_*) are compared with its
 instructions.  One name is taken out of both texts before they are compared: `__hip_cuid_<hash>`, a one-byte object that
 hipcc names after a hash of the SOURCE text, comments included -- it differs whenever the source does and says nothing about
-the code.
+the code.  Kernel by kernel, the number that the local labels .LBB<k>_, .Lfunc_end<k>, .LJTI<k>_ and .Ltmp<k> carry is taken
+out as well: it is the function's position in its translation unit, and a kernel added to a file moves it for every function
+the compiler emits behind the new one (template instantiations come last) without touching an instruction.
 
 Where the trees cut a source into different units, the kernels of all of the source's units are compared one by one, each with
 its entry of the `amdhsa.kernels` metadata (arguments, segment sizes); a kernel found in two units of one tree is an error,
@@ -55,6 +57,20 @@ def strip_cuid(text):
     return re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_", text)
 
 
+def unnumbered(lines):
+    """a kernel's lines without the number its local labels .LBB<k>_, .LJTI<k>_, .Lfunc_end<k> and .Ltmp<k> carry: the function's
+    position in its translation unit, which a kernel added in front of it moves -- and nothing else of its text"""
+    out = []
+    for l in lines:
+        l = re.sub(r"\.(LBB|LJTI)\d+_", r".\1_", l)
+        l = re.sub(r"\.(Lfunc_end|Ltmp)\d+", r".\1", l)
+        if ";" in l:                                # a comment names blocks as BB<k>_ and is aligned behind the (shorter) label
+            code, _, note = l.partition(";")
+            l = code.rstrip() + " ;" + re.sub(r"\bBB\d+_", "BB_", note)
+        out.append(l)
+    return out
+
+
 def by_name(kb, kt, res):
     """fill res with the names only in kb, only in kt, and the first differing line of those in both"""
     res["only_base"] = sorted(set(kb) - set(kt))
@@ -75,7 +91,7 @@ def compare(base_text, tree_text):
     res["kernels"] = len(set(kb) | set(kt))
     if base_text == tree_text:
         return res
-    by_name(kb, kt, res)
+    by_name({n: unnumbered(k) for n, k in kb.items()}, {n: unnumbered(k) for n, k in kt.items()}, res)
     res["outside"] = not (res["only_base"] or res["only_tree"] or res["differing"])
     return res
 
@@ -83,14 +99,7 @@ def compare(base_text, tree_text):
 def normalise(lines):
     """a kernel's lines without the function number of its local labels and without `;` comments (lines that held only a
     comment go)"""
-    out = []
-    for l in lines:
-        l = re.sub(r"\s*;.*$", "", l)
-        l = re.sub(r"\.(LBB|LJTI)\d+_", r".\1_", l)
-        l = re.sub(r"\.(Lfunc_end|Ltmp)\d+", r".\1", l)
-        if l.strip():
-            out.append(l)
-    return out
+    return [l for l in unnumbered(re.sub(r"\s*;.*$", "", l) for l in lines) if l.strip()]
 
 
 def kernel_metadata(text):
