@@ -28,6 +28,17 @@ typedef struct swarm_policy swarm_policy_t;
  * create returns SWARM_POLICY_ERR_INVALID with a message.  device < 0: the current device. */
 int  swarm_policy_create(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
                          const float *w4, const float *b4, int in_dim, int hidden, int act_dim, int device, swarm_policy_t **out);
+/* The same arguments, a handle that runs the WIDE geometry of the kernel (csrc/policy_wide.hip), always -- also for shapes
+ * swarm_policy_create serves.  Supported: 4 <= in_dim <= 384 (multiple of 4), 1 <= hidden <= 256, 1 <= act_dim <= 4: the env's
+ * rows up to num_obs_grid_max = 176 at the default topology, the reference's --hidden_dim up to 256.  Checked before any device
+ * call: a rejection returns SWARM_POLICY_ERR_INVALID with a message that starts "swarm_policy_create_wide:" and names the three
+ * limits.  Every call below takes such a handle; SWARM_POLICY_TPW is not read for it.  The arithmetic is the one stated under
+ * swarm_policy_set_precision; only the mechanism of the biases of layers 2-4 differs (no constant-one column: hidden = 256
+ * leaves no padded feature for it): the accumulators start at bf(bl), and in bf16x3 mode lo(bl) = bf(bl - bf(bl)) is added to
+ * them in fp32 -- the same terms, in an order that is not part of the contract.  Its packed weights
+ * (swarm_policy_read_packed) have their own layout and size. */
+int  swarm_policy_create_wide(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                              const float *w4, const float *b4, int in_dim, int hidden, int act_dim, int device, swarm_policy_t **out);
 void swarm_policy_destroy(swarm_policy_t *p);
 
 /* act[rows][act_dim] = tanh(fc4(lrelu(fc3(lrelu(fc2(lrelu(fc1(obs[rows][in_dim])))))))); obs / act are DEVICE pointers, rows

@@ -50,7 +50,7 @@ BATCHED_SYMBOLS = ("swarm_abi_version", "swarm_default_config", "swarm_create", 
                    "swarm_step_algorithmic_bytes", "swarm_timer_start", "swarm_timer_stop", "swarm_lattice_envs", "swarm_set_shapes", "swarm_reset", "swarm_get_cells", "swarm_get_shape_index", "swarm_metrics", "swarm_rule_action",
                    "swarm_host_outputs", "swarm_observe_host", "swarm_step_host", "swarm_get_llm_action", "swarm_select_shape", "swarm_path_envs",
                    "swarm_select_shapes", "swarm_reset_envs")
-POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_destroy", "swarm_policy_forward", "swarm_policy_forward_bf16",
+POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_create_wide", "swarm_policy_destroy", "swarm_policy_forward", "swarm_policy_forward_bf16",
                   "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_forward_explore_logpi",
                   "swarm_policy_set_precision", "swarm_policy_load_device", "swarm_policy_read_packed",
                   "swarm_policy_last_error")   # include/swarm_policy.h
@@ -89,6 +89,7 @@ def load():
     lib.swarm_legacy_last_error.argtypes = []; lib.swarm_legacy_last_error.restype = ctypes.c_char_p
     lib.swarm_rule_action.argtypes = [vp, vp]; lib.swarm_rule_action.restype = i32
     lib.swarm_policy_create.argtypes = [vp] * 8 + [i32] * 4 + [ctypes.POINTER(vp)]; lib.swarm_policy_create.restype = i32
+    lib.swarm_policy_create_wide.argtypes = [vp] * 8 + [i32] * 4 + [ctypes.POINTER(vp)]; lib.swarm_policy_create_wide.restype = i32
     lib.swarm_policy_destroy.argtypes = [vp]; lib.swarm_policy_destroy.restype = None
     lib.swarm_policy_forward.argtypes = [vp, vp, ctypes.c_int64, vp, vp]; lib.swarm_policy_forward.restype = i32
     lib.swarm_policy_forward_bf16.argtypes = [vp, vp, ctypes.c_int64, vp, vp]; lib.swarm_policy_forward_bf16.restype = i32

@@ -34,6 +34,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 # build_lib starts them.  swarm_env.hip seven times: its kernels by agent count, then its host part (see that file's head).
 UNITS = [("swarm_env_n%d" % n, "swarm_env.hip", ["-DSWARM_ENV_UNIT=%d" % n]) for n in (256, 16, 32, 64, 128, 8)] + [
     ("policy_mlp", "policy_mlp.hip", []),
+    ("policy_wide", "policy_wide.hip", []),
     ("rule_expert", "rule_expert.hip", []),
     ("env_large", "env_large.hip", []),
     ("env_kernels", "env_kernels.hip", []),

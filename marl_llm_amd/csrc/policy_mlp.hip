@@ -28,6 +28,7 @@
 
 #include "swarm_policy.h"
 #include "swarm_internal.h"
+#include "policy_wide.h"
 
 namespace {
 
@@ -373,6 +374,8 @@ struct SWARM_HIDDEN swarm_policy {     // hidden: its implicit destructor must n
     size_t blob_bytes = 0;
     MlpParams p;
     bool smem_set = false;
+    swarm_wide::Handle *wide = nullptr;    // swarm_policy_create_wide: the handle runs csrc/policy_wide.hip; d_blob and p stay empty
+    ~swarm_policy() { swarm_wide::destroy(wide); }
 };
 
 int swarm_internal_policy_info(const swarm_policy_t *p, swarm_policy_info *out)
@@ -468,6 +471,32 @@ int swarm_policy_create(const float *w1, const float *b1, const float *w2, const
     return SWARM_POLICY_OK;
 }
 
+int swarm_policy_create_wide(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                             const float *w4, const float *b4, int in_dim, int hidden, int act_dim, int device, swarm_policy_t **out)
+{
+    if (!out) return SWARM_POLICY_ERR_INVALID;
+    *out = nullptr;
+    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_create_wide: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
+    if (!swarm_wide::shape_ok(in_dim, hidden, act_dim)) {
+        g_policy_error = "swarm_policy_create_wide: supported shapes are in_dim <= 384 (multiple of 4), hidden <= 256, act_dim <= 4";
+        return SWARM_POLICY_ERR_INVALID;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_policy_error = "swarm_policy_create_wide: no HIP device (there is no CPU path)"; return SWARM_POLICY_ERR_HIP; }
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    const DeviceGuard guard(device < ndev ? device : -1);       // -1 is no device: !ok
+    if (!guard.ok) { g_policy_error = "swarm_policy_create_wide: bad device"; return SWARM_POLICY_ERR_HIP; }
+    swarm_policy *p = new (std::nothrow) swarm_policy;
+    if (!p) return SWARM_POLICY_ERR_INVALID;
+    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim;
+    const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
+    const int rc = swarm_wide::create(w, in_dim, hidden, act_dim, &p->wide, g_policy_error);
+    if (rc != SWARM_POLICY_OK) { delete p; return rc; }
+    (void)swarm_wide::blob(p->wide, &p->blob_bytes);
+    *out = p;
+    return SWARM_POLICY_OK;
+}
+
 void swarm_policy_destroy(swarm_policy_t *p)
 {
     if (!p) return;
@@ -485,6 +514,11 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
     if (rows == 0) return SWARM_POLICY_OK;
     const DeviceGuard guard(p->device);
     if (!guard.ok) { g_policy_error = "swarm_policy_forward: hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
+    if (p->wide) {                                          // a wide handle: its own kernel, SWARM_POLICY_TPW not read
+        const swarm_wide::ForwardArgs a = {obs, in_bf16, rows, act, log_pi, noise_scale, seed, step, row_offset, p->precision,
+                                           static_cast<hipStream_t>(stream)};
+        return swarm_wide::forward(p->wide, a, g_policy_error);
+    }
     MlpParams q = p->p;
     q.rows = rows;
     q.noise_scale = noise_scale > 0.0f ? noise_scale : 0.0f;
@@ -566,6 +600,10 @@ int swarm_policy_load_device(swarm_policy_t *p, const float *w1, const float *b1
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_load_device: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
     const DeviceGuard guard(p->device);
     if (!guard.ok) { g_policy_error = "swarm_policy_load_device: hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
+    if (p->wide) {
+        const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
+        return swarm_wide::load_device(p->wide, w, static_cast<hipStream_t>(stream), g_policy_error);
+    }
     static_assert(kPackPieces % 64 == 0 && sizeof(bf8) == sizeof(uint4), "one 16-byte piece per fragment lane");
     PackParams q;
     q.w1 = w1; q.b1 = b1; q.w2 = w2; q.b2 = b2; q.w3 = w3; q.b3 = b3; q.w4 = w4; q.b4 = b4;
@@ -588,7 +626,9 @@ int64_t swarm_policy_read_packed(swarm_policy_t *p, void *host_dst, int64_t capa
     const DeviceGuard guard(p->device);
     if (!guard.ok) { g_policy_error = "swarm_policy_read_packed: hipSetDevice failed"; return -SWARM_POLICY_ERR_HIP; }
     hipStream_t st = static_cast<hipStream_t>(stream);          // the copy on the stream, behind the loads enqueued there; then the wait
-    hipError_t e = hipMemcpyAsync(host_dst, p->d_blob.get(), p->blob_bytes, hipMemcpyDeviceToHost, st);
+    size_t unused;
+    const void *src = p->wide ? swarm_wide::blob(p->wide, &unused) : p->d_blob.get();
+    hipError_t e = hipMemcpyAsync(host_dst, src, p->blob_bytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { g_policy_error = std::string("swarm_policy_read_packed: ") + hipGetErrorString(e); return -SWARM_POLICY_ERR_HIP; }
     return bytes;

@@ -1,0 +1,40 @@
+// Interface between policy_mlp.hip (the fused actor's C ABI and its narrow kernel) and policy_wide.hip (the wide geometry:
+// in_dim <= 384, hidden <= 256).  A swarm_policy handle made by swarm_policy_create_wide owns one swarm_wide::Handle and every
+// entry point of include/swarm_policy.h dispatches on it.  Not installed, not exported.
+#ifndef SWARM_POLICY_WIDE_H
+#define SWARM_POLICY_WIDE_H
+
+#include <string>
+
+#include "swarm_internal.h"
+
+namespace swarm_wide __attribute__((visibility("hidden"))) {
+
+constexpr int kMaxIn = 384, kMaxHidden = 256, kMaxAct = 4;
+
+struct Handle;                      // policy_wide.hip: the packed weights on the device and their geometry
+
+struct ForwardArgs {
+    const void *obs;
+    bool in_bf16;
+    long long rows;                 // > 0
+    float *act, *log_pi;            // log_pi != NULL: the LOGPI instantiation
+    float noise_scale;
+    uint64_t seed, step, row_offset;
+    int precision;                  // SWARM_POLICY_BF16 / SWARM_POLICY_BF16X3
+    hipStream_t stream;
+};
+
+// true where the wide kernel serves the shape; decided without a device
+bool shape_ok(int in_dim, int hidden, int act_dim);
+// w: fc1.weight, fc1.bias, ..., fc4.bias (fp32, HOST), a shape that passed shape_ok; the caller holds `device` current
+int create(const float *const w[8], int in_dim, int hidden, int act_dim, Handle **out, std::string &err);
+void destroy(Handle *h);            // under the caller's DeviceGuard
+int forward(Handle *h, const ForwardArgs &a, std::string &err);
+// w: the same eight arrays on the DEVICE; one packing launch on `st`
+int load_device(Handle *h, const float *const w[8], hipStream_t st, std::string &err);
+const void *blob(const Handle *h, size_t *bytes);
+
+}  // namespace swarm_wide
+
+#endif

@@ -1,0 +1,607 @@
+// The fused actor's WIDE geometry: the kernel of policy_mlp.hip for observation rows up to 384 wide and hidden widths up to
+// 256 (num_obs_grid_max up to 176 at the default topology, --hidden_dim up to 256).  Same scheme -- bf16
+// v_mfma_f32_32x32x16_bf16 with fp32 accumulation, every layer transposed (H^T = W . X^T, a wavefront's 32 rows on the
+// lanes), the accumulator tile of layer l the B operand of layer l + 1, no activation ever leaves the registers, the weights
+// stream through a double-buffered LDS ring -- with three differences:
+//
+// 1. The weight stream is cut along K, not along the features: a chunk is ALL MT feature tiles x 4 k-steps (MT = 8: 32
+//    fragments, 32 KB; two buffers + bias tails = 66 KB of LDS).  All accumulators of a layer are live anyway, and layer 1
+//    then needs only the 4 B fragments of the current chunk: the observation row is read 64 columns at a time, the next
+//    piece in flight while the MFMAs of this one run, so in_dim = 384 (24 k-steps) costs no more registers than in_dim = 64.
+//    Layer 1's stream is also only as long as the row: ceil(in_dim / 64) chunks.
+// 2. Biases initialise the accumulators (there is no padded feature left for a constant-one column at hidden = 256).  The
+//    first chunk of every layer carries the layer's bias as fp32 values behind its fragments: b1 itself, bf(b) for layers
+//    2-4; in bf16x3 mode the LOW stream's chunk carries lo(b) = bf(b - bf(b)), added when that chunk arrives -- the terms
+//    hi and lo of include/swarm_policy.h, summed in fp32.
+// 3. Two padded hidden widths, chosen by the handle: MT = 6 (hidden <= 192) and MT = 8 (hidden <= 256).
+//
+// A workgroup is four wavefronts = 128 rows at both precisions, one wavefront per SIMD (launch bounds (256, 1): the unified
+// 512-register file holds 128 accumulators + 64 + 64 packed activation registers + the prefetched chunk without scratch).
+// Fragment maps as in policy_mlp.hip: A[row = l & 31][k = 8 (l >> 5) + j], B[k = 8 (l >> 5) + j][col = l & 31], C/D col = l & 31,
+// row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).  The arithmetic is the contract of include/swarm_policy.h;
+// tests/test_gpu_policy_wide.py holds the kernel to the float64 model of it.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "policy_wide.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf8;
+typedef __attribute__((ext_vector_type(16))) float f16v;
+
+using swarm_internal::pmix64;
+using swarm_internal::swarm_noise_key;
+
+constexpr int kWaves = 4;                 // wavefronts (32-row tiles) per workgroup
+constexpr int kThreads = 64 * kWaves;
+constexpr int kRowsPerBlock = 32 * kWaves;
+
+// Geometry of one padded hidden width, in 16-byte PIECES (one lane's share of a fragment: 8 bf16, or 4 fp32 of a bias tail).
+// Stream: [layer 1: n1 chunks][layer 2: KC][layer 3: KC][output layer: 1], every chunk in a slot of CH pieces:
+//   hidden-layer and layer-1 chunk g:   [feature tile mt][k-step 4 g + i][lane]  (W pieces), then the bias tail (TAIL pieces:
+//                                        32 MT fp32, live in a layer's first chunk only, zeros elsewhere)
+//   output chunk:                       [k-step][lane] of feature tile 0 (WOUT pieces), then the bias tail
+template <int MT>
+struct Geo {
+    static constexpr int KS = 2 * MT;                 // k-steps of a hidden layer
+    static constexpr int KC = MT / 2;                 // chunks of a hidden layer (4 k-steps each)
+    static constexpr int W = MT * 4 * 64;
+    static constexpr int TAIL = MT * 8;
+    static constexpr int CH = W + TAIL;
+    static constexpr int WOUT = KS * 64;
+    static constexpr int PRE = (CH + kThreads - 1) / kThreads;
+    static constexpr int SMEM = 2 * CH * 16;
+};
+
+// the raw values of one layer-1 chunk of a lane's row: 2 x 4 fp32 or 8 bf16 for each of the 4 k-steps
+template <bool IN_BF16>
+struct XRaw {
+    float4 f[IN_BF16 ? 1 : 4][2];
+    bf8 b[IN_BF16 ? 4 : 1];
+};
+
+struct WideParams {
+    const bf8 *hi, *lo;                // the high and the low stream
+    int in_dim, act_dim;
+    long long rows;
+    float noise_scale;                 // the exploration epilogue: as MlpParams of policy_mlp.hip
+    unsigned long long noise_key, row_offset;
+};
+
+// tanh, exploration noise, clamp and log-pi of one row: the generator and the formulas of include/swarm_policy.h, the
+// statements of k_policy_mlp's epilogue (the two kernels give the same bits for the same pre-tanh values)
+template <bool LOGPI>
+__device__ __forceinline__ void finish_row(const WideParams &P, const f16v &o, long long row, float *__restrict__ act,
+                                           float *__restrict__ log_pi, float logpi_c)
+{
+    float *y = act + (size_t)row * P.act_dim;
+    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (P.noise_scale > 0.0f) {
+        unsigned long long hk = pmix64(P.noise_key ^ (P.row_offset + (unsigned long long)row));
+#pragma unroll
+        for (int k = 0; k < 4; k += 2) {
+            if (k < P.act_dim) {
+                const float u1 = (float)((unsigned)(hk >> 40) + 1u) * 5.9604644775390625e-08f;      // (0, 1]
+                const float u2 = (float)((unsigned)(hk >> 16) & 0xFFFFFFu) * 5.9604644775390625e-08f; // [0, 1)
+                const float rad = sqrtf(-2.0f * logf(u1));
+                float sn, cs;
+                sincosf(6.283185307179586f * u2, &sn, &cs);
+                z[k] = rad * cs; z[k + 1] = rad * sn;
+                hk = pmix64(hk + 0x9E3779B97F4A7C15ull);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < P.act_dim) {
+            float v = tanhf(o[k]);
+            if (P.noise_scale > 0.0f) v = fminf(fmaxf(v + P.noise_scale * z[k], -1.0f), 1.0f);
+            y[k] = v;
+        }
+    if constexpr (LOGPI) {                                  // -(0.5 sum_k z_k^2) - c, the sum in k order
+        float lp = -0.0f;
+        if (P.noise_scale > 0.0f) {
+            float s = z[0] * z[0];
+#pragma unroll
+            for (int k = 1; k < 4; ++k)
+                if (k < P.act_dim) s = s + z[k] * z[k];
+            lp = -(0.5f * s) - logpi_c;
+        }
+        log_pi[row] = lp;
+    }
+}
+
+template <bool IN_BF16, bool X3, bool LOGPI, int MT>
+__global__ void __launch_bounds__(kThreads, (MT == 6 && !X3) ? 2 : 1)
+k_policy_wide(const WideParams P, const void *__restrict__ obs_, float *__restrict__ act, float *__restrict__ log_pi, float logpi_c)
+{
+    typedef Geo<MT> G;
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    bf8 *const lds = reinterpret_cast<bf8 *>(smem_raw);     // buffer b at lds + b * CH
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const long long row = ((long long)blockIdx.x * kWaves + wave) * 32 + r;
+    const bool wave_on = row - r < P.rows;                  // idle waves still stage and take the barriers
+
+    const int n1 = (P.in_dim + 63) >> 6;                    // layer-1 chunks: as long as the row
+    const int c_out = n1 + 2 * G::KC;                       // the output chunk, the last of the stream
+    constexpr int kParts = X3 ? 2 : 1;                      // X3: every chunk twice, high stream then low stream
+    const int n_steps = kParts * (c_out + 1);
+
+    bf8 pre[G::PRE];
+    auto pieces_of = [&](int c) {                           // what of chunk c's slot is staged
+        return c == c_out ? G::WOUT + G::TAIL : (c == 0 || c == n1 || c == n1 + G::KC) ? G::CH : G::W;
+    };
+    auto issue = [&](int s) {                               // step s of the stream -> registers
+        if (s >= n_steps) return;
+        const int c = X3 ? s >> 1 : s;
+        const bf8 *src = ((X3 && (s & 1)) ? P.lo : P.hi) + (size_t)c * G::CH;
+        const int n = pieces_of(c);
+#pragma unroll
+        for (int k = 0; k < G::PRE; ++k) { const int q = tid + k * kThreads; if (q < n) pre[k] = src[q]; }
+    };
+    auto commit = [&](int s) {                              // registers -> the LDS buffer of step s
+        if (s >= n_steps) return;
+        const int n = pieces_of(X3 ? s >> 1 : s);
+        bf8 *dst = lds + (s & 1) * G::CH;
+#pragma unroll
+        for (int k = 0; k < G::PRE; ++k) { const int q = tid + k * kThreads; if (q < n) dst[q] = pre[k]; }
+    };
+
+    // this lane's observation row; 64 columns (4 k-steps) at a time: the raw values of the next TWO layer-1 chunks are in
+    // flight, even chunks in xa and odd chunks in xo (one chunk ahead left fp32 rows waiting: 175 us instead of 87 us for bf16
+    // rows at (192,180,2))
+    const size_t xoff = (size_t)(row < P.rows ? row : P.rows - 1) * P.in_dim;
+    const float *x32 = static_cast<const float *>(obs_) + xoff;
+    const __bf16 *x16 = static_cast<const __bf16 *>(obs_) + xoff;
+    // (the bf16 instantiations of MT = 6 on fp32 rows keep ONE chunk in flight, in xa alone: two waves per SIMD leave no
+    // registers for the second -- 20 B of scratch)
+    constexpr int kAhead = (MT == 6 && !X3 && !IN_BF16) ? 1 : 2;
+    XRaw<IN_BF16> xa, xo;
+    auto load_x = [&](XRaw<IN_BF16> &x, int c) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k0 = 64 * c + 16 * i + 8 * h;
+            if constexpr (IN_BF16) {                        // the fragment as it lies in memory (in_dim % 8 == 0)
+                bf8 z;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) z[j] = (__bf16)0.0f;
+                x.b[i] = k0 < P.in_dim ? *reinterpret_cast<const bf8 *>(x16 + k0) : z;
+            } else {                                        // in_dim is a multiple of 4
+                x.f[i][0] = x.f[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (k0 < P.in_dim) x.f[i][0] = *reinterpret_cast<const float4 *>(x32 + k0);
+                if (k0 + 4 < P.in_dim) x.f[i][1] = *reinterpret_cast<const float4 *>(x32 + k0 + 4);
+            }
+        }
+    };
+
+    bf8 pk[G::KS];                                          // B fragments: layer 1 uses pk[0..3] for the current chunk
+    bf8 pl[X3 ? G::KS : 1];                                 // X3: their low parts
+    f16v acc[MT];
+    auto convert_x = [&](const XRaw<IN_BF16> &x) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if constexpr (IN_BF16) {
+                pk[i] = x.b[i];
+                if constexpr (X3) {                         // bf16 rows have no low part
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) pl[i][j] = (__bf16)0.0f;
+                }
+            } else {
+                const float xv[8] = {x.f[i][0].x, x.f[i][0].y, x.f[i][0].z, x.f[i][0].w, x.f[i][1].x, x.f[i][1].y, x.f[i][1].z, x.f[i][1].w};
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const __bf16 hj = (__bf16)xv[j];
+                    pk[i][j] = hj;
+                    if constexpr (X3) pl[i][j] = (__bf16)(xv[j] - (float)hj);
+                }
+            }
+        }
+    };
+    // the bias tail of the chunk in `wl` (at piece `off`): SET the first `tiles` accumulators to it, or ADD it (X3's low part)
+    auto bias = [&](const bf8 *wl, int off, int tiles, bool add) {
+        const float *bt = reinterpret_cast<const float *>(wl + off);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+            if (mt < tiles) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float4 v = *reinterpret_cast<const float4 *>(bt + 32 * mt + 8 * g + 4 * h);
+                    const float bv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[mt][4 * g + e] = add ? acc[mt][4 * g + e] + bv[e] : bv[e];
+                }
+            }
+    };
+    // the MFMAs of one hidden-width chunk: 4 k-steps, B fragments b0[0..3] (and their low parts), all MT feature tiles
+    // (with_lo = false: the low parts are known to be zero -- layer 1 on bf16 rows -- and their MFMAs are left out)
+    auto mma = [&](const bf8 *wl, const bf8 *b0, const bf8 *l0, bool low, bool with_lo) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                const bf8 a = wl[(mt * 4 + i) * 64 + lane];
+                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0[i], acc[mt], 0, 0, 0);
+                if constexpr (X3) {
+                    if (!low && with_lo) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, l0[i], acc[mt], 0, 0, 0);
+                }
+            }
+    };
+
+    int s = 0;                                              // the step that is in LDS buffer s & 1
+    issue(0);
+    if (wave_on) {
+        load_x(xa, 0);
+        if (kAhead == 2 && 1 < n1) load_x(xo, 1);
+    }
+    commit(0);
+    __syncthreads();
+
+    // ---- layer 1: n1 chunks, the row's columns of the two chunks behind this one loading while its MFMAs run
+    auto layer1_chunk = [&](XRaw<IN_BF16> &x, int c) {
+#pragma unroll
+        for (int part = 0; part < kParts; ++part) {
+            const bool low = part == 1;
+            issue(s + 1);
+            const bf8 *wl = lds + (s & 1) * G::CH;
+            if (wave_on) {
+                if (!low) {
+                    convert_x(x);
+                    if (c + kAhead < n1) load_x(x, c + kAhead);
+                    if (c == 0) bias(wl, G::W, MT, false);  // b1, fp32 (the low stream's tail of layer 1 is zero: not added)
+                }
+                mma(wl, pk, pl, low, !IN_BF16);
+            }
+            commit(s + 1);
+            __syncthreads();
+            ++s;
+        }
+    };
+#pragma unroll 1
+    for (int c = 0; c < n1; c += kAhead) {
+        layer1_chunk(xa, c);
+        if (kAhead == 2 && c + 1 < n1) layer1_chunk(xo, c + 1);
+    }
+
+    // leaky ReLU (slope 0.01, the product rounded in fp32) and the split into bf16 parts: the accumulator tile becomes the
+    // next layer's B fragments, k-step = 2 * feature tile + half
+    auto activate = [&]() {
+#pragma unroll
+        for (int kt = 0; kt < MT; ++kt)
+#pragma unroll
+            for (int sh = 0; sh < 2; ++sh)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float v = acc[kt][8 * sh + j];
+                    const float r_ = fmaxf(v, 0.01f * v);
+                    const __bf16 hj = (__bf16)r_;
+                    pk[2 * kt + sh][j] = hj;
+                    if constexpr (X3) pl[2 * kt + sh][j] = (__bf16)(r_ - (float)hj);
+                }
+    };
+
+    // ---- layers 2 and 3
+#pragma unroll 1
+    for (int layer = 0; layer < 2; ++layer) {
+        if (wave_on) activate();
+#pragma unroll
+        for (int kc = 0; kc < G::KC; ++kc)
+#pragma unroll
+            for (int part = 0; part < kParts; ++part) {
+                const bool low = part == 1;
+                issue(s + 1);
+                const bf8 *wl = lds + (s & 1) * G::CH;
+                if (wave_on) {
+                    if (kc == 0) bias(wl, G::W, MT, low);   // bf(b) sets the accumulators, lo(b) is added
+                    mma(wl, pk + 4 * kc, pl + (X3 ? 4 * kc : 0), low, true);
+                }
+                commit(s + 1);
+                __syncthreads();
+                ++s;
+            }
+    }
+
+    // ---- output layer: one feature tile; action k is accumulator register k of the lower lane half (row = reg, h = 0)
+    if (wave_on) activate();
+#pragma unroll
+    for (int part = 0; part < kParts; ++part) {
+        const bool low = part == 1;
+        issue(s + 1);
+        const bf8 *wl = lds + (s & 1) * G::CH;
+        if (wave_on) {
+            bias(wl, G::WOUT, 1, low);
+#pragma unroll
+            for (int ks = 0; ks < G::KS; ++ks) {
+                const bf8 a = wl[ks * 64 + lane];
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pk[ks], acc[0], 0, 0, 0);
+                if constexpr (X3) {
+                    if (!low) acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pl[ks], acc[0], 0, 0, 0);
+                }
+            }
+        }
+        if (part + 1 < kParts) {
+            commit(s + 1);
+            __syncthreads();
+            ++s;
+        }
+    }
+    if (wave_on && h == 0 && row < P.rows) finish_row<LOGPI>(P, acc[0], row, act, log_pi, logpi_c);
+}
+
+// ---- the packed stream, on the host (create) and on the device (load_device): the two are written independently and
+// tests/test_gpu_policy_wide.py compares their bytes.
+struct Layout {
+    int mt, kc, w, tail, ch, wout;     // Geo<MT>, at run time
+    int n1, n_chunks;                  // layer-1 chunks, chunks of the whole stream
+    int in_dim, hidden, act_dim;
+};
+
+Layout layout_of(int in_dim, int hidden, int act_dim)
+{
+    Layout g;
+    g.mt = hidden <= 192 ? 6 : 8;
+    g.kc = g.mt / 2; g.w = g.mt * 256; g.tail = g.mt * 8; g.ch = g.w + g.tail; g.wout = 2 * g.mt * 64;
+    g.n1 = (in_dim + 63) / 64;
+    g.n_chunks = g.n1 + 2 * g.kc + 1;
+    g.in_dim = in_dim; g.hidden = hidden; g.act_dim = act_dim;
+    return g;
+}
+
+struct PackParams {
+    const float *w[8];                 // fc1.weight, fc1.bias, ..., fc4.bias, device
+    uint4 *hi, *lo;                    // the two streams, n_chunks * ch pieces each
+    Layout g;
+};
+
+// round-to-nearest-even on the bit pattern (integer: no conversion's denormal mode to trust)
+__host__ __device__ inline unsigned rne_bf16(unsigned u)
+{
+    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (u >> 16) | 0x40u;     // NaN (outside the contract)
+    u += 0x7FFFu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+
+// One thread per piece of a stream: the piece's 8 weights as high and low bf16 parts, or 4 bias values of a layer's first
+// chunk (fp32: b1 | 0 for layer 1, bf(b) | bf(b - bf(b)) for the others), or the zeros of a slot's unused pieces.
+__global__ void __launch_bounds__(256) k_policy_wide_pack(const PackParams P)
+{
+    const Layout &g = P.g;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= g.n_chunks * g.ch) return;
+    const int c = q / g.ch, rp = q - c * g.ch;
+    int layer, kg;                                                          // chunk c = k-group kg of layer 0..3
+    if (c < g.n1) { layer = 0; kg = c; }
+    else if (c < g.n1 + g.kc) { layer = 1; kg = c - g.n1; }
+    else if (c < g.n1 + 2 * g.kc) { layer = 2; kg = c - g.n1 - g.kc; }
+    else { layer = 3; kg = 0; }
+    const float *__restrict__ wm = P.w[2 * layer], *__restrict__ bv = P.w[2 * layer + 1];
+    const int n_out = layer == 3 ? g.act_dim : g.hidden, n_in = layer == 0 ? g.in_dim : g.hidden;
+    const int n_w = layer == 3 ? g.wout : g.w;
+    unsigned hv[8], lv[8];
+    if (rp < n_w) {
+        const int lane = rp & 63, hh = lane >> 5;
+        const int mt = layer == 3 ? 0 : rp >> 8, ks = layer == 3 ? rp >> 6 : 4 * kg + ((rp >> 6) & 3);
+        const int o = 32 * mt + (lane & 31);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            // natural k order where B comes from memory, the accumulator tile's order elsewhere
+            const int k = layer == 0 ? 16 * ks + 8 * hh + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * hh + (j & 3);
+            const float v = (o < n_out && k < n_in) ? wm[(size_t)o * n_in + k] : 0.0f;
+            hv[j] = rne_bf16(__float_as_uint(v));
+            lv[j] = rne_bf16(__float_as_uint(v - __uint_as_float(hv[j] << 16)));      // the IEEE fp32 difference, denormals kept
+        }
+        P.hi[q] = make_uint4(hv[0] | hv[1] << 16, hv[2] | hv[3] << 16, hv[4] | hv[5] << 16, hv[6] | hv[7] << 16);
+        P.lo[q] = make_uint4(lv[0] | lv[1] << 16, lv[2] | lv[3] << 16, lv[4] | lv[5] << 16, lv[6] | lv[7] << 16);
+        return;
+    }
+    unsigned th[4] = {0u, 0u, 0u, 0u}, tl[4] = {0u, 0u, 0u, 0u};
+    const int t = rp - n_w;
+    if (kg == 0 && t < g.tail) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int f = 4 * t + e;
+            if (f < n_out) {
+                const unsigned u = __float_as_uint(bv[f]);
+                if (layer == 0) th[e] = u;
+                else {
+                    th[e] = rne_bf16(u) << 16;
+                    tl[e] = rne_bf16(__float_as_uint(bv[f] - __uint_as_float(th[e]))) << 16;
+                }
+            }
+        }
+    }
+    P.hi[q] = make_uint4(th[0], th[1], th[2], th[3]);
+    P.lo[q] = make_uint4(tl[0], tl[1], tl[2], tl[3]);
+}
+
+float bits_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+uint32_t float_bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+
+// The host packer: the stream built layer by layer into a zeroed blob.
+std::vector<unsigned char> pack_host(const Layout &g, const float *const w[8])
+{
+    const size_t stream_elems = (size_t)g.n_chunks * g.ch * 8;              // bf16 elements of one stream
+    std::vector<unsigned char> blob(2 * stream_elems * 2, 0);
+    uint16_t *hi = reinterpret_cast<uint16_t *>(blob.data()), *lo = hi + stream_elems;
+    auto put = [&](size_t piece, int j, float v) {
+        const uint16_t hb = (uint16_t)rne_bf16(float_bits(v));
+        hi[piece * 8 + j] = hb;
+        lo[piece * 8 + j] = (uint16_t)rne_bf16(float_bits(v - bits_float((uint32_t)hb << 16)));
+    };
+    auto k_acc = [](int ks, int h, int j) { return 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3); };
+    auto put_bias = [&](int chunk, int off, const float *b, int n, bool fp32) {
+        const size_t at = ((size_t)chunk * g.ch + off) * 16;                // byte offset inside a stream
+        unsigned char *th = blob.data() + at, *tl = blob.data() + stream_elems * 2 + at;
+        for (int f = 0; f < n; ++f) {
+            uint32_t uh = float_bits(b[f]), ul = 0;
+            if (!fp32) {
+                uh = rne_bf16(uh) << 16;
+                ul = rne_bf16(float_bits(b[f] - bits_float(uh))) << 16;
+            }
+            std::memcpy(th + 4 * f, &uh, 4);
+            std::memcpy(tl + 4 * f, &ul, 4);
+        }
+    };
+    for (int c = 0; c < g.n1; ++c)                                          // layer 1: natural k order
+        for (int mt = 0; mt < g.mt; ++mt)
+            for (int i = 0; i < 4; ++i)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < 8; ++j) {
+                        const int o = 32 * mt + (lane & 31), k = 16 * (4 * c + i) + 8 * (lane >> 5) + j;
+                        const float v = (o < g.hidden && k < g.in_dim) ? w[0][(size_t)o * g.in_dim + k] : 0.0f;
+                        put((size_t)c * g.ch + (mt * 4 + i) * 64 + lane, j, v);
+                    }
+    put_bias(0, g.w, w[1], g.hidden, true);
+    for (int l = 0; l < 2; ++l) {                                           // layers 2 and 3
+        const int base = g.n1 + l * g.kc;
+        for (int kc = 0; kc < g.kc; ++kc)
+            for (int mt = 0; mt < g.mt; ++mt)
+                for (int i = 0; i < 4; ++i)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 8; ++j) {
+                            const int o = 32 * mt + (lane & 31), k = k_acc(4 * kc + i, lane >> 5, j);
+                            const float v = (o < g.hidden && k < g.hidden) ? w[2 + 2 * l][(size_t)o * g.hidden + k] : 0.0f;
+                            put((size_t)(base + kc) * g.ch + (mt * 4 + i) * 64 + lane, j, v);
+                        }
+        put_bias(base, g.w, w[3 + 2 * l], g.hidden, false);
+    }
+    const int c_out = g.n1 + 2 * g.kc;                                      // the output layer: feature tile 0
+    for (int ks = 0; ks < 2 * g.mt; ++ks)
+        for (int lane = 0; lane < 64; ++lane)
+            for (int j = 0; j < 8; ++j) {
+                const int o = lane & 31, k = k_acc(ks, lane >> 5, j);
+                const float v = (o < g.act_dim && k < g.hidden) ? w[6][(size_t)o * g.hidden + k] : 0.0f;
+                put((size_t)c_out * g.ch + ks * 64 + lane, j, v);
+            }
+    put_bias(c_out, g.wout, w[7], g.act_dim, false);
+    return blob;
+}
+
+template <bool IN_BF16, bool X3, int MT>
+void launch(const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act, float *log_pi, float logpi_c)
+{
+    if (log_pi) hipLaunchKernelGGL((k_policy_wide<IN_BF16, X3, true, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, log_pi, logpi_c);
+    else hipLaunchKernelGGL((k_policy_wide<IN_BF16, X3, false, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, nullptr, 0.0f);
+}
+
+template <bool IN_BF16, bool X3, int MT>
+void set_smem()
+{
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide<IN_BF16, X3, false, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide<IN_BF16, X3, true, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
+}
+
+template <int MT>
+void set_smem_all()
+{
+    set_smem<false, false, MT>(); set_smem<true, false, MT>(); set_smem<false, true, MT>(); set_smem<true, true, MT>();
+}
+
+template <int MT>
+void launch_mt(bool in_bf16, bool x3, const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act, float *log_pi,
+               float logpi_c)
+{
+    if (x3) {
+        if (in_bf16) launch<true, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
+        else launch<false, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
+    } else {
+        if (in_bf16) launch<true, false, MT>(g, st, q, obs, act, log_pi, logpi_c);
+        else launch<false, false, MT>(g, st, q, obs, act, log_pi, logpi_c);
+    }
+}
+
+}  // namespace
+
+namespace swarm_wide {
+
+struct Handle {
+    Layout g;
+    swarm_internal::DevBuf<unsigned char> d_blob;
+    size_t blob_bytes = 0;
+    bool smem_set = false;
+};
+
+bool shape_ok(int in_dim, int hidden, int act_dim)
+{
+    return in_dim >= 4 && in_dim <= kMaxIn && !(in_dim & 3) && hidden >= 1 && hidden <= kMaxHidden && act_dim >= 1 && act_dim <= kMaxAct;
+}
+
+int create(const float *const w[8], int in_dim, int hidden, int act_dim, Handle **out, std::string &err)
+{
+    static_assert(Geo<8>::SMEM <= 160 * 1024 && kMaxHidden == 32 * 8 && kMaxIn % 64 == 0, "the widest geometry");
+    *out = nullptr;
+    Handle *p = new (std::nothrow) Handle;
+    if (!p) { err = "swarm_policy_create_wide: out of memory"; return SWARM_POLICY_ERR_INVALID; }
+    p->g = layout_of(in_dim, hidden, act_dim);
+    const std::vector<unsigned char> blob = pack_host(p->g, w);
+    p->blob_bytes = blob.size();
+    // the upload on a stream of its own, waited for here: no null-stream work (tests/test_stream_sources.py), complete on return
+    hipStream_t up = nullptr;
+    hipError_t e = p->d_blob.alloc(blob.size());
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_blob.get(), blob.data(), blob.size(), hipMemcpyHostToDevice, up);
+    if (e == hipSuccess) e = hipStreamSynchronize(up);
+    if (up) (void)hipStreamDestroy(up);
+    if (e != hipSuccess) {
+        delete p;
+        err = "swarm_policy_create_wide: device allocation / upload failed";
+        return SWARM_POLICY_ERR_HIP;
+    }
+    *out = p;
+    return SWARM_POLICY_OK;
+}
+
+void destroy(Handle *h) { delete h; }
+
+const void *blob(const Handle *h, size_t *bytes)
+{
+    *bytes = h->blob_bytes;
+    return h->d_blob.get();
+}
+
+int forward(Handle *p, const ForwardArgs &a, std::string &err)
+{
+    WideParams q;
+    q.hi = reinterpret_cast<const bf8 *>(p->d_blob.get());
+    q.lo = q.hi + (size_t)p->g.n_chunks * p->g.ch;
+    q.in_dim = p->g.in_dim; q.act_dim = p->g.act_dim; q.rows = a.rows;
+    q.noise_scale = a.noise_scale > 0.0f ? a.noise_scale : 0.0f;
+    q.noise_key = swarm_noise_key(a.seed, a.step);
+    q.row_offset = a.row_offset;
+    // log-pi's constant act_dim * log(noise_scale * sqrt(2 pi)), in double from the fp32 scale the kernel uses (swarm_policy.h)
+    const float logpi_c = q.noise_scale > 0.0f ? (float)((double)q.act_dim * std::log((double)q.noise_scale * std::sqrt(2.0 * M_PI))) : 0.0f;
+    if (!p->smem_set) {
+        set_smem_all<6>(); set_smem_all<8>();
+        p->smem_set = true;
+    }
+    const dim3 g((unsigned)((a.rows + kRowsPerBlock - 1) / kRowsPerBlock));
+    const bool x3 = a.precision == SWARM_POLICY_BF16X3;
+    if (p->g.mt == 6) launch_mt<6>(a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
+    else launch_mt<8>(a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("swarm_policy_forward: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
+    return SWARM_POLICY_OK;
+}
+
+int load_device(Handle *p, const float *const w[8], hipStream_t st, std::string &err)
+{
+    PackParams q;
+    for (int i = 0; i < 8; ++i) q.w[i] = w[i];
+    q.hi = reinterpret_cast<uint4 *>(p->d_blob.get());
+    q.lo = q.hi + (size_t)p->g.n_chunks * p->g.ch;
+    q.g = p->g;
+    const unsigned grid = (unsigned)((p->g.n_chunks * p->g.ch + 255) / 256);
+    hipLaunchKernelGGL(k_policy_wide_pack, dim3(grid), dim3(256), 0, st, q);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("swarm_policy_load_device: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
+    return SWARM_POLICY_OK;
+}
+
+}  // namespace swarm_wide

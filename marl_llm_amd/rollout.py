@@ -51,16 +51,24 @@ class FusedPolicy:
     layers chained through the accumulator registers) instead of four hipBLASLt GEMMs + elementwise kernels.  Inference
     only (rollouts); numerics = torch.autocast(bfloat16) on the module.  Built from a PolicyMLP (or any module with
     fc1..fc4); after the learner updated the weights call `sync()` (device parameters, in stream order, no host wait) or
-    `refresh()` (a new handle from a host copy; blocks).  No CPU path."""
+    `refresh()` (a new handle from a host copy; blocks).  No CPU path.
 
-    def __init__(self, module, device="cuda:0", precision="bf16"):
+    Two geometries of the kernel: the narrow one (in_dim <= 192, hidden <= 191: the reference's default shapes) and the wide
+    one (csrc/policy_wide.hip: in_dim <= 384, hidden <= 256 -- `--hidden_dim` up to 256, `num_obs_grid_max` up to 176 at the
+    default topology).  `.wide` says which one the handle runs."""
+
+    def __init__(self, module, device="cuda:0", precision="bf16", wide=None):
         """precision: "bf16" (operands rounded to bfloat16: torch.autocast's contract, ~4e-2 from the fp32 module) or "bf16x3"
         (high + low bfloat16 parts, three MFMAs per product: ~1e-4 from the fp32 module, the reference's actor arithmetic
-        for rollouts that must follow networks.py:6-44 closely)."""
+        for rollouts that must follow networks.py:6-44 closely).
+        wide: None -- the narrow kernel where it serves the module's shape, the wide one otherwise; True -- the wide kernel
+        always; False -- the narrow kernel, or its error."""
         import ctypes
         if precision not in ("bf16", "bf16x3"):
             raise ValueError("precision must be 'bf16' or 'bf16x3'")
         self.precision = precision
+        self._want_wide = wide
+        self.wide = bool(wide)
         from . import _lib
         self._ctypes = ctypes
         self.lib = _lib.load()
@@ -79,10 +87,14 @@ class FusedPolicy:
               (m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, m.fc3.weight, m.fc3.bias, m.fc4.weight, m.fc4.bias)]
         self.in_dim, self.hidden, self.act_dim = ws[0].shape[1], ws[0].shape[0], ws[6].shape[0]
         h = ct.c_void_p()
-        rc = self.lib.swarm_policy_create(*[ct.c_void_p(w.data_ptr()) for w in ws], self.in_dim, self.hidden, self.act_dim,
-                                          self.device.index, ct.byref(h))
+        narrow_serves = 4 <= self.in_dim <= 192 and self.in_dim % 4 == 0 and 1 <= self.hidden <= 191 and 1 <= self.act_dim <= 4
+        wide = (not narrow_serves) if self._want_wide is None else bool(self._want_wide)
+        name = "swarm_policy_create_wide" if wide else "swarm_policy_create"
+        rc = getattr(self.lib, name)(*[ct.c_void_p(w.data_ptr()) for w in ws], self.in_dim, self.hidden, self.act_dim,
+                                     self.device.index, ct.byref(h))
         if rc != 0:
-            raise RuntimeError("swarm_policy_create failed: " + self.lib.swarm_policy_last_error().decode())
+            raise RuntimeError(name + " failed: " + self.lib.swarm_policy_last_error().decode())
+        self.wide = wide
         self.close()
         self.handle = h
         if self.lib.swarm_policy_set_precision(self.handle, 1 if self.precision == "bf16x3" else 0) != 0:

@@ -23,9 +23,9 @@ for SYM in $(grep -o "^_ZN12_GLOBAL__N_15k_envI[A-Za-z0-9_]*:" $S | tr -d : | so
   E=$(awk -v L=$L 'NR>L && /\.end_amdhsa_kernel/{print NR; exit}' $S)
   echo "k_env<$K>" $(awk -v L=$L 'NR>L && /; (NumVgprs|ScratchSize|Occupancy|codeLenInByte)/{printf "%s ", $0; n++} n>=4{exit}' $S) "; spill instructions:" $(sed -n "${L},${E}p" $S | grep -c "Folded Spill\|Folded Reload")
 done
-# the large-swarm step kernels (env_large: no scratch, no spill in the pair, cell or filter loops), the env's side kernels, the policy kernel (VGPRs must not move: 218 for the bf16 instantiations), the rollout loop's kernels
+# the large-swarm step kernels (env_large: no scratch, no spill in the pair, cell or filter loops), the env's side kernels, the policy kernel (VGPRs must not move: 218 for the bf16 instantiations), its wide geometry (policy_wide: no scratch in any instantiation), the rollout loop's kernels
 # and the rule expert (no scratch)
-for F in env_large env_kernels policy_mlp rollout rule_expert; do
+for F in env_large env_kernels policy_mlp policy_wide rollout rule_expert; do
   $(cd $R && CMD $F) -c -o $T/$F.o \
       -Rpass-analysis=kernel-resource-usage 2>&1 | sed -n 's/.*remark: *//p' | sed 's/ \[-Rpass-analysis.*//' |
     awk '/^Function Name:/{if (l) print l; l=$3; next} /^(VGPRs|AGPRs|ScratchSize|Occupancy)/{l=l" ; "$0} END{if (l) print l}'
