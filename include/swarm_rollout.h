@@ -123,8 +123,64 @@ typedef struct swarm_eval_out {
 int swarm_rollout_eval(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps, const int32_t *switch_to,
                        const swarm_eval_out_t *out, void *stream);
 
-/* Message of the last failing swarm_rollout / swarm_rollout_logpi / swarm_rollout_expert / swarm_rollout_eval on the calling
- * thread. */
+/* Per-env exploration: the epsilon coin and the noise scale of agents.py:87-96 belong to ONE env (the reference flips
+ * np.random.rand() < self.epsilon per step of its env), so a batch of E envs flips E coins per step and may give every env
+ * its own epsilon and noise scale (an exploration spectrum over the width of the batch).  Everything is drawn on the device,
+ * counter-based, in stream order: a rollout is a function of (seed, step0, row_offset) and the arrays alone, on any rank.
+ *
+ * With key = swarm_noise_key(seed, step) (the policy's noise key above), n_agents N, global row g = row_offset + row,
+ * env e = row / N and global env ge = row_offset / N + e:
+ *
+ * Coin:
+ *   ckey = pmix64(key ^ 0xA0761D6478BD642F)            (its own salt: not the uniform-action salt 0x5851F42D4C957F2D)
+ *   h    = pmix64(ckey ^ ge)
+ *   u    = (float)(h >> 40) * 2^-24                    in [0, 1), exact in fp32
+ *   coin = u < epsilon[e]                              an fp32 compare: epsilon <= 0 or NaN never fires, epsilon >= 1 always
+ * Coin env: act[g] = the uniform action of global row g ("Uniform actions" above, keyed by g);
+ *   log_pi[g] = (float)(-2 ln 2).
+ * Other env, sigma[e] > 0: z = the normals of global row g (swarm_policy.h, "Gaussian noise");
+ *   act[g][k] = clamp(a[k] + sigma[e] * z[k], -1, 1) in fp32, no fused multiply-add, a = what the deterministic actor wrote;
+ *   log_pi[g] = -(0.5f * s) - log_c[e], s as in swarm_policy.h.
+ * Other env, sigma[e] <= 0 or NaN: act is left as it is; log_pi[g] = -0.0f.
+ *
+ * log_c is an input: the scalar path forms c = (float)((double)act_dim * log((double)sigma * sqrt(2 pi))) on the host with
+ * libm (swarm_policy.h), and a device log is not pinned to that; the caller computes log_c[e] with that expression from the
+ * fp32 sigma[e].  With epsilon = NULL and sigma[e] = s everywhere (log_c[e] = c of s) the rollout is bit for bit
+ * swarm_rollout / swarm_rollout_logpi with noise_scale = s; with epsilon[e] >= 1 everywhere it is those with every
+ * uniform_steps[t] = 1.
+ *
+ * The arrays are read when the kernels RUN, not when the call returns: as swarm_policy_load_device and swarm_reset_envs, the
+ * call only enqueues, a rewrite of the arrays enqueued on `stream` before the call is seen by it, one enqueued after it is
+ * not, and the caller keeps the arrays alive and unchanged until the stream has passed the call. */
+typedef struct swarm_explore {
+    const float *epsilon;  /* DEVICE [E] or NULL (= 0 everywhere) */
+    const float *sigma;    /* DEVICE [E], required: the noise scale of env e */
+    const float *log_c;    /* DEVICE [E]: env e's log-pi constant; required exactly when log_pi is given */
+    uint8_t     *coin;     /* DEVICE [steps][E] or NULL: 1 where env e took the uniform branch at step t */
+} swarm_explore_t;
+
+/* swarm_rollout (log_pi = NULL) / swarm_rollout_logpi (log_pi [n_slots][rows]) with per-env exploration.  Per step t:
+ *   1. swarm_policy_forward_explore_at with noise_scale = 0 on obs[c] into act[c] (the deterministic actor);
+ *   2. the exploration above applied in place to act[c] (and log_pi[c], ex->coin[t]) with (seed, step0 + t, row_offset);
+ *   3. swarm_step;  4. the reward count.
+ * The ring, the slots and reward_stats are as in swarm_rollout.  Validation first, nothing enqueued: everything swarm_rollout
+ * checks, plus: ex and ex->sigma not NULL, ex->log_c given when log_pi is, row_offset % n_agents == 0 (a coin belongs to a
+ * whole env).  The message (swarm_rollout_last_error) starts with "swarm_rollout_explore". */
+int swarm_rollout_explore(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, float *log_pi /* or NULL */,
+                          int32_t steps, const swarm_explore_t *ex, uint64_t seed, uint64_t step0, uint64_t row_offset,
+                          double *reward_stats, void *stream);
+
+/* The eager twin: one step's exploration applied in place to act[rows][2] (DEVICE, on the calling thread's current device),
+ * which holds the deterministic actor's output; rows = E * n_agents.  coin: DEVICE [rows / n_agents] or NULL (ex->coin is not
+ * used here).  One launch on `stream`, no host synchronisation.  Rejected with SWARM_ERR_INVALID, nothing enqueued: NULL act,
+ * ex or ex->sigma, log_pi without ex->log_c, rows < 0, n_agents < 1, rows or row_offset no multiple of n_agents.  The message
+ * (swarm_rollout_last_error) starts with "swarm_explore_envs". */
+int swarm_explore_envs(float *act, float *log_pi /* or NULL */, int64_t rows, int32_t n_agents, const swarm_explore_t *ex,
+                       uint8_t *coin /* [rows / n_agents] or NULL */, uint64_t seed, uint64_t step, uint64_t row_offset,
+                       void *stream);
+
+/* Message of the last failing swarm_rollout / swarm_rollout_logpi / swarm_rollout_explore / swarm_explore_envs /
+ * swarm_rollout_expert / swarm_rollout_eval on the calling thread. */
 const char *swarm_rollout_last_error(void);
 
 #ifdef __cplusplus

@@ -37,6 +37,10 @@ class SwarmEvalOut(ctypes.Structure):            # include/swarm_rollout.h swarm
     _fields_ = [("metrics", ctypes.c_void_p), ("p", ctypes.c_void_p), ("dp", ctypes.c_void_p), ("reward_stats", ctypes.c_void_p)]
 
 
+class SwarmExplore(ctypes.Structure):            # include/swarm_rollout.h swarm_explore_t
+    _fields_ = [("epsilon", ctypes.c_void_p), ("sigma", ctypes.c_void_p), ("log_c", ctypes.c_void_p), ("coin", ctypes.c_void_p)]
+
+
 class SwarmError(RuntimeError):
     pass
 
@@ -54,8 +58,9 @@ POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_create_wide", "swarm_poli
                   "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_forward_explore_logpi",
                   "swarm_policy_set_precision", "swarm_policy_load_device", "swarm_policy_read_packed",
                   "swarm_policy_last_error")   # include/swarm_policy.h
-ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_logpi", "swarm_rollout_expert", "swarm_rollout_eval",
+ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_logpi", "swarm_rollout_explore", "swarm_rollout_expert", "swarm_rollout_eval",
                    "swarm_rollout_last_error")   # include/swarm_rollout.h
+EXPLORE_SYMBOLS = ("swarm_explore_envs",)        # include/swarm_rollout.h: the eager twin of swarm_rollout_explore's kernel
 LEGACY_SYMBOLS = ("_get_observation", "_get_reward", "_sf_b2b_all", "_get_dist_b2w", "calculateActionPrior",
                   "swarm_legacy_status", "swarm_legacy_last_error")
 
@@ -107,6 +112,12 @@ def load():
     lib.swarm_rollout_logpi.argtypes = [vp, vp, ctypes.POINTER(SwarmRing), vp, ctypes.c_int32, vp, ctypes.c_float, ctypes.c_uint64,
                                         ctypes.c_uint64, ctypes.c_uint64, vp, vp]
     lib.swarm_rollout_logpi.restype = i32
+    lib.swarm_rollout_explore.argtypes = [vp, vp, ctypes.POINTER(SwarmRing), vp, ctypes.c_int32, ctypes.POINTER(SwarmExplore),
+                                          ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, vp, vp]
+    lib.swarm_rollout_explore.restype = i32
+    lib.swarm_explore_envs.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(SwarmExplore), vp, ctypes.c_uint64,
+                                       ctypes.c_uint64, ctypes.c_uint64, vp]
+    lib.swarm_explore_envs.restype = i32
     lib.swarm_rollout_expert.argtypes = [vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, ctypes.c_int32, vp, vp]
     lib.swarm_rollout_expert.restype = i32
     lib.swarm_rollout_eval.argtypes = [vp, vp, ctypes.POINTER(SwarmRing), ctypes.c_int32, vp, ctypes.POINTER(SwarmEvalOut), vp]

@@ -2,6 +2,7 @@
 // transitions written straight into a chained replay ring.  The loop itself is host code that only enqueues: per step the
 // policy kernel (policy_mlp.hip) or the uniform-action kernel below, the env step (swarm_env.hip) and, optionally, the
 // reward-count kernel below, all on one stream; the reward statistics are finished by one launch after the loop.
+// swarm_rollout_explore is that loop with the exploration per env: the actor without noise, then k_explore_envs below.
 // swarm_rollout_expert is the same loop with an expert in place of the policy: the rule-based expert kernel (rule_expert.hip,
 // after the env's index-export observation pass) or a copy of the env's own 'llm' action.  swarm_rollout_eval is the evaluation loop:
 // the actor without noise, and per step a state trace, an optional device-side shape switch and the wrapper metrics.
@@ -83,6 +84,66 @@ __global__ void __launch_bounds__(kThreads) k_uniform_actions(float2 *__restrict
     a.y = (float)(unsigned)((h >> 16) & 0xFFFFFFull) * 1.1920928955078125e-07f - 1.0f;
     act[row] = a;
     if constexpr (LOGPI) log_pi[row] = kLogPiUniform;
+}
+
+// Per-env exploration (swarm_rollout.h "Per-env exploration"), in place on the deterministic actor's output: one thread per
+// row.  Env e's coin picks the uniform action of k_uniform_actions for all of its rows; otherwise sigma[e] > 0 adds the policy
+// kernel's Gaussian noise -- the Box-Muller block of policy_mlp.hip restated for act_dim 2 with the same calls (logf, sqrtf,
+// sincosf) in the same order, so that a constant sigma reproduces that kernel's epilogue bit for bit -- and sigma[e] <= 0 / NaN
+// leaves the action alone.  epsilon[e], sigma[e] and log_c[e] are one address per wave where n_agents is a multiple of 64.
+// The first row of each env writes coin[e].  LOGPI: also log_pi[row].
+struct ExploreParams {
+    const float *epsilon, *sigma, *log_c;      // [E]; epsilon may be NULL, log_c is read with LOGPI only
+    unsigned long long key, ckey, ukey;        // the step's noise key, and its coin and uniform-action keys
+    unsigned long long row_offset, env_offset; // global row of row 0, global env of env 0
+    long long rows;
+    int n_agents;
+};
+constexpr unsigned long long kCoinSalt = 0xA0761D6478BD642Full;          // separates the coin stream from the other two
+
+template <bool LOGPI>
+__global__ void __launch_bounds__(kThreads) k_explore_envs(float2 *__restrict__ act, float *__restrict__ log_pi,
+                                                           uint8_t *__restrict__ coin, const ExploreParams P)
+{
+    const long long row = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (row >= P.rows) return;
+    // rows below 2^31 (every batch in practice): a 32-bit division
+    const long long e = P.rows <= 0x7FFFFFFFll ? (long long)((unsigned)row / (unsigned)P.n_agents) : row / P.n_agents;
+    const unsigned long long g = P.row_offset + (unsigned long long)row;
+    const unsigned long long hc = pmix64(P.ckey ^ (P.env_offset + (unsigned long long)e));
+    const float u = (float)(unsigned)(hc >> 40) * 5.9604644775390625e-08f;                              // 2^-24: [0, 1)
+    const bool fire = P.epsilon != nullptr && u < P.epsilon[e];
+    if (coin != nullptr && row == e * P.n_agents) coin[e] = fire ? 1 : 0;
+    if (fire) {
+        const unsigned long long h = pmix64(P.ukey ^ g);
+        float2 a;
+        a.x = (float)(unsigned)((h >> 40) & 0xFFFFFFull) * 1.1920928955078125e-07f - 1.0f;             // 2^-23
+        a.y = (float)(unsigned)((h >> 16) & 0xFFFFFFull) * 1.1920928955078125e-07f - 1.0f;
+        act[row] = a;
+        if constexpr (LOGPI) log_pi[row] = kLogPiUniform;
+        return;
+    }
+    const float sg = P.sigma[e];
+    float lp = -0.0f;                                                       // no noise: -act_dim log(1) = -0.0
+    if (sg > 0.0f) {
+        const unsigned long long hk = pmix64(P.key ^ g);
+        const float u1 = (float)((unsigned)(hk >> 40) + 1u) * 5.9604644775390625e-08f;                  // (0, 1]
+        const float u2 = (float)((unsigned)(hk >> 16) & 0xFFFFFFu) * 5.9604644775390625e-08f;           // [0, 1)
+        const float rad = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.283185307179586f * u2, &sn, &cs);
+        const float z0 = rad * cs, z1 = rad * sn;
+        float2 a = act[row];
+        a.x = fminf(fmaxf(a.x + sg * z0, -1.0f), 1.0f);
+        a.y = fminf(fmaxf(a.y + sg * z1, -1.0f), 1.0f);
+        act[row] = a;
+        if constexpr (LOGPI) {                                              // -(0.5 sum_k z_k^2) - c, the sum in k order
+            float s = z0 * z0;
+            s = s + z1 * z1;
+            lp = -(0.5f * s) - P.log_c[e];
+        }
+    }
+    if constexpr (LOGPI) log_pi[row] = lp;
 }
 
 // Number of nonzero rewards of one step, added (one 64-bit atomic per workgroup) to the zeroed counter that shares the
@@ -308,11 +369,97 @@ int rollout_impl(const char *who, bool want_logpi, swarm_env_t *env, swarm_polic
     });
 }
 
+// The pointer checks of a swarm_explore_t shared by swarm_rollout_explore and swarm_explore_envs; "" = fine.
+const char *check_explore(const swarm_explore_t *ex, const float *log_pi)
+{
+    if (!ex || !ex->sigma) return "null ex or ex->sigma (a [E] fp32 device array of noise scales is required)";
+    if (log_pi && !ex->log_c) return "log_pi is given: ex->log_c (the [E] log-pi constants) is required";
+    return "";
+}
+
+// One step's k_explore_envs on `st`: rows = E * n_agents rows of act (log_pi, coin [E]: NULL = off), row_offset % n_agents == 0.
+hipError_t launch_explore(float *act, float *log_pi, uint8_t *coin, long long rows, int n_agents, const swarm_explore_t *ex,
+                          uint64_t seed, uint64_t step, uint64_t row_offset, hipStream_t st)
+{
+    if (rows == 0) return hipSuccess;
+    ExploreParams P;
+    P.epsilon = ex->epsilon; P.sigma = ex->sigma; P.log_c = ex->log_c;
+    P.key = swarm_noise_key(seed, step);
+    P.ckey = pmix64(P.key ^ kCoinSalt);
+    P.ukey = pmix64(P.key ^ kUniformSalt);
+    P.row_offset = row_offset; P.env_offset = row_offset / (unsigned long long)n_agents;
+    P.rows = rows; P.n_agents = n_agents;
+    const dim3 grid((unsigned)((rows + kThreads - 1) / kThreads));
+    if (log_pi)
+        hipLaunchKernelGGL(k_explore_envs<true>, grid, dim3(kThreads), 0, st, reinterpret_cast<float2 *>(act), log_pi, coin, P);
+    else
+        hipLaunchKernelGGL(k_explore_envs<false>, grid, dim3(kThreads), 0, st, reinterpret_cast<float2 *>(act), nullptr, coin, P);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
 
 const char *swarm_rollout_last_error(void) { return g_rollout_error.c_str(); }
+
+int swarm_rollout_explore(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, float *log_pi, int32_t steps,
+                          const swarm_explore_t *ex, uint64_t seed, uint64_t step0, uint64_t row_offset, double *reward_stats,
+                          void *stream)
+{
+    static const char *const who = "swarm_rollout_explore";
+    // ---- validation: nothing is enqueued before all of it passed
+    if (!env || !pol || !ring) return fail(SWARM_ERR_INVALID, "null env, policy or ring", who);
+    if (const char *m = check_explore(ex, log_pi); *m) return fail(SWARM_ERR_INVALID, m, who);
+    swarm_env_info ei;
+    swarm_policy_info pi;
+    if (int rc = check_handles(who, env, steps, ei, pol, &pi)) return rc;
+    if (ei.obs_dtype != SWARM_F32 && ei.obs_dtype != SWARM_BF16)
+        return fail(SWARM_ERR_INVALID, "the env handle's obs dtype must be SWARM_F32 or SWARM_BF16 (the policy reads no fp64 rows)", who);
+    if (int rc = check_policy_ring(who, ei, pi, ring)) return rc;
+    if (row_offset % (uint64_t)ei.n_agents != 0) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "row_offset %llu is no multiple of n_agents %d (a coin belongs to a whole env)",
+                      (unsigned long long)row_offset, ei.n_agents);
+        return fail(SWARM_ERR_INVALID, msg, who);
+    }
+    if (int rc = check_observed(who, ei)) return rc;
+    if (steps == 0) return SWARM_OK;
+
+    // ---- enqueue
+    const Loop L(who, env, ei, ring, stream);
+    if (L.rc != SWARM_OK) return L.rc;
+    return run_loop(L, steps, reward_stats, [&](int t) {
+        float *const act = L.act(t);
+        float *const lp = log_pi ? log_pi + (size_t)L.c(t) * L.rows : nullptr;
+        if (swarm_policy_forward_explore_at(pol, L.obs(L.c(t)), L.bf16, L.rows, act, 0.0f, seed, step0 + t, row_offset, stream) != SWARM_POLICY_OK)
+            return fail(SWARM_ERR_HIP, swarm_policy_last_error(), who);
+        uint8_t *const coin = ex->coin ? ex->coin + (size_t)t * ei.n_env : nullptr;
+        if (int rc = L.check(launch_explore(act, lp, coin, L.rows, ei.n_agents, ex, seed, step0 + t, row_offset, L.st), "k_explore_envs")) return rc;
+        return L.step(act, SWARM_F32, t);
+    });
+}
+
+int swarm_explore_envs(float *act, float *log_pi, int64_t rows, int32_t n_agents, const swarm_explore_t *ex, uint8_t *coin,
+                       uint64_t seed, uint64_t step, uint64_t row_offset, void *stream)
+{
+    static const char *const who = "swarm_explore_envs";
+    if (!act) return fail(SWARM_ERR_INVALID, "null act", who);
+    if (const char *m = check_explore(ex, log_pi); *m) return fail(SWARM_ERR_INVALID, m, who);
+    if (rows < 0 || n_agents < 1 || rows % n_agents != 0) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "rows %lld must be >= 0 and a multiple of n_agents %d >= 1", (long long)rows, n_agents);
+        return fail(SWARM_ERR_INVALID, msg, who);
+    }
+    if (row_offset % (uint64_t)n_agents != 0) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "row_offset %llu is no multiple of n_agents %d (a coin belongs to a whole env)",
+                      (unsigned long long)row_offset, n_agents);
+        return fail(SWARM_ERR_INVALID, msg, who);
+    }
+    return hip_check(who, launch_explore(act, log_pi, coin, rows, n_agents, ex, seed, step, row_offset, static_cast<hipStream_t>(stream)),
+                     "k_explore_envs");
+}
 
 int swarm_rollout(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps, const uint8_t *uniform_steps,
                   float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset, double *reward_stats, void *stream)

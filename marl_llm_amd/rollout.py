@@ -11,7 +11,8 @@ ring buffer (train_assembly.py:91-111, maddpg.py:72-87, agents.py:69-96, buffer_
 * `ChainedReplay` -- the same transitions stored as a ring of env steps that share observation rows (half the copy per push).
 * `rollout`       -- obs -> policy -> exploration noise (agents.py:82-96 continuous branch) -> env.step_tensor -> push.
 * `rollout_device`-- the same loop (fused policy, chained ring) as ONE library call per episode: swarm_rollout; with
-                     log_pi=True also each action's log-probability (swarm_rollout_logpi), the AIRL agent side's log_pi.
+                     log_pi=True also each action's log-probability (swarm_rollout_logpi), the AIRL agent side's log_pi;
+                     with coin="env" the epsilon coin and the noise scale per env, drawn on the device (swarm_rollout_explore).
 * `rollout_expert`-- expert rollouts (rule-based expert or the prior's 'llm' twin) into the same ring, one library call per
                      episode batch: swarm_rollout_expert (collect_expert_data.py's loop on the device).
 * `EpisodeClock`  -- staggered episodes for the device loops: the resets= schedule (whole-batch and per-env resets inside a
@@ -369,17 +370,89 @@ def gaussian_log_pi(z, noise_scale):
     return -(0.5 * s) - c
 
 
+COINS = ("batch", "env")
+
+
+def explore_log_c(sigma, act_dim=2):
+    """The log-pi constants of per-env noise scales, as include/swarm_policy.h states them for the scalar path: for every
+    fp32 sigma[e] > 0 the fp32 rounding of act_dim * log(sigma[e] * sqrt(2 pi)) evaluated in double with libm; 0 where
+    sigma[e] <= 0 or NaN (such an env records -0.0 and never reads its constant).  sigma: array-like -> float32 array."""
+    import math
+    s = np.asarray(sigma, dtype=np.float32).reshape(-1)
+    return np.array([np.float32(act_dim * math.log(float(v) * math.sqrt(2.0 * math.pi))) if v > 0 else np.float32(0.0) for v in s],
+                    dtype=np.float32)
+
+
+class _Explore:
+    """The per-env exploration arrays of one coin="env" call, checked and on the device: epsilon (None = 0 everywhere), sigma,
+    log_c (None without log_pi), coin_out (None = not recorded).  Built before anything is enqueued."""
+
+    def __init__(self, who, E, steps, device, epsilon, noise_scale, log_pi, log_c, coin_out):
+        def vector(x, name):
+            """float / array-like [E] / float32 tensor [E] on the device -> (array or tensor [E], is it the caller's tensor)"""
+            if isinstance(x, torch.Tensor) and (x.is_cuda or x.device == device):
+                if x.dtype != torch.float32 or tuple(x.shape) != (E,) or not x.is_contiguous() or x.device != device:
+                    raise ValueError(f"{who}: a device {name} must be a contiguous float32 tensor [{E}] on {device}")
+                return x, True
+            a = np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32)
+            if a.ndim == 0:
+                a = np.full(E, a, np.float32)
+            if a.shape != (E,):
+                raise ValueError(f"{who}: {name} must be a float or hold one value per env, [{E}]; got shape {a.shape}")
+            return np.ascontiguousarray(a), False
+
+        eps, eps_dev = (None, False) if (not isinstance(epsilon, torch.Tensor) and np.ndim(epsilon) == 0 and not epsilon > 0) \
+            else vector(epsilon, "epsilon")
+        sig, sig_dev = vector(noise_scale, "noise_scale")
+        lc = None
+        if log_pi:
+            if log_c is not None:
+                lc, lc_dev = vector(log_c, "log_c")
+            elif sig_dev:
+                raise ValueError(f"{who}: a cuda-tensor noise_scale with log_pi=True needs log_c= (its constants are formed on "
+                                 "the host in double, rollout.explore_log_c; a device log is not pinned to that)")
+            else:
+                lc = explore_log_c(sig)
+        elif log_c is not None:
+            raise ValueError(f"{who}: log_c= is the log-pi constant; it needs log_pi=True")
+        if coin_out is not None and (not isinstance(coin_out, torch.Tensor) or coin_out.dtype != torch.uint8 or coin_out.device != device
+                                     or tuple(coin_out.shape) != (steps, E) or not coin_out.is_contiguous()):
+            raise ValueError(f"{who}: coin_out must be a contiguous uint8 tensor [{steps}, {E}] on {device}")
+        up = lambda a: a if a is None or isinstance(a, torch.Tensor) else torch.from_numpy(a).to(device)
+        self.epsilon, self.sigma, self.log_c, self.coin_out, self.E = up(eps), up(sig), up(lc), coin_out, E
+
+    def struct(self, step=0):
+        """swarm_explore_t with the coins of step `step` on (a stretch of a call starts there)."""
+        from . import _lib
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        coin = self.coin_out.data_ptr() + step * self.E if self.coin_out is not None else None
+        return _lib.SwarmExplore(ptr(self.epsilon), ptr(self.sigma), ptr(self.log_c), coin)
+
+
+def _check_coin(who, coin, log_c, coin_out):
+    if coin not in COINS:
+        raise ValueError(f"{who}: coin must be 'batch' (one host coin per step for the whole batch) or 'env' (one device coin "
+                         "per env and step)")
+    if coin == "batch" and (log_c is not None or coin_out is not None):
+        raise ValueError(f"{who}: log_c= and coin_out= belong to coin='env'")
+
+
 @torch.no_grad()
 def rollout(env, policy, steps, obs, replay=None, noise_scale=0.0, epsilon=0.0, generator=None, host_rng=None,
-            track_reward=True, seed=0, step0=0, log_pi=False):
+            track_reward=True, seed=0, step0=0, log_pi=False, coin="batch", log_c=None, coin_out=None):
     """Run `steps` env steps entirely on the device.
 
     env   : object with step_tensor(action[E,N,2]) -> (obs[E,N,D], rew[E,N], done[E,N], a_prior[E,N,2]|None)
             (marl_llm_amd.env.AssemblySwarmEnv, or a SwarmBatch through `step`)
     obs   : current observation tensor [E,N,D] (from reset_tensor / the previous rollout)
-    The epsilon coin of agents.py:89 is drawn on the HOST (numpy, like the reference's np.random.rand()): a device-side
-    draw would cost a host synchronisation every step.  `host_rng`: anything with a .random() method -- the np.random
-    module (default), a RandomState or a Generator (np.random.default_rng).
+    coin="batch" (default): ONE epsilon coin of agents.py:89 per step for the whole batch, drawn on the HOST (numpy, like the
+    reference's np.random.rand()).  `host_rng`: anything with a .random() method -- the np.random module (default), a
+    RandomState or a Generator (np.random.default_rng).
+    coin="env" (the fused path only): one coin per ENV and step, as E copies of the reference's loop flip it, drawn on the
+    device by a counter-based generator keyed by (seed, step0 + t, env) -- no host synchronisation and no host RNG.  epsilon
+    and noise_scale may each be a float, an array-like [E] or a float32 cuda tensor [E]; log_c and coin_out ([steps, E] uint8)
+    as in rollout_device.  Per step: the actor without noise, then swarm_explore_envs (include/swarm_rollout.h) in place on
+    the ring slot.  This loop is the witness of rollout_device(coin="env"): the same bits.
 
     Fused path (policy is a FusedPolicy, replay a ChainedReplay, env a SwarmBatch): TWO launches per step and no copies --
     the policy kernel adds the exploration noise in its epilogue (counter-based generator keyed by (seed, step0 + t, row))
@@ -397,11 +470,33 @@ def rollout(env, policy, steps, obs, replay=None, noise_scale=0.0, epsilon=0.0, 
     step = env.step_tensor if hasattr(env, "step_tensor") else env.step
     E, N, D = obs.shape
     rews = torch.zeros(steps, device=obs.device) if track_reward else None
-    coin = host_rng if host_rng is not None else np.random
     fused = isinstance(policy, FusedPolicy) and isinstance(replay, ChainedReplay) and isinstance(env, SwarmBatch)
+    _check_coin("rollout", coin, log_c, coin_out)
+    per_env = None
+    if coin == "env":
+        if not fused:
+            raise ValueError("rollout(coin='env') runs on the fused path: a FusedPolicy, a ChainedReplay and a SwarmBatch")
+        import ctypes
+        from . import _lib
+        per_env = _Explore("rollout", E, steps, policy.device, epsilon, noise_scale, log_pi, log_c, coin_out)
+        m64 = 2 ** 64 - 1
+    draw = host_rng if host_rng is not None else np.random
     for t in range(steps):
-        explore_uniform = epsilon > 0 and coin.random() < epsilon                                     # agents.py:89-91
-        if fused:
+        explore_uniform = per_env is None and epsilon > 0 and draw.random() < epsilon                 # agents.py:89-91
+        if per_env is not None:
+            sl = replay.begin_step(obs)
+            policy(sl["obs_in"], out=sl["act"], noise_scale=0.0, seed=seed, step=step0 + t)
+            ex = per_env.struct()
+            rc = policy.lib.swarm_explore_envs(sl["act"].data_ptr(), sl["log_pi"].data_ptr() if log_pi else None, E * N, N,
+                                               ctypes.byref(ex), coin_out[t].data_ptr() if coin_out is not None else None,
+                                               int(seed) & m64, (int(step0) + t) & m64, 0,
+                                               ctypes.c_void_p(torch.cuda.current_stream(policy.device).cuda_stream))
+            if rc != 0:
+                raise _lib.SwarmError(f"libswarmenv error {rc}: {policy.lib.swarm_rollout_last_error().decode()}")
+            next_obs, rew, done, pri = env.step(sl["act"].view(E, N, 2),
+                                                out=dict(obs=sl["next_obs"], rew=sl["rew"], done=sl["done"], prior=sl["prior"]))
+            replay.end_step()
+        elif fused:
             sl = replay.begin_step(obs)
             if explore_uniform:
                 sl["act"].copy_(torch.rand((E * N, policy.act_dim), device=obs.device, generator=generator) * 2 - 1)
@@ -454,7 +549,7 @@ def _is_view_of(t, slot):
 
 @torch.no_grad()
 def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, epsilon=0.0, host_rng=None, seed=0, step0=0,
-                   row_offset=0, reset=None, track_reward=True, log_pi=False, resets=None):
+                   row_offset=0, reset=None, track_reward=True, log_pi=False, resets=None, coin="batch", log_c=None, coin_out=None):
     """`steps` exploring-actor + env steps in ONE library call (swarm_rollout, include/swarm_rollout.h): the launches are
     enqueued on torch's current stream and the call returns without a host synchronisation.
 
@@ -468,6 +563,17 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
                starts a new chain through replay.new_chain(): the stored transitions keep their true next_obs.
     epsilon  : the coin of agents.py:89-91, drawn on the host before the call, one host_rng.random() per step (the order and
                count rollout() uses); a coin step takes counter-based uniform actions instead of the policy.
+    coin     : "batch" (default) -- the line above: one host coin per step, every env of the batch explores uniformly at the
+               same instant.  "env" -- one coin per ENV and step, what E independent copies of the reference's episode loop
+               flip (swarm_rollout_explore, include/swarm_rollout.h "Per-env exploration"): drawn on the device in stream
+               order from (seed, step0 + t, row_offset // N + e), so host_rng is not consumed and the call is a function of
+               its arguments alone, on any rank (row_offset must be a multiple of N).  epsilon and noise_scale may then each
+               be a float, an array-like [E] or a float32 cuda tensor [E] -- an exploration spectrum over the width of the
+               batch; device tensors are read when the kernels run (values written on the stream before the call are seen)
+               and cost no upload.  With epsilon 0 and one noise_scale the result is bit for bit coin="batch"'s.
+    log_c    : coin="env" with log_pi=True: the log-pi constants [E] (explore_log_c).  Computed on the host in double from the
+               fp32 noise_scale unless given; a cuda-tensor noise_scale needs it given (ValueError otherwise).
+    coin_out : coin="env": a uint8 cuda tensor [steps, E] that receives 1 where env e took the uniform branch at step t.
     resets   : {step: (seed, episode[, env_offset])} with 0 <= step < steps -- episode boundaries inside the call (SwarmBatch
                only; EpisodeClock writes such schedules).  An int episode is the whole-batch reset, an int array-like /
                int64 cuda tensor [E] the per-env one (SwarmBatch.reset_envs: -1 keeps the env).  The reset of step t comes
@@ -502,14 +608,22 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
     replay = _device_ring(sb, replay, log_pi)
     if log_pi and replay.log_pi is None:
         raise ValueError("rollout_device(log_pi=True) needs a ChainedReplay built with log_pi=True")
+    _check_coin("rollout_device", coin, log_c, coin_out)
+    # coin="env": the arrays are checked and uploaded here, before the ring is touched and before anything is enqueued
+    per_env = _Explore("rollout_device", E, steps, sb.device, epsilon, noise_scale, log_pi, log_c, coin_out) if coin == "env" else None
     lib = _lib.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream(sb.device).cuda_stream)
 
     def call(k, coins, stats, a=0):
         ring = _ring_struct(sb, replay)
-        tail = (k, coins.ctypes.data_as(ctypes.c_void_p) if coins is not None else None, float(noise_scale),
-                int(seed) & (2 ** 64 - 1), (int(step0) + a) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1),
+        keys = (int(seed) & (2 ** 64 - 1), (int(step0) + a) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1),
                 ctypes.c_void_p(stats[a:].data_ptr()) if stats is not None else None, stream)
+        if per_env is not None:
+            ex = per_env.struct(a)
+            rc = lib.swarm_rollout_explore(sb.handle, policy.handle, ctypes.byref(ring),
+                                           ctypes.c_void_p(replay.log_pi.data_ptr()) if log_pi else None, k, ctypes.byref(ex), *keys)
+            return _check_rollout(lib, rc, k, first)
+        tail = (k, coins.ctypes.data_as(ctypes.c_void_p) if coins is not None else None, float(noise_scale)) + keys
         if log_pi:
             rc = lib.swarm_rollout_logpi(sb.handle, policy.handle, ctypes.byref(ring), ctypes.c_void_p(replay.log_pi.data_ptr()), *tail)
         else:
@@ -517,9 +631,9 @@ def rollout_device(env, policy, steps, obs=None, replay=None, noise_scale=0.0, e
         _check_rollout(lib, rc, k, first)
 
     coins = None
-    if epsilon > 0:
-        coin = host_rng if host_rng is not None else np.random
-        coins = np.array([coin.random() < epsilon for _ in range(steps)], dtype=np.uint8)          # agents.py:89
+    if per_env is None and epsilon > 0:
+        draw = host_rng if host_rng is not None else np.random
+        coins = np.array([draw.random() < epsilon for _ in range(steps)], dtype=np.uint8)          # agents.py:89
     stats = torch.empty((steps, 2), dtype=torch.float64, device=sb.device) if track_reward else None
     _run_stretches(aenv, sb, replay, obs, reset, plan, steps, lambda: call(0, None, None),
                    lambda a, b: call(b - a, np.ascontiguousarray(coins[a:b]) if coins is not None else None, stats, a), "rollout_device")
