@@ -131,6 +131,36 @@ int  swarm_policy_load_device(swarm_policy_t *p, const float *w1, const float *b
  * negative capacity returns -SWARM_POLICY_ERR_INVALID, a HIP error -SWARM_POLICY_ERR_HIP, with a message. */
 int64_t swarm_policy_read_packed(swarm_policy_t *p, void *host_dst, int64_t capacity, void *stream);
 
+/* ---- Actor bank: one handle, M actors, one launch.
+ * A bank holds `members` weight sets of ONE shape (in_dim, hidden, act_dim), one precision and one geometry.  Every forward
+ * call above takes a bank handle: over `rows` rows, member m evaluates the contiguous rows [m R, (m + 1) R), R = rows / members
+ * -- equal, contiguous groups, the split a scalar: no table, no per-row index, nothing to upload.  rows % members != 0 is
+ * rejected with SWARM_POLICY_ERR_INVALID, a message that names both numbers, and nothing enqueued.  Row r of the call gets, bit
+ * for bit, what a plain handle built from member (r / R)'s arrays gives for that row (actions and log_pi): the noise is keyed
+ * by row_offset + r as for a plain handle, so it does not depend on M, and log-pi's constant is one per call.  A workgroup
+ * serves rows of one member only and never reads or writes a row past its member's last.
+ *
+ * w[8 m + i]: HOST pointers in the order fc1.weight, fc1.bias, ..., fc4.bias of member m (torch.nn.Linear layout, fp32).
+ * wide = 0: the narrow geometry and swarm_policy_create's shape limits; wide = 1: the wide geometry and
+ * swarm_policy_create_wide's.  1 <= members <= SWARM_POLICY_BANK_MAX; device memory is members x the single handle's packed
+ * weights, and member m's slice is byte for byte what swarm_policy_create / swarm_policy_create_wide builds from the same
+ * arrays.  Everything is checked before any device call; a rejection returns SWARM_POLICY_ERR_INVALID with a message that
+ * starts "swarm_policy_bank_create:"; without a device: SWARM_POLICY_ERR_HIP, "no HIP device".
+ * swarm_policy_set_precision applies to all members.  swarm_policy_load_device and swarm_policy_read_packed on a bank of more
+ * than one member are rejected (SWARM_POLICY_ERR_INVALID, the message names the bank call below). */
+#define SWARM_POLICY_BANK_MAX 256
+int  swarm_policy_bank_create(const float *const *w, int members, int in_dim, int hidden, int act_dim, int wide, int device,
+                              swarm_policy_t **out);
+/* The members of a bank; 1 for a plain handle (0 for NULL). */
+int  swarm_policy_bank_members(const swarm_policy_t *p);
+/* swarm_policy_load_device for ONE member (0 <= member < members, else SWARM_POLICY_ERR_INVALID and nothing enqueued): enqueue
+ * only, stream order, the same bytes as the host packer; the other members' bytes are untouched.  Messages start
+ * "swarm_policy_bank_load_device:". */
+int  swarm_policy_bank_load_device(swarm_policy_t *p, int member, const float *w1, const float *b1, const float *w2, const float *b2,
+                                   const float *w3, const float *b3, const float *w4, const float *b4, void *stream);
+/* swarm_policy_read_packed for ONE member's slice (the size returned is one member's). */
+int64_t swarm_policy_bank_read_packed(swarm_policy_t *p, int member, void *host_dst, int64_t capacity, void *stream);
+
 const char *swarm_policy_last_error(void);
 
 #ifdef __cplusplus

@@ -58,7 +58,11 @@ typedef struct swarm_ring {
  * swarm_set_stream).  uniform_steps: HOST [steps], 1 = the uniform (epsilon) branch for that step; NULL = none.
  * reward_stats: DEVICE [steps][2] doubles, NULL = off.  The env handle must be observed (swarm_observe / swarm_reset) and
  * the policy's act_dim must be 2.  Returns SWARM_OK, SWARM_ERR_INVALID / SWARM_ERR_STATE (nothing enqueued) or
- * SWARM_ERR_HIP; the message is in swarm_rollout_last_error. */
+ * SWARM_ERR_HIP; the message is in swarm_rollout_last_error.
+ * An actor bank (swarm_policy_bank_create, swarm_policy.h) is taken by swarm_rollout, swarm_rollout_logpi, swarm_rollout_explore
+ * and swarm_rollout_eval unchanged: with E envs and M members, env e acts with member e / (E / M) at every step -- the
+ * bank's contiguous row groups, whole envs each.  E % M != 0 is SWARM_ERR_INVALID, found during validation (nothing enqueued),
+ * with a message that starts with the entry point's name. */
 int swarm_rollout(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps,
                   const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset,
                   double *reward_stats, void *stream);

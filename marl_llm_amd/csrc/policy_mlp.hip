@@ -84,190 +84,20 @@ constexpr int kSmemBytes = 2 * kChunkFrags * 64 * 16;                       // 7
 // LDS buffers: twice as many chunk steps); a high chunk meets both activation parts, a low chunk the high part only.
 // LOGPI: also write log_pi[row], the log-density of the row's Gaussian exploration noise (include/swarm_policy.h).  A template
 // parameter rather than a run-time test, so that the instantiations without it compile exactly as before (218 VGPRs).
-template <bool IN_BF16, int TPW, bool X3, bool LOGPI>
-__global__ void __launch_bounds__(64 * waves_of(X3), (TPW == 1 && !X3) ? 2 : 1)
-k_policy_mlp(const MlpParams P, const void *__restrict__ obs_, float *__restrict__ act, float *__restrict__ log_pi, float logpi_c)
-{
-    constexpr int kWaves = waves_of(X3), kPre = pre_of(kWaves);
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    bf8 *const buf[2] = {reinterpret_cast<bf8 *>(smem_raw), reinterpret_cast<bf8 *>(smem_raw) + kChunkFrags * 64};
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const long long row0 = ((long long)blockIdx.x * kWaves + wave) * (32 * TPW) + r;    // this lane's row in tile 0
-    const bool wave_on = row0 - r < P.rows;                                             // idle waves still stage and take the barriers
-
-    bf8 pre[kPre];
-    // chunk step cc: X3 interleaves (chunk c, high) and (chunk c, low)
-    constexpr int kSteps = X3 ? 2 * kChunks : kChunks;
-    auto issue = [&](int cc) {                                              // chunk step cc of the weight stream -> registers
-        const int c = X3 ? cc >> 1 : cc;
-        const bool low = X3 && (cc & 1);
-        const bf8 *b1_ = low ? P.l1 : P.w1, *b2_ = low ? P.l2 : P.w2, *b3_ = low ? P.l3 : P.w3, *b4_ = low ? P.l4 : P.w4;
-        const bf8 *w = c < 2 ? b1_ + (size_t)c * kChunkFrags * 64 : c < 4 ? b2_ + (size_t)(c - 2) * kChunkFrags * 64
-                     : c < 6 ? b3_ + (size_t)(c - 4) * kChunkFrags * 64 : b4_;
-        const int n = (c < 6 ? kChunkFrags : kKS) * 64;
-#pragma unroll
-        for (int k = 0; k < kPre; ++k) { const int q = tid + k * 64 * kWaves; if (q < n) pre[k] = w[q]; }
-    };
-    auto commit = [&](int cc) {                                             // registers -> LDS buffer of chunk step cc
-        const int c = X3 ? cc >> 1 : cc;
-        const int n = (c < 6 ? kChunkFrags : kKS) * 64;
-#pragma unroll
-        for (int k = 0; k < kPre; ++k) { const int q = tid + k * 64 * kWaves; if (q < n) buf[cc & 1][q] = pre[k]; }
-    };
-
-    issue(0);
-    // the 12 B fragments of layer 1, straight from the observation row (natural k order); later `pk` holds the packed
-    // activations of the previous layer (k-step = 2 * feature tile + s)
-    bf8 pk[TPW][kKS];
-    bf8 pl[X3 ? TPW : 1][X3 ? kKS : 1];                                     // X3: the low parts of the activations
-    f16v acc[TPW][kMT];
-    if (wave_on) {
-#pragma unroll
-        for (int t = 0; t < TPW; ++t) {
-            const long long row = row0 + 32 * t;
-            const size_t xoff = (size_t)(row < P.rows ? row : P.rows - 1) * P.in_dim;
-            const float *x = static_cast<const float *>(obs_) + xoff;
-            const __bf16 *xb = static_cast<const __bf16 *>(obs_) + xoff;
-#pragma unroll
-            for (int ks = 0; ks < kKS; ++ks) {
-                const int k0 = 16 * ks + 8 * h;
-                if constexpr (IN_BF16) {                                    // the fragment as it lies in memory (in_dim % 8 == 0)
-                    bf8 z;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) z[j] = (__bf16)0.0f;
-                    pk[t][ks] = k0 < P.in_dim ? *reinterpret_cast<const bf8 *>(xb + k0) : z;
-                    if constexpr (X3) pl[t][ks] = z;                        // bf16 rows have no low part
-                    continue;
-                }
-                float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-                if (k0 < P.in_dim) lo = *reinterpret_cast<const float4 *>(x + k0);          // in_dim is a multiple of 4
-                if (k0 + 4 < P.in_dim) hi = *reinterpret_cast<const float4 *>(x + k0 + 4);
-                const float xv[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const __bf16 hj = (__bf16)xv[j];
-                    pk[t][ks][j] = hj;
-                    if constexpr (X3) pl[t][ks][j] = (__bf16)(xv[j] - (float)hj);
-                }
-            }
-        }
-#pragma unroll
-        for (int mt = 0; mt < kMT; ++mt)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const float bv = P.b1[feat_of(mt, reg, h)];
-#pragma unroll
-                for (int t = 0; t < TPW; ++t) acc[t][mt][reg] = bv;
-            }
-    }
-    commit(0);
-    __syncthreads();
-
-#pragma unroll
-    for (int cc = 0; cc < kSteps; ++cc) {
-        const int c = X3 ? cc >> 1 : cc;
-        const bool low = X3 && (cc & 1);                                    // this step holds LOW weight parts
-        const bool last_part = !X3 || low;                                  // the chunk's sums are complete after this step
-        if (cc + 1 < kSteps) issue(cc + 1);
-        const bf8 *wl = buf[cc & 1];
-        if (wave_on) {
-            if (c < 6) {
-                const int half = c & 1;
-#pragma unroll
-                for (int ks = 0; ks < kKS; ++ks)
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) {
-                        const bf8 a = wl[(m * kKS + ks) * 64 + lane];
-#pragma unroll
-                        for (int t = 0; t < TPW; ++t) {
-                            acc[t][3 * half + m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pk[t][ks], acc[t][3 * half + m], 0, 0, 0);
-                            if constexpr (X3) {
-                                if (!low) acc[t][3 * half + m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pl[t][ks], acc[t][3 * half + m], 0, 0, 0);
-                            }
-                        }
-                    }
-                if (half == 1 && last_part) {                               // layer complete: leaky ReLU (slope 0.01, networks.py:40-42), pack
-#pragma unroll
-                    for (int t = 0; t < TPW; ++t) {
-#pragma unroll
-                        for (int kt = 0; kt < kMT; ++kt)
-#pragma unroll
-                            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                                for (int j = 0; j < 8; ++j) {
-                                    const float v = acc[t][kt][8 * s + j];
-                                    const float r_ = fmaxf(v, 0.01f * v);
-                                    const __bf16 hj = (__bf16)r_;
-                                    pk[t][2 * kt + s][j] = hj;
-                                    if constexpr (X3) pl[t][2 * kt + s][j] = (__bf16)(r_ - (float)hj);
-                                }
-#pragma unroll
-                        for (int mt = 0; mt < kMT; ++mt)
-#pragma unroll
-                            for (int reg = 0; reg < 16; ++reg) acc[t][mt][reg] = 0.0f;
-                    }
-                }
-            } else {
-                // output layer: one feature tile; action k is accumulator register k of the lower lane half (row = reg, h = 0)
-#pragma unroll
-                for (int t = 0; t < TPW; ++t) {
-                    f16v o = acc[t][0];                                     // zeros (X3: the high step's sums on the low step)
-#pragma unroll
-                    for (int ks = 0; ks < kKS; ++ks) {
-                        o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[ks * 64 + lane], pk[t][ks], o, 0, 0, 0);
-                        if constexpr (X3) {
-                            if (!low) o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[ks * 64 + lane], pl[t][ks], o, 0, 0, 0);
-                        }
-                    }
-                    if constexpr (X3) { if (!low) { acc[t][0] = o; continue; } }
-                    const long long row = row0 + 32 * t;
-                    if (h == 0 && row < P.rows) {
-                        float *y = act + (size_t)row * P.act_dim;
-                        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                        if (P.noise_scale > 0.0f) {
-                            unsigned long long hk = pmix64(P.noise_key ^ (P.row_offset + (unsigned long long)row));
-#pragma unroll
-                            for (int k = 0; k < 4; k += 2) {
-                                if (k < P.act_dim) {
-                                    const float u1 = (float)((unsigned)(hk >> 40) + 1u) * 5.9604644775390625e-08f;      // (0, 1]
-                                    const float u2 = (float)((unsigned)(hk >> 16) & 0xFFFFFFu) * 5.9604644775390625e-08f; // [0, 1)
-                                    const float rad = sqrtf(-2.0f * logf(u1));
-                                    float sn, cs;
-                                    sincosf(6.283185307179586f * u2, &sn, &cs);
-                                    z[k] = rad * cs; z[k + 1] = rad * sn;
-                                    hk = pmix64(hk + 0x9E3779B97F4A7C15ull);
-                                }
-                            }
-                        }
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (k < P.act_dim) {
-                                float v = tanhf(o[k]);                      // networks.py:43 tanh output
-                                if (P.noise_scale > 0.0f) v = fminf(fmaxf(v + P.noise_scale * z[k], -1.0f), 1.0f);
-                                y[k] = v;
-                            }
-                        if constexpr (LOGPI) {                              // -(0.5 sum_k z_k^2) - c, the sum in k order
-                            float lp = -0.0f;                               // no noise: -act_dim log(1) = -0.0
-                            if (P.noise_scale > 0.0f) {
-                                float s = z[0] * z[0];
-#pragma unroll
-                                for (int k = 1; k < 4; ++k)
-                                    if (k < P.act_dim) s = s + z[k] * z[k];
-                                lp = -(0.5f * s) - logpi_c;
-                            }
-                            log_pi[row] = lp;
-                        }
-                    }
-                }
-            }
-        }
-        if (cc + 1 < kSteps) {
-            commit(cc + 1);                                                 // the other buffer: last read in step cc - 1, behind the barrier
-            __syncthreads();
-        }
-    }
-}
+//
+// The kernel itself is csrc/policy_mlp_kernel.h, compiled twice: k_policy_mlp for a plain handle, k_policy_mlp_bank for an
+// actor bank (BANK: blockIdx.y is the member; swarm_policy_bank_create) -- that file says why it is text and not a template.
+constexpr size_t kMemberPieces = ((3 * kMT * kKS + kKS) * 64 * 2 * 16 + (3 * kKP + 32) * 4) / 16;   // a member's blob: high, low, biases
+#define POLICY_MLP_KERNEL k_policy_mlp
+#define POLICY_MLP_BANK false
+#include "policy_mlp_kernel.h"
+#undef POLICY_MLP_KERNEL
+#undef POLICY_MLP_BANK
+#define POLICY_MLP_KERNEL k_policy_mlp_bank
+#define POLICY_MLP_BANK true
+#include "policy_mlp_kernel.h"
+#undef POLICY_MLP_KERNEL
+#undef POLICY_MLP_BANK
 
 // swarm_policy_load_device's packer: the whole blob of a handle re-written from fp32 DEVICE weights (torch.nn.Linear layout),
 // in the layout swarm_policy_create packs on the host -- which stays the independent witness: tests/test_gpu_policy_load.py
@@ -365,52 +195,34 @@ void launch_pack(const PackParams &q, hipStream_t st)
     hipLaunchKernelGGL(k_policy_pack<THREADS>, dim3(grid), dim3(THREADS), 0, st, q);
 }
 
-}  // namespace
-
-struct SWARM_HIDDEN swarm_policy {     // hidden: its implicit destructor must not become an exported weak symbol
-    int device, in_dim, hidden, act_dim;
-    int precision = 0;             // 0 = bf16 (default), 1 = bf16x3
-    swarm_internal::DevBuf<unsigned char> d_blob;     // the packed weights and biases p points into
-    size_t blob_bytes = 0;
-    MlpParams p;
-    bool smem_set = false;
-    swarm_wide::Handle *wide = nullptr;    // swarm_policy_create_wide: the handle runs csrc/policy_wide.hip; d_blob and p stay empty
-    ~swarm_policy() { swarm_wide::destroy(wide); }
-};
-
-int swarm_internal_policy_info(const swarm_policy_t *p, swarm_policy_info *out)
+// The same for a bank handle (behind the plain handle's templates, so that their instantiations come first as before).
+template <bool IN_BF16, bool X3>
+void launch_bank(const dim3 &g, const dim3 &b, hipStream_t st, const MlpParams &q, const void *obs, float *act, float *log_pi, float logpi_c)
 {
-    if (!p || !out) return SWARM_POLICY_ERR_INVALID;
-    out->device = p->device; out->in_dim = p->in_dim; out->act_dim = p->act_dim;
-    return SWARM_POLICY_OK;
+    if (log_pi) hipLaunchKernelGGL((k_policy_mlp_bank<IN_BF16, 1, X3, true>), g, b, kSmemBytes, st, q, obs, act, log_pi, logpi_c);
+    else hipLaunchKernelGGL((k_policy_mlp_bank<IN_BF16, 1, X3, false>), g, b, kSmemBytes, st, q, obs, act, nullptr, 0.0f);
 }
 
-extern "C" {
-
-const char *swarm_policy_last_error(void) { return g_policy_error.c_str(); }
-
-int swarm_policy_create(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
-                        const float *w4, const float *b4, int in_dim, int hidden, int act_dim, int device, swarm_policy_t **out)
+template <bool IN_BF16, bool X3>
+void set_smem_bank()
 {
-    if (!out) return SWARM_POLICY_ERR_INVALID;
-    *out = nullptr;
-    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_create: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
-    if (in_dim < 4 || in_dim > kKP || (in_dim & 3) || hidden < 1 || hidden >= kKP || act_dim < 1 || act_dim > 4) {
-        g_policy_error = "swarm_policy_create: supported shapes are in_dim <= 192 (multiple of 4), hidden <= 191, act_dim <= 4";
-        return SWARM_POLICY_ERR_INVALID;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_policy_error = "swarm_policy_create: no HIP device (there is no CPU path)"; return SWARM_POLICY_ERR_HIP; }
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    const DeviceGuard guard(device < ndev ? device : -1);       // -1 is no device: !ok
-    if (!guard.ok) { g_policy_error = "swarm_policy_create: bad device"; return SWARM_POLICY_ERR_HIP; }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp_bank<IN_BF16, 1, X3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp_bank<IN_BF16, 1, X3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
+}
 
-    // blob: [w1 | w2 | w3 | w4] fragments (8 bf16 per lane), then [b1 | b2 | b3 | b4] fp32
-    const size_t frag = 64 * 8;                                   // bf16 elements per fragment
-    const size_t n_hid = (size_t)kMT * kKS * frag, n_out = (size_t)kKS * frag;
-    const size_t w_elems = 3 * n_hid + n_out;
-    const size_t bytes = 2 * w_elems * 2 + (3 * kKP + 32) * 4;                // high parts, low parts, biases
-    std::vector<unsigned char> blob(bytes, 0);
+// The blob of one actor as swarm_policy_create uploads it (and a bank holds once per member): [w1 | w2 | w3 | w4] fragments
+// (8 bf16 per lane), their low parts in the same layout, then [b1 | b2 | b3 | b4] fp32.
+constexpr size_t kFrag = 64 * 8;                                              // bf16 elements per fragment
+constexpr size_t kHidElems = (size_t)kMT * kKS * kFrag, kOutElems = (size_t)kKS * kFrag;
+constexpr size_t kWElems = 3 * kHidElems + kOutElems;
+constexpr size_t kBlobBytes = 2 * kWElems * 2 + (3 * kKP + 32) * 4;           // high parts, low parts, biases
+static_assert(kBlobBytes == kMemberPieces * 16 && kWElems / 8 == (size_t)kPackPieces && kPackBias == 3 * kKP + 32, "a member's blob is whole pieces");
+
+std::vector<unsigned char> pack_host(const float *const w[8], int in_dim, int hidden, int act_dim)
+{
+    const float *w1 = w[0], *b1 = w[1], *w2 = w[2], *b2 = w[3], *w3 = w[4], *b3 = w[5], *w4 = w[6], *b4 = w[7];
+    const size_t n_hid = kHidElems, w_elems = kWElems;
+    std::vector<unsigned char> blob(kBlobBytes, 0);
     uint16_t *wp = reinterpret_cast<uint16_t *>(blob.data());
     uint16_t *lp = wp + w_elems;                                              // low parts: bf16(w - bf16(w)), same layout
     float *bp = reinterpret_cast<float *>(blob.data() + 2 * w_elems * 2);
@@ -451,6 +263,116 @@ int swarm_policy_create(const float *w1, const float *b1, const float *w2, const
     { const std::vector<float> a = with_bias(w4, b4, act_dim, false); pack(wp + 3 * n_hid, a.data(), kKP, kKP, 1, false); }
     for (int k = 0; k < hidden; ++k) bp[k] = b1[k];
     bp[one] = 1.0f;
+    return blob;
+}
+
+bool narrow_shape_ok(int in_dim, int hidden, int act_dim)
+{
+    return !(in_dim < 4 || in_dim > kKP || (in_dim & 3) || hidden < 1 || hidden >= kKP || act_dim < 1 || act_dim > 4);
+}
+
+// the kernel's pointers into a handle's (first member's) blob at `base`
+void point_params(MlpParams &p, const unsigned char *base, int in_dim, int act_dim)
+{
+    const bf8 *wd = reinterpret_cast<const bf8 *>(base);
+    const float *bd = reinterpret_cast<const float *>(base + 2 * kWElems * 2);
+    p.w1 = wd; p.w2 = wd + kHidElems / 8; p.w3 = wd + 2 * kHidElems / 8; p.w4 = wd + 3 * kHidElems / 8;
+    const bf8 *ld = wd + kWElems / 8;
+    p.l1 = ld; p.l2 = ld + kHidElems / 8; p.l3 = ld + 2 * kHidElems / 8; p.l4 = ld + 3 * kHidElems / 8;
+    p.b1 = bd; p.b2 = bd + kKP; p.b3 = bd + 2 * kKP; p.b4 = bd + 3 * kKP;
+    p.in_dim = in_dim; p.act_dim = act_dim; p.rows = 0; p.noise_scale = 0.0f; p.noise_key = 0; p.row_offset = 0;
+}
+
+}  // namespace
+
+struct SWARM_HIDDEN swarm_policy {     // hidden: its implicit destructor must not become an exported weak symbol
+    int device, in_dim, hidden, act_dim;
+    int precision = 0;             // 0 = bf16 (default), 1 = bf16x3
+    swarm_internal::DevBuf<unsigned char> d_blob;     // the packed weights and biases p points into
+    size_t blob_bytes = 0;
+    MlpParams p;
+    bool smem_set = false;
+    swarm_wide::Handle *wide = nullptr;    // swarm_policy_create_wide: the handle runs csrc/policy_wide.hip; d_blob and p stay empty
+    // swarm_policy_bank_create: `members` blobs of blob_bytes each, one behind the other (d_blob, or the wide handle's); p points
+    // into the first.  A bank handle runs the BANK kernels, also with one member.
+    bool bank = false;
+    int members = 1;
+    ~swarm_policy() { swarm_wide::destroy(wide); }
+};
+
+int swarm_internal_policy_info(const swarm_policy_t *p, swarm_policy_info *out)
+{
+    if (!p || !out) return SWARM_POLICY_ERR_INVALID;
+    out->device = p->device; out->in_dim = p->in_dim; out->act_dim = p->act_dim; out->members = p->members;
+    return SWARM_POLICY_OK;
+}
+
+namespace {
+
+// The packing launch of swarm_policy_load_device / swarm_policy_bank_load_device: member `member`'s slice of the blob.
+int load_member(const char *who, swarm_policy_t *p, int member, const float *const w[8], void *stream)
+{
+    const DeviceGuard guard(p->device);
+    if (!guard.ok) { g_policy_error = std::string(who) + ": hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
+    if (p->wide) {
+        const int rc = swarm_wide::load_device(p->wide, member, w, static_cast<hipStream_t>(stream), g_policy_error);
+        if (rc != SWARM_POLICY_OK) g_policy_error = std::string(who) + ": " + g_policy_error;
+        return rc;
+    }
+    static_assert(kPackPieces % 64 == 0 && sizeof(bf8) == sizeof(uint4), "one 16-byte piece per fragment lane");
+    PackParams q;
+    q.w1 = w[0]; q.b1 = w[1]; q.w2 = w[2]; q.b2 = w[3]; q.w3 = w[4]; q.b3 = w[5]; q.w4 = w[6]; q.b4 = w[7];
+    q.hi = reinterpret_cast<uint4 *>(p->d_blob.get() + (size_t)member * p->blob_bytes);
+    q.lo = q.hi + kPackPieces;
+    q.bias = reinterpret_cast<float *>(q.lo + kPackPieces);
+    q.in_dim = p->in_dim; q.hidden = p->hidden; q.act_dim = p->act_dim;
+    launch_pack<kPackThreads>(q, static_cast<hipStream_t>(stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_policy_error = std::string(who) + ": " + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
+    return SWARM_POLICY_OK;
+}
+
+// swarm_policy_read_packed / swarm_policy_bank_read_packed: member `member`'s slice, on the stream, waited for.
+int64_t read_member(const char *who, swarm_policy_t *p, int member, void *host_dst, int64_t capacity, void *stream)
+{
+    const int64_t bytes = (int64_t)p->blob_bytes;
+    if (!host_dst || capacity < bytes) return bytes;
+    const DeviceGuard guard(p->device);
+    if (!guard.ok) { g_policy_error = std::string(who) + ": hipSetDevice failed"; return -SWARM_POLICY_ERR_HIP; }
+    hipStream_t st = static_cast<hipStream_t>(stream);          // the copy on the stream, behind the loads enqueued there; then the wait
+    size_t unused;
+    const unsigned char *src = p->wide ? static_cast<const unsigned char *>(swarm_wide::blob(p->wide, &unused)) : p->d_blob.get();
+    hipError_t e = hipMemcpyAsync(host_dst, src + (size_t)member * p->blob_bytes, p->blob_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { g_policy_error = std::string(who) + ": " + hipGetErrorString(e); return -SWARM_POLICY_ERR_HIP; }
+    return bytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *swarm_policy_last_error(void) { return g_policy_error.c_str(); }
+
+int swarm_policy_create(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                        const float *w4, const float *b4, int in_dim, int hidden, int act_dim, int device, swarm_policy_t **out)
+{
+    if (!out) return SWARM_POLICY_ERR_INVALID;
+    *out = nullptr;
+    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_create: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
+    if (in_dim < 4 || in_dim > kKP || (in_dim & 3) || hidden < 1 || hidden >= kKP || act_dim < 1 || act_dim > 4) {
+        g_policy_error = "swarm_policy_create: supported shapes are in_dim <= 192 (multiple of 4), hidden <= 191, act_dim <= 4";
+        return SWARM_POLICY_ERR_INVALID;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_policy_error = "swarm_policy_create: no HIP device (there is no CPU path)"; return SWARM_POLICY_ERR_HIP; }
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    const DeviceGuard guard(device < ndev ? device : -1);       // -1 is no device: !ok
+    if (!guard.ok) { g_policy_error = "swarm_policy_create: bad device"; return SWARM_POLICY_ERR_HIP; }
+
+    const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
+    const std::vector<unsigned char> blob = pack_host(w, in_dim, hidden, act_dim);
+    const size_t bytes = blob.size();
 
     swarm_policy *p = new (std::nothrow) swarm_policy;
     if (!p) return SWARM_POLICY_ERR_INVALID;
@@ -460,13 +382,7 @@ int swarm_policy_create(const float *w1, const float *b1, const float *w2, const
         g_policy_error = "swarm_policy_create: device allocation / upload failed";
         return SWARM_POLICY_ERR_HIP;
     }
-    const bf8 *wd = reinterpret_cast<const bf8 *>(p->d_blob.get());
-    const float *bd = reinterpret_cast<const float *>(p->d_blob.get() + 2 * w_elems * 2);
-    p->p.w1 = wd; p->p.w2 = wd + n_hid / 8; p->p.w3 = wd + 2 * n_hid / 8; p->p.w4 = wd + 3 * n_hid / 8;
-    const bf8 *ld = wd + w_elems / 8;
-    p->p.l1 = ld; p->p.l2 = ld + n_hid / 8; p->p.l3 = ld + 2 * n_hid / 8; p->p.l4 = ld + 3 * n_hid / 8;
-    p->p.b1 = bd; p->p.b2 = bd + kKP; p->p.b3 = bd + 2 * kKP; p->p.b4 = bd + 3 * kKP;
-    p->p.in_dim = in_dim; p->p.act_dim = act_dim; p->p.rows = 0; p->p.noise_scale = 0.0f; p->p.noise_key = 0; p->p.row_offset = 0;
+    point_params(p->p, p->d_blob.get(), in_dim, act_dim);
     *out = p;
     return SWARM_POLICY_OK;
 }
@@ -490,12 +406,75 @@ int swarm_policy_create_wide(const float *w1, const float *b1, const float *w2, 
     if (!p) return SWARM_POLICY_ERR_INVALID;
     p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim;
     const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
-    const int rc = swarm_wide::create(w, in_dim, hidden, act_dim, &p->wide, g_policy_error);
-    if (rc != SWARM_POLICY_OK) { delete p; return rc; }
+    const int rc = swarm_wide::create(w, 1, in_dim, hidden, act_dim, &p->wide, g_policy_error);
+    if (rc != SWARM_POLICY_OK) { delete p; g_policy_error = "swarm_policy_create_wide: " + g_policy_error; return rc; }
     (void)swarm_wide::blob(p->wide, &p->blob_bytes);
     *out = p;
     return SWARM_POLICY_OK;
 }
+
+int swarm_policy_bank_create(const float *const *w, int members, int in_dim, int hidden, int act_dim, int wide, int device,
+                             swarm_policy_t **out)
+{
+    if (!out) { g_policy_error = "swarm_policy_bank_create: null out"; return SWARM_POLICY_ERR_INVALID; }
+    *out = nullptr;
+    if (members < 1 || members > SWARM_POLICY_BANK_MAX) {
+        g_policy_error = "swarm_policy_bank_create: members " + std::to_string(members) + " outside [1, " + std::to_string(SWARM_POLICY_BANK_MAX) + "]";
+        return SWARM_POLICY_ERR_INVALID;
+    }
+    if (wide != 0 && wide != 1) { g_policy_error = "swarm_policy_bank_create: wide must be 0 (narrow geometry) or 1 (wide geometry)"; return SWARM_POLICY_ERR_INVALID; }
+    if (!w) { g_policy_error = "swarm_policy_bank_create: null weight table"; return SWARM_POLICY_ERR_INVALID; }
+    for (int i = 0; i < 8 * members; ++i)
+        if (!w[i]) {
+            g_policy_error = "swarm_policy_bank_create: null weight pointer (member " + std::to_string(i / 8) + ", array " + std::to_string(i % 8) + ")";
+            return SWARM_POLICY_ERR_INVALID;
+        }
+    if (wide ? !swarm_wide::shape_ok(in_dim, hidden, act_dim) : !narrow_shape_ok(in_dim, hidden, act_dim)) {
+        g_policy_error = wide ? "swarm_policy_bank_create: supported shapes of the wide geometry are in_dim <= 384 (multiple of 4), hidden <= 256, act_dim <= 4"
+                              : "swarm_policy_bank_create: supported shapes of the narrow geometry are in_dim <= 192 (multiple of 4), hidden <= 191, act_dim <= 4";
+        return SWARM_POLICY_ERR_INVALID;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_policy_error = "swarm_policy_bank_create: no HIP device (there is no CPU path)"; return SWARM_POLICY_ERR_HIP; }
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    const DeviceGuard guard(device < ndev ? device : -1);       // -1 is no device: !ok
+    if (!guard.ok) { g_policy_error = "swarm_policy_bank_create: bad device"; return SWARM_POLICY_ERR_HIP; }
+    swarm_policy *p = new (std::nothrow) swarm_policy;
+    if (!p) { g_policy_error = "swarm_policy_bank_create: out of memory"; return SWARM_POLICY_ERR_INVALID; }
+    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim; p->bank = true; p->members = members;
+    if (wide) {
+        const int rc = swarm_wide::create(w, members, in_dim, hidden, act_dim, &p->wide, g_policy_error);
+        if (rc != SWARM_POLICY_OK) { delete p; g_policy_error = "swarm_policy_bank_create: " + g_policy_error; return rc; }
+        (void)swarm_wide::blob(p->wide, &p->blob_bytes);
+        *out = p;
+        return SWARM_POLICY_OK;
+    }
+    // every member's slice is the blob swarm_policy_create builds from the same arrays: the same packer, M times
+    std::vector<unsigned char> blob;
+    blob.reserve((size_t)members * kBlobBytes);
+    for (int m = 0; m < members; ++m) {
+        const std::vector<unsigned char> one = pack_host(w + 8 * m, in_dim, hidden, act_dim);
+        blob.insert(blob.end(), one.begin(), one.end());
+    }
+    p->blob_bytes = kBlobBytes;
+    // the upload on a stream of its own, waited for here: no null-stream work, complete on return
+    hipStream_t up = nullptr;
+    hipError_t e = p->d_blob.alloc(blob.size());
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_blob.get(), blob.data(), blob.size(), hipMemcpyHostToDevice, up);
+    if (e == hipSuccess) e = hipStreamSynchronize(up);
+    if (up) (void)hipStreamDestroy(up);
+    if (e != hipSuccess) {
+        delete p;
+        g_policy_error = "swarm_policy_bank_create: device allocation / upload failed";
+        return SWARM_POLICY_ERR_HIP;
+    }
+    point_params(p->p, p->d_blob.get(), in_dim, act_dim);
+    *out = p;
+    return SWARM_POLICY_OK;
+}
+
+int swarm_policy_bank_members(const swarm_policy_t *p) { return p ? p->members : 0; }
 
 void swarm_policy_destroy(swarm_policy_t *p)
 {
@@ -511,12 +490,16 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
 {
     if (!p || !obs || !act || rows < 0) { g_policy_error = "swarm_policy_forward: bad argument"; return SWARM_POLICY_ERR_INVALID; }
     if (in_bf16 && (p->in_dim & 7)) { g_policy_error = "swarm_policy_forward_bf16: in_dim must be a multiple of 8"; return SWARM_POLICY_ERR_INVALID; }
+    if (rows % p->members != 0) {                           // a bank: every member owns rows / members whole rows
+        g_policy_error = "swarm_policy_forward: rows " + std::to_string((long long)rows) + " is no multiple of the bank's members " + std::to_string(p->members);
+        return SWARM_POLICY_ERR_INVALID;
+    }
     if (rows == 0) return SWARM_POLICY_OK;
     const DeviceGuard guard(p->device);
     if (!guard.ok) { g_policy_error = "swarm_policy_forward: hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
     if (p->wide) {                                          // a wide handle: its own kernel, SWARM_POLICY_TPW not read
         const swarm_wide::ForwardArgs a = {obs, in_bf16, rows, act, log_pi, noise_scale, seed, step, row_offset, p->precision,
-                                           static_cast<hipStream_t>(stream)};
+                                           static_cast<hipStream_t>(stream), p->bank};
         return swarm_wide::forward(p->wide, a, g_policy_error);
     }
     MlpParams q = p->p;
@@ -538,11 +521,23 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
         set_smem<false, 1, false>(); set_smem<true, 1, false>();
         set_smem<false, 2, false>(); set_smem<true, 2, false>();
         set_smem<false, 1, true>(); set_smem<true, 1, true>();
+        set_smem_bank<false, false>(); set_smem_bank<true, false>(); set_smem_bank<false, true>(); set_smem_bank<true, true>();
         p->smem_set = true;
     }
     const dim3 g(grid), b(64 * n_waves);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->precision == 1) {
+    if (p->bank) {                                          // (ceil(R / rows per workgroup), members); SWARM_POLICY_TPW not read
+        q.rows = rows / p->members;                         // the kernel's P.rows: the MEMBER's rows
+        const long long bank_block = (long long)n_waves * 32;
+        const dim3 gb((unsigned)((q.rows + bank_block - 1) / bank_block), (unsigned)p->members);
+        if (p->precision == 1) {
+            if (in_bf16) launch_bank<true, true>(gb, b, st, q, obs, act, log_pi, logpi_c);
+            else launch_bank<false, true>(gb, b, st, q, obs, act, log_pi, logpi_c);
+        } else {
+            if (in_bf16) launch_bank<true, false>(gb, b, st, q, obs, act, log_pi, logpi_c);
+            else launch_bank<false, false>(gb, b, st, q, obs, act, log_pi, logpi_c);
+        }
+    } else if (p->precision == 1) {
         if (in_bf16) launch_policy<true, 1, true>(g, b, st, q, obs, act, log_pi, logpi_c);
         else launch_policy<false, 1, true>(g, b, st, q, obs, act, log_pi, logpi_c);
     } else if (tpw == 2) {
@@ -598,40 +593,47 @@ int swarm_policy_load_device(swarm_policy_t *p, const float *w1, const float *b1
 {
     if (!p) { g_policy_error = "swarm_policy_load_device: null handle"; return SWARM_POLICY_ERR_INVALID; }
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_load_device: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
-    const DeviceGuard guard(p->device);
-    if (!guard.ok) { g_policy_error = "swarm_policy_load_device: hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
-    if (p->wide) {
-        const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
-        return swarm_wide::load_device(p->wide, w, static_cast<hipStream_t>(stream), g_policy_error);
+    if (p->members > 1) {
+        g_policy_error = "swarm_policy_load_device: the handle is a bank of " + std::to_string(p->members) + " members (swarm_policy_bank_load_device loads one of them)";
+        return SWARM_POLICY_ERR_INVALID;
     }
-    static_assert(kPackPieces % 64 == 0 && sizeof(bf8) == sizeof(uint4), "one 16-byte piece per fragment lane");
-    PackParams q;
-    q.w1 = w1; q.b1 = b1; q.w2 = w2; q.b2 = b2; q.w3 = w3; q.b3 = b3; q.w4 = w4; q.b4 = b4;
-    q.hi = reinterpret_cast<uint4 *>(p->d_blob.get());
-    q.lo = q.hi + kPackPieces;
-    q.bias = reinterpret_cast<float *>(q.lo + kPackPieces);
-    q.in_dim = p->in_dim; q.hidden = p->hidden; q.act_dim = p->act_dim;
-    launch_pack<kPackThreads>(q, static_cast<hipStream_t>(stream));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_policy_error = std::string("swarm_policy_load_device: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
-    return SWARM_POLICY_OK;
+    const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
+    return load_member("swarm_policy_load_device", p, 0, w, stream);
+}
+
+int swarm_policy_bank_load_device(swarm_policy_t *p, int member, const float *w1, const float *b1, const float *w2, const float *b2,
+                                  const float *w3, const float *b3, const float *w4, const float *b4, void *stream)
+{
+    if (!p) { g_policy_error = "swarm_policy_bank_load_device: null handle"; return SWARM_POLICY_ERR_INVALID; }
+    if (member < 0 || member >= p->members) {
+        g_policy_error = "swarm_policy_bank_load_device: member " + std::to_string(member) + " outside [0, " + std::to_string(p->members) + ")";
+        return SWARM_POLICY_ERR_INVALID;
+    }
+    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_bank_load_device: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
+    const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
+    return load_member("swarm_policy_bank_load_device", p, member, w, stream);
 }
 
 int64_t swarm_policy_read_packed(swarm_policy_t *p, void *host_dst, int64_t capacity, void *stream)
 {
     if (!p) { g_policy_error = "swarm_policy_read_packed: null handle"; return -SWARM_POLICY_ERR_INVALID; }
     if (capacity < 0) { g_policy_error = "swarm_policy_read_packed: negative capacity"; return -SWARM_POLICY_ERR_INVALID; }
-    const int64_t bytes = (int64_t)p->blob_bytes;
-    if (!host_dst || capacity < bytes) return bytes;
-    const DeviceGuard guard(p->device);
-    if (!guard.ok) { g_policy_error = "swarm_policy_read_packed: hipSetDevice failed"; return -SWARM_POLICY_ERR_HIP; }
-    hipStream_t st = static_cast<hipStream_t>(stream);          // the copy on the stream, behind the loads enqueued there; then the wait
-    size_t unused;
-    const void *src = p->wide ? swarm_wide::blob(p->wide, &unused) : p->d_blob.get();
-    hipError_t e = hipMemcpyAsync(host_dst, src, p->blob_bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { g_policy_error = std::string("swarm_policy_read_packed: ") + hipGetErrorString(e); return -SWARM_POLICY_ERR_HIP; }
-    return bytes;
+    if (p->members > 1) {
+        g_policy_error = "swarm_policy_read_packed: the handle is a bank of " + std::to_string(p->members) + " members (swarm_policy_bank_read_packed reads one of them)";
+        return -SWARM_POLICY_ERR_INVALID;
+    }
+    return read_member("swarm_policy_read_packed", p, 0, host_dst, capacity, stream);
+}
+
+int64_t swarm_policy_bank_read_packed(swarm_policy_t *p, int member, void *host_dst, int64_t capacity, void *stream)
+{
+    if (!p) { g_policy_error = "swarm_policy_bank_read_packed: null handle"; return -SWARM_POLICY_ERR_INVALID; }
+    if (member < 0 || member >= p->members) {
+        g_policy_error = "swarm_policy_bank_read_packed: member " + std::to_string(member) + " outside [0, " + std::to_string(p->members) + ")";
+        return -SWARM_POLICY_ERR_INVALID;
+    }
+    if (capacity < 0) { g_policy_error = "swarm_policy_bank_read_packed: negative capacity"; return -SWARM_POLICY_ERR_INVALID; }
+    return read_member("swarm_policy_bank_read_packed", p, member, host_dst, capacity, stream);
 }
 
 }  // extern "C"

@@ -23,16 +23,19 @@ struct ForwardArgs {
     uint64_t seed, step, row_offset;
     int precision;                  // SWARM_POLICY_BF16 / SWARM_POLICY_BF16X3
     hipStream_t stream;
+    bool bank;                      // a bank handle: the BANK kernels, member m on rows [m rows / members, (m + 1) rows / members)
 };
 
 // true where the wide kernel serves the shape; decided without a device
 bool shape_ok(int in_dim, int hidden, int act_dim);
-// w: fc1.weight, fc1.bias, ..., fc4.bias (fp32, HOST), a shape that passed shape_ok; the caller holds `device` current
-int create(const float *const w[8], int in_dim, int hidden, int act_dim, Handle **out, std::string &err);
+// w[8 m + i]: fc1.weight, fc1.bias, ..., fc4.bias of member m (fp32, HOST), a shape that passed shape_ok; members >= 1 blobs,
+// one behind the other; the caller holds `device` current.  err: the reason, without the entry point's name
+int create(const float *const *w, int members, int in_dim, int hidden, int act_dim, Handle **out, std::string &err);
 void destroy(Handle *h);            // under the caller's DeviceGuard
 int forward(Handle *h, const ForwardArgs &a, std::string &err);
-// w: the same eight arrays on the DEVICE; one packing launch on `st`
-int load_device(Handle *h, const float *const w[8], hipStream_t st, std::string &err);
+// w: the eight arrays of one member on the DEVICE; one packing launch on `st` into that member's blob
+int load_device(Handle *h, int member, const float *const w[8], hipStream_t st, std::string &err);
+// the first member's blob and the bytes of ONE member's
 const void *blob(const Handle *h, size_t *bytes);
 
 }  // namespace swarm_wide

@@ -118,222 +118,17 @@ __device__ __forceinline__ void finish_row(const WideParams &P, const f16v &o, l
     }
 }
 
-template <bool IN_BF16, bool X3, bool LOGPI, int MT>
-__global__ void __launch_bounds__(kThreads, (MT == 6 && !X3) ? 2 : 1)
-k_policy_wide(const WideParams P, const void *__restrict__ obs_, float *__restrict__ act, float *__restrict__ log_pi, float logpi_c)
-{
-    typedef Geo<MT> G;
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    bf8 *const lds = reinterpret_cast<bf8 *>(smem_raw);     // buffer b at lds + b * CH
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const long long row = ((long long)blockIdx.x * kWaves + wave) * 32 + r;
-    const bool wave_on = row - r < P.rows;                  // idle waves still stage and take the barriers
-
-    const int n1 = (P.in_dim + 63) >> 6;                    // layer-1 chunks: as long as the row
-    const int c_out = n1 + 2 * G::KC;                       // the output chunk, the last of the stream
-    constexpr int kParts = X3 ? 2 : 1;                      // X3: every chunk twice, high stream then low stream
-    const int n_steps = kParts * (c_out + 1);
-
-    bf8 pre[G::PRE];
-    auto pieces_of = [&](int c) {                           // what of chunk c's slot is staged
-        return c == c_out ? G::WOUT + G::TAIL : (c == 0 || c == n1 || c == n1 + G::KC) ? G::CH : G::W;
-    };
-    auto issue = [&](int s) {                               // step s of the stream -> registers
-        if (s >= n_steps) return;
-        const int c = X3 ? s >> 1 : s;
-        const bf8 *src = ((X3 && (s & 1)) ? P.lo : P.hi) + (size_t)c * G::CH;
-        const int n = pieces_of(c);
-#pragma unroll
-        for (int k = 0; k < G::PRE; ++k) { const int q = tid + k * kThreads; if (q < n) pre[k] = src[q]; }
-    };
-    auto commit = [&](int s) {                              // registers -> the LDS buffer of step s
-        if (s >= n_steps) return;
-        const int n = pieces_of(X3 ? s >> 1 : s);
-        bf8 *dst = lds + (s & 1) * G::CH;
-#pragma unroll
-        for (int k = 0; k < G::PRE; ++k) { const int q = tid + k * kThreads; if (q < n) dst[q] = pre[k]; }
-    };
-
-    // this lane's observation row; 64 columns (4 k-steps) at a time: the raw values of the next TWO layer-1 chunks are in
-    // flight, even chunks in xa and odd chunks in xo (one chunk ahead left fp32 rows waiting: 175 us instead of 87 us for bf16
-    // rows at (192,180,2))
-    const size_t xoff = (size_t)(row < P.rows ? row : P.rows - 1) * P.in_dim;
-    const float *x32 = static_cast<const float *>(obs_) + xoff;
-    const __bf16 *x16 = static_cast<const __bf16 *>(obs_) + xoff;
-    // (the bf16 instantiations of MT = 6 on fp32 rows keep ONE chunk in flight, in xa alone: two waves per SIMD leave no
-    // registers for the second -- 20 B of scratch)
-    constexpr int kAhead = (MT == 6 && !X3 && !IN_BF16) ? 1 : 2;
-    XRaw<IN_BF16> xa, xo;
-    auto load_x = [&](XRaw<IN_BF16> &x, int c) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k0 = 64 * c + 16 * i + 8 * h;
-            if constexpr (IN_BF16) {                        // the fragment as it lies in memory (in_dim % 8 == 0)
-                bf8 z;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) z[j] = (__bf16)0.0f;
-                x.b[i] = k0 < P.in_dim ? *reinterpret_cast<const bf8 *>(x16 + k0) : z;
-            } else {                                        // in_dim is a multiple of 4
-                x.f[i][0] = x.f[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (k0 < P.in_dim) x.f[i][0] = *reinterpret_cast<const float4 *>(x32 + k0);
-                if (k0 + 4 < P.in_dim) x.f[i][1] = *reinterpret_cast<const float4 *>(x32 + k0 + 4);
-            }
-        }
-    };
-
-    bf8 pk[G::KS];                                          // B fragments: layer 1 uses pk[0..3] for the current chunk
-    bf8 pl[X3 ? G::KS : 1];                                 // X3: their low parts
-    f16v acc[MT];
-    auto convert_x = [&](const XRaw<IN_BF16> &x) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (IN_BF16) {
-                pk[i] = x.b[i];
-                if constexpr (X3) {                         // bf16 rows have no low part
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) pl[i][j] = (__bf16)0.0f;
-                }
-            } else {
-                const float xv[8] = {x.f[i][0].x, x.f[i][0].y, x.f[i][0].z, x.f[i][0].w, x.f[i][1].x, x.f[i][1].y, x.f[i][1].z, x.f[i][1].w};
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const __bf16 hj = (__bf16)xv[j];
-                    pk[i][j] = hj;
-                    if constexpr (X3) pl[i][j] = (__bf16)(xv[j] - (float)hj);
-                }
-            }
-        }
-    };
-    // the bias tail of the chunk in `wl` (at piece `off`): SET the first `tiles` accumulators to it, or ADD it (X3's low part)
-    auto bias = [&](const bf8 *wl, int off, int tiles, bool add) {
-        const float *bt = reinterpret_cast<const float *>(wl + off);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-            if (mt < tiles) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 v = *reinterpret_cast<const float4 *>(bt + 32 * mt + 8 * g + 4 * h);
-                    const float bv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[mt][4 * g + e] = add ? acc[mt][4 * g + e] + bv[e] : bv[e];
-                }
-            }
-    };
-    // the MFMAs of one hidden-width chunk: 4 k-steps, B fragments b0[0..3] (and their low parts), all MT feature tiles
-    // (with_lo = false: the low parts are known to be zero -- layer 1 on bf16 rows -- and their MFMAs are left out)
-    auto mma = [&](const bf8 *wl, const bf8 *b0, const bf8 *l0, bool low, bool with_lo) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const bf8 a = wl[(mt * 4 + i) * 64 + lane];
-                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0[i], acc[mt], 0, 0, 0);
-                if constexpr (X3) {
-                    if (!low && with_lo) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, l0[i], acc[mt], 0, 0, 0);
-                }
-            }
-    };
-
-    int s = 0;                                              // the step that is in LDS buffer s & 1
-    issue(0);
-    if (wave_on) {
-        load_x(xa, 0);
-        if (kAhead == 2 && 1 < n1) load_x(xo, 1);
-    }
-    commit(0);
-    __syncthreads();
-
-    // ---- layer 1: n1 chunks, the row's columns of the two chunks behind this one loading while its MFMAs run
-    auto layer1_chunk = [&](XRaw<IN_BF16> &x, int c) {
-#pragma unroll
-        for (int part = 0; part < kParts; ++part) {
-            const bool low = part == 1;
-            issue(s + 1);
-            const bf8 *wl = lds + (s & 1) * G::CH;
-            if (wave_on) {
-                if (!low) {
-                    convert_x(x);
-                    if (c + kAhead < n1) load_x(x, c + kAhead);
-                    if (c == 0) bias(wl, G::W, MT, false);  // b1, fp32 (the low stream's tail of layer 1 is zero: not added)
-                }
-                mma(wl, pk, pl, low, !IN_BF16);
-            }
-            commit(s + 1);
-            __syncthreads();
-            ++s;
-        }
-    };
-#pragma unroll 1
-    for (int c = 0; c < n1; c += kAhead) {
-        layer1_chunk(xa, c);
-        if (kAhead == 2 && c + 1 < n1) layer1_chunk(xo, c + 1);
-    }
-
-    // leaky ReLU (slope 0.01, the product rounded in fp32) and the split into bf16 parts: the accumulator tile becomes the
-    // next layer's B fragments, k-step = 2 * feature tile + half
-    auto activate = [&]() {
-#pragma unroll
-        for (int kt = 0; kt < MT; ++kt)
-#pragma unroll
-            for (int sh = 0; sh < 2; ++sh)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float v = acc[kt][8 * sh + j];
-                    const float r_ = fmaxf(v, 0.01f * v);
-                    const __bf16 hj = (__bf16)r_;
-                    pk[2 * kt + sh][j] = hj;
-                    if constexpr (X3) pl[2 * kt + sh][j] = (__bf16)(r_ - (float)hj);
-                }
-    };
-
-    // ---- layers 2 and 3
-#pragma unroll 1
-    for (int layer = 0; layer < 2; ++layer) {
-        if (wave_on) activate();
-#pragma unroll
-        for (int kc = 0; kc < G::KC; ++kc)
-#pragma unroll
-            for (int part = 0; part < kParts; ++part) {
-                const bool low = part == 1;
-                issue(s + 1);
-                const bf8 *wl = lds + (s & 1) * G::CH;
-                if (wave_on) {
-                    if (kc == 0) bias(wl, G::W, MT, low);   // bf(b) sets the accumulators, lo(b) is added
-                    mma(wl, pk + 4 * kc, pl + (X3 ? 4 * kc : 0), low, true);
-                }
-                commit(s + 1);
-                __syncthreads();
-                ++s;
-            }
-    }
-
-    // ---- output layer: one feature tile; action k is accumulator register k of the lower lane half (row = reg, h = 0)
-    if (wave_on) activate();
-#pragma unroll
-    for (int part = 0; part < kParts; ++part) {
-        const bool low = part == 1;
-        issue(s + 1);
-        const bf8 *wl = lds + (s & 1) * G::CH;
-        if (wave_on) {
-            bias(wl, G::WOUT, 1, low);
-#pragma unroll
-            for (int ks = 0; ks < G::KS; ++ks) {
-                const bf8 a = wl[ks * 64 + lane];
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pk[ks], acc[0], 0, 0, 0);
-                if constexpr (X3) {
-                    if (!low) acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pl[ks], acc[0], 0, 0, 0);
-                }
-            }
-        }
-        if (part + 1 < kParts) {
-            commit(s + 1);
-            __syncthreads();
-            ++s;
-        }
-    }
-    if (wave_on && h == 0 && row < P.rows) finish_row<LOGPI>(P, acc[0], row, act, log_pi, logpi_c);
-}
+// The kernel itself is csrc/policy_wide_kernel.h, compiled twice: for a plain handle, and for an actor bank (BANK).
+#define POLICY_WIDE_KERNEL k_policy_wide
+#define POLICY_WIDE_BANK false
+#include "policy_wide_kernel.h"
+#undef POLICY_WIDE_KERNEL
+#undef POLICY_WIDE_BANK
+#define POLICY_WIDE_KERNEL k_policy_wide_bank
+#define POLICY_WIDE_BANK true
+#include "policy_wide_kernel.h"
+#undef POLICY_WIDE_KERNEL
+#undef POLICY_WIDE_BANK
 
 // ---- the packed stream, on the host (create) and on the device (load_device): the two are written independently and
 // tests/test_gpu_policy_wide.py compares their bytes.
@@ -498,17 +293,40 @@ void set_smem()
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide<IN_BF16, X3, true, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
 }
 
+template <bool IN_BF16, bool X3, int MT>
+void launch_bank(const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act, float *log_pi, float logpi_c)
+{
+    if (log_pi) hipLaunchKernelGGL((k_policy_wide_bank<IN_BF16, X3, true, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, log_pi, logpi_c);
+    else hipLaunchKernelGGL((k_policy_wide_bank<IN_BF16, X3, false, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, nullptr, 0.0f);
+}
+
+template <bool IN_BF16, bool X3, int MT>
+void set_smem_bank()
+{
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide_bank<IN_BF16, X3, false, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide_bank<IN_BF16, X3, true, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
+}
+
 template <int MT>
 void set_smem_all()
 {
     set_smem<false, false, MT>(); set_smem<true, false, MT>(); set_smem<false, true, MT>(); set_smem<true, true, MT>();
+    set_smem_bank<false, false, MT>(); set_smem_bank<true, false, MT>(); set_smem_bank<false, true, MT>(); set_smem_bank<true, true, MT>();
 }
 
 template <int MT>
-void launch_mt(bool in_bf16, bool x3, const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act, float *log_pi,
-               float logpi_c)
+void launch_mt(bool bank, bool in_bf16, bool x3, const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act,
+               float *log_pi, float logpi_c)
 {
-    if (x3) {
+    if (bank) {
+        if (x3) {
+            if (in_bf16) launch_bank<true, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
+            else launch_bank<false, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
+        } else {
+            if (in_bf16) launch_bank<true, false, MT>(g, st, q, obs, act, log_pi, logpi_c);
+            else launch_bank<false, false, MT>(g, st, q, obs, act, log_pi, logpi_c);
+        }
+    } else if (x3) {
         if (in_bf16) launch<true, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
         else launch<false, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
     } else {
@@ -523,8 +341,9 @@ namespace swarm_wide {
 
 struct Handle {
     Layout g;
-    swarm_internal::DevBuf<unsigned char> d_blob;
+    swarm_internal::DevBuf<unsigned char> d_blob;        // `members` blobs of blob_bytes each, one behind the other
     size_t blob_bytes = 0;
+    int members = 1;
     bool smem_set = false;
 };
 
@@ -533,15 +352,20 @@ bool shape_ok(int in_dim, int hidden, int act_dim)
     return in_dim >= 4 && in_dim <= kMaxIn && !(in_dim & 3) && hidden >= 1 && hidden <= kMaxHidden && act_dim >= 1 && act_dim <= kMaxAct;
 }
 
-int create(const float *const w[8], int in_dim, int hidden, int act_dim, Handle **out, std::string &err)
+int create(const float *const *w, int members, int in_dim, int hidden, int act_dim, Handle **out, std::string &err)
 {
     static_assert(Geo<8>::SMEM <= 160 * 1024 && kMaxHidden == 32 * 8 && kMaxIn % 64 == 0, "the widest geometry");
     *out = nullptr;
     Handle *p = new (std::nothrow) Handle;
-    if (!p) { err = "swarm_policy_create_wide: out of memory"; return SWARM_POLICY_ERR_INVALID; }
+    if (!p) { err = "out of memory"; return SWARM_POLICY_ERR_INVALID; }
     p->g = layout_of(in_dim, hidden, act_dim);
-    const std::vector<unsigned char> blob = pack_host(p->g, w);
+    p->members = members;
+    std::vector<unsigned char> blob = pack_host(p->g, w);
     p->blob_bytes = blob.size();
+    for (int m = 1; m < members; ++m) {                     // a bank: the same packer, member by member
+        const std::vector<unsigned char> one = pack_host(p->g, w + 8 * m);
+        blob.insert(blob.end(), one.begin(), one.end());
+    }
     // the upload on a stream of its own, waited for here: no null-stream work (tests/test_stream_sources.py), complete on return
     hipStream_t up = nullptr;
     hipError_t e = p->d_blob.alloc(blob.size());
@@ -551,7 +375,7 @@ int create(const float *const w[8], int in_dim, int hidden, int act_dim, Handle 
     if (up) (void)hipStreamDestroy(up);
     if (e != hipSuccess) {
         delete p;
-        err = "swarm_policy_create_wide: device allocation / upload failed";
+        err = "device allocation / upload failed";
         return SWARM_POLICY_ERR_HIP;
     }
     *out = p;
@@ -581,26 +405,29 @@ int forward(Handle *p, const ForwardArgs &a, std::string &err)
         set_smem_all<6>(); set_smem_all<8>();
         p->smem_set = true;
     }
-    const dim3 g((unsigned)((a.rows + kRowsPerBlock - 1) / kRowsPerBlock));
+    // a bank handle: grid (ceil(R / 128), members), and the kernel's P.rows is the MEMBER's rows R = rows / members (the caller
+    // has checked the division)
+    if (a.bank) q.rows = a.rows / p->members;
+    const dim3 g((unsigned)((q.rows + kRowsPerBlock - 1) / kRowsPerBlock), a.bank ? (unsigned)p->members : 1u);
     const bool x3 = a.precision == SWARM_POLICY_BF16X3;
-    if (p->g.mt == 6) launch_mt<6>(a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
-    else launch_mt<8>(a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
+    if (p->g.mt == 6) launch_mt<6>(a.bank, a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
+    else launch_mt<8>(a.bank, a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { err = std::string("swarm_policy_forward: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
     return SWARM_POLICY_OK;
 }
 
-int load_device(Handle *p, const float *const w[8], hipStream_t st, std::string &err)
+int load_device(Handle *p, int member, const float *const w[8], hipStream_t st, std::string &err)
 {
     PackParams q;
     for (int i = 0; i < 8; ++i) q.w[i] = w[i];
-    q.hi = reinterpret_cast<uint4 *>(p->d_blob.get());
+    q.hi = reinterpret_cast<uint4 *>(p->d_blob.get() + (size_t)member * p->blob_bytes);
     q.lo = q.hi + (size_t)p->g.n_chunks * p->g.ch;
     q.g = p->g;
     const unsigned grid = (unsigned)((p->g.n_chunks * p->g.ch + 255) / 256);
     hipLaunchKernelGGL(k_policy_wide_pack, dim3(grid), dim3(256), 0, st, q);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = std::string("swarm_policy_load_device: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
+    if (e != hipSuccess) { err = hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
     return SWARM_POLICY_OK;
 }
 

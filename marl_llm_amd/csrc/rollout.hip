@@ -229,6 +229,12 @@ int check_policy_ring(const char *who, const swarm_env_info &ei, const swarm_pol
     }
     if (pi.act_dim != 2) return fail(SWARM_ERR_INVALID, "policy act_dim must be 2 (the env's action)", who);
     if (ei.obs_dtype == SWARM_BF16 && (pi.in_dim & 7)) return fail(SWARM_ERR_INVALID, "bf16 observation rows need obs_dim % 8 == 0", who);
+    if (ei.n_env % pi.members != 0) {                                       // a bank: a member owns whole envs
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "n_env %d is no multiple of the policy bank's members %d (a member acts for whole envs)",
+                      ei.n_env, pi.members);
+        return fail(SWARM_ERR_INVALID, msg, who);
+    }
     m = check_ring_slots(ei, ring);
     return m.empty() ? SWARM_OK : fail(SWARM_ERR_INVALID, m, who);
 }

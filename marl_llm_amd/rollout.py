@@ -7,6 +7,8 @@ ring buffer (train_assembly.py:91-111, maddpg.py:72-87, agents.py:69-96, buffer_
 * `PolicyMLP`     -- the reference's actor shape (networks.py:6-44: 4 x Linear, leaky-ReLU, tanh out) as a plain torch
                      module (the learner trains this one).
 * `FusedPolicy`   -- the same forward as one hand-written bf16-MFMA kernel (csrc/policy_mlp.hip) for the rollout.
+* `FusedPolicyBank` -- M actors of one shape in one handle and one launch: env group m of a batch acts with member m
+                     (checkpoints of a run, seeds of a sweep, a population of learners); a FusedPolicy to every loop below.
 * `DeviceReplay`  -- the ring buffer of buffer_agent.py:13-128 with one row per (env, agent) transition, as device tensors.
 * `ChainedReplay` -- the same transitions stored as a ring of env steps that share observation rows (half the copy per push).
 * `rollout`       -- obs -> policy -> exploration noise (agents.py:82-96 continuous branch) -> env.step_tensor -> push.
@@ -175,6 +177,102 @@ class FusedPolicy:
             self.close()
         except Exception:
             pass
+
+
+def _fc_params(m):
+    return (m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, m.fc3.weight, m.fc3.bias, m.fc4.weight, m.fc4.bias)
+
+
+def _bank_shape(modules):
+    """(in_dim, hidden, act_dim) shared by the modules of a bank; ValueError where they differ (no library call)."""
+    if len(modules) < 1:
+        raise ValueError("FusedPolicyBank needs at least one module")
+    shapes = [[tuple(t.shape) for t in _fc_params(m)] for m in modules]
+    in_dim, hidden, act_dim = shapes[0][0][1], shapes[0][0][0], shapes[0][6][0]
+    want = [(hidden, in_dim), (hidden,), (hidden, hidden), (hidden,), (hidden, hidden), (hidden,), (act_dim, hidden), (act_dim,)]
+    for k, s in enumerate(shapes):
+        if s != want:
+            raise ValueError("FusedPolicyBank: module %d has parameter shapes %s; a bank's members share one shape, (in_dim, "
+                             "hidden, act_dim) = (%d, %d, %d) of module 0" % (k, s, in_dim, hidden, act_dim))
+    return in_dim, hidden, act_dim
+
+
+class FusedPolicyBank(FusedPolicy):
+    """M actors of one shape in ONE handle and one launch per forward (swarm_policy_bank_create, include/swarm_policy.h): over
+    `rows` rows, member m evaluates the contiguous rows [m R, (m + 1) R), R = rows / M -- in a rollout the envs
+    [m E / M, (m + 1) E / M).  Every row gets the bits a plain FusedPolicy of its member's module gives it (actions and
+    log_pi; the noise is keyed by row_offset + row as ever).  A FusedPolicy to `rollout`, `rollout_device` and `rollout_eval`:
+    they take it unchanged, and refuse E % M != 0.
+
+    modules: the members, each with fc1..fc4 of the same shapes (ValueError otherwise, before any library call).
+    precision, wide: as FusedPolicy, for all members; wide=None picks the geometry by FusedPolicy's rule.
+    `.members` = M, `.modules` the list; `refresh()` builds a new handle from host copies of all members; `sync(member=None)`
+    loads the device parameters of one member, or of all (one packing launch each), in stream order."""
+
+    def __init__(self, modules, device="cuda:0", precision="bf16", wide=None):
+        self.modules = list(modules)
+        self.members = len(self.modules)
+        _bank_shape(self.modules)
+        super().__init__(self.modules[0], device=device, precision=precision, wide=wide)
+
+    def refresh(self):
+        ct = self._ctypes
+        self.in_dim, self.hidden, self.act_dim = _bank_shape(self.modules)
+        ws = [t.detach().to("cpu", torch.float32).contiguous() for m in self.modules for t in _fc_params(m)]
+        narrow_serves = 4 <= self.in_dim <= 192 and self.in_dim % 4 == 0 and 1 <= self.hidden <= 191 and 1 <= self.act_dim <= 4
+        wide = (not narrow_serves) if self._want_wide is None else bool(self._want_wide)
+        table = (ct.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
+        h = ct.c_void_p()
+        rc = self.lib.swarm_policy_bank_create(table, self.members, self.in_dim, self.hidden, self.act_dim, int(wide),
+                                               self.device.index, ct.byref(h))
+        if rc != 0:
+            raise RuntimeError("swarm_policy_bank_create failed: " + self.lib.swarm_policy_last_error().decode())
+        self.wide = wide
+        self.close()
+        self.handle = h
+        if self.lib.swarm_policy_set_precision(self.handle, 1 if self.precision == "bf16x3" else 0) != 0:
+            raise RuntimeError("swarm_policy_set_precision failed: " + self.lib.swarm_policy_last_error().decode())
+
+    def sync(self, member=None):
+        """FusedPolicy.sync() for member `member` (its module's current device parameters into its slice of the handle; the
+        other members' bytes stay), or for all members when None: one packing launch each on torch's current stream.  Enqueue
+        only; everything is validated for all the members asked for before the first launch."""
+        ct = self._ctypes
+        if member is None:
+            which = range(self.members)
+        else:
+            if not 0 <= int(member) < self.members:
+                raise ValueError("sync(): member %d outside [0, %d)" % (int(member), self.members))
+            which = [int(member)]
+        want = [(self.hidden, self.in_dim), (self.hidden,), (self.hidden, self.hidden), (self.hidden,),
+                (self.hidden, self.hidden), (self.hidden,), (self.act_dim, self.hidden), (self.act_dim,)]
+        for k in which:
+            ps = _fc_params(self.modules[k])
+            if any(tuple(t.shape) != w for t, w in zip(ps, want)):
+                raise ValueError("sync(): module %d's (in_dim, hidden, act_dim) are not the handle's (%d, %d, %d); refresh() builds "
+                                 "a handle for new shapes" % (k, self.in_dim, self.hidden, self.act_dim))
+            if any(t.device != self.device for t in ps):
+                raise ValueError("sync() reads the parameters on %s; refresh() loads parameters kept on another device" % (self.device,))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        for k in which:
+            ws = [t.detach() if t.dtype == torch.float32 and t.is_contiguous() else t.detach().to(torch.float32).contiguous()
+                  for t in _fc_params(self.modules[k])]
+            rc = self.lib.swarm_policy_bank_load_device(self.handle, k, *[ct.c_void_p(w.data_ptr()) for w in ws], ct.c_void_p(stream))
+            if rc != 0:
+                raise RuntimeError("swarm_policy_bank_load_device failed: " + self.lib.swarm_policy_last_error().decode())
+
+    def __call__(self, obs, out=None, noise_scale=0.0, seed=0, step=0, log_pi=None, row_offset=0):
+        """FusedPolicy.__call__ over rows that are a multiple of the members: rows [m R, (m + 1) R) by member m."""
+        if isinstance(obs, torch.Tensor) and obs.shape[-1] == self.in_dim and (obs.numel() // self.in_dim) % self.members != 0:
+            raise ValueError("FusedPolicyBank: rows %d is no multiple of the %d members" % (obs.numel() // self.in_dim, self.members))
+        return super().__call__(obs, out=out, noise_scale=noise_scale, seed=seed, step=step, log_pi=log_pi, row_offset=row_offset)
+
+    def member_of_env(self, E):
+        """[E] int64: the member env e acts with, e // (E / M)."""
+        E = int(E)
+        if E < 1 or E % self.members != 0:
+            raise ValueError("member_of_env: E = %d is no positive multiple of the %d members" % (E, self.members))
+        return np.arange(E, dtype=np.int64) // (E // self.members)
 
 
 class DeviceReplay:
@@ -1151,16 +1249,43 @@ def save_eval_by_shape(trace, file_dir, n_shapes):
     S = int(n_shapes)
     if S < 1:
         raise ValueError("n_shapes must be >= 1")
-    mean, std = np.full((T, S, 3), np.nan), np.full((T, S, 3), np.nan)
-    count = np.zeros((T, S), np.int64)
+    return _save_by_group(m, shape_env, S, file_dir, "metrics_by_shape.npz")
+
+
+def _save_by_group(m, group, G, file_dir, name):
+    """mean, std [T, G, 3] and count [T, G] of the metrics m [T, E, 3] over the envs with group[t, e] == g, NaN-aware, into
+    file_dir/name (save_eval_by_shape's file; a group outside [0, G) is in none); returns the path."""
+    import os
+    import warnings
+    T = m.shape[0]
+    mean, std = np.full((T, G, 3), np.nan), np.full((T, G, 3), np.nan)
+    count = np.zeros((T, G), np.int64)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)            # all-NaN groups: the mean / std stay NaN
-        for s in range(S):
-            held = shape_env == s
+        for s in range(G):
+            held = group == s
             count[:, s] = held.sum(axis=1)
             for t in np.nonzero(count[:, s])[0]:
                 mean[t, s], std[t, s] = np.nanmean(m[t, held[t]], axis=0), np.nanstd(m[t, held[t]], axis=0)
     os.makedirs(file_dir, exist_ok=True)
-    path = os.path.join(file_dir, "metrics_by_shape.npz")
+    path = os.path.join(file_dir, name)
     np.savez(path, mean=mean, std=std, count=count)
     return path
+
+
+def save_eval_by_member(trace, members, file_dir):
+    """Write metrics_by_member.npz for a rollout_eval trace of a FusedPolicyBank and return its path: save_eval_by_shape's file
+    and NaN rules with the member of an env in place of its shape -- mean, std [T, M, 3] of the three metrics over the envs
+    member m acts for (a NaN metric of an env is left out; all NaN stays NaN) and count [T, M], the number of those envs.
+    members: an int array [E], the member of every env (FusedPolicyBank.member_of_env(E)), entries in [0, M) with M = its
+    maximum + 1, or -1 for an env in no group.  Waits for the GPU (it reads the trace back)."""
+    m = _host_array(trace.metrics).astype(np.float64, copy=False)
+    if m.ndim != 3 or m.shape[2] != 3:
+        raise ValueError("trace.metrics must be [steps, E, 3]")
+    T, E, _ = m.shape
+    members = np.asarray(members)
+    if members.shape != (E,) or members.dtype.kind not in "iu":
+        raise ValueError("members must be an int array [E = %d]" % E)
+    if members.min() < -1 or members.max() < 0:
+        raise ValueError("members must hold member indices >= 0 (or -1 for an env in no group)")
+    return _save_by_group(m, np.broadcast_to(members, (T, E)), int(members.max()) + 1, file_dir, "metrics_by_member.npz")
