@@ -360,6 +360,123 @@ __device__ __forceinline__ float psi5_u_f32(float u)
     return c;
 }
 
+// The list walk of the LIST_LEAN kernels (k_env, part (E)): one lane emits the kept cells of ranks k0 .. k1 - 1 of its agent's
+// list into `row` and sums their exploration-reward terms, as the plain loop of k_env does -- the same cells in the same order,
+// so the slots and the fp32 sums are that loop's bit for bit -- in fewer instructions per cell:
+//  - A lane that has cells left always holds a window row with a kept bit, so a trip is one predicated block: the cell, and
+//    behind it ONE test "cells left" that also ends the loop.  Under the cap the slot address is the counter (it steps by one
+//    slot and is compared with the range's end address).
+//  - The next window row's word and its lattice row mask are read one row ahead of their use: a row change takes them from
+//    registers and issues the reads of the row after, so no trip waits on a read it has just issued.  A row that kept no cell
+//    is stepped over inside the trip, by a loop of its own off the usual path (dbf takes the same additions of inv_r as in the
+//    plain loop).  A lane at its range's end steps one row on for nothing, and the reads ahead may pass the window's last row
+//    by two: they stay inside the launch's LDS and their values are never used.
+//  - The first cell of the range: the position of the set bit of rank `left` in the row by five popcounts of a low part of the
+//    word against `left` itself.
+//  - CAP (a wave that holds an agent over the cap G): `take` -- the cell's rank is the next selected one, or the agent is
+//    under the cap -- is one predicate for the store, the slot and the next selected rank.
+// srp / rmp: the window row / lattice row mask of the range's first cell, left = k0 - (kept cells in front of that row).
+template <bool CAP, int AG>
+__device__ __forceinline__ void list_walk_lean(const KP &P, const unsigned *srp, const u64 *rmp, const int aca0, const int k0,
+                                               const int k1, const int left, const int nk, float dbf, const float inv_r,
+                                               const float apr_s, short *row, float &n0, float &n1, float &dn)
+{
+    const int G = P.g_max;
+    const unsigned nm1 = (unsigned)(nk - 1);
+    const unsigned wd0 = *srp;
+    u64 rm0 = *rmp;
+    srp += AG; ++rmp;
+    unsigned nw = *srp;                                          // one row ahead
+    u64 nm = *rmp;
+    unsigned kept = k0 < k1 ? (wd0 & 0x1FFFFu) : 0u;
+    {
+        int pb = 0;
+#pragma unroll
+        for (int sh = 16; sh >= 1; sh >>= 1) {
+            const int c = __popc(__builtin_amdgcn_ubfe(kept, 0u, (unsigned)(pb + sh)));   // pb + sh <= 31
+            pb = c <= left ? pb + sh : pb;
+        }
+        kept = (kept >> pb) << pb;
+    }
+    int base = (int)(wd0 >> 17);
+    unsigned relm = (unsigned)(rm0 >> aca0);
+    float db2 = dbf * dbf;
+    auto rank_of = [&](int q) -> int {                               // as in k_env
+        if (P.cap_int) {
+            const unsigned x = 2u * (unsigned)q * nm1 + (unsigned)(G - 1);
+            const unsigned hq_ = __umulhi(x, P.cap_magic);
+            return (int)((((x - hq_) >> 1) + hq_) >> P.cap_shift);
+        }
+        const double v = q * ((double)nm1 / (G - 1));
+        return (int)(P.cap_even ? rint(v) : round(v));
+    };
+    const bool cap = CAP && nk > G;
+    int k = k0, slot = k0, nxt = 0;
+    if constexpr (CAP) {
+        if (cap) {
+            if (P.cap_int) slot = k0 > 0 ? (int)((unsigned)((2 * k0 - 1) * (G - 1) + 2 * (int)nm1 - 1) / (2u * nm1)) : 0;
+            else {
+                slot = 0;
+#pragma clang loop vectorize(disable) interleave(disable)
+                while (slot < G && rank_of(slot) < k0) ++slot;
+            }
+            slot = slot < G ? slot : G;
+            nxt = slot < G ? rank_of(slot) : 0x7FFFFFFF;
+        }
+    }
+    short *p = row + k0;
+    const short *const pend = row + k1;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    f32x2 n10 = {n1, n0};
+    auto more = [&]() -> bool { return CAP ? k < k1 : p < pend; };
+    while (__any(more())) {
+        if (more()) {                                                // kept != 0 here
+            const int c = __builtin_ctz(kept);
+            kept &= kept - 1;
+            const int cell = base + __popc(relm & ((1u << c) - 1u));
+            const float da = fmaf((float)c, inv_r, -apr_s);
+            const float u = fmaf(da, da, db2);
+            float psi = psi5_u_f32(u);
+            if constexpr (CAP) {
+                const bool take = !cap || k == nxt;
+                if (take) {
+                    row[slot] = (short)cell;
+                    ++slot;
+                    if (cap) nxt = slot < G ? rank_of(slot) : 0x7FFFFFFF;
+                }
+                psi = take ? psi : 0.0f;
+                ++k;
+            } else {
+                *p = (short)cell;
+                asm volatile("" ::: "memory");                       // (the store in front of the address's step: no copy of p)
+                ++p;
+            }
+            // n1 += psi dbf, n0 += psi da: one packed fma (each half an fmaf).  The sums stay in front of the row change:
+            // sunk behind it they cost a copy of dbf and db2 per trip
+            n10 = __builtin_elementwise_fma(f32x2{psi, psi}, f32x2{dbf, da}, n10); dn += psi;
+            asm volatile("" : "+v"(n10), "+v"(dn));
+            if (kept == 0) {                                         // (a lane at its range's end steps once more, for nothing)
+                kept = nw & 0x1FFFFu; base = (int)(nw >> 17);
+                relm = (unsigned)(nm >> aca0);
+                dbf += inv_r;
+                if (__builtin_expect(kept == 0, 0)) {                // a row that kept no cell: stepped over within the trip
+                    while (kept == 0 && more()) {
+                        srp += AG; ++rmp;
+                        const unsigned wd = *srp;
+                        kept = wd & 0x1FFFFu; base = (int)(wd >> 17);
+                        relm = (unsigned)(*rmp >> aca0);
+                        dbf += inv_r;
+                    }
+                }
+                srp += AG; ++rmp;
+                nw = *srp; nm = *rmp;                                // the row after, ahead of its use
+                db2 = dbf * dbf;
+            }
+        }
+    }
+    n1 = n10.x; n0 = n10.y;
+}
+
 // The nearest-cell candidates of the lattice rows b = wr, wr + WS, ... < nrows of one env for the WALK_LEAN kernels (k_env,
 // part 3): per row the nearest set column below the split column a_r (`dn`) and from it on (`up`), best and runner-up d2
 // in lattice units, and the cell index of the best (0 when the lane is inactive or saw no cell).  MT: the row-mask word.
@@ -1866,6 +1983,8 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
     // below it) and its reward weight psi(u), u = (distance / d_sen)^2 from the LATTICE coordinates -- |v| is invariant
     // under the lattice's rotation, so the sums run in lattice steps and need neither the stored cells nor a list
     // read-back.  The fp32 result only DECIDES outside a guard band; inside it the sums are redone in fp64 below.
+    // LIST_LEAN (the lattice kernels of 64 agents, full geometry): the walk of a range is list_walk_lean, above the kernel.
+    constexpr bool LIST_LEAN = LAT && NPAD == 64 && !HALF;
     float qn0 = 0.0f, qn1 = 0.0f, qdn = 0.0f, qrl = 1.0f; int qnk = 0;      // the quad's reward sums / list length / d_sen in steps
     for (int rep = 0, reps = REPS(11); rep < reps; ++rep) {
         FENCE();
@@ -1885,7 +2004,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
         const int s0 = (int)__builtin_amdgcn_sad_u8(cq.x, 0u, 0u), s1 = (int)__builtin_amdgcn_sad_u8(cq.y, 0u, 0u);
         const int s2 = (int)__builtin_amdgcn_sad_u8(cq.z, 0u, 0u), s3 = (int)__builtin_amdgcn_sad_u8(cq.w, 0u, 0u);
         const int nk = s0 + s1 + s2 + s3;
-        const int per = (nk + LPA - 1) / LPA;
+        const int per = LIST_LEAN ? (int)((unsigned)(nk + LPA - 1) / (unsigned)LPA) : (nk + LPA - 1) / LPA;   // (nk >= 0: a shift)
         const int k0 = sub * per < nk ? sub * per : nk;
         const int k1 = k0 + per < nk ? k0 + per : nk;
         // the window row holding rank k0: the LAST row whose first rank is <= k0 (empty rows in front of it are skipped)
@@ -1979,7 +2098,13 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
                 }
             }
         };
-        if (__any(nk > G)) walk_range(std::true_type{}); else walk_range(std::false_type{});
+        // (switched by LIST_LEAN alone, the loop a function outside the kernel: the other 150 kernels keep their code)
+        if constexpr (LIST_LEAN) {
+            if (__any(nk > G)) list_walk_lean<true, AG>(P, srow + t * AG + ea, rmp, aca0, k0, k1, k0 - before, nk, dbf, inv_r, apr_s, row, n0, n1, dn);
+            else list_walk_lean<false, AG>(P, srow + t * AG + ea, rmp, aca0, k0, k1, k0 - before, nk, dbf, inv_r, apr_s, row, n0, n1, dn);
+        } else {
+            if (__any(nk > G)) walk_range(std::true_type{}); else walk_range(std::false_type{});
+        }
         // the quad's partial sums -> every lane of the quad (two DPP exchanges)
         auto quad_sum = [](float v) -> float {
             v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
