@@ -120,7 +120,8 @@ bool detect_lattice(const double *gx, const double *gy, int n, LatEnv &L)
 int window_rows(float R) { return (int)std::floor(2.0f * (R + 0.01f)) + 1; }
 
 // Decide the cell path of the next launches and lay out its LDS.  A cell set WALKS (row-space lattice path) when it is a
-// lattice subset whose own sensing window is at most 15 lattice rows; any other set takes the generic scan, which handles
+// lattice subset whose own sensing window is at most 15 lattice rows (and, at 64 agent threads, whose covered window is at
+// most 29: classify_cells); any other set takes the generic scan, which handles
 // arbitrary cell sets.  any_walk / any_scan: some env of the batch may hold a walking / a scanning set; rmax, cmax,
 // ncols_max: the maxima over the walking sets.  All walk: one lattice launch; none walks: one generic launch; both kinds:
 // PATH_MIXED, two launches that share the envs out by workgroup (env_launch) -- or, with debug_flags bit 3, one generic
@@ -192,7 +193,10 @@ LatInfo classify_cells(const swarm_env *h, const double *gx, const double *gy, i
     }
     const double l = L.R;
     L.R = (float)(h->kp.d_sen / l); L.Rc = (float)((h->kp.r_avoid / 2.0) / l);
-    const LatInfo info = {true, window_rows(L.R) <= 15, window_rows(L.R) > 15, L.R, L.Rc, L.ncols};
+    // (64 agent threads: those lattice kernels also keep a row's covered columns as a 32-bit word from the agent's first
+    // possible column, which holds a covered window of at most 29 rows -- r_avoid / 2 < 14.49 steps; see row_sel_lean)
+    const bool walks = window_rows(L.R) <= 15 && !(h->npad == 64 && window_rows(L.Rc) > 29);
+    const LatInfo info = {true, walks, !walks, L.R, L.Rc, L.ncols};
     if (!info.walk) std::memset(&L, 0, sizeof(L));
     return info;
 }

@@ -492,6 +492,11 @@ __device__ __forceinline__ void list_walk_lean(const KP &P, const unsigned *srp,
 //    constant of the select, the trip is noted once, behind its rows.  The last trip holds one to three rows: the rows past
 //    the lattice's last are empty words there, candidates at the sentinel distance.
 //  - Inactive lanes walk along (their coordinates are whatever the state buffer holds) and are set to +inf / cell 0 behind it.
+//  - Packed keys: best and runner-up are kept as (bits of d2 & ~7) | candidate number 0..7 of the trip --
+//    d2 >= +0, so the words order like the distances, the sentinels (>= 1.8e19) and kNoCand above every real candidate.  A
+//    candidate is one v_and_or_b32, one v_med3_u32 and one v_min_u32; the leader's number is the key's low bits; within a
+//    trip the number ascends with the cell index, so equal kept bits keep the first.  best32 / second32 leave without
+//    their last three mantissa bits: the caller's band `tol` carries the term that covers them (see there).
 constexpr float kNoCand = 1e18f;
 template <typename MT, int WS>
 __device__ __forceinline__ void nearest_rows_lean(const u64 *rm, const short *rs, const int nrows, const int wr, const float apf,
@@ -504,7 +509,9 @@ __device__ __forceinline__ void nearest_rows_lean(const u64 *rm, const short *rs
     auto ffbl = [](unsigned v) -> unsigned { unsigned r; asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(v)); return r; };
     auto ffbh = [](unsigned v) -> unsigned { unsigned r; asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(v)); return r; };
     auto sat = [](unsigned x, unsigned y) -> unsigned { return __builtin_elementwise_add_sat(x, y); };
-    int lead = 0, lead_b = 0;
+    auto umed3 = [](unsigned x, unsigned y, unsigned z) -> unsigned { unsigned r; asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z)); return r; };
+    int lead_b = 0;
+    unsigned kb = __float_as_uint(best32), ks = __float_as_uint(second32);          // best and runner-up key (+inf on entry)
     auto cand_row = [&](int b, MT rowm, auto kc) {
         constexpr int k = decltype(kc)::value;
         const float dy = (float)b - bpf, dy2 = dy * dy;
@@ -518,33 +525,91 @@ __device__ __forceinline__ void nearest_rows_lean(const u64 *rm, const short *rs
         const unsigned a_up = sat((unsigned)a_r, fu), a_dn = fd ^ (unsigned)(MB - 1);
         const float dxu = (float)a_up - apf, dxd = (float)a_dn - apf;
         const float d2u = fmaf(dxu, dxu, dy2), d2d = fmaf(dxd, dxd, dy2);
-        // lower cell index first: on an exact tie the strict compare keeps it (and the tie is re-done exactly)
-        second32 = __builtin_amdgcn_fmed3f(best32, second32, d2d);
-        bool lt = d2d < best32;
-        best32 = lt ? d2d : best32; lead = lt ? 2 * k : lead;
-        second32 = __builtin_amdgcn_fmed3f(best32, second32, d2u);
-        lt = d2u < best32;
-        best32 = lt ? d2u : best32; lead = lt ? 2 * k + 1 : lead;
+        // packed keys: a non-negative float orders like its bits, so (bits & ~7) | candidate number is one word that
+        // carries distance and candidate; runner-up and best are one v_med3_u32 and one v_min_u32.  Lower cell index first:
+        // within a trip equal kept bits keep the lower number (and every such tie is re-done exactly)
+        const unsigned kd = (__float_as_uint(d2d) & ~7u) | (unsigned)(2 * k), ku = (__float_as_uint(d2u) & ~7u) | (unsigned)(2 * k + 1);
+        ks = umed3(kb, ks, kd); kb = min(kb, kd);
+        ks = umed3(kb, ks, ku); kb = min(kb, ku);
     };
     auto trip = [&](int b, auto tail) {
         constexpr bool TAIL = decltype(tail)::value;
         const MT m0 = rowmask(b), m1 = (!TAIL || b + WS < nrows) ? rowmask(b + WS) : (MT)0;
         const MT m2 = (!TAIL || b + 2 * WS < nrows) ? rowmask(b + 2 * WS) : (MT)0;
-        const float best_in = best32;
+        const unsigned kb_in = kb;
         cand_row(b, m0, std::integral_constant<int, 0>{}); cand_row(b + WS, m1, std::integral_constant<int, 1>{});
         cand_row(b + 2 * WS, m2, std::integral_constant<int, 2>{});
         if constexpr (!TAIL) cand_row(b + 3 * WS, rowmask(b + 3 * WS), std::integral_constant<int, 3>{});
-        lead_b = best32 < best_in ? b : lead_b;
+        lead_b = kb < kb_in ? b : lead_b;
     };
     int b = wr;
     for (; b + 3 * WS < nrows; b += 4 * WS) trip(b, std::false_type{});
     if (b < nrows) trip(b, std::true_type{});
+    const int lead = (int)(kb & 7u);
+    best32 = __uint_as_float(kb & ~7u); second32 = __uint_as_float(ks & ~7u);
     const bool found = act && best32 < kNoCand;                  // (a split always has a row with a cell)
     const int lrow = found ? lead_b + (lead >> 1) * WS : 0;
     const MT below = rowmask(lrow) & lowm;
     const int lc = rs[lrow] + (MB == 32 ? __popc((unsigned)below) : __popcll((unsigned long long)below)) - 1 + (lead & 1);
     bc = found ? lc : 0;
     if (!act) { best32 = INFINITY; second32 = INFINITY; }
+}
+
+// The set columns of lattice row b within lattice distance rho of one agent, for the WALK_LEAN kernels (k_env, part 3): what
+// the kernel's row_sel lambda answers, shifted down to the agent's first possible column c0 -- a 32-bit word, bit q = column
+// c0 + q.  Both passes call it: the sensed radius with c0 = ca0 (the word is the window row as srow keeps it), the covered
+// radius with a first column of its own.  Returns the columns that are in range for certain; `bnd` takes the (rare) boundary
+// columns, which the caller puts to the reference's fp64 test on the stored cell.  MT: the row-mask word.
+//  - The row word is shifted to c0 once, in front; everything behind it is 32-bit.  No column below c0 can be in range (c0 =
+//    ceil(a - (rho + 2 lat_m)) clamped to 0..63, an interval starts at ceil(a - ho) with ho <= rho + lat_m), and the interval
+//    ends less than 2 rho + 1 + 3 lat_m columns behind c0.  The host holds both radii to what the word takes
+//    (classify_cells, env_api.hip): a set walks only if its sensed window is at most 15 rows (rho < 7.5: <= 16 columns
+//    behind c0) and, on these kernels, its covered window at most 29 rows (rho_c < 14.49: < 30 columns behind c0, the
+//    clamp of cmax at 30 cuts nothing); any other set takes the generic scan.
+//  - Interval: ax = (float)(a - c0) is the agent's column coordinate relative to c0, the ends are ceil(ax - ho) and
+//    floor(ax + ho) clamped to 0 and to cmax = min(ncols - 1 - c0, 30).  cmax < 0 (c0 behind the last column) and an interval
+//    wholly left or right of the lattice give hi < lo: that empties the row word, with the lane and row tests, in one
+//    select.  hi >= lo means 0 <= lo <= hi <= 30, so the range is 2 (1 << hi) - (1 << lo) and no shift is out of range
+//    (the `& 31` only say so for the empty case, whose word is 0 whatever the range).
+//  - Numerics: the bound documented above the lattice path holds with room to spare.  |ax| <= |a| (c0 lies between 0 and a's
+//    window), so the cast error 2^-24 |ax| is at most that of the absolute coordinate, the column c - c0 is an exact small
+//    integer, and fit tolerance and sqrt roundings are what they were: < 2e-5 steps against lat_m >= 1e-4.  Columns inside the
+//    radius shrunk by lat_m (ri2) are in range for certain, columns outside the radius grown by lat_m (ro2) are not, and only
+//    the two END columns can lie between: those are `bnd`.  An end that the clamp moved is tested like any other end
+//    (lof / hif are the clamped ends).
+//  - No callable parameter: a closure handed in here keeps the address of the kernel's argument struct alive until the
+//    inliner is through, the struct is then copied field by field in the entry block, and the scalar registers of all 69
+//    fields spill to lanes (594 lane reads in the headline kernel, +5.5 us: profiles/r25).
+template <typename MT>
+__device__ __forceinline__ unsigned row_sel_lean(const u64 *rm, const int nrows, const bool act, const int b, const float bpf,
+                                                 const float ax, const int c0, const int cmax, const float ro2, const float ri2,
+                                                 unsigned &bnd)
+{
+    constexpr int MB = (int)sizeof(MT) * 8;
+    auto rowmask = [&](int q) -> MT { return MB == 32 ? (MT)reinterpret_cast<const unsigned *>(rm)[2 * q] : (MT)rm[q]; };
+    const bool rowok = act && (unsigned)b < (unsigned)nrows;
+    const int bq = b < 0 ? 0 : (b > 63 ? 63 : b);
+    // read whatever the lane: all 64 entries of the table are written, and a read under a branch of its own would cut the
+    // row's arithmetic into blocks (the clamp below then costs a canonicalising v_max in front of its own)
+    const MT rowm = rowmask(bq);
+    const float dy = (float)b - bpf, dy2 = dy * dy;
+    const float ho2 = ro2 - dy2;
+    // raw v_sqrt_f32 (1 ulp): its error is far inside the margin
+    const float ho = __builtin_amdgcn_sqrtf(__builtin_amdgcn_fmed3f(ho2, 0.0f, INFINITY));
+    const float f0 = ceilf(ax - ho), f1 = floorf(ax + ho);           // columns that may be in range, relative to c0
+    // (the ends stay floats for their tests: no round trip through integers)
+    const float lof = fmaxf(f0, 0.0f), hif = fminf(f1, (float)cmax);
+    const int lo = (int)lof, hi = (int)hif;
+    const float e0 = lof - ax, e1 = hif - ax;
+    // one select empties the word: a lane or a row outside, no column at this row's height, or hi < lo
+    const bool any_o = rowok && ho2 > 0.0f && hi >= lo;
+    const unsigned wrow = any_o ? (unsigned)(rowm >> (c0 & (MB - 1))) : 0u;
+    // an end column is certain when its own model distance is inside the shrunk radius
+    const bool ok0 = fmaf(e0, e0, dy2) < ri2, ok1 = fmaf(e1, e1, dy2) < ri2;
+    const unsigned bl = 1u << (lo & 31), bh = 1u << (hi & 31);                   // (hi >= lo: 0 <= lo, hi <= 30)
+    const unsigned m = ((bh - bl) + bh) & wrow;                                  // columns lo .. hi of the row: 2 bh - bl
+    bnd = ((ok0 ? 0u : bl) | (ok1 ? 0u : bh)) & m;                               // boundary columns: the caller's exact test
+    return m ^ bnd;
 }
 
 // LAT: every env's target cells are a lattice subset (host-detected, KP::lattice) -- a compile-time switch, so that each
@@ -588,8 +653,9 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
     constexpr bool DIAG = kDiagBuild || !(LAT && NPAD == 64 && !HALF);
     // the same twelve kernels walk the lattice rows in fewer instructions (part 3): the nearest-cell loop takes empty sides by
     // a sentinel distance, four rows a trip and the winner's cell index once; an env picks the 32-bit walk by its own width;
-    // split B leaves out the lattice coordinates that only the walking splits read.  The switch below exists for A/B builds
-    // (profiles/r18).
+    // split B leaves out the lattice coordinates that only the walking splits read; the window rows are 32-bit words relative
+    // to the agent's first column from the start (row_sel_lean), best and runner-up packed keys (profiles/r25).  The switch
+    // below exists for A/B builds (profiles/r18).
     constexpr bool WALK_LEAN = LAT && NPAD == 64 && !HALF;
 #ifndef SWARM_WALK_ENV32
 #define SWARM_WALK_ENV32 1                     // an env of <= 32 columns takes the 32-bit walk whatever the batch's widest (0: lat_n32 alone)
@@ -1149,16 +1215,14 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
         auto range = [](int lo, int hi) -> MT { return hi >= lo ? (MT)((~(MT)0 >> (MB - 1 - hi)) & (~(MT)0 << lo)) : (MT)0; };
         auto row_sel = [&](int b, float rho, double cut) -> MT {
             // columns of row b within lattice distance rho of (apf, bpf); exact test d2 < cut on the boundary columns
-            // (LEAN: one unsigned compare for both ends of the row range, and the clamp of ho2 as one v_med3 -- fmaxf costs
-            // a canonicalising v_max in front of its own; the same values)
-            constexpr bool LEAN = WALK_LEAN;
-            const bool rowok = LEAN ? act && (unsigned)b < (unsigned)nrows : act && b >= 0 && b < nrows;
+            // (the WALK_LEAN kernels use row_sel_lean instead)
+            const bool rowok = act && b >= 0 && b < nrows;
             const float dy = (float)b - bpf, dy2 = dy * dy;
             const float ro = rho + lat_m, ri = rho - lat_m, ri2 = ri > 0.0f ? ri * ri : 0.0f;
             const float ho2 = ro * ro - dy2;
             const bool any_o = rowok && ho2 > 0.0f;
             // raw v_sqrt_f32 (1 ulp): its error is far inside the margin
-            const float ho = __builtin_amdgcn_sqrtf(LEAN ? __builtin_amdgcn_fmed3f(ho2, 0.0f, INFINITY) : fmaxf(ho2, 0.0f));
+            const float ho = __builtin_amdgcn_sqrtf(fmaxf(ho2, 0.0f));
             int ao0 = (int)ceilf(apf - ho), ao1 = (int)floorf(apf + ho);     // columns that may be in range
             ao0 = ao0 < 0 ? 0 : ao0; ao1 = ao1 > ncols - 1 ? ncols - 1 : ao1;
             const int bq = b < 0 ? 0 : (b > 63 ? 63 : b);
@@ -1188,6 +1252,52 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             FENCE();
             // rows b with |b - bpf| < rho + margin: the first is ceil(bpf - rho - margin), at most floor(2 (rho + margin)) + 1
             // of them (lat_nrs / lat_nrc: that count for the largest rho of any env)
+            if constexpr (WALK_LEAN) {
+                // row_sel_lean, above the kernel: the same columns as a word relative to the pass's first column c0, in fewer
+                // instructions per row; its boundary columns take the reference's test on the stored cell here.  The cell
+                // index is rowstart + the row's set columns below c0 + q; row mask and rowstart are read again for it, in
+                // the rare branch, so the common path holds neither.
+                auto lean_row = [&](int b, float ax, int c0, int cmax, float ro2, float ri2, double cut) -> unsigned {
+                    unsigned bnd;
+                    unsigned sel = row_sel_lean<MT>(rm, nrows, act, b, bpf, ax, c0, cmax, ro2, ri2, bnd);
+                    while (__any(bnd != 0)) {
+                        if (bnd != 0) {
+                            const int q = __builtin_ctz(bnd);
+                            bnd &= bnd - 1;
+                            int br = b < 0 ? 0 : (b > 63 ? 63 : b);
+                            asm volatile("" : "+v"(br));                         // (the addresses below are worked out here, not per row)
+                            const int c = rs[br] + popc(rowmask(br) & (MT)(((MT)1 << (c0 + q)) - 1));   // c0 + q is a set column: < MB
+                            const double2 g = cell64(c);
+                            const double ex = g.x - px, ey = g.y - py;
+                            if (ex * ex + ey * ey < cut) sel |= 1u << q;
+                        }
+                    }
+                    return sel;
+                };
+                {
+                    const float ax = (float)(apd - (double)ca0);                 // (hdr.x)
+                    const int cm = ncols - 1 - ca0, cmax = cm > 30 ? 30 : cm;
+                    const float ro = L.R + lat_m, ri = L.R - lat_m, ro2 = ro * ro, ri2 = ri > 0.0f ? ri * ri : 0.0f;
+                    for (int t = wr; t < P.lat_nrs; t += WS)
+                        srow[t * AG + at] = lean_row(b0s + t, ax, ca0, cmax, ro2, ri2, P.c_sen);
+                }
+                // the same walk with radius r_avoid/2: the env's "covered by any agent" columns, per lattice row.  The pass
+                // has a first column of its own; its words go back to lattice columns for the OR.
+                const int b0c = (int)ceilf(bpf - (L.Rc + 2.0f * lat_m));
+                int ca0c = (int)ceilf(apf - (L.Rc + 2.0f * lat_m));
+                ca0c = ca0c < 0 ? 0 : (ca0c > 63 ? 63 : ca0c);
+                const float axc = (float)(apd - (double)ca0c);
+                const int cmc = ncols - 1 - ca0c, cmaxc = cmc > 30 ? 30 : cmc;
+                const float roc = L.Rc + lat_m, ric = L.Rc - lat_m, ro2c = roc * roc, ri2c = ric > 0.0f ? ric * ric : 0.0f;
+                for (int t = wr; t < P.lat_nrc; t += WS) {
+                    const unsigned selc = lean_row(b0c + t, axc, ca0c, cmaxc, ro2c, ri2c, P.c_occ);
+                    const int bq = b0c + t < 0 ? 0 : (b0c + t > 63 ? 63 : b0c + t);     // selc == 0 outside the lattice
+                    if (selc != 0) {                                             // (a set bit: ca0c + its place < MB)
+                        if constexpr (MB == 32) atomicOr(reinterpret_cast<unsigned *>(&covrow[el * 64 + bq]), selc << (ca0c & 31));
+                        else atomicOr(reinterpret_cast<unsigned long long *>(&covrow[el * 64 + bq]), (unsigned long long)selc << ca0c);
+                    }
+                }
+            } else {
             for (int t = wr; t < P.lat_nrs; t += WS)
                 srow[t * AG + at] = (unsigned)(row_sel(b0s + t, L.R, P.c_sen) >> ca0);
             // the same walk with radius r_avoid/2: the env's "covered by any agent" columns, per lattice row
@@ -1199,6 +1309,7 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
                     if constexpr (MB == 32) atomicOr(reinterpret_cast<unsigned *>(&covrow[el * 64 + bq]), (unsigned)selc);
                     else atomicOr(reinterpret_cast<unsigned long long *>(&covrow[el * 64 + bq]), (unsigned long long)selc);
                 }
+            }
             }
             // nearest cell (CPP:858-908) from the lattice too: in row b the nearest cell is the set column closest to
             // the agent's column coordinate, on either side of it -- two candidates per row, rows dealt over the splits.
@@ -1248,7 +1359,16 @@ k_env(const KP P, const void *__restrict__ action, const int act_mode, OT *__res
             // cast + 1e-6 lattice fit tolerance, in steps): decide among this split's candidates with the reference's
             // fp64 distances, first minimum in ascending cell order (rows ascending, left candidate before right).
             const float lat_dlt = 1.2e-7f * fmaxf(fabsf(apf), fabsf(bpf)) + 2e-6f;
-            const float tol = 6.0f * sqrtf(second32) * lat_dlt + 1e-9f;
+            // (WALK_LEAN, packed keys: best32 and second32 arrive without their last three mantissa bits, each up to
+            // 2^-20 of itself too low, and the candidate that leads is the first of those that agree in the kept bits.  The
+            // test second - best <= tol then sees a difference up to 2^-20 best32 too large and a tol up to 2^-21 of
+            // itself too small, and the true model minimum lies up to 2^-20 best32 above best32: 2^-19 second32 on top of
+            // tol covers the three, so every lane the full-width test sends to the exact scan still goes, with a threshold
+            // no lower.  Which term is the larger depends on where the agent stands, lat_dlt growing with its coordinates:
+            // at lat_dlt's floor of 2e-6 the first up to about 12 steps from the shape, this one further out.)
+            float tol_keys = 0.0f;
+            if constexpr (WALK_LEAN) tol_keys = 0x1p-19f * second32;
+            const float tol = 6.0f * sqrtf(second32) * lat_dlt + 1e-9f + tol_keys;
             const bool unc_min = act && (wave_exact || (second32 < no_cand && (second32 - best32) <= tol));
             if (__any(unc_min)) {
                 if (unc_min) {
