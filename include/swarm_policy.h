@@ -161,6 +161,41 @@ int  swarm_policy_bank_load_device(swarm_policy_t *p, int member, const float *w
 /* swarm_policy_read_packed for ONE member's slice (the size returned is one member's). */
 int64_t swarm_policy_bank_read_packed(swarm_policy_t *p, int member, void *host_dst, int64_t capacity, void *stream);
 
+/* ---- Routing by env: which member acts for each env comes from a device table; groups of any size, in any order.
+ * Route the bank's rows by env.  member_of_env: DEVICE int32 [n_env], read when the routing kernel RUNS (stream order, as
+ * swarm_policy_bank_load_device reads its arrays).  While a route is in force, a forward call over rows == n_env * rows_per_env
+ * gives row r, bit for bit (act and log_pi), what a plain handle of member member_of_env[r / rows_per_env] gives that row
+ * with the same (noise_scale, seed, step, row_offset): the noise key stays row_offset + r.
+ * An env whose entry is outside [0, members) is served by nobody: none of its rows is read or written.
+ * member_of_env == NULL with n_env == 0 ends the route (equal contiguous groups again).
+ *   Enqueue only: one launch of the routing kernel on `stream`.  The first route, and a route with a larger n_env * rows_per_env
+ *     than any before, allocate the tables (and wait for `stream` before the old ones are freed); every other call allocates
+ *     nothing and waits for nothing.  Ending the route enqueues nothing.
+ *   Stream order: a forward enqueued on the stream before the call uses the previous table, one enqueued after it the new
+ *     one; re-routing between two steps needs no host wait.  The table must stay valid and hold the intended values until
+ *     the routing kernel has run (writes enqueued on the stream before the call are seen); afterwards it is not read again.
+ *     Which route is "in force" for the rows check below is the host's view: the last call made.
+ *   How it runs: the routing kernel gathers each member's envs -- env_order, by member and by ascending env inside a member:
+ *     numpy's stable argsort of the table over the served envs -- and cuts every member's rows into whole workgroup tiles of
+ *     its own; the forward kernels launch floor(rows / T) + min(members, n_env) workgroups (T rows each), an upper bound of
+ *     the tiles in use that needs no read-back, and the surplus workgroups return at once.  A workgroup never reads or
+ *     writes a row of another member or of an unserved env.  The outputs do not depend on env_order.
+ *   Refusals, each SWARM_POLICY_ERR_INVALID with nothing enqueued, the route in force kept, and a message that starts
+ *     "swarm_policy_bank_route:" -- the arguments are checked before the handle: n_env < 0; n_env > 0 with a NULL table;
+ *     n_env == 0 with a table; rows_per_env < 1 when n_env > 0; n_env * rows_per_env >= 2^31; a NULL handle; a plain (non-bank)
+ *     handle.  A HIP error (SWARM_POLICY_ERR_HIP: the allocation of the tables, the launch) is no refusal: it ENDS the
+ *     route -- equal contiguous groups again -- because the tables may no longer describe one.
+ *   Under a route a forward whose `rows` is not n_env * rows_per_env is refused (SWARM_POLICY_ERR_INVALID, the message names
+ *     both numbers): there is no silent fall-back to equal groups.  The rows % members check applies only without a route.
+ *   swarm_policy_set_precision, swarm_policy_bank_load_device and swarm_policy_bank_read_packed are unchanged under a route
+ *     (the tables serve both precisions). */
+int  swarm_policy_bank_route(swarm_policy_t *p, const int32_t *member_of_env, int32_t n_env, int32_t rows_per_env, void *stream);
+/* Waits for `stream`, then: counts[members] = envs per member, *unserved = envs outside [0, members), env_order[n_env] (may be
+ * NULL) = the envs in the order the kernel serves them (n_env - *unserved entries, then -1).  Returns n_env of the route in
+ * force (0: none, and nothing is written or waited for), or -SWARM_POLICY_ERR_INVALID (a NULL handle, NULL counts or
+ * unserved) / -SWARM_POLICY_ERR_HIP with a message that starts "swarm_policy_bank_route_read:". */
+int  swarm_policy_bank_route_read(swarm_policy_t *p, int32_t *counts, int32_t *unserved, int32_t *env_order, void *stream);
+
 const char *swarm_policy_last_error(void);
 
 #ifdef __cplusplus

@@ -62,7 +62,13 @@ typedef struct swarm_ring {
  * An actor bank (swarm_policy_bank_create, swarm_policy.h) is taken by swarm_rollout, swarm_rollout_logpi, swarm_rollout_explore
  * and swarm_rollout_eval unchanged: with E envs and M members, env e acts with member e / (E / M) at every step -- the
  * bank's contiguous row groups, whole envs each.  E % M != 0 is SWARM_ERR_INVALID, found during validation (nothing enqueued),
- * with a message that starts with the entry point's name. */
+ * with a message that starts with the entry point's name.
+ * A bank under a route (swarm_policy_bank_route): env e acts with member member_of_env[e] instead.  The route must be the env
+ * handle's -- n_env == E and rows_per_env == N; anything else is SWARM_ERR_INVALID, found during validation (nothing enqueued),
+ * with a message that starts with the entry point's name and names the numbers -- and then E % M is not checked.  An env the
+ * route leaves unserved (an entry outside [0, M)) gets no action written: its rows of act[c] (and of log_pi[c]) keep whatever
+ * they held, and the env steps with those values.  The route is read at validation: re-routing takes effect between calls,
+ * not inside one. */
 int swarm_rollout(swarm_env_t *env, swarm_policy_t *pol, const swarm_ring_t *ring, int32_t steps,
                   const uint8_t *uniform_steps, float noise_scale, uint64_t seed, uint64_t step0, uint64_t row_offset,
                   double *reward_stats, void *stream);

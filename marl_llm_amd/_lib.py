@@ -58,6 +58,7 @@ POLICY_SYMBOLS = ("swarm_policy_create", "swarm_policy_create_wide", "swarm_poli
                   "swarm_policy_forward_explore", "swarm_policy_forward_explore_at", "swarm_policy_forward_explore_logpi",
                   "swarm_policy_set_precision", "swarm_policy_load_device", "swarm_policy_read_packed",
                   "swarm_policy_bank_create", "swarm_policy_bank_members", "swarm_policy_bank_load_device", "swarm_policy_bank_read_packed",
+                  "swarm_policy_bank_route", "swarm_policy_bank_route_read",
                   "swarm_policy_last_error")   # include/swarm_policy.h
 ROLLOUT_SYMBOLS = ("swarm_rollout", "swarm_rollout_logpi", "swarm_rollout_explore", "swarm_rollout_expert", "swarm_rollout_eval",
                    "swarm_rollout_last_error")   # include/swarm_rollout.h
@@ -133,6 +134,8 @@ def load():
     lib.swarm_policy_bank_members.argtypes = [vp]; lib.swarm_policy_bank_members.restype = i32
     lib.swarm_policy_bank_load_device.argtypes = [vp, i32] + [vp] * 9; lib.swarm_policy_bank_load_device.restype = i32
     lib.swarm_policy_bank_read_packed.argtypes = [vp, i32, vp, ctypes.c_int64, vp]; lib.swarm_policy_bank_read_packed.restype = ctypes.c_int64
+    lib.swarm_policy_bank_route.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp]; lib.swarm_policy_bank_route.restype = i32
+    lib.swarm_policy_bank_route_read.argtypes = [vp, vp, vp, vp, vp]; lib.swarm_policy_bank_route_read.restype = i32
     lib.swarm_policy_last_error.argtypes = []; lib.swarm_policy_last_error.restype = ctypes.c_char_p
     lib.swarm_observe.argtypes = [vp, vp]; lib.swarm_observe.restype = i32
     lib.swarm_step.argtypes = [vp, vp, i32, vp, vp, vp, vp]; lib.swarm_step.restype = i32

@@ -85,11 +85,14 @@ constexpr int kSmemBytes = 2 * kChunkFrags * 64 * 16;                       // 7
 // LOGPI: also write log_pi[row], the log-density of the row's Gaussian exploration noise (include/swarm_policy.h).  A template
 // parameter rather than a run-time test, so that the instantiations without it compile exactly as before (218 VGPRs).
 //
-// The kernel itself is csrc/policy_mlp_kernel.h, compiled twice: k_policy_mlp for a plain handle, k_policy_mlp_bank for an
-// actor bank (BANK: blockIdx.y is the member; swarm_policy_bank_create) -- that file says why it is text and not a template.
+// The kernel itself is csrc/policy_mlp_kernel.h, compiled three times: k_policy_mlp for a plain handle, k_policy_mlp_bank for
+// an actor bank (BANK: blockIdx.y is the member; swarm_policy_bank_create), k_policy_mlp_route for a bank under a route (ROUTE:
+// workgroup b serves entry b of the route's tile table; swarm_policy_bank_route) -- that file says why it is text and not a
+// template.
 constexpr size_t kMemberPieces = ((3 * kMT * kKS + kKS) * 64 * 2 * 16 + (3 * kKP + 32) * 4) / 16;   // a member's blob: high, low, biases
 #define POLICY_MLP_KERNEL k_policy_mlp
 #define POLICY_MLP_BANK false
+#define POLICY_MLP_ROUTE 0
 #include "policy_mlp_kernel.h"
 #undef POLICY_MLP_KERNEL
 #undef POLICY_MLP_BANK
@@ -98,6 +101,14 @@ constexpr size_t kMemberPieces = ((3 * kMT * kKS + kKS) * 64 * 2 * 16 + (3 * kKP
 #include "policy_mlp_kernel.h"
 #undef POLICY_MLP_KERNEL
 #undef POLICY_MLP_BANK
+#undef POLICY_MLP_ROUTE
+#define POLICY_MLP_KERNEL k_policy_mlp_route
+#define POLICY_MLP_BANK false
+#define POLICY_MLP_ROUTE 1
+#include "policy_mlp_kernel.h"
+#undef POLICY_MLP_KERNEL
+#undef POLICY_MLP_BANK
+#undef POLICY_MLP_ROUTE
 
 // swarm_policy_load_device's packer: the whole blob of a handle re-written from fp32 DEVICE weights (torch.nn.Linear layout),
 // in the layout swarm_policy_create packs on the host -- which stays the independent witness: tests/test_gpu_policy_load.py
@@ -210,6 +221,125 @@ void set_smem_bank()
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp_bank<IN_BF16, 1, X3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
 }
 
+// The same for a bank under a route (behind the bank's, for the same reason).
+template <bool IN_BF16, bool X3>
+void launch_route(const dim3 &g, const dim3 &b, hipStream_t st, const MlpParams &q, const void *obs, float *act, float *log_pi, float logpi_c,
+                  const swarm_wide::RouteView &rv)
+{
+    if (log_pi) hipLaunchKernelGGL((k_policy_mlp_route<IN_BF16, 1, X3, true>), g, b, kSmemBytes, st, q, obs, act, log_pi, logpi_c, rv);
+    else hipLaunchKernelGGL((k_policy_mlp_route<IN_BF16, 1, X3, false>), g, b, kSmemBytes, st, q, obs, act, nullptr, 0.0f, rv);
+}
+
+template <bool IN_BF16, bool X3>
+void set_smem_route()
+{
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp_route<IN_BF16, 1, X3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp_route<IN_BF16, 1, X3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
+}
+
+// ---- swarm_policy_bank_route's kernel: the route's tables from member_of_env, for both geometries.
+// One workgroup.  Wave 0 walks the envs twice in blocks of 64, one env per lane: a lane's key is its env's member, `members`
+// for an env nobody serves, members + 1 for a lane past n_env; the lanes that hold its key (nine ballots, one per key bit)
+// give its rank among them and their number.  Pass 1 adds that number to the key's count in LDS (the lowest lane of each key:
+// distinct keys, distinct addresses -- no atomics); one thread then turns the counts into first positions (exclusive prefix
+// by member) and, per tile size, into first tiles; pass 2 places env e at first position of its key + envs of that key seen
+// in earlier blocks + rank: by member, ascending env inside a member -- numpy's stable argsort, a pure function of the table.
+// Meanwhile the other waves (and wave 0 behind them) write the tile tables: entry b = (member, first slot, slot count, 0) by a
+// binary search of b in the members' first tiles; the entries behind the last tile carry count 0.
+struct RouteTableParams {
+    const int32_t *member_of_env;      // [n_env], device
+    int32_t *counts;                   // [SWARM_POLICY_BANK_MAX + 1]: envs per member, the unserved count in the last word
+    int32_t *env_order;                // [served envs]
+    int4 *tiles[2];                    // one table per tile size
+    int t_rows[2], n_tiles[2];         // rows per tile (0: no such table) and entries = rows / T + min(members, n_env)
+    int n_env, rows_per_env, members;
+};
+
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) k_policy_route_table(const RouteTableParams P)
+{
+    constexpr int kM = SWARM_POLICY_BANK_MAX;
+    __shared__ int run[kM + 2];                    // per key: the count (pass 1), then the next free position (pass 2)
+    __shared__ int cnt[kM], first[kM], tbase[2][kM + 1];
+    const int tid = threadIdx.x, lane = tid & 63, M = P.members;
+    for (int i = tid; i < kM + 2; i += THREADS) run[i] = 0;
+    __syncthreads();
+    // one block of 64 envs: this lane's env and key, its rank among the lanes of its key, their number and their lowest lane
+    auto block = [&](int e0, int &e, int &key, int &rank, int &n, int &lead) {
+        e = e0 + lane;
+        key = M + 1;
+        if (e < P.n_env) { const int m = P.member_of_env[e]; key = (m >= 0 && m < M) ? m : M; }
+        unsigned long long peers = ~0ull;
+#pragma unroll
+        for (int b = 0; b < 9; ++b) {                                       // keys < 2^9
+            const bool bit = (key >> b) & 1;
+            const unsigned long long bal = __ballot(bit);
+            peers &= bit ? bal : ~bal;
+        }
+        rank = __popcll(peers & ((1ull << lane) - 1ull));
+        n = __popcll(peers);
+        lead = __ffsll((long long)peers) - 1;
+    };
+    int e, key, rank, n, lead;
+    if (tid < 64) {
+        for (int e0 = 0; e0 < P.n_env; e0 += 64) {
+            block(e0, e, key, rank, n, lead);
+            if (lane == lead) run[key] += n;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int pos = 0, tb[2] = {0, 0};
+        for (int m = 0; m < M; ++m) {
+            const int c = run[m], rows_m = c * P.rows_per_env;             // <= n_env * rows_per_env < 2^31
+            cnt[m] = c; first[m] = pos;
+            pos += c;
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                tbase[g][m] = tb[g];
+                if (P.t_rows[g]) tb[g] += rows_m / P.t_rows[g] + (rows_m % P.t_rows[g] != 0);
+            }
+        }
+        tbase[0][M] = tb[0]; tbase[1][M] = tb[1];
+        P.counts[kM] = run[M];                                              // the unserved envs
+    }
+    __syncthreads();
+    for (int m = tid; m < M; m += THREADS) { P.counts[m] = cnt[m]; run[m] = first[m]; }
+    __syncthreads();
+    if (tid < 64) {
+        for (int e0 = 0; e0 < P.n_env; e0 += 64) {
+            block(e0, e, key, rank, n, lead);
+            int base = 0;
+            if (lane == lead) { base = run[key]; run[key] = base + n; }     // the leader alone touches LDS
+            base = __shfl(base, lead);
+            // (the bound holds whenever the table is the one pass 1 counted; it keeps a table rewritten under the kernel inside)
+            if (key < M && base + rank < P.n_env) P.env_order[base + rank] = e;
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        if (!P.t_rows[g]) continue;
+        const int T = P.t_rows[g], total = tbase[g][M];
+        for (int b = tid; b < P.n_tiles[g]; b += THREADS) {
+            int4 te = make_int4(0, 0, 0, 0);
+            if (b < total) {
+                int lo = 0, hi = M - 1;                                     // the last member whose first tile is <= b: it owns b
+                while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tbase[g][mid] <= b) lo = mid; else hi = mid - 1; }
+                const int j = b - tbase[g][lo], rows_m = cnt[lo] * P.rows_per_env;
+                te = make_int4(lo, first[lo] * P.rows_per_env + j * T, min(T, rows_m - j * T), 0);
+            }
+            P.tiles[g][b] = te;
+        }
+    }
+}
+
+template <int THREADS>
+void launch_route_table(const RouteTableParams &q, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_policy_route_table<THREADS>, dim3(1), dim3(THREADS), 0, st, q);
+}
+constexpr int kRouteThreads = 256;
+
 // The blob of one actor as swarm_policy_create uploads it (and a bank holds once per member): [w1 | w2 | w3 | w4] fragments
 // (8 bf16 per lane), their low parts in the same layout, then [b1 | b2 | b3 | b4] fp32.
 constexpr size_t kFrag = 64 * 8;                                              // bf16 elements per fragment
@@ -297,6 +427,22 @@ struct SWARM_HIDDEN swarm_policy {     // hidden: its implicit destructor must n
     // into the first.  A bank handle runs the BANK kernels, also with one member.
     bool bank = false;
     int members = 1;
+    // swarm_policy_bank_route: the route in force (n_env == 0: none) and its tables, one allocation of int32 words cut for
+    // cap_rows rows: [counts: SWARM_POLICY_BANK_MAX + 1][env_order: cap_rows][tile table per tile size: 4 words an entry].
+    // The narrow geometry keeps two tile tables (128 rows a workgroup at bf16, 256 at bf16x3: swarm_policy_set_precision may
+    // change under a route), the wide one (128 at both precisions).
+    struct Route {
+        int n_env = 0, rows_per_env = 0;
+        long long cap_rows = 0;
+        swarm_internal::DevBuf<int32_t> d_tab;
+        size_t off_order = 0, off_tiles[2] = {0, 0};
+        int t_rows[2] = {0, 0};
+        unsigned grid(int g, int members) const
+        {
+            const long long rows = (long long)n_env * rows_per_env;
+            return (unsigned)(rows / t_rows[g] + (members < n_env ? members : n_env));
+        }
+    } route;
     ~swarm_policy() { swarm_wide::destroy(wide); }
 };
 
@@ -304,6 +450,7 @@ int swarm_internal_policy_info(const swarm_policy_t *p, swarm_policy_info *out)
 {
     if (!p || !out) return SWARM_POLICY_ERR_INVALID;
     out->device = p->device; out->in_dim = p->in_dim; out->act_dim = p->act_dim; out->members = p->members;
+    out->route_n_env = p->route.n_env; out->route_rows_per_env = p->route.rows_per_env;
     return SWARM_POLICY_OK;
 }
 
@@ -490,16 +637,28 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
 {
     if (!p || !obs || !act || rows < 0) { g_policy_error = "swarm_policy_forward: bad argument"; return SWARM_POLICY_ERR_INVALID; }
     if (in_bf16 && (p->in_dim & 7)) { g_policy_error = "swarm_policy_forward_bf16: in_dim must be a multiple of 8"; return SWARM_POLICY_ERR_INVALID; }
-    if (rows % p->members != 0) {                           // a bank: every member owns rows / members whole rows
+    const bool routed = p->route.n_env > 0;
+    if (routed && rows != (int64_t)p->route.n_env * p->route.rows_per_env) {       // no silent fall-back to equal groups
+        g_policy_error = "swarm_policy_forward: rows " + std::to_string((long long)rows) + " is not the route's n_env * rows_per_env = " +
+                         std::to_string(p->route.n_env) + " * " + std::to_string(p->route.rows_per_env) + " = " +
+                         std::to_string((long long)p->route.n_env * p->route.rows_per_env) + " (swarm_policy_bank_route)";
+        return SWARM_POLICY_ERR_INVALID;
+    }
+    if (!routed && rows % p->members != 0) {                // a bank: every member owns rows / members whole rows
         g_policy_error = "swarm_policy_forward: rows " + std::to_string((long long)rows) + " is no multiple of the bank's members " + std::to_string(p->members);
         return SWARM_POLICY_ERR_INVALID;
     }
     if (rows == 0) return SWARM_POLICY_OK;
     const DeviceGuard guard(p->device);
     if (!guard.ok) { g_policy_error = "swarm_policy_forward: hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
+    // a route in force: the tile table of this launch's rows per workgroup (policy_wide.h RouteView)
+    const int rg = (!p->wide && p->precision == 1) ? 1 : 0;
+    const swarm_wide::RouteView rv = {routed ? reinterpret_cast<const int4 *>(p->route.d_tab.get() + p->route.off_tiles[rg]) : nullptr,
+                                      routed ? p->route.d_tab.get() + p->route.off_order : nullptr, p->route.rows_per_env};
     if (p->wide) {                                          // a wide handle: its own kernel, SWARM_POLICY_TPW not read
         const swarm_wide::ForwardArgs a = {obs, in_bf16, rows, act, log_pi, noise_scale, seed, step, row_offset, p->precision,
-                                           static_cast<hipStream_t>(stream), p->bank};
+                                           static_cast<hipStream_t>(stream), p->bank, routed ? &rv : nullptr,
+                                           routed ? p->route.grid(rg, p->members) : 0u};
         return swarm_wide::forward(p->wide, a, g_policy_error);
     }
     MlpParams q = p->p;
@@ -522,11 +681,21 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
         set_smem<false, 2, false>(); set_smem<true, 2, false>();
         set_smem<false, 1, true>(); set_smem<true, 1, true>();
         set_smem_bank<false, false>(); set_smem_bank<true, false>(); set_smem_bank<false, true>(); set_smem_bank<true, true>();
+        set_smem_route<false, false>(); set_smem_route<true, false>(); set_smem_route<false, true>(); set_smem_route<true, true>();
         p->smem_set = true;
     }
     const dim3 g(grid), b(64 * n_waves);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->bank) {                                          // (ceil(R / rows per workgroup), members); SWARM_POLICY_TPW not read
+    if (routed) {                                           // one workgroup per entry of the route's tile table; q.rows: the call's
+        const dim3 gr(p->route.grid(rg, p->members));
+        if (p->precision == 1) {
+            if (in_bf16) launch_route<true, true>(gr, b, st, q, obs, act, log_pi, logpi_c, rv);
+            else launch_route<false, true>(gr, b, st, q, obs, act, log_pi, logpi_c, rv);
+        } else {
+            if (in_bf16) launch_route<true, false>(gr, b, st, q, obs, act, log_pi, logpi_c, rv);
+            else launch_route<false, false>(gr, b, st, q, obs, act, log_pi, logpi_c, rv);
+        }
+    } else if (p->bank) {                                   // (ceil(R / rows per workgroup), members); SWARM_POLICY_TPW not read
         q.rows = rows / p->members;                         // the kernel's P.rows: the MEMBER's rows
         const long long bank_block = (long long)n_waves * 32;
         const dim3 gb((unsigned)((q.rows + bank_block - 1) / bank_block), (unsigned)p->members);
@@ -612,6 +781,87 @@ int swarm_policy_bank_load_device(swarm_policy_t *p, int member, const float *w1
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_bank_load_device: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
     const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
     return load_member("swarm_policy_bank_load_device", p, member, w, stream);
+}
+
+int swarm_policy_bank_route(swarm_policy_t *p, const int32_t *member_of_env, int32_t n_env, int32_t rows_per_env, void *stream)
+{
+    const char *who = "swarm_policy_bank_route: ";
+    if (n_env < 0) { g_policy_error = std::string(who) + "n_env " + std::to_string(n_env) + " < 0"; return SWARM_POLICY_ERR_INVALID; }
+    if (n_env > 0 && !member_of_env) { g_policy_error = std::string(who) + "null member_of_env with n_env " + std::to_string(n_env); return SWARM_POLICY_ERR_INVALID; }
+    if (n_env == 0 && member_of_env) { g_policy_error = std::string(who) + "n_env 0 with a table (a NULL table with n_env 0 ends the route)"; return SWARM_POLICY_ERR_INVALID; }
+    if (n_env > 0 && rows_per_env < 1) { g_policy_error = std::string(who) + "rows_per_env " + std::to_string(rows_per_env) + " < 1"; return SWARM_POLICY_ERR_INVALID; }
+    const long long rows = (long long)n_env * rows_per_env;
+    if (n_env > 0 && rows >= (1ll << 31)) {
+        g_policy_error = std::string(who) + "n_env * rows_per_env = " + std::to_string(n_env) + " * " + std::to_string(rows_per_env) + " reaches 2^31 rows";
+        return SWARM_POLICY_ERR_INVALID;
+    }
+    // (the arguments first, then the handle: every refusal above is decided without one)
+    if (!p) { g_policy_error = std::string(who) + "null handle"; return SWARM_POLICY_ERR_INVALID; }
+    if (!p->bank) { g_policy_error = std::string(who) + "the handle is no bank (swarm_policy_bank_create makes one; a plain handle has one actor for every row)"; return SWARM_POLICY_ERR_INVALID; }
+    if (n_env == 0) { p->route.n_env = 0; p->route.rows_per_env = 0; return SWARM_POLICY_OK; }     // equal contiguous groups again
+    const DeviceGuard guard(p->device);
+    if (!guard.ok) { g_policy_error = std::string(who) + "hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    swarm_policy::Route &r = p->route;
+    if (rows > r.cap_rows) {                                // the first route, or a larger one than any before: new tables
+        // forwards in flight on `stream` read the old ones: wait for them before the allocation is replaced
+        hipError_t e = r.d_tab ? hipStreamSynchronize(st) : hipSuccess;
+        const int t0 = p->wide ? swarm_wide::kRouteRows : 32 * waves_of(false), t1 = p->wide ? 0 : 32 * waves_of(true);
+        const auto up4 = [](size_t v) { return (v + 3) & ~(size_t)3; };             // tile entries are 16-byte loads
+        // env_order gets `rows` words although n_env are used: the contract ties allocation to rows alone (a later route over
+        // no more rows allocates nothing, whatever its n_env), and n_env <= rows is the only bound rows gives
+        const size_t off_order = up4(SWARM_POLICY_BANK_MAX + 1), off_t0 = off_order + up4((size_t)rows);
+        const size_t off_t1 = off_t0 + 4 * ((size_t)(rows / t0) + p->members);
+        const size_t words = off_t1 + (t1 ? 4 * ((size_t)(rows / t1) + p->members) : 0);
+        if (e == hipSuccess) e = r.d_tab.alloc(words);
+        if (e != hipSuccess) {
+            r.n_env = 0; r.rows_per_env = 0; r.cap_rows = 0;
+            g_policy_error = std::string(who) + "allocating the tables: " + hipGetErrorString(e);
+            return SWARM_POLICY_ERR_HIP;
+        }
+        r.cap_rows = rows; r.off_order = off_order; r.off_tiles[0] = off_t0; r.off_tiles[1] = off_t1; r.t_rows[0] = t0; r.t_rows[1] = t1;
+    }
+    r.n_env = n_env; r.rows_per_env = rows_per_env;
+    RouteTableParams q;
+    q.member_of_env = member_of_env; q.counts = r.d_tab.get(); q.env_order = r.d_tab.get() + r.off_order;
+    for (int g = 0; g < 2; ++g) {
+        q.tiles[g] = reinterpret_cast<int4 *>(r.d_tab.get() + r.off_tiles[g]);
+        q.t_rows[g] = r.t_rows[g];
+        q.n_tiles[g] = r.t_rows[g] ? (int)r.grid(g, p->members) : 0;
+    }
+    q.n_env = n_env; q.rows_per_env = rows_per_env; q.members = p->members;
+    launch_route_table<kRouteThreads>(q, st);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { r.n_env = 0; r.rows_per_env = 0; g_policy_error = std::string(who) + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
+    return SWARM_POLICY_OK;
+}
+
+int swarm_policy_bank_route_read(swarm_policy_t *p, int32_t *counts, int32_t *unserved, int32_t *env_order, void *stream)
+{
+    const char *who = "swarm_policy_bank_route_read: ";
+    if (!p) { g_policy_error = std::string(who) + "null handle"; return -SWARM_POLICY_ERR_INVALID; }
+    const swarm_policy::Route &r = p->route;
+    if (r.n_env == 0) return 0;
+    if (!counts || !unserved) { g_policy_error = std::string(who) + "null counts / unserved"; return -SWARM_POLICY_ERR_INVALID; }
+    const DeviceGuard guard(p->device);
+    if (!guard.ok) { g_policy_error = std::string(who) + "hipSetDevice failed"; return -SWARM_POLICY_ERR_HIP; }
+    hipStream_t st = static_cast<hipStream_t>(stream);      // the copies on the stream, behind the route enqueued there; then the wait
+    int32_t head[SWARM_POLICY_BANK_MAX + 1];
+    hipError_t e = hipMemcpyAsync(head, r.d_tab.get(), sizeof head, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    long long served = 0;
+    if (e == hipSuccess) {
+        for (int m = 0; m < p->members; ++m) { counts[m] = head[m]; served += head[m]; }
+        *unserved = head[SWARM_POLICY_BANK_MAX];
+        if (env_order) {                                    // the served envs, then -1 up to n_env
+            if (served > r.n_env) served = r.n_env;
+            for (long long i = served; i < r.n_env; ++i) env_order[i] = -1;
+            if (served > 0) e = hipMemcpyAsync(env_order, r.d_tab.get() + r.off_order, (size_t)served * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+        }
+    }
+    if (e != hipSuccess) { g_policy_error = std::string(who) + hipGetErrorString(e); return -SWARM_POLICY_ERR_HIP; }
+    return r.n_env;
 }
 
 int64_t swarm_policy_read_packed(swarm_policy_t *p, void *host_dst, int64_t capacity, void *stream)

@@ -1,6 +1,7 @@
-// The kernel of policy_mlp.hip, as text: that file includes this one twice, inside its anonymous namespace --
-//   POLICY_MLP_KERNEL = k_policy_mlp,      POLICY_MLP_BANK = false: the plain handle's kernel;
-//   POLICY_MLP_KERNEL = k_policy_mlp_bank, POLICY_MLP_BANK = true:  an actor bank's (swarm_policy_bank_create).
+// The kernel of policy_mlp.hip, as text: that file includes this one three times, inside its anonymous namespace --
+//   POLICY_MLP_KERNEL = k_policy_mlp,       POLICY_MLP_BANK = false, POLICY_MLP_ROUTE = 0: the plain handle's kernel;
+//   POLICY_MLP_KERNEL = k_policy_mlp_bank,  POLICY_MLP_BANK = true,  POLICY_MLP_ROUTE = 0: an actor bank's (swarm_policy_bank_create);
+//   POLICY_MLP_KERNEL = k_policy_mlp_route, POLICY_MLP_BANK = false, POLICY_MLP_ROUTE = 1: a bank's under swarm_policy_bank_route.
 // Text and not a shared inlined body or one more template parameter: the plain kernels keep their symbols and compile to the
 // device code they had before the bank existed, instruction for instruction (tools/isa_diff.py) -- every BANK term below
 // folds away in the front end.
@@ -10,9 +11,21 @@
 // handle's first member's plus member * kMemberPieces pieces -- uniform per workgroup, a scalar -- and every bound (wave_on,
 // the load clamp, the store predicate) is the member's END, not the call's: a tail tile of member m neither reads nor writes a
 // row of member m + 1.  The noise key stays row_offset + the call's row, so the noise does not depend on the members.
+//
+// ROUTE (one more kernel argument, the route's tables): the grid is 1-D and workgroup b serves entry b of the tile table the
+// routing kernel wrote (k_policy_route_table in policy_mlp.hip): (member, first slot, slot count).  Slots number the rows of
+// the served envs in env_order; a lane's slot is first + its index in the workgroup, the tile's last slot standing in for a
+// lane past the count (the clamp idiom of the other two kernels), and its TRUE row of the call is
+// env_order[slot / rows_per_env] * rows_per_env + slot % rows_per_env: the observation load, the act / log_pi addresses and
+// the noise key use that row, the store predicate the slot count.  A tile of count 0 (surplus of the grid's upper bound)
+// returns before the first barrier, the whole workgroup.  One tile per wave only.
 template <bool IN_BF16, int TPW, bool X3, bool LOGPI>
 __global__ void __launch_bounds__(64 * waves_of(X3), (TPW == 1 && !X3) ? 2 : 1)
-POLICY_MLP_KERNEL(const MlpParams P, const void *__restrict__ obs_, float *__restrict__ act, float *__restrict__ log_pi, float logpi_c)
+POLICY_MLP_KERNEL(const MlpParams P, const void *__restrict__ obs_, float *__restrict__ act, float *__restrict__ log_pi, float logpi_c
+#if POLICY_MLP_ROUTE
+                  , const swarm_wide::RouteView R
+#endif
+                  )
 {
     constexpr int kWaves = waves_of(X3), kPre = pre_of(kWaves);
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -20,12 +33,28 @@ POLICY_MLP_KERNEL(const MlpParams P, const void *__restrict__ obs_, float *__res
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     constexpr bool BANK = POLICY_MLP_BANK;
+    constexpr bool ROUTE = POLICY_MLP_ROUTE;
+#if POLICY_MLP_ROUTE
+    static_assert(TPW == 1, "a routed tile is one wave's 32 rows");
+    const int4 te = R.tiles[blockIdx.x];                                                // (member, first slot, slots, -)
+    if (te.z <= 0) return;                                                              // uniform, before the first barrier
+    const int li = wave * 32 + r;                                                       // this lane's index in the tile
+    const int slot = te.y + (li < te.z ? li : te.z - 1);
+    const int senv = slot / R.rows_per_env;
+    const long long rrow = (long long)R.env_order[senv] * R.rows_per_env + (slot - senv * R.rows_per_env);   // the TRUE row
+    const bool rlive = li < te.z, ron = wave * 32 < te.z;
+    const int rmember = te.x;
+#else
+    constexpr long long rrow = 0;
+    constexpr bool rlive = false, ron = false;
+    constexpr int rmember = 0;
+#endif
     // BANK: P.rows is the MEMBER's row count R and the call's rows are [0, gridDim.y * R); this workgroup serves member blockIdx.y
     const long long first = BANK ? (long long)blockIdx.y * P.rows : 0;                  // the member's first row of the call
     const long long end = BANK ? first + P.rows : P.rows;                               // one past the last row this workgroup may touch
-    const size_t woff = BANK ? (size_t)blockIdx.y * kMemberPieces : 0;                  // the member's blob, in 16-byte pieces
-    const long long row0 = (BANK ? first : 0) + ((long long)blockIdx.x * kWaves + wave) * (32 * TPW) + r;    // this lane's row in tile 0
-    const bool wave_on = row0 - r < end;                                                // idle waves still stage and take the barriers
+    const size_t woff = ROUTE ? (size_t)rmember * kMemberPieces : BANK ? (size_t)blockIdx.y * kMemberPieces : 0;   // the member's blob, in 16-byte pieces
+    const long long row0 = ROUTE ? rrow : (BANK ? first : 0) + ((long long)blockIdx.x * kWaves + wave) * (32 * TPW) + r;    // this lane's row in tile 0
+    const bool wave_on = ROUTE ? ron : row0 - r < end;                                  // idle waves still stage and take the barriers
 
     bf8 pre[kPre];
     // chunk step cc: X3 interleaves (chunk c, high) and (chunk c, low)
@@ -36,7 +65,7 @@ POLICY_MLP_KERNEL(const MlpParams P, const void *__restrict__ obs_, float *__res
         const bf8 *b1_ = low ? P.l1 : P.w1, *b2_ = low ? P.l2 : P.w2, *b3_ = low ? P.l3 : P.w3, *b4_ = low ? P.l4 : P.w4;
         const bf8 *w = c < 2 ? b1_ + (size_t)c * kChunkFrags * 64 : c < 4 ? b2_ + (size_t)(c - 2) * kChunkFrags * 64
                      : c < 6 ? b3_ + (size_t)(c - 4) * kChunkFrags * 64 : b4_;
-        if constexpr (BANK) w += woff;
+        if constexpr (BANK || ROUTE) w += woff;
         const int n = (c < 6 ? kChunkFrags : kKS) * 64;
 #pragma unroll
         for (int k = 0; k < kPre; ++k) { const int q = tid + k * 64 * kWaves; if (q < n) pre[k] = w[q]; }
@@ -58,7 +87,7 @@ POLICY_MLP_KERNEL(const MlpParams P, const void *__restrict__ obs_, float *__res
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
             const long long row = row0 + 32 * t;
-            const size_t xoff = (size_t)(row < end ? row : end - 1) * P.in_dim;
+            const size_t xoff = (size_t)(ROUTE ? row : (row < end ? row : end - 1)) * P.in_dim;     // (ROUTE: clamped by slot)
             const float *x = static_cast<const float *>(obs_) + xoff;
             const __bf16 *xb = static_cast<const __bf16 *>(obs_) + xoff;
 #pragma unroll
@@ -88,7 +117,7 @@ POLICY_MLP_KERNEL(const MlpParams P, const void *__restrict__ obs_, float *__res
         for (int mt = 0; mt < kMT; ++mt)
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const float bv = (BANK ? P.b1 + 4 * woff : P.b1)[feat_of(mt, reg, h)];
+                const float bv = ((BANK || ROUTE) ? P.b1 + 4 * woff : P.b1)[feat_of(mt, reg, h)];
 #pragma unroll
                 for (int t = 0; t < TPW; ++t) acc[t][mt][reg] = bv;
             }
@@ -154,7 +183,7 @@ POLICY_MLP_KERNEL(const MlpParams P, const void *__restrict__ obs_, float *__res
                     }
                     if constexpr (X3) { if (!low) { acc[t][0] = o; continue; } }
                     const long long row = row0 + 32 * t;
-                    if (h == 0 && row < end) {
+                    if (h == 0 && (ROUTE ? rlive : row < end)) {
                         float *y = act + (size_t)row * P.act_dim;
                         float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                         if (P.noise_scale > 0.0f) {

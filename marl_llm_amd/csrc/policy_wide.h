@@ -14,6 +14,15 @@ constexpr int kMaxIn = 384, kMaxHidden = 256, kMaxAct = 4;
 
 struct Handle;                      // policy_wide.hip: the packed weights on the device and their geometry
 
+// What a routed forward kernel (k_policy_mlp_route, k_policy_wide_route) reads of a route (swarm_policy_bank_route): the tile
+// table for its rows per workgroup and env_order, both written by the routing kernel of policy_mlp.hip.
+struct RouteView {
+    const int4 *tiles;              // [grid]: (member, first slot, slot count, 0); surplus entries carry count 0
+    const int32_t *env_order;       // the served envs, by member and ascending env inside a member
+    int rows_per_env;
+};
+constexpr int kRouteRows = 128;     // the wide geometry's rows per workgroup (policy_wide.hip checks it)
+
 struct ForwardArgs {
     const void *obs;
     bool in_bf16;
@@ -24,6 +33,8 @@ struct ForwardArgs {
     int precision;                  // SWARM_POLICY_BF16 / SWARM_POLICY_BF16X3
     hipStream_t stream;
     bool bank;                      // a bank handle: the BANK kernels, member m on rows [m rows / members, (m + 1) rows / members)
+    const RouteView *route;         // != NULL: a route is in force -- the ROUTE kernels on route_grid workgroups
+    unsigned route_grid;
 };
 
 // true where the wide kernel serves the shape; decided without a device

@@ -118,9 +118,11 @@ __device__ __forceinline__ void finish_row(const WideParams &P, const f16v &o, l
     }
 }
 
-// The kernel itself is csrc/policy_wide_kernel.h, compiled twice: for a plain handle, and for an actor bank (BANK).
+// The kernel itself is csrc/policy_wide_kernel.h, compiled three times: for a plain handle, for an actor bank (BANK) and for
+// a bank under a route (ROUTE: swarm_policy_bank_route).
 #define POLICY_WIDE_KERNEL k_policy_wide
 #define POLICY_WIDE_BANK false
+#define POLICY_WIDE_ROUTE 0
 #include "policy_wide_kernel.h"
 #undef POLICY_WIDE_KERNEL
 #undef POLICY_WIDE_BANK
@@ -129,6 +131,15 @@ __device__ __forceinline__ void finish_row(const WideParams &P, const f16v &o, l
 #include "policy_wide_kernel.h"
 #undef POLICY_WIDE_KERNEL
 #undef POLICY_WIDE_BANK
+#undef POLICY_WIDE_ROUTE
+#define POLICY_WIDE_KERNEL k_policy_wide_route
+#define POLICY_WIDE_BANK false
+#define POLICY_WIDE_ROUTE 1
+#include "policy_wide_kernel.h"
+#undef POLICY_WIDE_KERNEL
+#undef POLICY_WIDE_BANK
+#undef POLICY_WIDE_ROUTE
+static_assert(kRowsPerBlock == swarm_wide::kRouteRows, "the route's tile table is cut for this workgroup");
 
 // ---- the packed stream, on the host (create) and on the device (load_device): the two are written independently and
 // tests/test_gpu_policy_wide.py compares their bytes.
@@ -307,11 +318,40 @@ void set_smem_bank()
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide_bank<IN_BF16, X3, true, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
 }
 
+template <bool IN_BF16, bool X3, int MT>
+void launch_route(const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act, float *log_pi, float logpi_c,
+                  const swarm_wide::RouteView &rv)
+{
+    if (log_pi) hipLaunchKernelGGL((k_policy_wide_route<IN_BF16, X3, true, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, log_pi, logpi_c, rv);
+    else hipLaunchKernelGGL((k_policy_wide_route<IN_BF16, X3, false, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, nullptr, 0.0f, rv);
+}
+
+template <bool IN_BF16, bool X3, int MT>
+void set_smem_route()
+{
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide_route<IN_BF16, X3, false, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide_route<IN_BF16, X3, true, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
+}
+
 template <int MT>
 void set_smem_all()
 {
     set_smem<false, false, MT>(); set_smem<true, false, MT>(); set_smem<false, true, MT>(); set_smem<true, true, MT>();
     set_smem_bank<false, false, MT>(); set_smem_bank<true, false, MT>(); set_smem_bank<false, true, MT>(); set_smem_bank<true, true, MT>();
+    set_smem_route<false, false, MT>(); set_smem_route<true, false, MT>(); set_smem_route<false, true, MT>(); set_smem_route<true, true, MT>();
+}
+
+template <int MT>
+void launch_route_mt(bool in_bf16, bool x3, const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act,
+                     float *log_pi, float logpi_c, const swarm_wide::RouteView &rv)
+{
+    if (x3) {
+        if (in_bf16) launch_route<true, true, MT>(g, st, q, obs, act, log_pi, logpi_c, rv);
+        else launch_route<false, true, MT>(g, st, q, obs, act, log_pi, logpi_c, rv);
+    } else {
+        if (in_bf16) launch_route<true, false, MT>(g, st, q, obs, act, log_pi, logpi_c, rv);
+        else launch_route<false, false, MT>(g, st, q, obs, act, log_pi, logpi_c, rv);
+    }
 }
 
 template <int MT>
@@ -410,7 +450,12 @@ int forward(Handle *p, const ForwardArgs &a, std::string &err)
     if (a.bank) q.rows = a.rows / p->members;
     const dim3 g((unsigned)((q.rows + kRowsPerBlock - 1) / kRowsPerBlock), a.bank ? (unsigned)p->members : 1u);
     const bool x3 = a.precision == SWARM_POLICY_BF16X3;
-    if (p->g.mt == 6) launch_mt<6>(a.bank, a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
+    if (a.route) {                                          // a route in force: one workgroup per tile-table entry, the call's rows
+        q.rows = a.rows;
+        const dim3 gr(a.route_grid);
+        if (p->g.mt == 6) launch_route_mt<6>(a.in_bf16, x3, gr, a.stream, q, a.obs, a.act, a.log_pi, logpi_c, *a.route);
+        else launch_route_mt<8>(a.in_bf16, x3, gr, a.stream, q, a.obs, a.act, a.log_pi, logpi_c, *a.route);
+    } else if (p->g.mt == 6) launch_mt<6>(a.bank, a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
     else launch_mt<8>(a.bank, a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { err = std::string("swarm_policy_forward: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }

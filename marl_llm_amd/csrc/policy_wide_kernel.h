@@ -1,13 +1,20 @@
-// The kernel of policy_wide.hip, as text: that file includes this one twice, inside its anonymous namespace --
-//   POLICY_WIDE_KERNEL = k_policy_wide,      POLICY_WIDE_BANK = false: the plain handle's kernel;
-//   POLICY_WIDE_KERNEL = k_policy_wide_bank, POLICY_WIDE_BANK = true:  an actor bank's (swarm_policy_bank_create).
+// The kernel of policy_wide.hip, as text: that file includes this one three times, inside its anonymous namespace --
+//   POLICY_WIDE_KERNEL = k_policy_wide,       POLICY_WIDE_BANK = false, POLICY_WIDE_ROUTE = 0: the plain handle's kernel;
+//   POLICY_WIDE_KERNEL = k_policy_wide_bank,  POLICY_WIDE_BANK = true,  POLICY_WIDE_ROUTE = 0: an actor bank's (swarm_policy_bank_create);
+//   POLICY_WIDE_KERNEL = k_policy_wide_route, POLICY_WIDE_BANK = false, POLICY_WIDE_ROUTE = 1: a bank's under swarm_policy_bank_route.
 // As csrc/policy_mlp_kernel.h, and for its reason: the plain kernels keep their symbols and their device code
 // (tools/isa_diff.py).  BANK: blockIdx.y is the member, blockIdx.x the workgroup inside the member's R rows of the call, P.rows
 // carries R; the member's streams lie one whole blob (both streams) behind the previous member's, and every bound is the
 // member's end.  The noise key stays row_offset + the call's row.
+// ROUTE: as csrc/policy_mlp_kernel.h says -- workgroup b serves entry b of the route's tile table (member, first slot, slot
+// count), a lane's true row comes from env_order, a tile of count 0 returns before the first barrier.
 template <bool IN_BF16, bool X3, bool LOGPI, int MT>
 __global__ void __launch_bounds__(kThreads, (MT == 6 && !X3) ? 2 : 1)
-POLICY_WIDE_KERNEL(const WideParams P, const void *__restrict__ obs_, float *__restrict__ act, float *__restrict__ log_pi, float logpi_c)
+POLICY_WIDE_KERNEL(const WideParams P, const void *__restrict__ obs_, float *__restrict__ act, float *__restrict__ log_pi, float logpi_c
+#if POLICY_WIDE_ROUTE
+                   , const swarm_wide::RouteView R
+#endif
+                   )
 {
     typedef Geo<MT> G;
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -15,13 +22,28 @@ POLICY_WIDE_KERNEL(const WideParams P, const void *__restrict__ obs_, float *__r
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     constexpr bool BANK = POLICY_WIDE_BANK;
+    constexpr bool ROUTE = POLICY_WIDE_ROUTE;
+#if POLICY_WIDE_ROUTE
+    const int4 te = R.tiles[blockIdx.x];                    // (member, first slot, slots, -)
+    if (te.z <= 0) return;                                  // uniform, before the first barrier
+    const int li = wave * 32 + r;                           // this lane's index in the tile
+    const int slot = te.y + (li < te.z ? li : te.z - 1);
+    const int senv = slot / R.rows_per_env;
+    const long long rrow = (long long)R.env_order[senv] * R.rows_per_env + (slot - senv * R.rows_per_env);   // the TRUE row
+    const bool rlive = li < te.z, ron = wave * 32 < te.z;
+    const unsigned rmember = (unsigned)te.x;
+#else
+    constexpr long long rrow = 0;
+    constexpr bool rlive = false, ron = false;
+    constexpr unsigned rmember = 0;
+#endif
     // BANK: P.rows is the MEMBER's row count R and the call's rows are [0, gridDim.y * R); this workgroup serves member blockIdx.y
     const long long first = BANK ? (long long)blockIdx.y * P.rows : 0;      // the member's first row of the call
     const long long end = BANK ? first + P.rows : P.rows;                   // one past the last row this workgroup may touch
     // (the plain kernel names P.rows at each of its three uses below, as it always has: read through this one copy its scalar
     // registers are allocated differently, and its code must not move)
-    const long long row = (BANK ? first : 0) + ((long long)blockIdx.x * kWaves + wave) * 32 + r;
-    const bool wave_on = row - r < (BANK ? end : P.rows);                    // idle waves still stage and take the barriers
+    const long long row = ROUTE ? rrow : (BANK ? first : 0) + ((long long)blockIdx.x * kWaves + wave) * 32 + r;
+    const bool wave_on = ROUTE ? ron : row - r < (BANK ? end : P.rows);      // idle waves still stage and take the barriers
 
     const int n1 = (P.in_dim + 63) >> 6;                    // layer-1 chunks: as long as the row
     const int c_out = n1 + 2 * G::KC;                       // the output chunk, the last of the stream
@@ -38,6 +60,7 @@ POLICY_WIDE_KERNEL(const WideParams P, const void *__restrict__ obs_, float *__r
         const bf8 *src = ((X3 && (s & 1)) ? P.lo : P.hi) + (size_t)c * G::CH;
         // the member's two streams: 2 * (c_out + 1) chunk slots behind the previous member's
         if constexpr (BANK) src += (size_t)blockIdx.y * 2 * (size_t)(c_out + 1) * G::CH;
+        if constexpr (ROUTE) src += (size_t)rmember * 2 * (size_t)(c_out + 1) * G::CH;
         const int n = pieces_of(c);
 #pragma unroll
         for (int k = 0; k < G::PRE; ++k) { const int q = tid + k * kThreads; if (q < n) pre[k] = src[q]; }
@@ -53,7 +76,7 @@ POLICY_WIDE_KERNEL(const WideParams P, const void *__restrict__ obs_, float *__r
     // this lane's observation row; 64 columns (4 k-steps) at a time: the raw values of the next TWO layer-1 chunks are in
     // flight, even chunks in xa and odd chunks in xo (one chunk ahead left fp32 rows waiting: 175 us instead of 87 us for bf16
     // rows at (192,180,2))
-    const size_t xoff = (size_t)(BANK ? (row < end ? row : end - 1) : (row < P.rows ? row : P.rows - 1)) * P.in_dim;
+    const size_t xoff = (size_t)(ROUTE ? row : BANK ? (row < end ? row : end - 1) : (row < P.rows ? row : P.rows - 1)) * P.in_dim;
     const float *x32 = static_cast<const float *>(obs_) + xoff;
     const __bf16 *x16 = static_cast<const __bf16 *>(obs_) + xoff;
     // (the bf16 instantiations of MT = 6 on fp32 rows keep ONE chunk in flight, in xa alone: two waves per SIMD leave no
@@ -227,5 +250,5 @@ POLICY_WIDE_KERNEL(const WideParams P, const void *__restrict__ obs_, float *__r
             ++s;
         }
     }
-    if (wave_on && h == 0 && row < (BANK ? end : P.rows)) finish_row<LOGPI>(P, acc[0], row, act, log_pi, logpi_c);
+    if (wave_on && h == 0 && (ROUTE ? rlive : row < (BANK ? end : P.rows))) finish_row<LOGPI>(P, acc[0], row, act, log_pi, logpi_c);
 }

@@ -229,7 +229,14 @@ int check_policy_ring(const char *who, const swarm_env_info &ei, const swarm_pol
     }
     if (pi.act_dim != 2) return fail(SWARM_ERR_INVALID, "policy act_dim must be 2 (the env's action)", who);
     if (ei.obs_dtype == SWARM_BF16 && (pi.in_dim & 7)) return fail(SWARM_ERR_INVALID, "bf16 observation rows need obs_dim % 8 == 0", who);
-    if (ei.n_env % pi.members != 0) {                                       // a bank: a member owns whole envs
+    if (pi.route_n_env > 0) {                                               // a routed bank: the route must be this env handle's
+        if (pi.route_n_env != ei.n_env || pi.route_rows_per_env != ei.n_agents) {
+            char msg[256];
+            std::snprintf(msg, sizeof msg, "the policy bank's route is for n_env %d x rows_per_env %d, the env handle has n_env %d x n_agents %d "
+                          "(swarm_policy_bank_route)", pi.route_n_env, pi.route_rows_per_env, ei.n_env, ei.n_agents);
+            return fail(SWARM_ERR_INVALID, msg, who);
+        }
+    } else if (ei.n_env % pi.members != 0) {                                // a bank: a member owns whole envs
         char msg[256];
         std::snprintf(msg, sizeof msg, "n_env %d is no multiple of the policy bank's members %d (a member acts for whole envs)",
                       ei.n_env, pi.members);

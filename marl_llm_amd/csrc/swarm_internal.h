@@ -167,6 +167,7 @@ SWARM_HIDDEN int swarm_internal_metrics_step(swarm_env_t *h, double *out);
 struct swarm_policy_info {
     int device, in_dim, act_dim;
     int members;                        // 1, or the members of a bank (swarm_policy_bank_create)
+    int route_n_env, route_rows_per_env;    // the route in force (swarm_policy_bank_route); 0, 0: none
 };
 SWARM_HIDDEN int swarm_internal_policy_info(const swarm_policy_t *p, swarm_policy_info *out);
 

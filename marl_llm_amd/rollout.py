@@ -9,6 +9,7 @@ ring buffer (train_assembly.py:91-111, maddpg.py:72-87, agents.py:69-96, buffer_
 * `FusedPolicy`   -- the same forward as one hand-written bf16-MFMA kernel (csrc/policy_mlp.hip) for the rollout.
 * `FusedPolicyBank` -- M actors of one shape in one handle and one launch: env group m of a batch acts with member m
                      (checkpoints of a run, seeds of a sweep, a population of learners); a FusedPolicy to every loop below.
+                     `assign(member_of_env, N)` routes it by env instead: a device table names each env's member.
 * `DeviceReplay`  -- the ring buffer of buffer_agent.py:13-128 with one row per (env, agent) transition, as device tensors.
 * `ChainedReplay` -- the same transitions stored as a ring of env steps that share observation rows (half the copy per push).
 * `rollout`       -- obs -> policy -> exploration noise (agents.py:82-96 continuous branch) -> env.step_tensor -> push.
@@ -207,11 +208,16 @@ class FusedPolicyBank(FusedPolicy):
     modules: the members, each with fc1..fc4 of the same shapes (ValueError otherwise, before any library call).
     precision, wide: as FusedPolicy, for all members; wide=None picks the geometry by FusedPolicy's rule.
     `.members` = M, `.modules` the list; `refresh()` builds a new handle from host copies of all members; `sync(member=None)`
-    loads the device parameters of one member, or of all (one packing launch each), in stream order."""
+    loads the device parameters of one member, or of all (one packing launch each), in stream order.
+
+    Routing by env (swarm_policy_bank_route): `assign(member_of_env, rows_per_env)` puts a table in force that names the member
+    of every env -- unequal groups, any order, -1 for an env nobody serves, E % M free; `assign(None)` ends it.  The loops take
+    the routed bank unchanged; `routing()` reads back what the routing kernel built."""
 
     def __init__(self, modules, device="cuda:0", precision="bf16", wide=None):
         self.modules = list(modules)
         self.members = len(self.modules)
+        self._route = None              # (int32 device table [E], rows_per_env) of the assignment in force
         _bank_shape(self.modules)
         super().__init__(self.modules[0], device=device, precision=precision, wide=wide)
 
@@ -232,6 +238,86 @@ class FusedPolicyBank(FusedPolicy):
         self.handle = h
         if self.lib.swarm_policy_set_precision(self.handle, 1 if self.precision == "bf16x3" else 0) != 0:
             raise RuntimeError("swarm_policy_set_precision failed: " + self.lib.swarm_policy_last_error().decode())
+        if self._route is not None:                           # the assignment in force, for the new handle
+            self._enqueue_route(*self._route)
+
+    def _enqueue_route(self, table, rows_per_env):
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self.lib.swarm_policy_bank_route(self.handle, self._ctypes.c_void_p(table.data_ptr()), int(table.numel()), int(rows_per_env),
+                                              self._ctypes.c_void_p(stream))
+        if rc != 0:
+            if rc == 2:                                       # a HIP error ends the route in the library (swarm_policy.h)
+                self._route = None
+            raise RuntimeError("swarm_policy_bank_route failed: " + self.lib.swarm_policy_last_error().decode())
+
+    def assign(self, member_of_env, rows_per_env=None, n_env=None):
+        """Route the bank by env (swarm_policy_bank_route, include/swarm_policy.h): env e acts with member member_of_env[e],
+        every env being `rows_per_env` consecutive rows (the env's agents N).  The route goes on torch's current stream: a
+        forward or rollout enqueued before the call uses the previous assignment, one enqueued after it the new one.
+        With a DEVICE table the call is enqueue only (after the first assignment, which allocates).  With a HOST array it is
+        not: the copy of the array to the device is a pageable-memory copy on that stream, and the host waits in it for the
+        work the stream still holds -- re-assign from a device table where the host must not stall.
+        member_of_env:
+          * a host int array / sequence [E], entries in [-1, M) (-1: an env nobody serves -- its action rows are not written):
+            checked here (ValueError before any library call), then copied into an int32 device tensor the bank owns;
+          * a contiguous int32 cuda tensor [E] on the bank's device: used as it is, read when the routing kernel runs (writes
+            enqueued on the stream before are seen; entries outside [0, M) are unserved) and not read again afterwards: the
+            caller keeps it alive until then, and rewriting it later changes nothing until the next assign() -- or refresh(),
+            which routes the new handle from what the tensor then holds;
+          * None: ends the route -- equal contiguous groups again.
+        n_env (optional): the E the caller expects -- the env batch's -- so that a table of another length is a ValueError
+        here and not a refusal of the next rollout.  Anything else: ValueError."""
+        if member_of_env is None:
+            rc = self.lib.swarm_policy_bank_route(self.handle, None, 0, 0, None)
+            if rc != 0:
+                raise RuntimeError("swarm_policy_bank_route failed: " + self.lib.swarm_policy_last_error().decode())
+            self._route = None
+            return
+        if rows_per_env is None or int(rows_per_env) != rows_per_env or int(rows_per_env) < 1:
+            raise ValueError("assign(): rows_per_env must be a positive int (the rows of one env: its agents)")
+        if isinstance(member_of_env, torch.Tensor):
+            t = member_of_env
+            if t.device.type != "cpu":
+                if t.dtype != torch.int32 or t.dim() != 1 or t.numel() < 1 or not t.is_contiguous() or t.device != self.device:
+                    raise ValueError("assign(): a device table must be a contiguous int32 tensor [E] on %s" % (self.device,))
+                table = t
+            else:
+                member_of_env = t.numpy()
+                table = None
+        else:
+            table = None
+        if table is None:
+            a = np.asarray(member_of_env)
+            if a.ndim != 1 or a.size < 1 or a.dtype.kind not in "iu":
+                raise ValueError("assign(): member_of_env must be an int array [E] (or an int32 cuda tensor, or None)")
+            if a.min() < -1 or a.max() >= self.members:
+                raise ValueError("assign(): entries must lie in [-1, %d) (-1: an env nobody serves); got [%d, %d]"
+                                 % (self.members, int(a.min()), int(a.max())))
+        E = int(a.size if table is None else table.numel())
+        if n_env is not None and E != int(n_env):
+            raise ValueError("assign(): the table has %d entries, n_env is %d" % (E, int(n_env)))
+        if E * int(rows_per_env) >= 2 ** 31:
+            raise ValueError("assign(): E * rows_per_env = %d * %d reaches 2^31 rows" % (E, int(rows_per_env)))
+        if table is None:
+            table = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+        self._enqueue_route(table, int(rows_per_env))
+        self._route = (table, int(rows_per_env))
+
+    def routing(self):
+        """(counts [M], unserved, env_order) of the assignment in force, as the routing kernel built them
+        (swarm_policy_bank_route_read; waits for torch's current stream): envs per member, the number of envs nobody
+        serves, and the served envs in the order the kernel serves them -- by member, ascending env inside a member (numpy's
+        stable argsort of the table over the served envs).  None without an assignment."""
+        if self._route is None:
+            return None
+        E = self._route[0].numel()
+        counts, order, unserved = np.zeros(self.members, np.int32), np.zeros(E, np.int32), self._ctypes.c_int32(0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self.lib.swarm_policy_bank_route_read(self.handle, counts.ctypes.data, self._ctypes.addressof(unserved), order.ctypes.data,
+                                                   self._ctypes.c_void_p(stream))
+        if rc != E:
+            raise RuntimeError("swarm_policy_bank_route_read returned %d: %s" % (rc, self.lib.swarm_policy_last_error().decode()))
+        return counts, int(unserved.value), order[:E - int(unserved.value)]
 
     def sync(self, member=None):
         """FusedPolicy.sync() for member `member` (its module's current device parameters into its slice of the handle; the
@@ -262,14 +348,26 @@ class FusedPolicyBank(FusedPolicy):
                 raise RuntimeError("swarm_policy_bank_load_device failed: " + self.lib.swarm_policy_last_error().decode())
 
     def __call__(self, obs, out=None, noise_scale=0.0, seed=0, step=0, log_pi=None, row_offset=0):
-        """FusedPolicy.__call__ over rows that are a multiple of the members: rows [m R, (m + 1) R) by member m."""
-        if isinstance(obs, torch.Tensor) and obs.shape[-1] == self.in_dim and (obs.numel() // self.in_dim) % self.members != 0:
+        """FusedPolicy.__call__ over rows that are a multiple of the members: rows [m R, (m + 1) R) by member m.  Under an
+        assignment (`assign`): over its E * rows_per_env rows, the rows of env e by member member_of_env[e] (the library refuses
+        another row count)."""
+        if (self._route is None and isinstance(obs, torch.Tensor) and obs.shape[-1] == self.in_dim
+                and (obs.numel() // self.in_dim) % self.members != 0):
             raise ValueError("FusedPolicyBank: rows %d is no multiple of the %d members" % (obs.numel() // self.in_dim, self.members))
         return super().__call__(obs, out=out, noise_scale=noise_scale, seed=seed, step=step, log_pi=log_pi, row_offset=row_offset)
 
     def member_of_env(self, E):
-        """[E] int64: the member env e acts with, e // (E / M)."""
+        """[E] int64: the member env e acts with.  Under an assignment (`assign`): what the routing kernel READ, rebuilt from
+        `routing()` (it waits for torch's current stream) -- not the table tensor, which its owner may have rewritten since;
+        -1: nobody.  Otherwise e // (E / M)."""
         E = int(E)
+        if self._route is not None:
+            if self._route[0].numel() != E:
+                raise ValueError("member_of_env: the assignment in force is for %d envs, not %d" % (self._route[0].numel(), E))
+            counts, _, order = self.routing()
+            a = np.full(E, -1, np.int64)
+            a[order] = np.repeat(np.arange(self.members, dtype=np.int64), counts)
+            return a
         if E < 1 or E % self.members != 0:
             raise ValueError("member_of_env: E = %d is no positive multiple of the %d members" % (E, self.members))
         return np.arange(E, dtype=np.int64) // (E // self.members)
