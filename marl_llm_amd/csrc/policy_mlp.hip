@@ -135,8 +135,6 @@ __device__ __forceinline__ unsigned pack_bf16(float f)
     return u >> 16;
 }
 
-// (A template, launched through launch_pack at the end of the file, only so that the compiler emits it behind the
-// k_policy_mlp instantiations: their code, local labels included, stays what it was -- tools/isa_diff.py.)
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) k_policy_pack(const PackParams P)
 {
@@ -172,70 +170,18 @@ __global__ void __launch_bounds__(THREADS) k_policy_pack(const PackParams P)
     P.lo[q] = make_uint4(lv[0] | lv[1] << 16, lv[2] | lv[3] << 16, lv[4] | lv[5] << 16, lv[6] | lv[7] << 16);
 }
 
-uint16_t bf16_rne(float f)
-{
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (uint16_t)((u >> 16) | 0x40);   // NaN
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
 thread_local std::string g_policy_error;
 
-// The instantiations a (precision, TPW) choice launches, with and without log-pi.
-template <bool IN_BF16, int TPW, bool X3>
-void launch_policy(const dim3 &g, const dim3 &b, hipStream_t st, const MlpParams &q, const void *obs, float *act, float *log_pi,
-                   float logpi_c)
-{
-    if (log_pi) hipLaunchKernelGGL((k_policy_mlp<IN_BF16, TPW, X3, true>), g, b, kSmemBytes, st, q, obs, act, log_pi, logpi_c);
-    else hipLaunchKernelGGL((k_policy_mlp<IN_BF16, TPW, X3, false>), g, b, kSmemBytes, st, q, obs, act, nullptr, 0.0f);
-}
-
-template <bool IN_BF16, int TPW, bool X3>
-void set_smem()
-{
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<IN_BF16, TPW, X3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp<IN_BF16, TPW, X3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-}
-
-template <int THREADS>
-void launch_pack(const PackParams &q, hipStream_t st)
-{
-    const unsigned grid = (kPackPieces + kPackBias + THREADS - 1) / THREADS;
-    hipLaunchKernelGGL(k_policy_pack<THREADS>, dim3(grid), dim3(THREADS), 0, st, q);
-}
-
-// The same for a bank handle (behind the plain handle's templates, so that their instantiations come first as before).
-template <bool IN_BF16, bool X3>
-void launch_bank(const dim3 &g, const dim3 &b, hipStream_t st, const MlpParams &q, const void *obs, float *act, float *log_pi, float logpi_c)
-{
-    if (log_pi) hipLaunchKernelGGL((k_policy_mlp_bank<IN_BF16, 1, X3, true>), g, b, kSmemBytes, st, q, obs, act, log_pi, logpi_c);
-    else hipLaunchKernelGGL((k_policy_mlp_bank<IN_BF16, 1, X3, false>), g, b, kSmemBytes, st, q, obs, act, nullptr, 0.0f);
-}
-
-template <bool IN_BF16, bool X3>
-void set_smem_bank()
-{
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp_bank<IN_BF16, 1, X3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp_bank<IN_BF16, 1, X3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-}
-
-// The same for a bank under a route (behind the bank's, for the same reason).
-template <bool IN_BF16, bool X3>
-void launch_route(const dim3 &g, const dim3 &b, hipStream_t st, const MlpParams &q, const void *obs, float *act, float *log_pi, float logpi_c,
-                  const swarm_wide::RouteView &rv)
-{
-    if (log_pi) hipLaunchKernelGGL((k_policy_mlp_route<IN_BF16, 1, X3, true>), g, b, kSmemBytes, st, q, obs, act, log_pi, logpi_c, rv);
-    else hipLaunchKernelGGL((k_policy_mlp_route<IN_BF16, 1, X3, false>), g, b, kSmemBytes, st, q, obs, act, nullptr, 0.0f, rv);
-}
-
-template <bool IN_BF16, bool X3>
-void set_smem_route()
-{
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp_route<IN_BF16, 1, X3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_mlp_route<IN_BF16, 1, X3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmemBytes);
-}
+// The kernels a forward call chooses from, per kernel text: [x3][in_bf16][log_pi]; the two-tile measurement instantiations
+// (SWARM_POLICY_TPW=2: plain handles at bf16 only) are a table of their own, [in_bf16][log_pi].
+using MlpKernel = void (*)(MlpParams, const void *, float *, float *, float);
+using MlpRouteKernel = void (*)(MlpParams, const void *, float *, float *, float, swarm_wide::RouteView);
+#define MLP_KERNELS(K, TPW, X3) {{K<false, TPW, X3, false>, K<false, TPW, X3, true>}, {K<true, TPW, X3, false>, K<true, TPW, X3, true>}}
+const MlpKernel kPlain[2][2][2] = {MLP_KERNELS(k_policy_mlp, 1, false), MLP_KERNELS(k_policy_mlp, 1, true)};
+const MlpKernel kPlainTpw2[2][2] = MLP_KERNELS(k_policy_mlp, 2, false);
+const MlpKernel kBank[2][2][2] = {MLP_KERNELS(k_policy_mlp_bank, 1, false), MLP_KERNELS(k_policy_mlp_bank, 1, true)};
+const MlpRouteKernel kRoute[2][2][2] = {MLP_KERNELS(k_policy_mlp_route, 1, false), MLP_KERNELS(k_policy_mlp_route, 1, true)};
+#undef MLP_KERNELS
 
 // ---- swarm_policy_bank_route's kernel: the route's tables from member_of_env, for both geometries.
 // One workgroup.  Wave 0 walks the envs twice in blocks of 64, one env per lane: a lane's key is its env's member, `members`
@@ -333,11 +279,6 @@ __global__ void __launch_bounds__(THREADS) k_policy_route_table(const RouteTable
     }
 }
 
-template <int THREADS>
-void launch_route_table(const RouteTableParams &q, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_policy_route_table<THREADS>, dim3(1), dim3(THREADS), 0, st, q);
-}
 constexpr int kRouteThreads = 256;
 
 // The blob of one actor as swarm_policy_create uploads it (and a bank holds once per member): [w1 | w2 | w3 | w4] fragments
@@ -347,6 +288,15 @@ constexpr size_t kHidElems = (size_t)kMT * kKS * kFrag, kOutElems = (size_t)kKS 
 constexpr size_t kWElems = 3 * kHidElems + kOutElems;
 constexpr size_t kBlobBytes = 2 * kWElems * 2 + (3 * kKP + 32) * 4;           // high parts, low parts, biases
 static_assert(kBlobBytes == kMemberPieces * 16 && kWElems / 8 == (size_t)kPackPieces && kPackBias == 3 * kKP + 32, "a member's blob is whole pieces");
+
+uint16_t bf16_rne(float f)
+{
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (uint16_t)((u >> 16) | 0x40);   // NaN
+    u += 0x7FFFu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
 
 std::vector<unsigned char> pack_host(const float *const w[8], int in_dim, int hidden, int act_dim)
 {
@@ -418,15 +368,15 @@ void point_params(MlpParams &p, const unsigned char *base, int in_dim, int act_d
 struct SWARM_HIDDEN swarm_policy {     // hidden: its implicit destructor must not become an exported weak symbol
     int device, in_dim, hidden, act_dim;
     int precision = 0;             // 0 = bf16 (default), 1 = bf16x3
-    swarm_internal::DevBuf<unsigned char> d_blob;     // the packed weights and biases p points into
+    // the packed weights and biases of either geometry: `members` blobs of blob_bytes each, one behind the other
+    swarm_internal::DevBuf<unsigned char> d_blob;
     size_t blob_bytes = 0;
-    MlpParams p;
-    bool smem_set = false;
-    swarm_wide::Handle *wide = nullptr;    // swarm_policy_create_wide: the handle runs csrc/policy_wide.hip; d_blob and p stay empty
-    // swarm_policy_bank_create: `members` blobs of blob_bytes each, one behind the other (d_blob, or the wide handle's); p points
-    // into the first.  A bank handle runs the BANK kernels, also with one member.
-    bool bank = false;
     int members = 1;
+    bool wide = false;             // the handle runs csrc/policy_wide.hip on the stream layout `wl`; p stays empty
+    swarm_wide::Layout wl{};
+    MlpParams p{};                 // the narrow kernel's pointers into the first member's blob
+    bool smem_set = false;
+    bool bank = false;             // swarm_policy_bank_create: the handle runs the BANK kernels, also with one member
     // swarm_policy_bank_route: the route in force (n_env == 0: none) and its tables, one allocation of int32 words cut for
     // cap_rows rows: [counts: SWARM_POLICY_BANK_MAX + 1][env_order: cap_rows][tile table per tile size: 4 words an entry].
     // The narrow geometry keeps two tile tables (128 rows a workgroup at bf16, 256 at bf16x3: swarm_policy_set_precision may
@@ -443,7 +393,7 @@ struct SWARM_HIDDEN swarm_policy {     // hidden: its implicit destructor must n
             return (unsigned)(rows / t_rows[g] + (members < n_env ? members : n_env));
         }
     } route;
-    ~swarm_policy() { swarm_wide::destroy(wide); }
+    unsigned char *member_blob(int member) const { return d_blob.get() + (size_t)member * blob_bytes; }
 };
 
 int swarm_internal_policy_info(const swarm_policy_t *p, swarm_policy_info *out)
@@ -456,24 +406,75 @@ int swarm_internal_policy_info(const swarm_policy_t *p, swarm_policy_info *out)
 
 namespace {
 
+// A fresh allocation filled from host memory on a stream of its own, waited for here: no null-stream work
+// (tests/test_stream_sources.py), complete on return.
+hipError_t upload(swarm_internal::DevBuf<unsigned char> &dst, const std::vector<unsigned char> &src)
+{
+    hipStream_t up = nullptr;
+    hipError_t e = dst.alloc(src.size());
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(dst.get(), src.data(), src.size(), hipMemcpyHostToDevice, up);
+    if (e == hipSuccess) e = hipStreamSynchronize(up);
+    if (up) (void)hipStreamDestroy(up);
+    return e;
+}
+
+// What the three creation entry points share.  w[8 m + i]: fc1.weight, fc1.bias, ..., fc4.bias of member m (fp32, HOST); the
+// entry point `who` has checked `out`, the table and its own arguments.  Here: the shape, the device, then every member's blob
+// from the same host packer, one behind the other.
+int create_handle(const char *who, const float *const *w, int members, int in_dim, int hidden, int act_dim, bool wide, bool bank,
+                  int device, swarm_policy_t **out)
+{
+    const std::string pre = std::string(who) + ": ";
+    if (wide ? !swarm_wide::shape_ok(in_dim, hidden, act_dim) : !narrow_shape_ok(in_dim, hidden, act_dim)) {
+        g_policy_error = pre + "supported shapes " + (!bank ? "" : wide ? "of the wide geometry " : "of the narrow geometry ") + "are " +
+                         (wide ? "in_dim <= 384 (multiple of 4), hidden <= 256, act_dim <= 4" : "in_dim <= 192 (multiple of 4), hidden <= 191, act_dim <= 4");
+        return SWARM_POLICY_ERR_INVALID;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_policy_error = pre + "no HIP device (there is no CPU path)"; return SWARM_POLICY_ERR_HIP; }
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    const DeviceGuard guard(device < ndev ? device : -1);       // -1 is no device: !ok
+    if (!guard.ok) { g_policy_error = pre + "bad device"; return SWARM_POLICY_ERR_HIP; }
+    swarm_policy *p = new (std::nothrow) swarm_policy;
+    if (!p) { g_policy_error = pre + "out of memory"; return SWARM_POLICY_ERR_INVALID; }
+    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim;
+    p->wide = wide; p->bank = bank; p->members = members;
+    if (wide) p->wl = swarm_wide::layout_of(in_dim, hidden, act_dim);
+    std::vector<unsigned char> blob;
+    for (int m = 0; m < members; ++m) {
+        const std::vector<unsigned char> one = wide ? swarm_wide::pack_host(p->wl, w + 8 * m) : pack_host(w + 8 * m, in_dim, hidden, act_dim);
+        if (m == 0) { p->blob_bytes = one.size(); blob.reserve((size_t)members * one.size()); }
+        blob.insert(blob.end(), one.begin(), one.end());
+    }
+    if (upload(p->d_blob, blob) != hipSuccess) {
+        delete p;
+        g_policy_error = pre + "device allocation / upload failed";
+        return SWARM_POLICY_ERR_HIP;
+    }
+    if (!wide) point_params(p->p, p->d_blob.get(), in_dim, act_dim);
+    *out = p;
+    return SWARM_POLICY_OK;
+}
+
 // The packing launch of swarm_policy_load_device / swarm_policy_bank_load_device: member `member`'s slice of the blob.
 int load_member(const char *who, swarm_policy_t *p, int member, const float *const w[8], void *stream)
 {
     const DeviceGuard guard(p->device);
     if (!guard.ok) { g_policy_error = std::string(who) + ": hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
-    if (p->wide) {
-        const int rc = swarm_wide::load_device(p->wide, member, w, static_cast<hipStream_t>(stream), g_policy_error);
-        if (rc != SWARM_POLICY_OK) g_policy_error = std::string(who) + ": " + g_policy_error;
-        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (p->wide) swarm_wide::load_device(p->wl, p->member_blob(member), w, st);
+    else {
+        static_assert(kPackPieces % 64 == 0 && sizeof(bf8) == sizeof(uint4), "one 16-byte piece per fragment lane");
+        PackParams q;
+        q.w1 = w[0]; q.b1 = w[1]; q.w2 = w[2]; q.b2 = w[3]; q.w3 = w[4]; q.b3 = w[5]; q.w4 = w[6]; q.b4 = w[7];
+        q.hi = reinterpret_cast<uint4 *>(p->member_blob(member));
+        q.lo = q.hi + kPackPieces;
+        q.bias = reinterpret_cast<float *>(q.lo + kPackPieces);
+        q.in_dim = p->in_dim; q.hidden = p->hidden; q.act_dim = p->act_dim;
+        const unsigned grid = (kPackPieces + kPackBias + kPackThreads - 1) / kPackThreads;
+        hipLaunchKernelGGL(k_policy_pack<kPackThreads>, dim3(grid), dim3(kPackThreads), 0, st, q);
     }
-    static_assert(kPackPieces % 64 == 0 && sizeof(bf8) == sizeof(uint4), "one 16-byte piece per fragment lane");
-    PackParams q;
-    q.w1 = w[0]; q.b1 = w[1]; q.w2 = w[2]; q.b2 = w[3]; q.w3 = w[4]; q.b3 = w[5]; q.w4 = w[6]; q.b4 = w[7];
-    q.hi = reinterpret_cast<uint4 *>(p->d_blob.get() + (size_t)member * p->blob_bytes);
-    q.lo = q.hi + kPackPieces;
-    q.bias = reinterpret_cast<float *>(q.lo + kPackPieces);
-    q.in_dim = p->in_dim; q.hidden = p->hidden; q.act_dim = p->act_dim;
-    launch_pack<kPackThreads>(q, static_cast<hipStream_t>(stream));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { g_policy_error = std::string(who) + ": " + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
     return SWARM_POLICY_OK;
@@ -487,9 +488,7 @@ int64_t read_member(const char *who, swarm_policy_t *p, int member, void *host_d
     const DeviceGuard guard(p->device);
     if (!guard.ok) { g_policy_error = std::string(who) + ": hipSetDevice failed"; return -SWARM_POLICY_ERR_HIP; }
     hipStream_t st = static_cast<hipStream_t>(stream);          // the copy on the stream, behind the loads enqueued there; then the wait
-    size_t unused;
-    const unsigned char *src = p->wide ? static_cast<const unsigned char *>(swarm_wide::blob(p->wide, &unused)) : p->d_blob.get();
-    hipError_t e = hipMemcpyAsync(host_dst, src + (size_t)member * p->blob_bytes, p->blob_bytes, hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(host_dst, p->member_blob(member), p->blob_bytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { g_policy_error = std::string(who) + ": " + hipGetErrorString(e); return -SWARM_POLICY_ERR_HIP; }
     return bytes;
@@ -507,31 +506,8 @@ int swarm_policy_create(const float *w1, const float *b1, const float *w2, const
     if (!out) return SWARM_POLICY_ERR_INVALID;
     *out = nullptr;
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_create: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
-    if (in_dim < 4 || in_dim > kKP || (in_dim & 3) || hidden < 1 || hidden >= kKP || act_dim < 1 || act_dim > 4) {
-        g_policy_error = "swarm_policy_create: supported shapes are in_dim <= 192 (multiple of 4), hidden <= 191, act_dim <= 4";
-        return SWARM_POLICY_ERR_INVALID;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_policy_error = "swarm_policy_create: no HIP device (there is no CPU path)"; return SWARM_POLICY_ERR_HIP; }
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    const DeviceGuard guard(device < ndev ? device : -1);       // -1 is no device: !ok
-    if (!guard.ok) { g_policy_error = "swarm_policy_create: bad device"; return SWARM_POLICY_ERR_HIP; }
-
     const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
-    const std::vector<unsigned char> blob = pack_host(w, in_dim, hidden, act_dim);
-    const size_t bytes = blob.size();
-
-    swarm_policy *p = new (std::nothrow) swarm_policy;
-    if (!p) return SWARM_POLICY_ERR_INVALID;
-    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim; p->blob_bytes = bytes;
-    if (p->d_blob.alloc(bytes) != hipSuccess || hipMemcpy(p->d_blob.get(), blob.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        delete p;
-        g_policy_error = "swarm_policy_create: device allocation / upload failed";
-        return SWARM_POLICY_ERR_HIP;
-    }
-    point_params(p->p, p->d_blob.get(), in_dim, act_dim);
-    *out = p;
-    return SWARM_POLICY_OK;
+    return create_handle("swarm_policy_create", w, 1, in_dim, hidden, act_dim, false, false, device, out);
 }
 
 int swarm_policy_create_wide(const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
@@ -540,24 +516,8 @@ int swarm_policy_create_wide(const float *w1, const float *b1, const float *w2, 
     if (!out) return SWARM_POLICY_ERR_INVALID;
     *out = nullptr;
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) { g_policy_error = "swarm_policy_create_wide: null weight pointer"; return SWARM_POLICY_ERR_INVALID; }
-    if (!swarm_wide::shape_ok(in_dim, hidden, act_dim)) {
-        g_policy_error = "swarm_policy_create_wide: supported shapes are in_dim <= 384 (multiple of 4), hidden <= 256, act_dim <= 4";
-        return SWARM_POLICY_ERR_INVALID;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_policy_error = "swarm_policy_create_wide: no HIP device (there is no CPU path)"; return SWARM_POLICY_ERR_HIP; }
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    const DeviceGuard guard(device < ndev ? device : -1);       // -1 is no device: !ok
-    if (!guard.ok) { g_policy_error = "swarm_policy_create_wide: bad device"; return SWARM_POLICY_ERR_HIP; }
-    swarm_policy *p = new (std::nothrow) swarm_policy;
-    if (!p) return SWARM_POLICY_ERR_INVALID;
-    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim;
     const float *const w[8] = {w1, b1, w2, b2, w3, b3, w4, b4};
-    const int rc = swarm_wide::create(w, 1, in_dim, hidden, act_dim, &p->wide, g_policy_error);
-    if (rc != SWARM_POLICY_OK) { delete p; g_policy_error = "swarm_policy_create_wide: " + g_policy_error; return rc; }
-    (void)swarm_wide::blob(p->wide, &p->blob_bytes);
-    *out = p;
-    return SWARM_POLICY_OK;
+    return create_handle("swarm_policy_create_wide", w, 1, in_dim, hidden, act_dim, true, false, device, out);
 }
 
 int swarm_policy_bank_create(const float *const *w, int members, int in_dim, int hidden, int act_dim, int wide, int device,
@@ -576,49 +536,7 @@ int swarm_policy_bank_create(const float *const *w, int members, int in_dim, int
             g_policy_error = "swarm_policy_bank_create: null weight pointer (member " + std::to_string(i / 8) + ", array " + std::to_string(i % 8) + ")";
             return SWARM_POLICY_ERR_INVALID;
         }
-    if (wide ? !swarm_wide::shape_ok(in_dim, hidden, act_dim) : !narrow_shape_ok(in_dim, hidden, act_dim)) {
-        g_policy_error = wide ? "swarm_policy_bank_create: supported shapes of the wide geometry are in_dim <= 384 (multiple of 4), hidden <= 256, act_dim <= 4"
-                              : "swarm_policy_bank_create: supported shapes of the narrow geometry are in_dim <= 192 (multiple of 4), hidden <= 191, act_dim <= 4";
-        return SWARM_POLICY_ERR_INVALID;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_policy_error = "swarm_policy_bank_create: no HIP device (there is no CPU path)"; return SWARM_POLICY_ERR_HIP; }
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    const DeviceGuard guard(device < ndev ? device : -1);       // -1 is no device: !ok
-    if (!guard.ok) { g_policy_error = "swarm_policy_bank_create: bad device"; return SWARM_POLICY_ERR_HIP; }
-    swarm_policy *p = new (std::nothrow) swarm_policy;
-    if (!p) { g_policy_error = "swarm_policy_bank_create: out of memory"; return SWARM_POLICY_ERR_INVALID; }
-    p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->act_dim = act_dim; p->bank = true; p->members = members;
-    if (wide) {
-        const int rc = swarm_wide::create(w, members, in_dim, hidden, act_dim, &p->wide, g_policy_error);
-        if (rc != SWARM_POLICY_OK) { delete p; g_policy_error = "swarm_policy_bank_create: " + g_policy_error; return rc; }
-        (void)swarm_wide::blob(p->wide, &p->blob_bytes);
-        *out = p;
-        return SWARM_POLICY_OK;
-    }
-    // every member's slice is the blob swarm_policy_create builds from the same arrays: the same packer, M times
-    std::vector<unsigned char> blob;
-    blob.reserve((size_t)members * kBlobBytes);
-    for (int m = 0; m < members; ++m) {
-        const std::vector<unsigned char> one = pack_host(w + 8 * m, in_dim, hidden, act_dim);
-        blob.insert(blob.end(), one.begin(), one.end());
-    }
-    p->blob_bytes = kBlobBytes;
-    // the upload on a stream of its own, waited for here: no null-stream work, complete on return
-    hipStream_t up = nullptr;
-    hipError_t e = p->d_blob.alloc(blob.size());
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_blob.get(), blob.data(), blob.size(), hipMemcpyHostToDevice, up);
-    if (e == hipSuccess) e = hipStreamSynchronize(up);
-    if (up) (void)hipStreamDestroy(up);
-    if (e != hipSuccess) {
-        delete p;
-        g_policy_error = "swarm_policy_bank_create: device allocation / upload failed";
-        return SWARM_POLICY_ERR_HIP;
-    }
-    point_params(p->p, p->d_blob.get(), in_dim, act_dim);
-    *out = p;
-    return SWARM_POLICY_OK;
+    return create_handle("swarm_policy_bank_create", w, members, in_dim, hidden, act_dim, wide != 0, true, device, out);
 }
 
 int swarm_policy_bank_members(const swarm_policy_t *p) { return p ? p->members : 0; }
@@ -651,71 +569,50 @@ static int policy_forward(swarm_policy_t *p, const void *obs, bool in_bf16, int6
     if (rows == 0) return SWARM_POLICY_OK;
     const DeviceGuard guard(p->device);
     if (!guard.ok) { g_policy_error = "swarm_policy_forward: hipSetDevice failed"; return SWARM_POLICY_ERR_HIP; }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool x3 = p->precision == 1, lp = log_pi != nullptr;
     // a route in force: the tile table of this launch's rows per workgroup (policy_wide.h RouteView)
-    const int rg = (!p->wide && p->precision == 1) ? 1 : 0;
+    const int rg = (!p->wide && x3) ? 1 : 0;
     const swarm_wide::RouteView rv = {routed ? reinterpret_cast<const int4 *>(p->route.d_tab.get() + p->route.off_tiles[rg]) : nullptr,
                                       routed ? p->route.d_tab.get() + p->route.off_order : nullptr, p->route.rows_per_env};
-    if (p->wide) {                                          // a wide handle: its own kernel, SWARM_POLICY_TPW not read
-        const swarm_wide::ForwardArgs a = {obs, in_bf16, rows, act, log_pi, noise_scale, seed, step, row_offset, p->precision,
-                                           static_cast<hipStream_t>(stream), p->bank, routed ? &rv : nullptr,
-                                           routed ? p->route.grid(rg, p->members) : 0u};
-        return swarm_wide::forward(p->wide, a, g_policy_error);
-    }
-    MlpParams q = p->p;
-    q.rows = rows;
-    q.noise_scale = noise_scale > 0.0f ? noise_scale : 0.0f;
-    q.noise_key = swarm_noise_key(seed, step);
-    q.row_offset = row_offset;
-    // log-pi's constant act_dim * log(noise_scale * sqrt(2 pi)), in double from the fp32 scale the kernel uses (swarm_policy.h)
-    const float logpi_c = q.noise_scale > 0.0f ? (float)((double)p->act_dim * std::log((double)q.noise_scale * std::sqrt(2.0 * M_PI))) : 0.0f;
-    // one row tile per wave; the two-tile instantiation (SWARM_POLICY_TPW=2, measurement knob) is slower: 98 vs 87 us on
-    // 262144 bf16 rows, 118 vs 106 us on fp32 rows -- one wave per SIMD costs more than the halved LDS reads give back
-    int tpw = 1;
-    if (const char *ev = std::getenv("SWARM_POLICY_TPW")) tpw = ev[0] == '2' ? 2 : 1;
-    if (p->precision == 1) tpw = 1;
-    const int n_waves = waves_of(p->precision == 1);
-    const long long per_block = (long long)n_waves * 32 * tpw;
-    const unsigned grid = (unsigned)((rows + per_block - 1) / per_block);
-    if (!p->smem_set) {
-        set_smem<false, 1, false>(); set_smem<true, 1, false>();
-        set_smem<false, 2, false>(); set_smem<true, 2, false>();
-        set_smem<false, 1, true>(); set_smem<true, 1, true>();
-        set_smem_bank<false, false>(); set_smem_bank<true, false>(); set_smem_bank<false, true>(); set_smem_bank<true, true>();
-        set_smem_route<false, false>(); set_smem_route<true, false>(); set_smem_route<false, true>(); set_smem_route<true, true>();
-        p->smem_set = true;
-    }
-    const dim3 g(grid), b(64 * n_waves);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (routed) {                                           // one workgroup per entry of the route's tile table; q.rows: the call's
-        const dim3 gr(p->route.grid(rg, p->members));
-        if (p->precision == 1) {
-            if (in_bf16) launch_route<true, true>(gr, b, st, q, obs, act, log_pi, logpi_c, rv);
-            else launch_route<false, true>(gr, b, st, q, obs, act, log_pi, logpi_c, rv);
-        } else {
-            if (in_bf16) launch_route<true, false>(gr, b, st, q, obs, act, log_pi, logpi_c, rv);
-            else launch_route<false, false>(gr, b, st, q, obs, act, log_pi, logpi_c, rv);
-        }
-    } else if (p->bank) {                                   // (ceil(R / rows per workgroup), members); SWARM_POLICY_TPW not read
-        q.rows = rows / p->members;                         // the kernel's P.rows: the MEMBER's rows
-        const long long bank_block = (long long)n_waves * 32;
-        const dim3 gb((unsigned)((q.rows + bank_block - 1) / bank_block), (unsigned)p->members);
-        if (p->precision == 1) {
-            if (in_bf16) launch_bank<true, true>(gb, b, st, q, obs, act, log_pi, logpi_c);
-            else launch_bank<false, true>(gb, b, st, q, obs, act, log_pi, logpi_c);
-        } else {
-            if (in_bf16) launch_bank<true, false>(gb, b, st, q, obs, act, log_pi, logpi_c);
-            else launch_bank<false, false>(gb, b, st, q, obs, act, log_pi, logpi_c);
-        }
-    } else if (p->precision == 1) {
-        if (in_bf16) launch_policy<true, 1, true>(g, b, st, q, obs, act, log_pi, logpi_c);
-        else launch_policy<false, 1, true>(g, b, st, q, obs, act, log_pi, logpi_c);
-    } else if (tpw == 2) {
-        if (in_bf16) launch_policy<true, 2, false>(g, b, st, q, obs, act, log_pi, logpi_c);
-        else launch_policy<false, 2, false>(g, b, st, q, obs, act, log_pi, logpi_c);
+    const unsigned route_grid = routed ? p->route.grid(rg, p->members) : 0u;    // one workgroup per entry of that table
+    // the exploration epilogue's parameters, the same for both geometries: the clamped scale, the key of (seed, step), and
+    // log-pi's constant act_dim * log(noise_scale * sqrt(2 pi)), in double from the fp32 scale the kernel uses
+    // (swarm_policy.h); a kernel without log-pi gets (nullptr, 0.0f)
+    const float scale = noise_scale > 0.0f ? noise_scale : 0.0f;
+    const unsigned long long noise_key = swarm_noise_key(seed, step);
+    const float c = (lp && scale > 0.0f) ? (float)((double)p->act_dim * std::log((double)scale * std::sqrt(2.0 * M_PI))) : 0.0f;
+    if (p->wide) {                                          // a wide handle: its own kernels
+        const swarm_wide::ForwardArgs a = {obs, in_bf16, rows, act, log_pi, scale, c, noise_key, row_offset, p->precision,
+                                           st, !p->smem_set, p->bank, p->members, routed ? &rv : nullptr, route_grid};
+        swarm_wide::forward(p->wl, p->d_blob.get(), a);
     } else {
-        if (in_bf16) launch_policy<true, 1, false>(g, b, st, q, obs, act, log_pi, logpi_c);
-        else launch_policy<false, 1, false>(g, b, st, q, obs, act, log_pi, logpi_c);
+        MlpParams q = p->p;
+        q.rows = rows; q.noise_scale = scale; q.noise_key = noise_key; q.row_offset = row_offset;
+        if (!p->smem_set) {
+            using swarm_wide::raise_smem;
+            raise_smem(kPlain, kSmemBytes); raise_smem(kPlainTpw2, kSmemBytes); raise_smem(kBank, kSmemBytes); raise_smem(kRoute, kSmemBytes);
+        }
+        const int n_waves = waves_of(x3);
+        const long long per_block = (long long)n_waves * 32;
+        const dim3 b(64 * n_waves);
+        if (routed) {                                       // q.rows: the call's
+            hipLaunchKernelGGL(kRoute[x3][in_bf16][lp], dim3(route_grid), b, kSmemBytes, st, q, obs, act, log_pi, c, rv);
+        } else if (p->bank) {                               // (ceil(R / rows per workgroup), members)
+            q.rows = rows / p->members;                     // the kernel's P.rows: the MEMBER's rows
+            const dim3 gb((unsigned)((q.rows + per_block - 1) / per_block), (unsigned)p->members);
+            hipLaunchKernelGGL(kBank[x3][in_bf16][lp], gb, b, kSmemBytes, st, q, obs, act, log_pi, c);
+        } else {
+            // one row tile per wave; the two-tile instantiation (SWARM_POLICY_TPW=2, measurement knob, read for a plain narrow
+            // handle alone) is slower: 98 vs 87 us on 262144 bf16 rows, 118 vs 106 us on fp32 rows -- one wave per SIMD costs
+            // more than the halved LDS reads give back
+            const char *ev = std::getenv("SWARM_POLICY_TPW");
+            const int tpw = (ev && ev[0] == '2' && !x3) ? 2 : 1;
+            const dim3 g((unsigned)((rows + per_block * tpw - 1) / (per_block * tpw)));
+            hipLaunchKernelGGL(tpw == 2 ? kPlainTpw2[in_bf16][lp] : kPlain[x3][in_bf16][lp], g, b, kSmemBytes, st, q, obs, act, log_pi, c);
+        }
     }
+    p->smem_set = true;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { g_policy_error = std::string("swarm_policy_forward: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
     return SWARM_POLICY_OK;
@@ -830,7 +727,7 @@ int swarm_policy_bank_route(swarm_policy_t *p, const int32_t *member_of_env, int
         q.n_tiles[g] = r.t_rows[g] ? (int)r.grid(g, p->members) : 0;
     }
     q.n_env = n_env; q.rows_per_env = rows_per_env; q.members = p->members;
-    launch_route_table<kRouteThreads>(q, st);
+    hipLaunchKernelGGL(k_policy_route_table<kRouteThreads>, dim3(1), dim3(kRouteThreads), 0, st, q);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { r.n_env = 0; r.rows_per_env = 0; g_policy_error = std::string(who) + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
     return SWARM_POLICY_OK;

@@ -25,8 +25,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
-#include <string>
 #include <vector>
 
 #include "policy_wide.h"
@@ -37,7 +35,6 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf8;
 typedef __attribute__((ext_vector_type(16))) float f16v;
 
 using swarm_internal::pmix64;
-using swarm_internal::swarm_noise_key;
 
 constexpr int kWaves = 4;                 // wavefronts (32-row tiles) per workgroup
 constexpr int kThreads = 64 * kWaves;
@@ -141,24 +138,9 @@ __device__ __forceinline__ void finish_row(const WideParams &P, const f16v &o, l
 #undef POLICY_WIDE_ROUTE
 static_assert(kRowsPerBlock == swarm_wide::kRouteRows, "the route's tile table is cut for this workgroup");
 
-// ---- the packed stream, on the host (create) and on the device (load_device): the two are written independently and
+// ---- the packed stream, on the host (pack_host) and on the device (load_device): the two are written independently and
 // tests/test_gpu_policy_wide.py compares their bytes.
-struct Layout {
-    int mt, kc, w, tail, ch, wout;     // Geo<MT>, at run time
-    int n1, n_chunks;                  // layer-1 chunks, chunks of the whole stream
-    int in_dim, hidden, act_dim;
-};
-
-Layout layout_of(int in_dim, int hidden, int act_dim)
-{
-    Layout g;
-    g.mt = hidden <= 192 ? 6 : 8;
-    g.kc = g.mt / 2; g.w = g.mt * 256; g.tail = g.mt * 8; g.ch = g.w + g.tail; g.wout = 2 * g.mt * 64;
-    g.n1 = (in_dim + 63) / 64;
-    g.n_chunks = g.n1 + 2 * g.kc + 1;
-    g.in_dim = in_dim; g.hidden = hidden; g.act_dim = act_dim;
-    return g;
-}
+using swarm_wide::Layout;
 
 struct PackParams {
     const float *w[8];                 // fc1.weight, fc1.bias, ..., fc4.bias, device
@@ -230,6 +212,37 @@ __global__ void __launch_bounds__(256) k_policy_wide_pack(const PackParams P)
 float bits_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 uint32_t float_bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
+// The kernels a forward call chooses from, per kernel text: [mt == 8][x3][in_bf16][log_pi].
+using WideKernel = void (*)(WideParams, const void *, float *, float *, float);
+using WideRouteKernel = void (*)(WideParams, const void *, float *, float *, float, swarm_wide::RouteView);
+#define WIDE_KERNELS(K, X3, MT) {{K<false, X3, false, MT>, K<false, X3, true, MT>}, {K<true, X3, false, MT>, K<true, X3, true, MT>}}
+#define WIDE_TABLE(K) {{WIDE_KERNELS(K, false, 6), WIDE_KERNELS(K, true, 6)}, {WIDE_KERNELS(K, false, 8), WIDE_KERNELS(K, true, 8)}}
+const WideKernel kPlain[2][2][2][2] = WIDE_TABLE(k_policy_wide), kBank[2][2][2][2] = WIDE_TABLE(k_policy_wide_bank);
+const WideRouteKernel kRoute[2][2][2][2] = WIDE_TABLE(k_policy_wide_route);
+#undef WIDE_TABLE
+#undef WIDE_KERNELS
+static_assert(Geo<8>::SMEM <= 160 * 1024 && swarm_wide::kMaxHidden == 32 * 8 && swarm_wide::kMaxIn % 64 == 0, "the widest geometry");
+
+}  // namespace
+
+namespace swarm_wide {
+
+bool shape_ok(int in_dim, int hidden, int act_dim)
+{
+    return in_dim >= 4 && in_dim <= kMaxIn && !(in_dim & 3) && hidden >= 1 && hidden <= kMaxHidden && act_dim >= 1 && act_dim <= kMaxAct;
+}
+
+Layout layout_of(int in_dim, int hidden, int act_dim)
+{
+    Layout g;
+    g.mt = hidden <= 192 ? 6 : 8;
+    g.kc = g.mt / 2; g.w = g.mt * 256; g.tail = g.mt * 8; g.ch = g.w + g.tail; g.wout = 2 * g.mt * 64;
+    g.n1 = (in_dim + 63) / 64;
+    g.n_chunks = g.n1 + 2 * g.kc + 1;
+    g.in_dim = in_dim; g.hidden = hidden; g.act_dim = act_dim;
+    return g;
+}
+
 // The host packer: the stream built layer by layer into a zeroed blob.
 std::vector<unsigned char> pack_host(const Layout &g, const float *const w[8])
 {
@@ -290,190 +303,39 @@ std::vector<unsigned char> pack_host(const Layout &g, const float *const w[8])
     return blob;
 }
 
-template <bool IN_BF16, bool X3, int MT>
-void launch(const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act, float *log_pi, float logpi_c)
-{
-    if (log_pi) hipLaunchKernelGGL((k_policy_wide<IN_BF16, X3, true, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, log_pi, logpi_c);
-    else hipLaunchKernelGGL((k_policy_wide<IN_BF16, X3, false, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, nullptr, 0.0f);
-}
-
-template <bool IN_BF16, bool X3, int MT>
-void set_smem()
-{
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide<IN_BF16, X3, false, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide<IN_BF16, X3, true, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
-}
-
-template <bool IN_BF16, bool X3, int MT>
-void launch_bank(const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act, float *log_pi, float logpi_c)
-{
-    if (log_pi) hipLaunchKernelGGL((k_policy_wide_bank<IN_BF16, X3, true, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, log_pi, logpi_c);
-    else hipLaunchKernelGGL((k_policy_wide_bank<IN_BF16, X3, false, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, nullptr, 0.0f);
-}
-
-template <bool IN_BF16, bool X3, int MT>
-void set_smem_bank()
-{
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide_bank<IN_BF16, X3, false, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide_bank<IN_BF16, X3, true, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
-}
-
-template <bool IN_BF16, bool X3, int MT>
-void launch_route(const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act, float *log_pi, float logpi_c,
-                  const swarm_wide::RouteView &rv)
-{
-    if (log_pi) hipLaunchKernelGGL((k_policy_wide_route<IN_BF16, X3, true, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, log_pi, logpi_c, rv);
-    else hipLaunchKernelGGL((k_policy_wide_route<IN_BF16, X3, false, MT>), g, dim3(kThreads), Geo<MT>::SMEM, st, q, obs, act, nullptr, 0.0f, rv);
-}
-
-template <bool IN_BF16, bool X3, int MT>
-void set_smem_route()
-{
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide_route<IN_BF16, X3, false, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_policy_wide_route<IN_BF16, X3, true, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Geo<MT>::SMEM);
-}
-
-template <int MT>
-void set_smem_all()
-{
-    set_smem<false, false, MT>(); set_smem<true, false, MT>(); set_smem<false, true, MT>(); set_smem<true, true, MT>();
-    set_smem_bank<false, false, MT>(); set_smem_bank<true, false, MT>(); set_smem_bank<false, true, MT>(); set_smem_bank<true, true, MT>();
-    set_smem_route<false, false, MT>(); set_smem_route<true, false, MT>(); set_smem_route<false, true, MT>(); set_smem_route<true, true, MT>();
-}
-
-template <int MT>
-void launch_route_mt(bool in_bf16, bool x3, const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act,
-                     float *log_pi, float logpi_c, const swarm_wide::RouteView &rv)
-{
-    if (x3) {
-        if (in_bf16) launch_route<true, true, MT>(g, st, q, obs, act, log_pi, logpi_c, rv);
-        else launch_route<false, true, MT>(g, st, q, obs, act, log_pi, logpi_c, rv);
-    } else {
-        if (in_bf16) launch_route<true, false, MT>(g, st, q, obs, act, log_pi, logpi_c, rv);
-        else launch_route<false, false, MT>(g, st, q, obs, act, log_pi, logpi_c, rv);
-    }
-}
-
-template <int MT>
-void launch_mt(bool bank, bool in_bf16, bool x3, const dim3 &g, hipStream_t st, const WideParams &q, const void *obs, float *act,
-               float *log_pi, float logpi_c)
-{
-    if (bank) {
-        if (x3) {
-            if (in_bf16) launch_bank<true, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
-            else launch_bank<false, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
-        } else {
-            if (in_bf16) launch_bank<true, false, MT>(g, st, q, obs, act, log_pi, logpi_c);
-            else launch_bank<false, false, MT>(g, st, q, obs, act, log_pi, logpi_c);
-        }
-    } else if (x3) {
-        if (in_bf16) launch<true, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
-        else launch<false, true, MT>(g, st, q, obs, act, log_pi, logpi_c);
-    } else {
-        if (in_bf16) launch<true, false, MT>(g, st, q, obs, act, log_pi, logpi_c);
-        else launch<false, false, MT>(g, st, q, obs, act, log_pi, logpi_c);
-    }
-}
-
-}  // namespace
-
-namespace swarm_wide {
-
-struct Handle {
-    Layout g;
-    swarm_internal::DevBuf<unsigned char> d_blob;        // `members` blobs of blob_bytes each, one behind the other
-    size_t blob_bytes = 0;
-    int members = 1;
-    bool smem_set = false;
-};
-
-bool shape_ok(int in_dim, int hidden, int act_dim)
-{
-    return in_dim >= 4 && in_dim <= kMaxIn && !(in_dim & 3) && hidden >= 1 && hidden <= kMaxHidden && act_dim >= 1 && act_dim <= kMaxAct;
-}
-
-int create(const float *const *w, int members, int in_dim, int hidden, int act_dim, Handle **out, std::string &err)
-{
-    static_assert(Geo<8>::SMEM <= 160 * 1024 && kMaxHidden == 32 * 8 && kMaxIn % 64 == 0, "the widest geometry");
-    *out = nullptr;
-    Handle *p = new (std::nothrow) Handle;
-    if (!p) { err = "out of memory"; return SWARM_POLICY_ERR_INVALID; }
-    p->g = layout_of(in_dim, hidden, act_dim);
-    p->members = members;
-    std::vector<unsigned char> blob = pack_host(p->g, w);
-    p->blob_bytes = blob.size();
-    for (int m = 1; m < members; ++m) {                     // a bank: the same packer, member by member
-        const std::vector<unsigned char> one = pack_host(p->g, w + 8 * m);
-        blob.insert(blob.end(), one.begin(), one.end());
-    }
-    // the upload on a stream of its own, waited for here: no null-stream work (tests/test_stream_sources.py), complete on return
-    hipStream_t up = nullptr;
-    hipError_t e = p->d_blob.alloc(blob.size());
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_blob.get(), blob.data(), blob.size(), hipMemcpyHostToDevice, up);
-    if (e == hipSuccess) e = hipStreamSynchronize(up);
-    if (up) (void)hipStreamDestroy(up);
-    if (e != hipSuccess) {
-        delete p;
-        err = "device allocation / upload failed";
-        return SWARM_POLICY_ERR_HIP;
-    }
-    *out = p;
-    return SWARM_POLICY_OK;
-}
-
-void destroy(Handle *h) { delete h; }
-
-const void *blob(const Handle *h, size_t *bytes)
-{
-    *bytes = h->blob_bytes;
-    return h->d_blob.get();
-}
-
-int forward(Handle *p, const ForwardArgs &a, std::string &err)
+void forward(const Layout &g, const void *blob, const ForwardArgs &a)
 {
     WideParams q;
-    q.hi = reinterpret_cast<const bf8 *>(p->d_blob.get());
-    q.lo = q.hi + (size_t)p->g.n_chunks * p->g.ch;
-    q.in_dim = p->g.in_dim; q.act_dim = p->g.act_dim; q.rows = a.rows;
-    q.noise_scale = a.noise_scale > 0.0f ? a.noise_scale : 0.0f;
-    q.noise_key = swarm_noise_key(a.seed, a.step);
-    q.row_offset = a.row_offset;
-    // log-pi's constant act_dim * log(noise_scale * sqrt(2 pi)), in double from the fp32 scale the kernel uses (swarm_policy.h)
-    const float logpi_c = q.noise_scale > 0.0f ? (float)((double)q.act_dim * std::log((double)q.noise_scale * std::sqrt(2.0 * M_PI))) : 0.0f;
-    if (!p->smem_set) {
-        set_smem_all<6>(); set_smem_all<8>();
-        p->smem_set = true;
+    q.hi = reinterpret_cast<const bf8 *>(blob);
+    q.lo = q.hi + (size_t)g.n_chunks * g.ch;
+    q.in_dim = g.in_dim; q.act_dim = g.act_dim; q.rows = a.rows;
+    q.noise_scale = a.noise_scale; q.noise_key = a.noise_key; q.row_offset = a.row_offset;
+    const auto smem_of = [](int mt8) { return mt8 ? Geo<8>::SMEM : Geo<6>::SMEM; };
+    if (a.set_smem)
+        for (int m = 0; m < 2; ++m) { raise_smem(kPlain[m], smem_of(m)); raise_smem(kBank[m], smem_of(m)); raise_smem(kRoute[m], smem_of(m)); }
+    const int wide8 = g.mt == 8, x3 = a.precision == SWARM_POLICY_BF16X3, lp = a.log_pi != nullptr;
+    const unsigned smem = smem_of(wide8);
+    const dim3 b(kThreads);
+    if (a.route) {                                          // one workgroup per tile-table entry, q.rows the call's rows
+        hipLaunchKernelGGL(kRoute[wide8][x3][a.in_bf16][lp], dim3(a.route_grid), b, smem, a.stream, q, a.obs, a.act, a.log_pi, a.logpi_c, *a.route);
+        return;
     }
     // a bank handle: grid (ceil(R / 128), members), and the kernel's P.rows is the MEMBER's rows R = rows / members (the caller
     // has checked the division)
-    if (a.bank) q.rows = a.rows / p->members;
-    const dim3 g((unsigned)((q.rows + kRowsPerBlock - 1) / kRowsPerBlock), a.bank ? (unsigned)p->members : 1u);
-    const bool x3 = a.precision == SWARM_POLICY_BF16X3;
-    if (a.route) {                                          // a route in force: one workgroup per tile-table entry, the call's rows
-        q.rows = a.rows;
-        const dim3 gr(a.route_grid);
-        if (p->g.mt == 6) launch_route_mt<6>(a.in_bf16, x3, gr, a.stream, q, a.obs, a.act, a.log_pi, logpi_c, *a.route);
-        else launch_route_mt<8>(a.in_bf16, x3, gr, a.stream, q, a.obs, a.act, a.log_pi, logpi_c, *a.route);
-    } else if (p->g.mt == 6) launch_mt<6>(a.bank, a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
-    else launch_mt<8>(a.bank, a.in_bf16, x3, g, a.stream, q, a.obs, a.act, a.log_pi, logpi_c);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = std::string("swarm_policy_forward: ") + hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
-    return SWARM_POLICY_OK;
+    if (a.bank) q.rows = a.rows / a.members;
+    const dim3 grid((unsigned)((q.rows + kRowsPerBlock - 1) / kRowsPerBlock), a.bank ? (unsigned)a.members : 1u);
+    hipLaunchKernelGGL((a.bank ? kBank : kPlain)[wide8][x3][a.in_bf16][lp], grid, b, smem, a.stream, q, a.obs, a.act, a.log_pi, a.logpi_c);
 }
 
-int load_device(Handle *p, int member, const float *const w[8], hipStream_t st, std::string &err)
+void load_device(const Layout &g, void *dst, const float *const w[8], hipStream_t st)
 {
     PackParams q;
     for (int i = 0; i < 8; ++i) q.w[i] = w[i];
-    q.hi = reinterpret_cast<uint4 *>(p->d_blob.get() + (size_t)member * p->blob_bytes);
-    q.lo = q.hi + (size_t)p->g.n_chunks * p->g.ch;
-    q.g = p->g;
-    const unsigned grid = (unsigned)((p->g.n_chunks * p->g.ch + 255) / 256);
+    q.hi = static_cast<uint4 *>(dst);
+    q.lo = q.hi + (size_t)g.n_chunks * g.ch;
+    q.g = g;
+    const unsigned grid = (unsigned)((g.n_chunks * g.ch + 255) / 256);
     hipLaunchKernelGGL(k_policy_wide_pack, dim3(grid), dim3(256), 0, st, q);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = hipGetErrorString(e); return SWARM_POLICY_ERR_HIP; }
-    return SWARM_POLICY_OK;
 }
 
 }  // namespace swarm_wide

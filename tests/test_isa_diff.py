@@ -1,5 +1,5 @@
 """tools/isa_diff.py's splitter and comparer on hand-written assembly (CPU only, nothing is compiled): two files that are
-the same, one kernel changed, one kernel added."""
+the same, one kernel changed, one kernel added, the same kernels in another order."""
 import importlib.util
 import os
 
@@ -77,6 +77,30 @@ def test_one_kernel_added(tool):
 def test_difference_outside_the_kernels_is_reported(tool):
     r = tool.compare(HEAD + A, HEAD + A + '\t.ident\t"other compiler"\n')
     assert r["differing"] == [] and r["only_base"] == [] and r["only_tree"] == [] and r["outside"]
+
+
+def test_kernels_in_another_order_are_reordered_not_outside(tool):
+    r = tool.compare(HEAD + A + B, HEAD + B + A)
+    assert r["kernels"] == 2 and r["differing"] == [] and r["only_base"] == [] and r["only_tree"] == []
+    assert r["reordered"] and not r["outside"]
+    # the function number of a label outside the kernels moves with the order and does not count
+    r = tool.compare(HEAD + A + ".Lfunc_end0:\n" + B + ".Lfunc_end1:\n", HEAD + B + ".Lfunc_end0:\n" + A + ".Lfunc_end1:\n")
+    assert r["reordered"] and not r["outside"] and r["differing"] == []
+    # the same file is neither
+    r = tool.compare(HEAD + A + B, HEAD + A + B)
+    assert not r["reordered"] and not r["outside"]
+
+
+def test_another_order_and_another_line_outside_is_outside(tool):
+    r = tool.compare(HEAD + A + B, HEAD + B + A + '\t.ident\t"other compiler"\n')
+    assert r["differing"] == [] and r["only_base"] == [] and r["only_tree"] == []
+    assert r["outside"] and not r["reordered"]
+    # a line that is there twice is not the line once: multisets, not sets
+    r = tool.compare(HEAD + A + B, HEAD + B + A + '\t.text\n')
+    assert r["outside"] and not r["reordered"]
+    # a changed kernel in another order is a changed kernel
+    r = tool.compare(HEAD + A + B, HEAD + B_MOVED + A)
+    assert [d[0] for d in r["differing"]] == ["_Z1bv"] and not r["reordered"] and not r["outside"]
 
 
 # ---- one source cut into different units in the two trees: kernel by kernel over all units, local labels and comments normalised

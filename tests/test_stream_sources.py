@@ -28,7 +28,6 @@ PLAIN_CALLS = {
     ("env_api.hip", "swarm_set_cells", "hipMemcpy"): 2,     # behind the function's own hipStreamSynchronize(h->stream)
     ("env_api.hip", "swarm_set_shapes", "hipMemcpy"): 5,    # into buffers allocated aside that no enqueued work knows yet
     ("env_api.hip", "swarm_path_envs", "hipMemcpy2D"): 1,   # behind the function's own hipStreamSynchronize(h->stream)
-    ("policy_mlp.hip", "swarm_policy_create", "hipMemcpy"): 1,       # into the new handle's fresh blob, from pageable memory
     ("swarm_env.hip", "swarm_debug_stamps", "hipMemset"): 1,         # SWARM_STAMPS builds only (diagnostic)
     ("swarm_env.hip", "swarm_debug_stamps", "hipMemcpy"): 1,
 }

@@ -13,7 +13,9 @@ instructions.  One name is taken out of both texts before they are compared: `__
 hipcc names after a hash of the SOURCE text, comments included -- it differs whenever the source does and says nothing about
 the code.  Kernel by kernel, the number that the local labels .LBB<k>_, .Lfunc_end<k>, .LJTI<k>_ and .Ltmp<k> carry is taken
 out as well: it is the function's position in its translation unit, and a kernel added to a file moves it for every function
-the compiler emits behind the new one (template instantiations come last) without touching an instruction.
+the compiler emits behind the new one (template instantiations come last) without touching an instruction.  Two files whose
+kernels are all the same but come out in another order are not a changed file: the lines outside the kernels are then
+compared as multisets, after the same treatment of the labels, and where those are equal the file is reported as reordered.
 
 Where the trees cut a source into different units, the kernels of all of the source's units are compared one by one, each with
 its entry of the `amdhsa.kernels` metadata (arguments, segment sizes); a kernel found in two units of one tree is an error,
@@ -23,7 +25,7 @@ unit -- and the `;` comments.  Nothing else.
 
 Prints the kernels that are only in the base, only in the tree, or different (with the first differing line), then
 `kernels N, lines M, differing K`, and exits non-zero if K > 0, the sets of names differ, a kernel is there twice, or two
-files differ outside their kernels.  Arguments that start with `-` go to the compiler, for every unit (-DSWARM_STAMPS).  No
+files differ outside their kernels in more than the order of their lines.  Arguments that start with `-` go to the compiler, for every unit (-DSWARM_STAMPS).  No
 GPU is needed: hipcc cross-compiles."""
 import concurrent.futures
 import importlib.util
@@ -85,14 +87,18 @@ def by_name(kb, kt, res):
 def compare(base_text, tree_text):
     """Compare two assembly files.  Returns a dict: kernels (names in either), lines (of tree_text), only_base, only_tree
     (sorted names), differing ([(name, line number inside the kernel from 1, base line, tree line)]; a missing line is
-    None), outside (True if the files differ, but in no kernel)."""
-    res = {"lines": len(tree_text.splitlines()), "only_base": [], "only_tree": [], "differing": [], "outside": False}
-    kb, kt = split_kernels(base_text)[0], split_kernels(tree_text)[0]
+    None), reordered (True if the files differ only in the order of their kernels: the same kernels, and outside them the same
+    lines as multisets), outside (True if the files differ in no kernel and in more than that order)."""
+    res = {"lines": len(tree_text.splitlines()), "only_base": [], "only_tree": [], "differing": [], "outside": False,
+           "reordered": False}
+    (kb, ob), (kt, ot) = split_kernels(base_text), split_kernels(tree_text)
     res["kernels"] = len(set(kb) | set(kt))
     if base_text == tree_text:
         return res
     by_name({n: unnumbered(k) for n, k in kb.items()}, {n: unnumbered(k) for n, k in kt.items()}, res)
-    res["outside"] = not (res["only_base"] or res["only_tree"] or res["differing"])
+    if not (res["only_base"] or res["only_tree"] or res["differing"]):
+        res["reordered"] = sorted(unnumbered(ob)) == sorted(unnumbered(ot))
+        res["outside"] = not res["reordered"]
     return res
 
 
@@ -176,6 +182,11 @@ def compile_asm(hipcc, flags, root, rel, out):
         return strip_cuid(f.read())
 
 
+def bad_in(r):
+    """does a source's summed result fail the run?"""
+    return bool(r["only_base"] or r["only_tree"] or r["differing"] or r["outside"] or r.get("duplicates"))
+
+
 def main(argv):
     from marl_llm_amd.build import hipcc_path, jobs
     args = [a for a in argv if not a.startswith("-")]
@@ -215,7 +226,8 @@ def main(argv):
             # the same units in both trees (or a source that one tree lacks): unit by unit, whole files first
             rs = [compare(x, y) for x, y in zip(b, t)] if cut_b == cut_t else [compare(x, "") for x in b] + [compare("", y) for y in t]
             r = {k: sum((q[k] for q in rs), type(rs[0][k])()) for k in rs[0]}
-            print("%s: %s" % (rel, "identical" if b == t else "DIFFERENT"))
+            print("%s: %s" % (rel, "identical" if b == t else "kernels identical, emitted in another order"
+                              if r["reordered"] and not bad_in(r) else "DIFFERENT"))
         else:
             r = compare_units(b, t)
             same = not (r["only_base"] or r["only_tree"] or r["differing"] or r["duplicates"])
@@ -224,7 +236,7 @@ def main(argv):
         kernels += r["kernels"]
         lines += r["lines"]
         differing += len(r["differing"])
-        bad = bad or bool(r["only_base"] or r["only_tree"] or r["differing"] or r["outside"] or r.get("duplicates"))
+        bad = bad or bad_in(r)
         for side, name in r.get("duplicates", []):
             print("  in two units of %s: %s" % (base_ref if side == "base" else "the tree", name))
         for name in r["only_base"]:
