@@ -105,11 +105,11 @@ def compare(dev, ref, tag="", *, fields=FIELDS, indices=True, envs=None, env0=0)
             raise Mismatch(f, tag, envs[diff.reshape(len(diff), -1).any(axis=1)] + env0)
 
 
-def hold(cases, ref, *, lattice=None, fields=FIELDS, pad=3, **kw):
+def hold(cases, ref, *, lattice=None, paths=None, fields=FIELDS, pad=3, **kw):
     """Run `cases` [(p, dp, grid, l_cell)] through a fresh SwarmBatch(**kw) and hold every call to `ref` = (first, steps, ...)
-    as helpers.oracle_run returns it: cells padded by `pad` and uploaded, lattice_envs() == lattice if given, set_state and
-    observe compared, then one step per entry of `steps` with the action recorded under "act", all of `fields` compared
-    after each (tag: "observe", then the step number).  Returns the index arrays of every call, with p, dp and reward for the
+    as helpers.oracle_run returns it: cells padded by `pad` and uploaded, lattice_envs() == lattice and path_envs() == paths
+    (before the first and after the last call) if given, set_state and observe compared, then one step per entry of `steps`
+    with the action recorded under "act", all of `fields` compared after each (tag: "observe", then the step number).  Returns the index arrays of every call, with p, dp and reward for the
     steps."""
     from marl_llm_amd.batched import SwarmBatch
     import torch
@@ -122,6 +122,8 @@ def hold(cases, ref, *, lattice=None, fields=FIELDS, pad=3, **kw):
         sb.set_cells(cells, n_g, [c[3] for c in cases])
         if lattice is not None:
             assert sb.lattice_envs() == lattice, (sb.lattice_envs(), lattice)
+        if paths is not None:
+            assert sb.path_envs() == tuple(paths), (sb.path_envs(), paths)
         sb.set_state(np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
         dev = host_copy(sb, sb.observe(), state=False, indices=True)
         compare(dev, device_layout(first, dtype), "observe", fields=[f for f in OBSERVE if f in fields])
@@ -131,6 +133,8 @@ def hold(cases, ref, *, lattice=None, fields=FIELDS, pad=3, **kw):
             dev = host_copy(sb, sb.step(torch.from_numpy(want["act"]).to(sb.device)), indices=True)
             compare(dev, want, t, fields=fields)
             seen.append({k: dev[k] for k in IDX + ("p", "dp", "reward")})
+        if paths is not None:
+            assert sb.path_envs() == tuple(paths), (sb.path_envs(), paths)
     finally:
         sb.close()
     return seen
